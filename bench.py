@@ -16,16 +16,18 @@ RCCL SUM all-reduce of the flat parameter-gradient bucket of the reference's joi
 complete data-parallel step of the fused engine (joint + loss + gradients + that all-reduce on the real
 dW1, db1, dW2, db2) on the same ranks.
 
-`python bench.py --gpus N` without a launcher re-executes itself under torch.distributed.run with N
-ranks; under a launcher (WORLD_SIZE set) --gpus must equal WORLD_SIZE.
+`python bench.py --gpus N` without a launcher runs itself under torch.distributed.run with N ranks in a
+child process; under a launcher (WORLD_SIZE set) --gpus must equal WORLD_SIZE.
 
 Prints ONE JSON line (rank 0).  Extra objects: `roofline`, `cpu_baseline` (rank 0, N=1 only).
+`--dump-outputs DIR` also writes the costs and gradients of the last timed step (dump_outputs()).
 """
 import argparse
 import ctypes
 import json
 import os
 import socket
+import subprocess
 import sys
 import time
 
@@ -66,7 +68,17 @@ def parse(argv=None):
     ap.add_argument("--engine", choices=["hip", "stub"], default="hip",
                     help="stub = CPU/gloo stand-in with no kernels: exercises the launch / sharding / collective / reporting "
                          "path only (tests/test_bench_launch.py); it reports value null")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy: costs [B] "
+                         "and grads [B,T,U,V] f32, or, when the gradients exceed the 64 MB budget, grads_sample [n,V] = the "
+                         "gradient rows of n lattice cells drawn without replacement by np.random.default_rng(0), in "
+                         "ascending flat (b,t,u) order.  Inputs depend only on the arguments, so two builds can be compared")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and (a.fused_only or a.engine == "stub"):
+        ap.error("--dump-outputs records the headline op path; it does not combine with --fused-only or --engine stub")
+    return a
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -79,8 +91,8 @@ def _free_port():
 
 
 def ensure_world(a):
-    """Returns (world, rank, local_rank).  Re-executes under torch.distributed.run when --gpus N > 1 was asked for
-    without a launcher; refuses a launcher whose world size contradicts --gpus."""
+    """Returns (world, rank, local_rank).  Runs itself under torch.distributed.run in a child process (and exits with its
+    status) when --gpus N > 1 was asked for without a launcher; refuses a launcher whose world size contradicts --gpus."""
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None:
         if a.gpus > 1:
@@ -88,7 +100,8 @@ def ensure_world(a):
                    "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
             os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
             sys.stdout.flush()
-            os.execv(sys.executable, cmd)
+            # a fresh child, not exec: the launcher process is never replaced in place
+            raise SystemExit(subprocess.run(cmd).returncode)
         return 1, 0, 0
     world = int(env_world)
     if world != a.gpus:
@@ -477,6 +490,27 @@ def bench_op_shape(lib, _lib, dev, B, T, U, V, stream, reps):
                                  "(skipping_speedup_equivalent_GBs) is not a bandwidth"}}
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, costs, grads):
+    """--dump-outputs: the headline step's results as f32 .npy files, at most DUMP_BUDGET_BYTES in all.  A gradient tensor
+    over the budget is written as a fixed sample of whole lattice cells (all V entries of each), the same for every run
+    with the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    c = costs.float().cpu().numpy()
+    np.save(os.path.join(out_dir, "costs.npy"), c)
+    B, T, U, V = grads.shape
+    room = DUMP_BUDGET_BYTES - c.nbytes - (1 << 20)  # headroom: .npy headers, directory entries
+    if grads.numel() * 4 <= room:
+        np.save(os.path.join(out_dir, "grads.npy"), grads.float().cpu().numpy())
+        return
+    cells = B * T * U
+    pick = np.sort(np.random.default_rng(0).choice(cells, min(cells, room // (4 * V)), replace=False))
+    rows = grads.reshape(cells, V).index_select(0, torch.from_numpy(pick).to(grads.device))
+    np.save(os.path.join(out_dir, "grads_sample.npy"), rows.float().cpu().numpy())
+
+
 def joint_bucket_floats(H, J, V):
     return H * J + J + J * V + V
 
@@ -730,6 +764,8 @@ def main():
     for i in range(a.warmup):
         step(i)
     dt = timed(step, a.steps)
+    if a.dump_outputs and rank == 0:  # before any later leg overwrites costs / grads
+        dump_outputs(a.dump_outputs, costs, grads)
     cells = B * T * U
     value = world * cells * a.steps / dt
     # the same step on ONE buffer (what round 1 reported): part of the logits survives in the Infinity Cache
