@@ -354,6 +354,62 @@ RNNT_API rnntStatus_t compute_rnnt_joint_net_logits(const float *enc, const floa
                                                     int alphabet_size, int minibatch, float *logits, int joint_dtype,
                                                     void *workspace, rnntOptions options);
 
+/* Build-only extension: batched GREEDY DECODING.  Replaces the reference's one-utterance loop (utils/decoding.py:21-108: per
+ * encoder frame, emit the joint's argmax until it is the blank) with a decoder over every utterance of a batch at once.  The
+ * caller steps the prediction network; the library evaluates the joint for one lattice cell per hypothesis -- its current
+ * frame against its prediction-network output -- and does the argmax, the log-softmax of the decision and the state update
+ * in the same pass, without writing logits.
+ *
+ *   enc_proj      device f32 [minibatch, maxT, joint_size] = enc @ W1 + b1 (bias folded, as for compute_rnnt_joint_logits)
+ *   pred_proj     device f32 [minibatch, joint_size]       = pred @ W1 of each hypothesis's CURRENT prediction-network output
+ *   W2 [joint_size, alphabet_size], b2 [alphabet_size]     device f32 (model.py:165-166)
+ *   frame_lengths device i32 [minibatch]   frames of each utterance; clamped into [0, maxT]
+ *   max_symbols   device i32 [minibatch] or NULL: symbols each hypothesis may emit at most (negative = 0; NULL = no limit
+ *                 beyond max_hyp_len)
+ *   max_per_frame symbols per frame at most, then the next frame; <= 0: no cap (the reference's semantics)
+ *   options       loc RNNT_GPU, stream, blank_label (the stop symbol, < alphabet_size), maxT; maxU >= 1 (unused).
+ *                 The same options for begin and every step of one decode.
+ *
+ * compute_rnnt_greedy_begin (once per decode) builds the W2 operand image, the e^{2x} tables of enc_proj for every frame and
+ * resets every hypothesis: frame 0, no symbols, score 0; done when frame_lengths[b] or max_symbols[b] is 0.  The workspace then
+ * holds everything the steps need: enc_proj and W2 may be reused or freed by the caller.
+ * compute_rnnt_greedy_step (once per decode step), for every hypothesis b that is not done:
+ *   k = argmax_v logits[b, v] (lowest index on ties, as torch.argmax), logits = tanh(enc_proj[b, t_b] + pred_proj[b]) @ W2 + b2;
+ *   scores[b] += log_softmax(logits)[k];  k == blank_label: t_b += 1;  else hyps[b, n_b] = k, n_b += 1, and t_b += 1 when
+ *   max_per_frame symbols were emitted at this frame;  done when t_b >= frame_lengths[b] or n_b >= max_symbols[b].
+ *   Outputs, all device, caller-owned:
+ *     hyps        i32 [minibatch, max_hyp_len]  symbols are appended; nothing else is written (zero-fill it for zero padding)
+ *     hyp_lengths i32 [minibatch], scores f32 [minibatch]  written for every hypothesis at every step (f64 sum inside)
+ *     emitted     i32 [minibatch]  the symbol hypothesis b emitted in this step, or -1 (blank, done, or paused): the caller
+ *                 advances its prediction network for exactly these rows
+ *     all_done    i32 [1]  0: some hypothesis is running; 1: every hypothesis is done; 2: none is running, but some are PAUSED
+ *                 because they filled max_hyp_len symbols below their max_symbols -- steps with a larger max_hyp_len (a hyps
+ *                 buffer grown by the caller, contents kept) resume them
+ *     logit_stats f32 [minibatch, 2] or NULL: {max logit, logsumexp} of this step's joint, written for the hypotheses that ran
+ *   A hypothesis that is done (or paused) reads nothing and writes only hyp_lengths / scores (unchanged) and emitted = -1.
+ *
+ * Numerics: the argmax and the max logit are bitwise those of compute_rnnt_joint_logits called with that hypothesis alone
+ * (minibatch = maxT = maxU = 1, the same joint_dtype), so a decoder sees the logits the loss was trained on.  The two kernels'
+ * call-wide route switches (the direct tanh when some |projection| leaves the e^{2x} table range) are taken per hypothesis, from
+ * its own enc_proj row and pred_proj row.  logsumexp: f32 partial sums per 32-symbol chunk, combined in f64.
+ * Shapes: joint_dtype 0 (f32-grade) on the shapes compute_rnnt_joint_logits takes for it; joint_dtype 1 (binary16 operands)
+ * joint_size a multiple of 128 up to 640 and alphabet_size 1 ... 8192 (padded inside to chunks of 32 symbols that take no part).
+ * joint_dtype carries no flag bits.  workspace: get_rnnt_greedy_workspace_size(maxT, minibatch, ...) bytes, 256-byte aligned,
+ * owned by one decode from its begin to its last step.  Neither entry point synchronises the host.
+ */
+RNNT_API rnntStatus_t get_rnnt_greedy_workspace_size(int maxT, int minibatch, int joint_size, int alphabet_size, int joint_dtype,
+                                                     size_t *size_bytes);
+
+RNNT_API rnntStatus_t compute_rnnt_greedy_begin(const float *enc_proj, const int *frame_lengths, const int *max_symbols,
+                                                const float *W2, const float *b2, int joint_size, int alphabet_size,
+                                                int minibatch, int max_per_frame, int joint_dtype, void *workspace,
+                                                rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_greedy_step(const float *pred_proj, int *hyps, int max_hyp_len, int *hyp_lengths,
+                                               float *scores, int *emitted, int *all_done, float *logit_stats,
+                                               int joint_size, int alphabet_size, int minibatch, int joint_dtype,
+                                               void *workspace, rnntOptions options);
+
 #ifdef __cplusplus
 }
 #endif

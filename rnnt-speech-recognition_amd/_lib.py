@@ -35,6 +35,9 @@ SYMBOLS = [
     "compute_rnnt_joint_net_loss",
     "compute_rnnt_joint_net_loss_fwd",
     "compute_rnnt_joint_net_loss_bwd",
+    "get_rnnt_greedy_workspace_size",
+    "compute_rnnt_greedy_begin",
+    "compute_rnnt_greedy_step",
 ]
 
 
@@ -121,6 +124,13 @@ def load():
         lib.compute_rnnt_joint_net_loss_fwd.argtypes = [vp] * 9 + [ci] * 4 + [vp, ci, vp, rnntOptions]
         lib.compute_rnnt_joint_net_loss_bwd.restype = ci
         lib.compute_rnnt_joint_net_loss_bwd.argtypes = [vp] * 10 + [ci] * 4 + [vp] * 6 + [ci, vp, rnntOptions]
+    if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "compute_rnnt_greedy_step"):
+        lib.get_rnnt_greedy_workspace_size.restype = ci
+        lib.get_rnnt_greedy_workspace_size.argtypes = [ci] * 5 + [ctypes.POINTER(ctypes.c_size_t)]
+        lib.compute_rnnt_greedy_begin.restype = ci
+        lib.compute_rnnt_greedy_begin.argtypes = [vp] * 5 + [ci] * 5 + [vp, rnntOptions]
+        lib.compute_rnnt_greedy_step.restype = ci
+        lib.compute_rnnt_greedy_step.argtypes = [vp, vp, ci] + [vp] * 5 + [ci] * 4 + [vp, rnntOptions]
     _lib = lib
     return lib
 
@@ -156,6 +166,13 @@ def joint_net_workspace_bytes(maxT: int, maxU: int, minibatch: int, hidden_size:
     n = ctypes.c_size_t(0)
     check(load().get_joint_net_workspace_size(maxT, maxU, minibatch, hidden_size, joint_size, alphabet_size, ctypes.byref(n)),
           "get_joint_net_workspace_size")
+    return int(n.value)
+
+
+def greedy_workspace_bytes(maxT: int, minibatch: int, joint_size: int, alphabet_size: int, joint_dtype: int) -> int:
+    n = ctypes.c_size_t(0)
+    check(load().get_rnnt_greedy_workspace_size(maxT, minibatch, joint_size, alphabet_size, joint_dtype, ctypes.byref(n)),
+          "get_rnnt_greedy_workspace_size")
     return int(n.value)
 
 

@@ -1,0 +1,438 @@
+// greedy_kernels.hip -- batched greedy transducer decoding (utils/decoding.py:21-108 for every utterance of a batch at once).
+//
+// One decode step evaluates the joint for ONE lattice cell per hypothesis -- frame t_b of utterance b against the prediction
+// network's current output -- takes the argmax, and moves the hypothesis on.  Per step, for every hypothesis that is not done:
+//   step    (greedy_step_kernel<DT>)  h = tanh(enc_proj[b, t_b] + pred_proj[b]) built straight into the MFMA B-operand image in
+//           LDS (32 hypotheses = the 32 columns of v_mfma_f32_32x32x16_f16), logits^T = W2^T . h^T chunk by chunk of 32
+//           symbols; epilogue per hypothesis: max logit, argmax (lowest index on ties), sum of exps against the max.  A workgroup
+//           owns a fixed slice of the vocabulary (four chunks, one per wave) for every step: W2 is read once per hypothesis
+//           tile and step, and the slice a workgroup streams is the same every step.  Out: one partial (max, argmax, sum) per
+//           (slice, hypothesis).  Nothing of size [B x V] is written.
+//   update  (greedy_update_kernel)  one workgroup: the partials of each hypothesis -> (argmax, max, logsumexp) in float64, the
+//           state update (emit / advance the frame / done), the all-done word.  A second launch: the kernel boundary makes the
+//           partials visible (no inter-workgroup protocol; DESIGN.md "Batched greedy decoding").
+// prepare (greedy_begin_kernel, greedy_w2_f16_kernel or joint_prep_kernel via launch_joint_w2_image), once per decode: e^{2x}
+//           tables of enc_proj for all frames, a raw copy of it (the direct-tanh route), the per-frame table-range flag, the W2
+//           operand image and bias tables, the per-hypothesis state.
+//
+// Arithmetic: the (argmax, max logit) pair of a hypothesis is bitwise what compute_rnnt_joint_logits computes for that
+// hypothesis alone (minibatch = maxT = maxU = 1): the same h (rnnt_joint_math.h), the same operand roundings and W2 scale, the
+// same MFMA chains in the same K order, the same epilogue arithmetic:
+//   DT 1  f16 joint (jh_logits_kernel MODE 3): h, W2 rounded to binary16; even k-steps into one accumulator, odd ones into a
+//         second, summed; logit = fmaf(acc, log2 e, b2 log2 e) ln 2.
+//   DT 0  f32-grade joint, J <= 640 (joint_fwd_kernel): r = (1 - h) / 2 (or h itself when max |W2| > kRFormLimit) and s2 W2 split
+//         into binary16 hi + lo; three MFMAs per k-step in one chain; logit = fmaf(acc, m2inv, bh) + bl (b2s tables).
+//   DT 2  f32-grade joint, 640 < J <= 704 (joint_phase1s_kernel): h split into hi + lo as the A operand; logit = fmaf(acc, 1/s2, b2).
+// The call-wide route switches of those kernels are decided PER HYPOTHESIS here: the direct-tanh route (some |x| beyond
+// kExpTabLimit) when this hypothesis's enc_proj row or pred_proj row leaves the table range -- exactly when the single-hypothesis
+// logits call would raise its flag.  The h / r form depends on W2 alone and is the same for every hypothesis.
+#include "rnnt_common.h"
+#include "rnnt_joint_math.h"
+
+#include <limits.h>
+#include <math.h>
+
+namespace rnnt {
+
+typedef _Float16 gf16;
+typedef _Float16 gh8 __attribute__((ext_vector_type(8)));
+typedef float gf32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kGrWaves = 4;  // waves per step workgroup: wave w of slice s takes vocabulary chunk kGrWaves s + w
+
+// per-hypothesis decoder state (workspace)
+struct GreedyState {
+    int t;       // current frame
+    int n;       // symbols emitted
+    int nf;      // symbols emitted at the current frame
+    int done;    // 1: t >= Tb or n >= maxsym
+    int Tb;      // frames of the utterance (clamped to [0, maxT])
+    int maxsym;  // symbol budget (clamped to >= 0; INT_MAX: none)
+    int cap;     // symbols per frame at most (<= 0: no cap)
+    int pad;
+    double score;  // sum of the log-softmax of every decision taken
+};
+
+struct GreedyArgs {
+    const float *enc_proj, *W2, *b2;
+    const int *frame_lengths, *max_symbols;
+    const float *pred_proj;
+    int *hyps, *hyp_lengths, *emitted, *all_done;
+    float *scores, *stats;
+    GreedyState *st;
+    float *part_m, *part_s;
+    int *part_i;
+    int *rowflag;      // [B][T] 1: some |enc_proj| of the row beyond kExpTabLimit (or NaN)
+    float *expE;       // [B][T][J] e^{2 enc_proj}
+    float *encraw;     // [B][T][J] enc_proj (the direct-tanh route)
+    gf16 *img;         // W2 operand image: DT 1 [NC][J/16][2][32][8] binary16; DT 0 / 2 joint_prep_kernel's W2s
+    float *btab;       // DT 1: b2 log2 e [NC 32]; DT 2: b2 [32]
+    const float *tflag;  // DT 0 / 2: joint_prep_kernel's flag words (+ 64: b2s)
+    int B, T, J, V, NC, NS, blank, max_per_frame, max_hyp_len;
+};
+
+// ---------------------------------------------------------------------------------------------
+// prepare
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void greedy_begin_kernel(const GreedyArgs a) {
+    const int J = a.J, rows = a.B * a.T;
+    for (int r = blockIdx.x; r < rows; r += gridDim.x) {  // (block-uniform trip count: the barrier below is safe)
+        bool big = false;
+        const size_t base = (size_t)r * J;
+        for (int j = threadIdx.x; j < J; j += 256) {
+            const float x = a.enc_proj[base + j];
+            big |= exp_tab_out_of_range(x);  // also catches NaN
+            a.expE[base + j] = exp_tab(x);
+            a.encraw[base + j] = x;
+        }
+        big = __syncthreads_or(big);
+        if (threadIdx.x == 0) a.rowflag[r] = big ? 1 : 0;
+    }
+    if (blockIdx.x == 0) {
+        for (int b = threadIdx.x; b < a.B; b += 256) {
+            GreedyState s;
+            s.t = 0, s.n = 0, s.nf = 0;
+            s.Tb = min(max(a.frame_lengths[b], 0), a.T);  // out-of-range lengths: clamped into the tensor
+            s.maxsym = a.max_symbols ? max(a.max_symbols[b], 0) : INT_MAX;
+            s.done = (s.Tb == 0 || s.maxsym == 0) ? 1 : 0;
+            s.cap = a.max_per_frame, s.pad = 0;
+            s.score = 0.0;
+            a.st[b] = s;
+        }
+        if (a.b2 && a.btab)  // DT 2: the bias as joint_phase1s_kernel reads it
+            for (int v = threadIdx.x; v < a.V; v += 256) a.btab[v] = a.b2[v];
+    }
+}
+
+// DT 1: W2 -> binary16 in the A-fragment order of jh_prep_kernel's W2Tp (lane l of k-step ks holds W2[16 ks + 8 (l >> 5) + 0..7]
+// [32 vc + (l & 31)]), zero beyond V; b2 log2 e.  The same conversions as jh_prep_kernel.
+__global__ __launch_bounds__(256) void greedy_w2_f16_kernel(const float *W2, const float *b2, const int J, const int V, const int NC,
+                                                            gf16 *img, float *b2l) {
+    const size_t n = (size_t)NC * 32 * J;
+    const int KS = J >> 4;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const int e = (int)(i & 7), v31 = (int)((i >> 3) & 31), hf = (int)((i >> 8) & 1);
+        const size_t rest = i >> 9;
+        const int ks = (int)(rest % KS), vc = (int)(rest / KS);
+        const int j = 16 * ks + 8 * hf + e, v = 32 * vc + v31;
+        img[i] = (v < V) ? (gf16)W2[(size_t)j * V + v] : (gf16)0.0f;
+    }
+    for (int v = blockIdx.x * 256 + threadIdx.x; v < NC * 32; v += gridDim.x * 256) b2l[v] = (v < V) ? b2[v] * kLog2e : 0.f;
+}
+
+// ---------------------------------------------------------------------------------------------
+// step: grid (NS vocabulary slices, ceil(B / 32) hypothesis tiles), 4 waves.  LDS: the B-operand image of the tile's 32
+// hypotheses, [J/16 k-steps][64 lanes][8] binary16 (DT 0 / 2: hi, then lo).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ constexpr int gr_cdrow(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
+
+__device__ __forceinline__ bool gr_live(const GreedyState &s, const int max_hyp_len) {
+    return !s.done && s.n < min(s.maxsym, max_hyp_len);  // (a full hyps buffer pauses a hypothesis: greedy_update_kernel)
+}
+
+template <int DT>
+__global__ __launch_bounds__(kGrWaves * 64) void greedy_step_kernel(const GreedyArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int s_t[32], s_live[32], s_slow[32];
+    __shared__ float r_m[kGrWaves * 64], r_s[kGrWaves * 64];
+    __shared__ int r_i[kGrWaves * 64];
+    __shared__ float stage[DT == 2 ? 32 * 33 : 1];
+    const int J = a.J, KS = J >> 4;
+    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, n31 = lane & 31;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int slice = blockIdx.x, b0 = blockIdx.y * 32;
+
+    bool live = false;
+    if (tid < 32) {
+        const int b = b0 + tid;
+        int t = 0, slow = 0;
+        if (b < a.B) {
+            const GreedyState s = a.st[b];
+            live = gr_live(s, a.max_hyp_len);
+            t = min(max(s.t, 0), a.T - 1);
+            if (live) slow = a.rowflag[(size_t)b * a.T + t];
+        }
+        s_live[tid] = live ? 1 : 0, s_t[tid] = t, s_slow[tid] = slow;
+    }
+    if (!__syncthreads_or(live)) return;  // a tile of done hypotheses reads and writes nothing
+    {   // the pred-side half of the route switch: 8 threads per hypothesis scan its pred_proj row
+        const int n = tid >> 3, q = tid & 7;
+        bool big = false;
+        if (s_live[n])
+            for (int j = q; j < J; j += 8) big |= exp_tab_out_of_range(a.pred_proj[(size_t)(b0 + n) * J + j]);
+        if (big) s_slow[n] = 1;
+    }
+    __syncthreads();
+    // h (DT 1) or r / h split into hi + lo (DT 0 / 2), in B-fragment order: lane n + 32 half of k-step ks holds units
+    // 16 ks + 8 half + 0..7 of hypothesis n
+    gf16 *hA = (gf16 *)smem, *hL = hA + (size_t)J * 32;
+    const bool hform = DT == 0 && a.tflag[1] != 0.f;
+    for (int i = tid; i < 32 * J; i += kGrWaves * 64) {
+        const int n = i / J, j = i - n * J;
+        float x = 0.f;
+        if (s_live[n]) {
+            const size_t er = ((size_t)(b0 + n) * a.T + s_t[n]) * J + j;
+            const float pv = a.pred_proj[(size_t)(b0 + n) * J + j];
+            if (!s_slow[n]) {
+                const float ea = a.expE[er], ec = exp_tab(pv);
+                x = DT == 0 ? r_from_exp(ea, ec) : tanh_from_exp(ea, ec);
+            } else {
+                const float ev = a.encraw[er];
+                x = DT == 0 ? fast_r(ev + pv) : fast_tanh(ev + pv);
+            }
+            if (hform) x = fmaf(x, -2.0f, 1.0f);
+        }
+        const int off = (((j >> 4) * 64 + n + 32 * ((j >> 3) & 1)) << 3) + (j & 7);
+        const gf16 hi = (gf16)x;
+        hA[off] = hi;
+        if (DT != 1) hL[off] = (gf16)(x - (float)hi);  // exact residual in f32, then rounded: split_pair's hi / lo
+    }
+    __syncthreads();
+
+    // ---- this wave's chunk of 32 symbols
+    const int vc = slice * kGrWaves + wave;
+    float bm = -INFINITY, bs = 0.f;
+    int bi = INT_MAX;
+    if (vc < a.NC) {
+        gf32x16 acc;
+        const gh8 *hb = (const gh8 *)hA + lane, *hl = (const gh8 *)hL + lane;
+        if (DT == 1) {
+            const gh8 *w = (const gh8 *)a.img + (size_t)vc * KS * 64 + lane;
+            gf32x16 acc0, acc1;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc0[r] = 0.f, acc1[r] = 0.f;
+            for (int ks = 0; ks < KS; ks += 2) {
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[ks * 64], hb[ks * 64], acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[(ks + 1) * 64], hb[(ks + 1) * 64], acc1, 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = acc0[r] + acc1[r];
+        } else {
+            const gh8 *w = (const gh8 *)a.img + (size_t)vc * J * 8 + lane;  // tile vc: [J/16][hi, lo][64 lanes] fragments
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+            for (int ks = 0; ks < KS; ++ks) {
+                const gh8 wh = w[(2 * ks) * 64], wl = w[(2 * ks + 1) * 64], bh = hb[ks * 64], bl = hl[ks * 64];
+                if (DT == 0) {
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, bh, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, bl, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, bh, acc, 0, 0, 0);
+                } else {  // h as the A operand: D[hypothesis][symbol]
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, wh, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl, wh, acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, wl, acc, 0, 0, 0);
+                }
+            }
+        }
+        if (DT == 2) {  // transpose through LDS: afterwards lane n31 holds hypothesis n31, symbols gr_cdrow(r, half), as for DT 0 / 1
+#pragma unroll
+            for (int r = 0; r < 16; ++r) stage[gr_cdrow(r, half) * 33 + n31] = acc[r];
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (one wave: its LDS operations complete in order)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = stage[n31 * 33 + gr_cdrow(r, half)];
+        }
+        // epilogue: logits of this lane's hypothesis, in increasing symbol order
+        float m2inv = 0.f;
+        if (DT == 0) m2inv = hform ? a.tflag[2] : -2.0f * a.tflag[2];
+        const float w2inv = DT == 2 ? a.tflag[2] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int vv = gr_cdrow(r, half), v = 32 * vc + vv;
+            float l;
+            if (DT == 1) l = fmaf(acc[r], kLog2e, a.btab[v]) * kLn2;
+            else if (DT == 0) l = fmaf(acc[r], m2inv, a.tflag[64 + 64 * vc + vv]) + a.tflag[64 + 64 * vc + 32 + vv];
+            else l = fmaf(acc[r], w2inv, a.btab[v]);
+            if (v < a.V) {  // padding columns take no part
+                if (l > bm) {
+                    bs = fmaf(bs, __builtin_amdgcn_exp2f((bm - l) * kLog2e), 1.0f);
+                    bm = l, bi = v;
+                } else {
+                    bs += __builtin_amdgcn_exp2f((l - bm) * kLog2e);
+                }
+            }
+        }
+    }
+    r_m[tid] = bm, r_s[tid] = bs, r_i[tid] = bi;
+    __syncthreads();
+    if (tid < 32 && s_live[tid]) {  // the 2 kGrWaves partials of hypothesis tid, in a fixed order
+        float M = -INFINITY;
+        int k = INT_MAX;
+        for (int q = 0; q < 2 * kGrWaves; ++q) {
+            const int src = (q >> 1) * 64 + tid + 32 * (q & 1);
+            if (r_m[src] > M || (r_m[src] == M && r_i[src] < k)) M = r_m[src], k = r_i[src];
+        }
+        float S = 0.f;
+        for (int q = 0; q < 2 * kGrWaves; ++q) {
+            const int src = (q >> 1) * 64 + tid + 32 * (q & 1);
+            if (r_s[src] > 0.f) S += r_s[src] * __builtin_amdgcn_exp2f((r_m[src] - M) * kLog2e);
+        }
+        const size_t o = (size_t)slice * a.B + b0 + tid;
+        a.part_m[o] = M, a.part_s[o] = S, a.part_i[o] = k;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// update: one workgroup over all hypotheses
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void greedy_update_kernel(const GreedyArgs a) {
+    bool running = false, paused = false;
+    for (int b = threadIdx.x; b < a.B; b += 256) {
+        GreedyState s = a.st[b];
+        int em = -1;
+        if (gr_live(s, a.max_hyp_len)) {
+            float M = -INFINITY;
+            int k = INT_MAX;
+            for (int q = 0; q < a.NS; ++q) {
+                const float m = a.part_m[(size_t)q * a.B + b];
+                const int i = a.part_i[(size_t)q * a.B + b];
+                if (m > M || (m == M && i < k)) M = m, k = i;
+            }
+            double S = 0.0;
+            for (int q = 0; q < a.NS; ++q) {
+                const float ps = a.part_s[(size_t)q * a.B + b];
+                if (ps > 0.f) S += (double)ps * exp((double)a.part_m[(size_t)q * a.B + b] - (double)M);
+            }
+            const double lse = (double)M + log(S);
+            if (a.stats) a.stats[2 * b] = M, a.stats[2 * b + 1] = (float)lse;
+            s.score += (double)M - lse;
+            if (k == a.blank || k >= a.V) {  // blank (or no finite logit at all): next frame
+                s.t += 1, s.nf = 0;
+            } else {
+                a.hyps[(size_t)b * a.max_hyp_len + s.n] = k;
+                s.n += 1, s.nf += 1, em = k;
+                if (s.cap > 0 && s.nf >= s.cap) s.t += 1, s.nf = 0;
+            }
+            if (s.t >= s.Tb || s.n >= s.maxsym) s.done = 1;
+            a.st[b] = s;
+        }
+        a.emitted[b] = em;
+        a.hyp_lengths[b] = s.n;
+        a.scores[b] = (float)s.score;
+        if (!s.done) {
+            if (s.n < a.max_hyp_len) running = true;
+            else paused = true;
+        }
+    }
+    const int any_running = __syncthreads_or(running), any_paused = __syncthreads_or(paused);
+    if (threadIdx.x == 0) a.all_done[0] = any_running ? 0 : (any_paused ? 2 : 1);
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+bool joint_dtype_supported(int joint_dtype, int J, int V);
+size_t joint_w2_image_bytes(int J, int V);
+hipError_t launch_joint_w2_image(const float *W2, const float *b2, int J, int V, float *tflag, void *W2s, hipStream_t s);
+
+struct GreedyLayout {
+    size_t st, pm, ps, pi, rowflag, expE, encraw, img, btab, tflag, total;
+    int NC, NS, DT;
+};
+
+// DT of the step kernel for (joint_dtype, J, V), or -1 when the shape is not taken: joint_dtype 0 on the shapes of the f32-grade
+// joint (joint_dtype_supported), joint_dtype 1 on J a multiple of 128 up to 640 and 1 <= V <= 8192 (the vocabulary is padded to
+// whole chunks of 32 inside the image; the padding takes no part)
+static int greedy_dt(int joint_dtype, int J, int V) {
+    if (joint_dtype == 0) return joint_dtype_supported(0, J, V) ? (J > 640 ? 2 : 0) : -1;
+    if (joint_dtype == 1) return (J >= 128 && J <= 640 && J % 128 == 0 && V >= 1 && V <= 8192) ? 1 : -1;
+    return -1;
+}
+
+static bool make_greedy_layout(int T, int B, int J, int V, int joint_dtype, GreedyLayout &L) {
+    L.DT = greedy_dt(joint_dtype, J, V);
+    if (L.DT < 0 || T <= 0 || B <= 0) return false;
+    if ((unsigned long long)B * T * J >= (1ull << 31)) return false;
+    L.NC = (V + 31) / 32;
+    L.NS = (L.NC + kGrWaves - 1) / kGrWaves;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + bytes, 256);
+        return o;
+    };
+    L.st = take((size_t)B * sizeof(GreedyState));
+    L.pm = take((size_t)L.NS * B * sizeof(float));
+    L.ps = take((size_t)L.NS * B * sizeof(float));
+    L.pi = take((size_t)L.NS * B * sizeof(int));
+    L.rowflag = take((size_t)B * T * sizeof(int));
+    L.expE = take((size_t)B * T * J * sizeof(float));
+    L.encraw = take((size_t)B * T * J * sizeof(float));
+    L.img = take(L.DT == 1 ? (size_t)L.NC * 32 * J * sizeof(gf16) : joint_w2_image_bytes(J, V));
+    L.btab = take((size_t)L.NC * 32 * sizeof(float));
+    L.tflag = take(256 + 1024);  // joint_prep_kernel's flag words + b2s (64 words per tile, up to 4 tiles)
+    L.total = off;
+    return true;
+}
+
+static void greedy_bind(GreedyArgs &a, const GreedyLayout &L, void *workspace) {
+    char *ws = (char *)workspace;
+    a.st = (GreedyState *)(ws + L.st);
+    a.part_m = (float *)(ws + L.pm), a.part_s = (float *)(ws + L.ps), a.part_i = (int *)(ws + L.pi);
+    a.rowflag = (int *)(ws + L.rowflag);
+    a.expE = (float *)(ws + L.expE), a.encraw = (float *)(ws + L.encraw);
+    a.img = (gf16 *)(ws + L.img), a.btab = (float *)(ws + L.btab), a.tflag = (const float *)(ws + L.tflag);
+    a.NC = L.NC, a.NS = L.NS;
+}
+
+hipError_t greedy_workspace_bytes(int T, int B, int J, int V, int joint_dtype, size_t *bytes) {
+    GreedyLayout L;
+    if (!make_greedy_layout(T, B, J, V, joint_dtype, L)) return hipErrorInvalidValue;
+    *bytes = L.total;
+    return hipSuccess;
+}
+
+hipError_t launch_greedy_begin(const float *enc_proj, const int *frame_lengths, const int *max_symbols, const float *W2,
+                               const float *b2, int J, int V, int B, int T, int max_per_frame, int joint_dtype, void *workspace,
+                               hipStream_t s) {
+    GreedyLayout L;
+    if (!make_greedy_layout(T, B, J, V, joint_dtype, L)) return hipErrorInvalidValue;
+    GreedyArgs a = {};
+    greedy_bind(a, L, workspace);
+    a.enc_proj = enc_proj, a.frame_lengths = frame_lengths, a.max_symbols = max_symbols;
+    a.B = B, a.T = T, a.J = J, a.V = V, a.max_per_frame = max_per_frame;
+    a.b2 = L.DT == 2 ? b2 : nullptr;
+    hipError_t e;
+    if (L.DT == 1) {
+        const size_t n = (size_t)L.NC * 32 * J;
+        const unsigned grid = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+        hipLaunchKernelGGL(greedy_w2_f16_kernel, dim3(grid), dim3(256), 0, s, W2, b2, J, V, L.NC, a.img, a.btab);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    } else if ((e = launch_joint_w2_image(W2, b2, J, V, (float *)a.tflag, a.img, s)) != hipSuccess) {
+        return e;
+    }
+    const int rows = B * T;
+    hipLaunchKernelGGL(greedy_begin_kernel, dim3(rows < 2048 ? rows : 2048), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+template <int DT>
+static hipError_t launch_step_dt(const GreedyArgs &a, size_t shm, hipStream_t s) {
+    if (shm > 65536) {
+        const hipError_t e = hipFuncSetAttribute((const void *)greedy_step_kernel<DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(greedy_step_kernel<DT>, dim3(a.NS, (a.B + 31) / 32), dim3(kGrWaves * 64), shm, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_greedy_step(const float *pred_proj, int *hyps, int max_hyp_len, int *hyp_lengths, float *scores, int *emitted,
+                              int *all_done, float *stats, int J, int V, int B, int T, int blank, int joint_dtype, void *workspace,
+                              hipStream_t s) {
+    GreedyLayout L;
+    if (!make_greedy_layout(T, B, J, V, joint_dtype, L)) return hipErrorInvalidValue;
+    GreedyArgs a = {};
+    greedy_bind(a, L, workspace);
+    a.pred_proj = pred_proj, a.hyps = hyps, a.hyp_lengths = hyp_lengths, a.scores = scores, a.emitted = emitted;
+    a.all_done = all_done, a.stats = stats;
+    a.B = B, a.T = T, a.J = J, a.V = V, a.blank = blank, a.max_hyp_len = max_hyp_len;
+    hipError_t e;
+    const size_t shm = (size_t)J * 32 * sizeof(gf16) * (L.DT == 1 ? 1 : 2);
+    if (L.DT == 1) e = launch_step_dt<1>(a, shm, s);
+    else if (L.DT == 0) e = launch_step_dt<0>(a, shm, s);
+    else e = launch_step_dt<2>(a, shm, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(greedy_update_kernel, dim3(1), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace rnnt

@@ -36,6 +36,7 @@
 //   ds_read_b64_tr_b16: lane p of 16-lane group g supplies &X[k0 + (p>>2)][n0 + 4*(p&3)] and receives X[k0+0..3][n0+p].
 #include "rnnt_common.h"
 #include "rnnt_cell.h"
+#include "rnnt_joint_math.h"
 
 #include <math.h>
 #ifdef JH_TRACE
@@ -58,15 +59,10 @@ typedef __attribute__((address_space(3))) s4 lds_s4;
 
 __device__ __forceinline__ float hex2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ float hlg2(float x) { return __builtin_amdgcn_logf(x); }
-__device__ __forceinline__ float htanh(float x) {
-    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + hex2(x * 2.8853900817779268f));
-}
-// tanh(a + c) from the tabulated factors ea = e^{2a}, ec = e^{2c}: one multiply-add, one reciprocal, one multiply-add.
-// Exact to ~1e-7 absolute while |a|, |c| <= kExpTabLimit (both factors normal f32 numbers; an overflowing product gives +1,
-// an underflowing one -1, as tanh does).  Beyond that limit the prep kernel raises a flag and the kernels use htanh(a + c).
-__device__ __forceinline__ float htanh2(float ea, float ec) {
-    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(fmaf(ea, ec, 1.0f));
-}
+__device__ __forceinline__ float htanh(float x) { return fast_tanh(x); }
+// tanh(a + c) from the tabulated factors ea = e^{2a}, ec = e^{2c} (rnnt_joint_math.h tanh_from_exp).
+// Beyond kExpTabLimit the prep kernel raises a flag and the kernels use htanh(a + c).
+__device__ __forceinline__ float htanh2(float ea, float ec) { return tanh_from_exp(ea, ec); }
 __device__ __forceinline__ constexpr int cdrow(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void wait_lgkm() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }

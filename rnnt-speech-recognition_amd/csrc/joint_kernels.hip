@@ -30,6 +30,7 @@
 #include "rnnt_common.h"
 #include "rnnt_cell.h"
 #include "rnnt_redo.h"
+#include "rnnt_joint_math.h"
 
 #include <math.h>
 #ifdef JH_TRACE
@@ -48,21 +49,7 @@ typedef __attribute__((address_space(1))) const void jglb_cvoid;
 
 __device__ __forceinline__ float jex2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ float jlg2(float x) { return __builtin_amdgcn_logf(x); }
-// tanh(x) = 1 - 2/(1+e^{2x}); saturates correctly at +-inf, absolute error ~1e-7
-__device__ __forceinline__ float fast_tanh(float x) {
-    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + jex2(x * 2.8853900817779268f));
-}
-// tanh(a + c) from the tabulated factors ea = e^{2a}, ec = e^{2c} (joint_prep_kernel): one multiply-add, one reciprocal,
-// one multiply-add instead of an exponential and a reciprocal.  Exact to ~1e-7 while |a|, |c| <= kExpTabLimit (both
-// factors are normal f32 numbers; an overflowing product gives +1, an underflowing one -1, like tanh).  Beyond that
-// the prep kernel raises a flag and the kernels evaluate fast_tanh(a + c) on the raw projections.
-__device__ __forceinline__ float tanh_from_exp(float ea, float ec) {
-    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(fmaf(ea, ec, 1.0f));
-}
-// r = (1 - tanh(a + c)) / 2 = 1 / (1 + e^{2(a + c)}), the quantity joint_fwd_kernel puts on the matrix units (same tables, same
-// saturation behaviour: 0 for an overflowing product, 1 for an underflowing one)
-__device__ __forceinline__ float r_from_exp(float ea, float ec) { return __builtin_amdgcn_rcpf(fmaf(ea, ec, 1.0f)); }
-__device__ __forceinline__ float fast_r(float x) { return __builtin_amdgcn_rcpf(1.0f + jex2(x * 2.8853900817779268f)); }
+// fast_tanh, tanh_from_exp, r_from_exp, fast_r: rnnt_joint_math.h
 // row of the 32x32 MFMA C/D tile held in register `reg` of a lane in half `half` (= lane >> 5)
 __device__ __forceinline__ constexpr int cd_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
@@ -2603,6 +2590,24 @@ hipError_t launch_joint_loss(const float *enc_proj, const float *pred_proj, cons
         }
     }
 #endif
+    return hipGetLastError();
+}
+
+// The W2 operand image of the forward kernels alone, for a caller that runs the J x V products in kernels of its own (the greedy
+// decoder's step kernel, greedy_kernels.hip): joint_prep_kernel on an empty lattice writes the fragment image W2s (s2 W2 as
+// binary16 hi + lo parts, per vocabulary tile), tflag[1] (h / r form), tflag[2] (1 / s2) and the bias tables b2s = tflag + 64 --
+// the same words compute_rnnt_joint_logits computes its logits from.  tflag: 64 + 64 kMaxVT floats; W2s: joint_w2_image_bytes.
+size_t joint_w2_image_bytes(int J, int V) { return (size_t)((V + 31) / 32) * (size_t)J * 64 * sizeof(jf16); }
+hipError_t launch_joint_w2_image(const float *W2, const float *b2, int J, int V, float *tflag, void *W2s, hipStream_t s) {
+    if (!joint_supported(J, V)) return hipErrorInvalidValue;
+    JointParams jp = {};
+    jp.lp.V = V, jp.lp.B = 0, jp.lp.T = 1, jp.lp.U = 1;  // no lattice: no e^{2x} tables, no flag from the projections
+    jp.W2 = W2, jp.b2 = b2, jp.J = J;
+    jp.VT = (V + 31) / 32, jp.vt = 0;
+    jp.tflag = tflag, jp.b2s = tflag + 64, jp.W2s = (jf16 *)W2s;
+    hipError_t e;
+    if ((e = launch_fill(tflag, 0, 256, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(joint_prep_kernel, dim3(1024), dim3(256), 0, s, jp);
     return hipGetLastError();
 }
 

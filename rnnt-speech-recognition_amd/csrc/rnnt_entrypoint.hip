@@ -39,6 +39,14 @@ hipError_t launch_joint_logits(const float *enc_proj, const float *pred_proj, co
 hipError_t joint_f16_workspace_bytes(int T, int U, int B, int J, int V, size_t *bytes);
 hipError_t launch_joint_logits_f16(const float *enc_proj, const float *pred_proj, const float *W2, const float *b2, int J, int V,
                                    int B, int T, int U, float *logits, void *workspace, hipStream_t s);
+// greedy_kernels.hip (batched greedy decoding)
+hipError_t greedy_workspace_bytes(int T, int B, int J, int V, int joint_dtype, size_t *bytes);
+hipError_t launch_greedy_begin(const float *enc_proj, const int *frame_lengths, const int *max_symbols, const float *W2,
+                               const float *b2, int J, int V, int B, int T, int max_per_frame, int joint_dtype, void *workspace,
+                               hipStream_t s);
+hipError_t launch_greedy_step(const float *pred_proj, int *hyps, int max_hyp_len, int *hyp_lengths, float *scores, int *emitted,
+                              int *all_done, float *stats, int J, int V, int B, int T, int blank, int joint_dtype, void *workspace,
+                              hipStream_t s);
 }  // namespace rnnt
 
 static rnntStatus_t check_options(const rnntOptions &o) {
@@ -477,6 +485,52 @@ rnntStatus_t compute_rnnt_joint_net_logits(const float *enc, const float *pred, 
     if (joint_dtype == 1)
         return from_hip(launch_joint_logits_f16(ep, pp, W2, b2, joint_size, alphabet_size, B, T, U, logits, workspace, s));
     return from_hip(launch_joint_logits(ep, pp, W2, b2, joint_size, alphabet_size, B, T, U, logits, workspace, s));
+}
+
+
+// Batched greedy decoding (include/rnnt.h).  Everything is checked before anything is enqueued.
+static rnntStatus_t check_greedy(int maxT, int joint_size, int alphabet_size, int minibatch, int joint_dtype, const rnntOptions &o) {
+    if (joint_size <= 0 || alphabet_size <= 0 || minibatch <= 0 || maxT <= 0) return RNNT_STATUS_INVALID_VALUE;
+    if (joint_dtype != 0 && joint_dtype != 1) return RNNT_STATUS_INVALID_VALUE;  // (RNNT_VISIT_ALL means nothing here: refused)
+    const rnntStatus_t st = check_options(o);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (o.blank_label >= alphabet_size) return RNNT_STATUS_INVALID_VALUE;
+    size_t n = 0;
+    if (greedy_workspace_bytes(maxT, minibatch, joint_size, alphabet_size, joint_dtype, &n) != hipSuccess) return RNNT_STATUS_INVALID_VALUE;
+    return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t get_rnnt_greedy_workspace_size(int maxT, int minibatch, int joint_size, int alphabet_size, int joint_dtype,
+                                            size_t *size_bytes) {
+    if (!size_bytes) return RNNT_STATUS_INVALID_VALUE;
+    if (joint_dtype != 0 && joint_dtype != 1) return RNNT_STATUS_INVALID_VALUE;
+    return greedy_workspace_bytes(maxT, minibatch, joint_size, alphabet_size, joint_dtype, size_bytes) == hipSuccess
+               ? RNNT_STATUS_SUCCESS
+               : RNNT_STATUS_INVALID_VALUE;
+}
+
+rnntStatus_t compute_rnnt_greedy_begin(const float *enc_proj, const int *frame_lengths, const int *max_symbols, const float *W2,
+                                       const float *b2, int joint_size, int alphabet_size, int minibatch, int max_per_frame,
+                                       int joint_dtype, void *workspace, rnntOptions options) {
+    if (!enc_proj || !frame_lengths || !W2 || !b2 || !workspace) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_greedy(options.maxT, joint_size, alphabet_size, minibatch, joint_dtype, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
+    return from_hip(launch_greedy_begin(enc_proj, frame_lengths, max_symbols, W2, b2, joint_size, alphabet_size, minibatch,
+                                        options.maxT, max_per_frame, joint_dtype, workspace, (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_greedy_step(const float *pred_proj, int *hyps, int max_hyp_len, int *hyp_lengths, float *scores,
+                                      int *emitted, int *all_done, float *logit_stats, int joint_size, int alphabet_size,
+                                      int minibatch, int joint_dtype, void *workspace, rnntOptions options) {
+    if (!pred_proj || !hyps || !hyp_lengths || !scores || !emitted || !all_done || !workspace) return RNNT_STATUS_INVALID_VALUE;
+    if (max_hyp_len <= 0 || (long long)max_hyp_len * minibatch >= (1ll << 31)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_greedy(options.maxT, joint_size, alphabet_size, minibatch, joint_dtype, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
+    return from_hip(launch_greedy_step(pred_proj, hyps, max_hyp_len, hyp_lengths, scores, emitted, all_done, logit_stats, joint_size,
+                                       alphabet_size, minibatch, options.maxT, options.blank_label, joint_dtype, workspace,
+                                       (hipStream_t)options.stream));
 }
 
 }  // extern "C"

@@ -12,12 +12,19 @@ the reference's formulation (used by the tests as the cross-check).
 
 The joint is evaluated for ONE lattice cell at a time (T = U = 1), as the reference does (`joint`, utils/decoding.py:6-18).
 On the device it goes through the engine's logits-only entry point (compute_rnnt_joint_logits via JointLoss.cell_logits):
-the forward kernels of the fused loss, so the decoder sees the logits the loss was trained on."""
+the forward kernels of the fused loss, so the decoder sees the logits the loss was trained on.
+
+greedy_decode_batch decodes EVERY utterance of a batch with the same per-utterance semantics: one decode step per decision
+for all hypotheses at once, the joint + argmax + state update in one library call (compute_rnnt_greedy_step), no host sync
+per step."""
 from __future__ import annotations
 
 from typing import List, Optional
 
 import torch
+
+from .joint import GreedyJoint
+from .loss import reduced_lengths
 
 
 @torch.no_grad()
@@ -72,4 +79,115 @@ def greedy_decode_fn(model):
     """The reference's factory shape: greedy_decode_fn(model, hparams) -> fn(inputs, max_length)."""
     def fn(inputs: torch.Tensor, max_length: Optional[int] = None) -> torch.Tensor:
         return greedy_decode(model, inputs, max_length)
+    return fn
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Batched greedy decoding
+# ---------------------------------------------------------------------------------------------------------------------------
+CHECK_EVERY = 32  # decode steps between two reads of the all-done word (the only host reads of the loop)
+_WORKSPACES = {}  # (device, stream) -> the greedy workspace of the last decode there
+LAST_STEPS = 0    # decode steps the last greedy_decode_batch / greedy_search_batch took (timing tools)
+
+
+def read_flag(x: torch.Tensor) -> int:
+    """The loop's one host read (the all-done word, or a length bound), with torch's sync debug mode lowered around it."""
+    mode = torch.cuda.get_sync_debug_mode() if x.is_cuda else 0
+    if mode:
+        torch.cuda.set_sync_debug_mode(0)
+    try:
+        return int(x.reshape(-1)[0].item())
+    finally:
+        if mode:
+            torch.cuda.set_sync_debug_mode(mode)
+
+
+def _pred_step(pred_net, tokens: torch.Tensor, states):
+    """One symbol through the prediction network for every row: tokens [B] -> (output [B, H], new states)."""
+    y = pred_net.embed(tokens.long()[:, None])
+    new = []
+    for blk, st in zip(pred_net.blocks, states):
+        y, hc = blk.lstm(y, st)
+        y = blk.norm(blk.drop(y))
+        new.append(hc)
+    return y[:, 0, :], new
+
+
+@torch.no_grad()
+def greedy_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, max_length=None,
+                        max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY):
+    """Greedy search over encoder outputs enc [B, T', H] with frame_lengths [B] (the model in eval mode).  See greedy_decode_batch."""
+    global LAST_STEPS
+    B, T = enc.shape[0], enc.shape[1]
+    dev = enc.device
+    if max_length is None:
+        maxsym, N = None, T + 16  # no bound (the reference's): the buffer grows when a hypothesis fills it
+    elif isinstance(max_length, torch.Tensor):
+        maxsym = max_length.to(device=dev, dtype=torch.int32).reshape(B)
+        N = max(1, read_flag(maxsym.max().reshape(1)))
+    else:
+        maxsym = torch.full((B,), int(max_length), dtype=torch.int32, device=dev)
+        N = max(1, int(max_length))
+    jg = GreedyJoint(model.joint)  # (the current weights: a model may be trained between two decodes)
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream) if enc.is_cuda else None
+    jg._ws = _WORKSPACES.get(key)  # the workspace of the last decode on this stream, when it is large enough
+    jg.begin(enc, frame_lengths, maxsym, int(max_symbols_per_frame or 0), N)
+    if jg._ws is not None:
+        _WORKSPACES[key] = jg._ws
+    pred_net = model.prediction
+    g, states = _pred_step(pred_net, torch.zeros(B, dtype=torch.int32, device=dev), [None] * len(pred_net.blocks))
+    steps = 0
+    while True:
+        emitted = jg.step(g)
+        steps += 1
+        if steps % check_every == 0:
+            flag = read_flag(jg.all_done)
+            if flag == 1:
+                break
+            if flag == 2:
+                jg.grow_hyps()
+        # rows that emitted a symbol advance their prediction network; the others keep their state
+        mask = emitted >= 0
+        g2, states2 = _pred_step(pred_net, emitted.clamp(min=0), states)
+        g = torch.where(mask[:, None], g2, g)
+        states = [(torch.where(mask[None, :, None], h2, h), torch.where(mask[None, :, None], c2, c))
+                  for (h2, c2), (h, c) in zip(states2, states)]
+    LAST_STEPS = steps
+    return jg.hyps, jg.lengths, jg.scores
+
+
+@torch.no_grad()
+def greedy_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[torch.Tensor] = None, max_length=None,
+                        max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY):
+    """Greedy decoding of EVERY utterance of a batch at once -> (ids int32 [B, N] zero-padded, lengths int32 [B], scores [B]).
+
+    Per utterance the semantics of greedy_decode (utils/decoding.py:21-108): the hypothesis starts from token 0, symbols are
+    emitted at a frame until the joint's argmax is joint.blank_label, then the next frame.  max_length (an int, or an int tensor
+    [B]) bounds the symbols of an utterance (max_length = 0: none; greedy_decode stops only after its first symbol there);
+    max_symbols_per_frame, when given, moves to the next frame after that many symbols at one frame (None: no cap, as the
+    reference).  spec_lengths are spectrogram frames, reduced as Transducer.loss reduces them; None: every frame of every row.
+    scores[b] = the sum of the log-softmax of every decision taken for utterance b (float32 on the engine; the model's dtype on
+    the torch route).
+
+    The prediction network steps all B rows at once (rows that emitted nothing keep their state), and on an MI355X the joint is
+    the library's greedy step (GreedyJoint): no host synchronisation per step -- the all-done word is read every
+    `check_every` steps (read_flag)."""
+    was_training = model.training
+    model.eval()
+    try:
+        enc = model.encoder(mel_specs)  # [B, T', H]
+        B, T = enc.shape[0], enc.shape[1]
+        if spec_lengths is None:
+            frames = torch.full((B,), T, dtype=torch.int32, device=enc.device)
+        else:
+            frames = reduced_lengths(spec_lengths.to(enc.device), model.hp.time_reduction_factor)
+        return greedy_search_batch(model, enc, frames, max_length, max_symbols_per_frame, check_every)
+    finally:
+        model.train(was_training)
+
+
+def greedy_decode_batch_fn(model):
+    """fn(inputs, max_length=None, spec_lengths=None) -> (ids, lengths, scores) of greedy_decode_batch."""
+    def fn(inputs: torch.Tensor, max_length=None, spec_lengths: Optional[torch.Tensor] = None):
+        return greedy_decode_batch(model, inputs, spec_lengths, max_length)
     return fn

@@ -382,3 +382,132 @@ class JointLoss(torch.nn.Module):
                 return self.logits(enc, pred)
             return joint_logits(enc, pred, self.W1, self.b1, self.W2, self.b2, reuse_buffers=reuse_buffers)
         return self.logits(enc, pred)
+
+
+class GreedyJoint:
+    """The joint of the batched greedy decoder (decoding.greedy_decode_batch): one lattice cell per hypothesis and step, argmax,
+    log-softmax of the decision and the decoder state in one pass.
+
+    On an MI355X this is the ENGINE (include/rnnt.h compute_rnnt_greedy_begin / _step): the object owns the workspace (reused by
+    the next decode when it is large enough) and the joint-unit padding of W1 / b1 / W2 (as joint_logits pads them; the vocabulary
+    needs none: the step kernel skips padding columns itself).  The first Dense layer runs through torch.matmul on both sides:
+    the encoder side once per decode, the prediction side once per step -- a [B, H] x [H, J] product, one hipBLASLt launch, where
+    the library's dense path would be a second entry point and a workspace round trip for B rows.  CPU tensors and shapes the
+    kernels do not take (joint sizes beyond 704 / 640) run the same state machine in torch on JointLoss.logits.
+
+    begin(enc [B, T, H], frame_lengths [B], max_symbols [B] or None, max_per_frame, max_hyp_len) allocates the outputs
+    (`hyps` [B, max_hyp_len] zero-filled, `lengths`, `scores`, `emitted`, `all_done`); step(pred [B, H]) advances every hypothesis
+    by one decision and returns `emitted` (the symbol per row, or -1).  all_done[0]: 0 running, 1 finished, 2 paused on a full
+    `hyps` buffer (grow_hyps() resumes them)."""
+
+    def __init__(self, joint: "JointLoss", joint_dtype: str = "auto"):
+        self.joint = joint
+        self.blank = int(joint.blank_label)
+        W1, b1, W2, b2 = (x.detach() for x in (joint.W1, joint.b1, joint.W2, joint.b2))
+        J, V = W2.shape
+        self.V = V
+        self.engine = W2.is_cuda
+        if self.engine:
+            if joint_dtype == "auto":
+                joint_dtype = _auto_joint_dtype(J, V)
+            try:
+                Jp, _ = padded_joint_shape(J, V, joint_dtype)
+            except ValueError:  # (the same rule as JointLoss.cell_logits)
+                self.engine = False
+        if self.engine:
+            self.dtype = JOINT_DTYPES[joint_dtype]
+            self.Jp = Jp
+            pad = lambda x, p: torch.nn.functional.pad(x.float(), p).contiguous()  # noqa: E731
+            self.W1, self.b1 = pad(W1, (0, Jp - J)), pad(b1, (0, Jp - J))
+            self.W2, self.b2 = pad(W2, (0, 0, 0, Jp - J)), b2.float().contiguous()
+        self._ws = None
+
+    # ---- engine
+    def begin(self, enc, frame_lengths, max_symbols, max_per_frame: int, max_hyp_len: int):
+        B, T = enc.shape[0], enc.shape[1]
+        dev = enc.device
+        self.B, self.T = B, T
+        self.hyps = torch.zeros(B, max_hyp_len, dtype=torch.int32, device=dev)
+        self.lengths = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.emitted = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        self.all_done = torch.zeros(1, dtype=torch.int32, device=dev)
+        frames = frame_lengths.to(device=dev, dtype=torch.int32)
+        maxsym = None if max_symbols is None else max_symbols.to(device=dev, dtype=torch.int32)
+        if not self.engine:
+            return self._torch_begin(enc, frames, maxsym, max_per_frame)
+        lib = _lib.load()
+        self.scores = torch.zeros(B, dtype=torch.float32, device=dev)
+        ep = (torch.matmul(enc.float(), self.W1) + self.b1).contiguous()
+        frames = frames.contiguous()
+        self._keep = (frames, maxsym.contiguous() if maxsym is not None else None)
+        with torch.cuda.device(dev):
+            nbytes = _lib.greedy_workspace_bytes(T, B, self.Jp, self.V, self.dtype)
+            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
+                self._ws = _new_workspace(nbytes, dev)
+            elif _WORKSPACE_FILL is not None:
+                self._ws.fill_(int(_WORKSPACE_FILL))
+            self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
+            ms = self._keep[1]
+            st = lib.compute_rnnt_greedy_begin(ep.data_ptr(), self._keep[0].data_ptr(), None if ms is None else ms.data_ptr(),
+                                               self.W2.data_ptr(), self.b2.data_ptr(), self.Jp, self.V, B, int(max_per_frame),
+                                               self.dtype, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_greedy_begin")
+
+    def step(self, pred, logit_stats=None):
+        """pred [B, H]: the prediction network's output of every row -> emitted [B] (int32, -1 where nothing was emitted)."""
+        if not self.engine:
+            return self._torch_step(pred)
+        pp = torch.matmul(pred.float(), self.W1).contiguous()
+        st = _lib.load().compute_rnnt_greedy_step(pp.data_ptr(), self.hyps.data_ptr(), self.hyps.shape[1], self.lengths.data_ptr(),
+                                                  self.scores.data_ptr(), self.emitted.data_ptr(), self.all_done.data_ptr(),
+                                                  None if logit_stats is None else logit_stats.data_ptr(), self.Jp, self.V, self.B,
+                                                  self.dtype, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_greedy_step")
+        return self.emitted
+
+    def grow_hyps(self):
+        """Double the hyps buffer (contents kept): paused hypotheses resume at the next step."""
+        h = self.hyps
+        self.hyps = torch.zeros(h.shape[0], 2 * h.shape[1], dtype=h.dtype, device=h.device)
+        self.hyps[:, : h.shape[1]] = h
+
+    # ---- torch composition: the same state machine (greedy_update_kernel) on JointLoss.logits
+    def _torch_begin(self, enc, frames, maxsym, max_per_frame):
+        B, T = enc.shape[0], enc.shape[1]
+        dev = enc.device
+        self._enc = enc
+        self.scores = torch.zeros(B, dtype=torch.promote_types(enc.dtype, torch.float32), device=dev)
+        self._Tb = frames.clamp(0, T).long()
+        self._maxsym = (torch.full((B,), 2**31 - 1, dtype=torch.long, device=dev) if maxsym is None else maxsym.clamp(min=0).long())
+        self._cap = int(max_per_frame)
+        self._t = torch.zeros(B, dtype=torch.long, device=dev)
+        self._n = torch.zeros(B, dtype=torch.long, device=dev)
+        self._nf = torch.zeros(B, dtype=torch.long, device=dev)
+        self._done = (self._Tb == 0) | (self._maxsym == 0)
+
+    def _torch_step(self, pred):
+        B, T, N = self.B, self.T, self.hyps.shape[1]
+        ar = torch.arange(B, device=pred.device)
+        live = ~self._done & (self._n < self._maxsym.clamp(max=N))
+        e = self._enc[ar, self._t.clamp(0, T - 1)]
+        logits = self.joint.logits(e[:, None, :], pred[:, None, :])[:, 0, 0, :]
+        k = torch.argmax(logits, dim=-1)
+        M = logits.gather(1, k[:, None])[:, 0]
+        lse = torch.logsumexp(logits, dim=-1)
+        self.scores = torch.where(live, self.scores + (M - lse).to(self.scores.dtype), self.scores)
+        emit = live & (k != self.blank)
+        pos = self._n.clamp(max=N - 1)[:, None]
+        self.hyps.scatter_(1, pos, torch.where(emit, k.to(torch.int32), self.hyps.gather(1, pos)[:, 0])[:, None])
+        self._n = self._n + emit.long()
+        self._nf = torch.where(emit, self._nf + 1, self._nf)
+        adv = live & ~emit  # blank: next frame
+        if self._cap > 0:  # per-frame cap reached: next frame too
+            adv = adv | (emit & (self._nf >= self._cap))
+        self._t = self._t + adv.long()
+        self._nf = torch.where(adv, torch.zeros_like(self._nf), self._nf)
+        self._done = self._done | (live & ((self._t >= self._Tb) | (self._n >= self._maxsym)))
+        self.lengths.copy_(self._n.to(torch.int32))
+        self.emitted.copy_(torch.where(emit, k, torch.full_like(k, -1)).to(torch.int32))
+        running, paused = ~self._done & (self._n < N), ~self._done & (self._n >= N)
+        self.all_done.copy_(torch.where(running.any(), 0, torch.where(paused.any(), 2, 1)).to(torch.int32).reshape(1))
+        return self.emitted

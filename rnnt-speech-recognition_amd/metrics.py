@@ -73,3 +73,30 @@ def build_wer_fn(decode_fn, idx_to_text: Callable):
         decoded = _as_list(decode_fn(inputs, max_length=len(first)))
         return token_error_rate(first, decoded, tok_fn=lambda t: t.split(" "), idx_to_text=idx_to_text)
     return WER
+
+
+def _batch_rates(decode_batch_fn, inputs, y_true, rate):
+    """Mean over ALL utterances of rate(y_true[b], decoded_b), each decode capped at len(y_true[b]) as build_accuracy_fn caps
+    the first one; decode_batch_fn(inputs, max_length=[B] tensor) -> (ids, lengths, scores) (decoding.greedy_decode_batch_fn)."""
+    import torch
+
+    truths = [_as_list(y_true[b]) for b in range(len(y_true))]
+    caps = torch.tensor([len(t) for t in truths], dtype=torch.int32)
+    ids, lengths, _ = decode_batch_fn(inputs, max_length=caps.to(inputs.device))
+    ids, lengths = ids.tolist(), lengths.tolist()
+    return sum(rate(truths[b], ids[b][: lengths[b]]) for b in range(len(truths))) / float(len(truths))
+
+
+def build_batch_accuracy_fn(decode_batch_fn):
+    """Accuracy(inputs, y_true) over every utterance of the batch: the mean of build_accuracy_fn's per-utterance rate."""
+    def Accuracy(inputs, y_true) -> float:
+        return _batch_rates(decode_batch_fn, inputs, y_true, lambda t, d: 1.0 - error_rate(t, d))
+    return Accuracy
+
+
+def build_batch_wer_fn(decode_batch_fn, idx_to_text: Callable):
+    """WER(inputs, y_true) over every utterance of the batch: the mean of build_wer_fn's per-utterance rate."""
+    def WER(inputs, y_true) -> float:
+        return _batch_rates(decode_batch_fn, inputs, y_true,
+                            lambda t, d: token_error_rate(t, d, tok_fn=lambda s: s.split(" "), idx_to_text=idx_to_text))
+    return WER
