@@ -172,12 +172,13 @@ RNNT_API rnntStatus_t compute_rnnt_loss_ex(const float *acts, float *grads, cons
 
 /* Build-only flag (no upstream counterpart): RNNT_VISIT_ALL switches the occupancy floor OFF -- the gradient kernels then visit
  * every lattice cell / row, as the reference's op and TensorFlow's autodiff do (run_rnnt.py:284), whatever the data.  Where the
- * floor applies (vocabularies above 60 symbols here; the backward of the fused joints below) a cell, or a lattice row of a
+ * floor applies (the op at every vocabulary size; the backward of the fused joints below) a cell, or a lattice row of a
  * 32-column tile, whose occupancy alpha.beta/L is at most 2^-50 (the op) / 2^-40 (the fused joints: see get_rnnt_joint_backward_rows)
  * gets exact zeros without its logits being read: results differ from the all-visited ones by less than 2^-44 |cost_scale| per
  * element (the op; the fused joints skip only what is an exact zero already) and run times follow the width of the alignment band.
  * The floor hides no NaN: the forward pass reads every cell, a NaN logit makes the utterance's lattice, cost and occupancies NaN,
- * and a NaN occupancy counts as occupied (tests/test_loss_gpu.py::test_occupancy_floor_and_its_opt_out).  The flag is there for
+ * and a NaN occupancy counts as occupied (tests/test_loss_gpu.py::test_occupancy_floor_and_its_opt_out above 60 symbols,
+ * tests/test_tile_floor_gpu.py at and below).  The range certificate of the linear lattice still runs on every skipped cell.  The flag is there for
  * parity debugging and for timing that does not depend on the data (bench.py reports both).
  *   compute_rnnt_loss_flags = compute_rnnt_loss_ex with `flags` (0 or RNNT_VISIT_ALL);  costs == NULL: the gradient pass alone
  *   (compute_rnnt_loss_bwd), grads == NULL: the forward alone.

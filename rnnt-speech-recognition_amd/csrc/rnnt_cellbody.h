@@ -12,9 +12,11 @@ namespace rnnt {
 // GRAD=false: softmax denominator + the two lattice edge weights;  GRAD=true: the V gradients
 // (written to `out`, zeros for padded cells; the patch kernels pass out = xs: the LDS image is rewritten in place).
 // LIN: the linear-domain lattice (rnnt_lin.h): edge probabilities instead of log2 weights and no lse store in the lsm pass;
-// in the gradient pass the softmax numerators are recomputed and scaled by occupancies formed from mantissas + frames.
+// in the gradient pass the softmax numerators are recomputed and scaled by occupancies formed from mantissas + frames: `lg`, the
+// cell's lin_grad_setup, which the caller forms (and certifies) before it stages the logits.
 template <int VP, bool V4, bool GRAD, bool LIN = false, bool SC1 = false>
-__device__ __forceinline__ float cell_body(const LossParams &p, const Cell &cl, const uint32_t c, const float *xs, float *out) {
+__device__ __forceinline__ float cell_body(const LossParams &p, const Cell &cl, const uint32_t c, const float *xs, float *out,
+                                           const LinGrad *lg = nullptr) {
     float stat = 0.f;  // LIN lsm: the cell's decay statistic (rnnt_lin.h), else unused
     const int V = p.V;
     if (cl.valid) {
@@ -37,8 +39,7 @@ __device__ __forceinline__ float cell_body(const LossParams &p, const Cell &cl, 
         if (!GRAD && LIN) {
             stat = lin_cell_lsm<VP>(p, cl, x, xs);
         } else if (GRAD && LIN) {
-            const LinGrad g = lin_grad_setup(p, cl);
-            if (g.bad) atomicOr(p.flags + 4 * cl.b + kFlagG, 1);  // (rare) the utterance is redone in the log domain
+            const LinGrad &g = *lg;
             float m = x[0];
 #pragma unroll
             for (int i = 1; i < VP; ++i) m = fmaxf(m, x[i]);
@@ -111,7 +112,11 @@ __device__ __forceinline__ float cell_body(const LossParams &p, const Cell &cl, 
             if (g.has_label) out[g.lab] -= g.scale * ex2(fmaf(xl, kLog2e, g.nl) + g.cl);
         }
     } else if (GRAD) {
-        for (int i = 0; i < V; ++i) out[i] = 0.f;
+        if (V4) {
+            for (int i = 0; i < V / 4; ++i) ((float4 *)out)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            for (int i = 0; i < V; ++i) out[i] = 0.f;
+        }
     }
 
     return stat;

@@ -161,6 +161,52 @@ __global__ __launch_bounds__(256) void cell_tile_kernel(const LossParams p) {
         return;
     }
 
+    const uint32_t r = fdiv((uint32_t)tid, tg.divUU);
+    const int cu = tid - (int)r * tg.UU;
+    Cell cl;
+    cl.b = b, cl.t = t0 + (int)r, cl.u = u0 + cu, cl.Tb = Tb, cl.Ub = Ub;
+    cl.valid = ((int)r < rows_valid) && (cu < cols_valid);
+    const uint32_t c = ((uint32_t)(b * p.T + cl.t)) * (uint32_t)p.U + (uint32_t)cl.u;
+
+    // Gradient pass of the linear lattice: the occupancy floor of cell_wave_range (rnnt_cellwave.h), decided BEFORE staging.  Every
+    // valid cell forms its set-up from mantissas + frames first and runs the range certificate on it, dead or alive: a cell whose
+    // alpha^ was flushed to zero looks dead, and only the certificate tells whether that flush was harmless.  A cell is dead when
+    // alpha beta / L <= 2^-kOccFloorWave (every gradient of it is then below 2^-49 |cost_scale|): its logits are not staged and it
+    // writes V zeros into its slot of the patch image.  NaN counts as live; RNNT_VISIT_ALL (p.visit_all) makes every cell live.
+    // The liveness bits reach the staging waves (rows `wave`, `wave + 4`, ... are other waves' cells) through the first words of
+    // the patch image, before any LDS-DMA lands there: one 32-bit word per 32 cells (ceil(TT UU / 32) words <= the TT UU V floats
+    // of the image), so the LDS allocation -- and with it the workgroups per CU -- stays what it was.
+    LinGrad lg = {};
+    uint32_t lword = ~0u;  // lane j < 8: the liveness word of cells [32 j, 32 j + 32) of the patch
+    if (GRAD && LIN) {
+        bool live = false;
+        if (cl.valid) {
+            lg = lin_grad_setup(p, cl);
+            if (lg.bad) atomicOr(p.flags + 4 * cl.b + kFlagG, 1);  // (rare) the utterance is redone in the log domain
+            live = p.visit_all || !(lg.l2occ <= (float)-kOccFloorWave);
+            cl.valid = live;  // a dead cell takes cell_body's padding route: zeros into its slot
+        }
+        const uint64_t m = __ballot(live);
+        const int ncell = tg.TT * tg.UU, nw = (ncell + 31) >> 5;
+        uint32_t *const lw = (uint32_t *)lds;
+        if (lane == 0 && wave * 64 < ncell) lw[2 * wave] = (uint32_t)m;
+        if (lane == 0 && wave * 64 + 32 < ncell) lw[2 * wave + 1] = (uint32_t)(m >> 32);
+        __syncthreads();
+        lword = lane < nw ? lw[lane] : 0u;
+        __syncthreads();  // every wave holds the words before the LDS-DMA overwrites them
+        if (__ballot(lword != 0u) == 0) {  // a dead patch: zeros, no staging, no arithmetic
+            for (int rr = wave; rr < rows_in; rr += 4) store_row(rr, nullptr);
+            return;
+        }
+    }
+    // Are any of the patch cells [klo, khi] (khi - klo < 32: one chunk's cells) live?  Two ds_bpermute reads of lane words: they
+    // must run with the whole wave active (a read from an inactive lane returns 0), so this is called outside divergent code.
+    auto cells_live = [&](const int klo, const int khi) -> bool {
+        const uint32_t wlo = (uint32_t)__shfl((int)lword, klo >> 5), whi = (uint32_t)__shfl((int)lword, khi >> 5);
+        const uint64_t bits = ((uint64_t)whi << 32 | wlo) >> (klo & 31);  // bit i: cell klo + i
+        return (bits & ((2ull << (khi - klo)) - 1ull)) != 0;
+    };
+
     // ---- stage: each wave streams whole row segments HBM -> LDS with 16-byte LDS-DMA ----
     for (int r = wave; r < rows_valid; r += 4) {
         const size_t s0 = patch0 + r * row_f;
@@ -170,7 +216,13 @@ __global__ __launch_bounds__(256) void cell_tile_kernel(const LossParams p) {
         const int nq = AL ? q_valid : (a + cols_valid * V + 3) / 4;
         for (int q0 = 0; q0 < nq; q0 += 64) {
             const int q = q0 + lane;
-            if (q < nq) {
+            bool need = q < nq;
+            if (GRAD && LIN) {  // only chunks that hold logits of a live cell (V % 4 == 0: the chunk lies in one cell)
+                const int e = min(q, nq - 1) * 4 - a;  // row element of the chunk's first float
+                const int lo = (int)fdiv((uint32_t)max(0, e), p.divV), hi = AL ? lo : (int)fdiv((uint32_t)min(e + 3, cols_valid * V - 1), p.divV);
+                need = cells_live(r * tg.UU + lo, r * tg.UU + hi) && need;
+            }
+            if (need) {
                 // default cache policy: non-temporal loads lose the Infinity-Cache reuse between the two cell passes
                 __builtin_amdgcn_global_load_lds((glb_void *)(src + q * 4), (lds_void *)(dst + q0 * 4), 16, 0, 0);
             }
@@ -179,18 +231,12 @@ __global__ __launch_bounds__(256) void cell_tile_kernel(const LossParams p) {
     wait_vm0();
     __syncthreads();
 
-    const uint32_t r = fdiv((uint32_t)tid, tg.divUU);
-    const int cu = tid - (int)r * tg.UU;
-    Cell cl;
-    cl.b = b, cl.t = t0 + (int)r, cl.u = u0 + cu, cl.Tb = Tb, cl.Ub = Ub;
-    cl.valid = ((int)r < rows_valid) && (cu < cols_valid);
-    const uint32_t c = ((uint32_t)(b * p.T + cl.t)) * (uint32_t)p.U + (uint32_t)cl.u;
     float stat = 0.f;
     if (AL) {
-        if ((GRAD && tid < tg.TT * tg.UU) || cl.valid) stat = cell_body<VP, true, GRAD, LIN>(p, cl, c, lds + tid * V, lds + tid * V);  // (lanes beyond the patch own no LDS)
+        if ((GRAD && tid < tg.TT * tg.UU) || cl.valid) stat = cell_body<VP, true, GRAD, LIN>(p, cl, c, lds + tid * V, lds + tid * V, &lg);  // (lanes beyond the patch own no LDS)
     } else if ((int)r < tg.TT) {
         const int a = (int)((patch0 + r * row_f) & 3);
-        if (GRAD || cl.valid) stat = cell_body<VP, false, GRAD, LIN>(p, cl, c, lds + r * row_lds + a + cu * V, lds + r * row_lds + a + cu * V);
+        if (GRAD || cl.valid) stat = cell_body<VP, false, GRAD, LIN>(p, cl, c, lds + r * row_lds + a + cu * V, lds + r * row_lds + a + cu * V, &lg);
     }
     if (!GRAD && LIN) {  // wave sums by butterfly (no LDS: the patch image is still being read by other waves)
         float cnt = cl.valid ? 1.f : 0.f;

@@ -84,6 +84,7 @@ struct LinGrad {
     float h0;  // cost_scale * occupancy            (x e_v / s = the softmax term)
     float hb;  // cost_scale * alpha p(..) beta(t+1,u) / L without the p: multiplies e_blank / s
     float hl;  // the same for the label edge
+    float l2occ;  // log2 of the occupancy alpha beta / L (no cost_scale): the occupancy floor of the gradient pass (rnnt_kernels.hip)
     bool has_blank_corr, has_label, bad;
     int lab;
 };
@@ -106,6 +107,8 @@ __device__ __forceinline__ LinGrad lin_grad_setup(const LossParams &p, const Cel
     const float qa = scale * frexp_m(ma) * __builtin_amdgcn_rcpf(mL);
     const int base = ea + xa - EL;
     g.h0 = ldexp_f(qa * frexp_m(mb), base + eb + xb);
+    // (a zero mantissa gives -inf: dead; a NaN or infinite likelihood / mantissa gives NaN or +inf: live)
+    g.l2occ = lg2(frexp_m(ma) * frexp_m(mb) * __builtin_amdgcn_rcpf(mL)) + (float)(ea + xa + eb + xb - EL);
     g.has_blank_corr = true;
     g.hb = 0.f;
     if (cl.t < cl.Tb - 1) {
