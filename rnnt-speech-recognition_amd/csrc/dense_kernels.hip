@@ -264,15 +264,11 @@ constexpr int kNtPartA = kNtM * 64, kNtPartB = kNtN * 64;      // bytes per hi (
 constexpr int kNtStage = 2 * kNtPartA + 2 * kNtPartB;          // 48 KB
 constexpr int kNtStages = 3;
 
-#ifndef DENSE_NT_LOADERS
-#define DENSE_NT_LOADERS 0  // loader waves per workgroup; 0 (shipped): the compute waves issue the LDS-DMA themselves.  Measured at
-                            // C2: 4 loaders 75.5 us, 0 loaders 73.7 us -- the fill is not issue-bound (PMC: matrix pipe 40 % busy,
-                            // HBM fetch 94 MB for 451 MB of tile loads, L2 hit rate 83 %: the stages wait for L2 -> LDS data)
-#endif
-constexpr int kNtLoaders = DENSE_NT_LOADERS;
-constexpr int kNtThreads = (8 + kNtLoaders) * 64;
-constexpr int kNtIssuers = kNtLoaders ? kNtLoaders : 8;   // waves that issue DMA pieces
-constexpr int kNtPieces = 48 / kNtIssuers;                // pieces per issuing wave and stage
+// The eight compute waves issue the LDS-DMA themselves.  Dedicated loader waves were measured at C2: 4 loaders 75.5 us,
+// none 73.7 us -- the fill is not issue-bound (PMC: matrix pipe 40 % busy, HBM fetch 94 MB for 451 MB of tile loads, L2 hit
+// rate 83 %: the stages wait for L2 -> LDS data).
+constexpr int kNtThreads = 512;
+constexpr int kNtPieces = 6;  // pieces per wave and stage (48 per stage)
 
 __global__ __launch_bounds__(kNtThreads) void dense_gemm_nt_kernel(const DenseNT g) {
     extern __shared__ __attribute__((aligned(16))) char dsm[];
@@ -285,58 +281,30 @@ __global__ __launch_bounds__(kNtThreads) void dense_gemm_nt_kernel(const DenseNT
     const int m0 = mt * kNtM, n0 = nt * kNtN;
     const int K = g.K;
     const int nK = K / kNtK;
-    const bool loader = kNtLoaders && wave >= 8;          // wave-uniform
-    const int iw = kNtLoaders ? wave - 8 : wave;          // index among the issuing waves
 
-    // LDS-DMA pieces: wave-instructions i = iw + kNtIssuers k of the 48 that fill one stage.
+    // LDS-DMA pieces: wave-instructions i = wave + 8 k of the 48 that fill one stage.
     //   i <  16: A hi rows 16 i .. ; i < 32: A lo ; i < 40: B hi rows 16 (i - 32) .. ; else B lo.
     // A lane moves 16 bytes: row = 16 (block) + lane / 4, LDS chunk position p = lane & 3 holds logical chunk p ^ ((row >> 2) & 3)
-    // (Issuing a piece costs a wave 60-180 cycles of its in-order stream; moving the pieces to dedicated loader waves --
-    // DENSE_NT_LOADERS -- did not change the kernel's time, see above.)
+    // (Issuing a piece costs a wave 60-180 cycles of its in-order stream; moving the pieces to dedicated loader waves did not
+    // change the kernel's time, see above.)
     const df16 *src[kNtPieces];
     int ldsoff[kNtPieces];
-    if (!kNtLoaders || loader) {
 #pragma unroll
-        for (int k = 0; k < kNtPieces; ++k) {
-            const int i = iw + kNtIssuers * k;
-            const bool isA = i < 32;
-            const int blk = isA ? (i & 15) : ((i - 32) & 7);
-            const bool lo = isA ? (i >= 16) : (i >= 40);
-            const int row = blk * 16 + (lane >> 2);
-            const int c = (lane & 3) ^ ((row >> 2) & 3);
-            const int grow = isA ? min(m0 + row, g.M - 1) : min(n0 + row, g.N - 1);
-            const df16 *base = isA ? (lo ? g.Alo : g.Ahi) : (lo ? g.Blo : g.Bhi);
-            src[k] = base + (size_t)grow * K + c * 8;
-            ldsoff[k] = (isA ? (lo ? kNtPartA : 0) : 2 * kNtPartA + (lo ? kNtPartB : 0)) + blk * 1024;
-        }
+    for (int k = 0; k < kNtPieces; ++k) {
+        const int i = wave + 8 * k;
+        const bool isA = i < 32;
+        const int blk = isA ? (i & 15) : ((i - 32) & 7);
+        const bool lo = isA ? (i >= 16) : (i >= 40);
+        const int row = blk * 16 + (lane >> 2);
+        const int c = (lane & 3) ^ ((row >> 2) & 3);
+        const int grow = isA ? min(m0 + row, g.M - 1) : min(n0 + row, g.N - 1);
+        const df16 *base = isA ? (lo ? g.Alo : g.Ahi) : (lo ? g.Blo : g.Bhi);
+        src[k] = base + (size_t)grow * K + c * 8;
+        ldsoff[k] = (isA ? (lo ? kNtPartA : 0) : 2 * kNtPartA + (lo ? kNtPartB : 0)) + blk * 1024;
     }
     auto dma_piece = [&](const int k, const int kc, const int stage) {
         lds_dma16(src[k] + kc * kNtK, dsm + stage * kNtStage + ldsoff[k]);
     };
-
-    if (loader) {
-        // ---- loader wave: stage kc + 2 goes out right after the barrier that frees its ring slot
-#pragma unroll
-        for (int k = 0; k < kNtPieces; ++k) dma_piece(k, 0, 0);
-        if (nK > 1) {
-#pragma unroll
-            for (int k = 0; k < kNtPieces; ++k) dma_piece(k, 1, 1);
-        }
-        int sc = 0;
-        for (int kc = 0; kc < nK; ++kc) {
-            if (kc + 1 < nK) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kNtPieces) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();  // stage kc complete in LDS; every compute wave is done with stage kc - 1
-            if (kc + 2 < nK) {
-                const int sp = (sc + 2) % kNtStages;
-#pragma unroll
-                for (int k = 0; k < kNtPieces; ++k) dma_piece(k, kc + 2, sp);
-            }
-            sc = (sc + 1) % kNtStages;
-        }
-        __builtin_amdgcn_s_barrier();  // the epilogue's barrier (the compute waves re-use the ring as staging tiles)
-        return;
-    }
 
     df32x16 acc[2][2];
 #pragma unroll
@@ -346,13 +314,11 @@ __global__ __launch_bounds__(kNtThreads) void dense_gemm_nt_kernel(const DenseNT
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
 
-    if (!kNtLoaders) {
 #pragma unroll
-        for (int k = 0; k < kNtPieces; ++k) dma_piece(k, 0, 0);
-        if (nK > 1) {
+    for (int k = 0; k < kNtPieces; ++k) dma_piece(k, 0, 0);
+    if (nK > 1) {
 #pragma unroll
-            for (int k = 0; k < kNtPieces; ++k) dma_piece(k, 1, 1);
-        }
+        for (int k = 0; k < kNtPieces; ++k) dma_piece(k, 1, 1);
     }
     // fragment addresses of this lane inside a stage (bytes): rows of its two A tiles and its two B tiles
     int arow[2], brow[2];
@@ -361,14 +327,12 @@ __global__ __launch_bounds__(kNtThreads) void dense_gemm_nt_kernel(const DenseNT
 
     int sc = 0;
     for (int kc = 0; kc < nK; ++kc) {
-        if (!kNtLoaders) {
-            if (kc + 1 < nK) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        if (kc + 1 < nK) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();  // stage kc complete in LDS; the stage of kc - 1 (refilled next) is free
         asm volatile("" ::: "memory");
         const char *S = dsm + sc * kNtStage;
-        const bool pf = !kNtLoaders && kc + 2 < nK;
+        const bool pf = kc + 2 < nK;
         const int sp = (sc + 2) % kNtStages;
         // fragments of k-step ks in [ks & 1]: read one k-step ahead of their MFMAs
         dh8 ah[2][2], al[2][2], bh[2][2], bl[2][2];
@@ -387,12 +351,10 @@ __global__ __launch_bounds__(kNtThreads) void dense_gemm_nt_kernel(const DenseNT
         for (int ks = 0; ks < 2; ++ks) {
             if (ks == 0) rd(1, ah[1], al[1], bh[1], bl[1]);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (kNtLoaders == 0) {
-                if (pf) {  // three of the six pieces of stage kc + 2 per k-step, between the MFMA groups
-                    dma_piece(3 * ks + 0, kc + 2, sp);
-                    dma_piece(3 * ks + 1, kc + 2, sp);
-                    dma_piece(3 * ks + 2, kc + 2, sp);
-                }
+            if (pf) {  // three of the six pieces of stage kc + 2 per k-step, between the MFMA groups
+                dma_piece(3 * ks + 0, kc + 2, sp);
+                dma_piece(3 * ks + 1, kc + 2, sp);
+                dma_piece(3 * ks + 2, kc + 2, sp);
             }
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi)
@@ -414,7 +376,7 @@ __global__ __launch_bounds__(kNtThreads) void dense_gemm_nt_kernel(const DenseNT
     const float inv0 = 1.0f / (__hip_atomic_load(g.scal + g.sa0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * sB);
     const float inv1 = 1.0f / (__hip_atomic_load(g.scal + g.sa1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * sB);
     const bool tables = g.E0 != nullptr;
-    __builtin_amdgcn_s_barrier();  // every compute wave is done reading the last stage (the loaders join this barrier, then leave)
+    __builtin_amdgcn_s_barrier();  // every wave is done reading the last stage
     constexpr int kPitch = 68;     // floats per tile row in LDS: 16-byte aligned rows, conflict-free column writes
     float *tile = (float *)dsm + wave * 64 * kPitch;
 #pragma unroll
@@ -733,7 +695,7 @@ static void dense_absmax(const AbsmaxJob &job, hipStream_t s) {
 
 static hipError_t dense_nt_launch(DenseNT &g, hipStream_t s) {
     const size_t shm = (size_t)kNtStages * kNtStage;
-    hipError_t e = hipFuncSetAttribute((const void *)dense_gemm_nt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    hipError_t e = set_lds(dense_gemm_nt_kernel, shm);
     if (e != hipSuccess) return e;
     g.tiles_n = (g.N + kNtN - 1) / kNtN;
     hipLaunchKernelGGL(dense_gemm_nt_kernel, dim3((unsigned)(((g.M + kNtM - 1) / kNtM) * g.tiles_n)), dim3(kNtThreads), shm, s, g);

@@ -407,10 +407,8 @@ hipError_t launch_greedy_begin(const float *enc_proj, const int *frame_lengths, 
 
 template <int DT>
 static hipError_t launch_step_dt(const GreedyArgs &a, size_t shm, hipStream_t s) {
-    if (shm > 65536) {
-        const hipError_t e = hipFuncSetAttribute((const void *)greedy_step_kernel<DT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = set_lds(greedy_step_kernel<DT>, shm);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(greedy_step_kernel<DT>, dim3(a.NS, (a.B + 31) / 32), dim3(kGrWaves * 64), shm, s, a);
     return hipGetLastError();
 }

@@ -39,11 +39,6 @@
 #include "rnnt_joint_math.h"
 
 #include <math.h>
-#ifdef JH_TRACE
-#include <stdio.h>
-#include <stdlib.h>
-#include <vector>
-#endif
 
 namespace rnnt {
 
@@ -66,21 +61,11 @@ __device__ __forceinline__ float htanh2(float ea, float ec) { return tanh_from_e
 __device__ __forceinline__ constexpr int cdrow(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void wait_lgkm() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ float dot8(const h8 a, const h8 b, float c) {
-    c = __builtin_amdgcn_fdot2(__builtin_shufflevector(a, a, 0, 1), __builtin_shufflevector(b, b, 0, 1), c, false);
-    c = __builtin_amdgcn_fdot2(__builtin_shufflevector(a, a, 2, 3), __builtin_shufflevector(b, b, 2, 3), c, false);
-    c = __builtin_amdgcn_fdot2(__builtin_shufflevector(a, a, 4, 5), __builtin_shufflevector(b, b, 4, 5), c, false);
-    c = __builtin_amdgcn_fdot2(__builtin_shufflevector(a, a, 6, 7), __builtin_shufflevector(b, b, 6, 7), c, false);
-    return c;
-}
 // An opaque copy: what is computed from it cannot be hoisted out of the region it is made in (values derived from the thread
 // index that a kernel's epilogue needs must not stay in registers through its main loop).
 __device__ __forceinline__ int launder(int x) {
     asm volatile("" : "+v"(x));
     return x;
-}
-__device__ __forceinline__ float lane_f32(float x, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l));
 }
 // XCD-aware bijective remap: XCD (blockIdx % 8) owns a contiguous range of logical work items
 __device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t nwg) {
@@ -104,10 +89,7 @@ constexpr int kStageStride = 36;   // halfs per row of the K1/K2 staging tile: o
                                    // the 32 rows a half-wave writes (8 bytes per lane) fall into 32 different bank pairs
                                    // (20 dwords per row: 2.5e8 conflict cycles per launch at config 5, rows n and n + 16 collide)
 constexpr float kRefLimit = 30000.0f;  // chunk references are kept as int16
-#ifndef JH_TQ
-#define JH_TQ 128
-#endif
-constexpr int kTQ = JH_TQ;         // lattice rows per K4 work unit
+constexpr int kTQ = 128;           // lattice rows per K4 work unit
 
 struct JhParams {
     LossParams lp;  // lattice workspace, labels, lengths, costs, cost_scale (acts / grads unused)
@@ -139,19 +121,7 @@ struct JhParams {
     int b2_lds_off;  // K1/K2: byte offset of the bias table in LDS, -1 = read it from global memory (does not fit)
     float *logits_out;  // MODE 3 of K1 (compute_rnnt_joint_logits, decoding): f32 logits [cells][V]
     int logits_only;    // every lattice cell is wanted: the prep kernel writes full lengths + zero labels into the workspace
-#ifdef JH_TRACE
-    long long *trace;  // dev builds only (-DJH_TRACE): per-wave s_memtime stamps of a few workgroups of K1
-#endif
 };
-#ifdef JH_TRACE
-constexpr int kTraceSlots = 160, kTraceBlocks = 4, kTraceStride = 4096;
-#define JT(slot)                                                                     \
-    do {                                                                             \
-        if (tr && lane == 0) tr[(slot)] = (long long)__builtin_amdgcn_s_memtime();   \
-    } while (0)
-#else
-#define JT(slot) do { } while (0)
-#endif
 
 // ---------------------------------------------------------------------------------------------
 // prep: binary16 copies of W2 and the dlogits scale
@@ -240,12 +210,6 @@ __global__ __launch_bounds__(512) void jh_logits_kernel(const JhParams jp) {
     const bool cell_valid = wave_live && (u < Ub);
     const uint32_t c = ((uint32_t)(b * p.T + tc)) * (uint32_t)p.U + (uint32_t)uc;
 
-#ifdef JH_TRACE
-    long long *tr = nullptr;
-    if (!BWD && (blockIdx.x % kTraceStride) == kTraceStride / 2 && blockIdx.x / kTraceStride < kTraceBlocks)
-        tr = jp.trace + ((blockIdx.x / kTraceStride) * 8 + wave) * kTraceSlots;
-#endif
-    JT(0);
     // one 1 KB piece (wave-instruction) of the LDS-DMA that brings W2^T chunk vc in; a wave owns pieces wave, wave+8, ..
     constexpr int kPieces = (KS + 7) / 8;
     auto dma_piece = [&](const int vc, char *dst, const int k) {
@@ -311,7 +275,6 @@ __global__ __launch_bounds__(512) void jh_logits_kernel(const JhParams jp) {
 #pragma unroll
     for (int k = 0; k < kPieces; ++k) dma_piece(0, wbuf0, k);
 
-    JT(1);
     // ---- per-cell scalars
     float xb = 0.f, xl = 0.f;  // blank / label logits
     int lab = 0;
@@ -484,7 +447,6 @@ __global__ __launch_bounds__(512) void jh_logits_kernel(const JhParams jp) {
     const int NC = V >> 5;
     f32x16 acc;
     for (int vc = 0; vc < NC; ++vc) {
-        JT(2 + 4 * vc);
         wait_vm();
         __syncthreads();  // chunk vc is in LDS; every wave is done with the other buffer
         char *nbuf = ((vc + 1) & 1) ? wbuf1 : wbuf0;
@@ -493,10 +455,8 @@ __global__ __launch_bounds__(512) void jh_logits_kernel(const JhParams jp) {
 #pragma unroll
             for (int k = 0; k < kPieces; ++k) dma_piece(vc + 1, nbuf, k);
         }
-        JT(3 + 4 * vc);
         if (!wave_live) continue;
         if (late && vc > 0) epilogue(acc, vc - 1);
-        JT(4 + 4 * vc);
         const char *wb = ((vc & 1) ? wbuf1 : wbuf0) + lane * 16;
         constexpr bool kTwoChains = !(STAGE && KS > 32);  // two accumulation chains unless registers are short
         f32x16 acc0, acc1;
@@ -557,10 +517,8 @@ __global__ __launch_bounds__(512) void jh_logits_kernel(const JhParams jp) {
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = kTwoChains ? acc0[r] + acc1[r] : acc0[r];
-        JT(5 + 4 * vc);
         if (!late) epilogue(acc, vc);
     }
-    JT(2 + 4 * 32);
     if (late && wave_live) epilogue(acc, NC - 1);
     if (STAGE && wave_live) {  // the last chunk's pieces
         stage_store(0, NC - 1, stage_read(0));
@@ -602,9 +560,7 @@ __global__ __launch_bounds__(512) void jh_logits_kernel(const JhParams jp) {
 // and add exact zeros.  (N(0,1) projections at config 5: 34.8 % -> 31 % of the rows.)
 // ---------------------------------------------------------------------------------------------
 constexpr int kOccFloorH = 40;
-#ifndef JH_DHX_WGS
-#define JH_DHX_WGS 2560  // (measured at config 5: 1280 / 2560 / 3840 workgroups: pruned N(0,1) 5.5 / 5.3 ms, trained-like 2.5 / 1.9 ms, all rows the same)
-#endif
+constexpr int kDhxWgs = 2560;  // K3 workgroups (measured at config 5: 1280 / 2560 / 3840 workgroups: pruned N(0,1) 5.5 / 5.3 ms, trained-like 2.5 / 1.9 ms, all rows the same)
 __host__ __device__ inline int rowcnt_stamp(int T, int U, int B, int J, int V) {
     return (int)(0x16f16000u ^ ((unsigned)T * 73856093u) ^ ((unsigned)U * 19349663u) ^ ((unsigned)B * 83492791u) ^ ((unsigned)J * 2654435761u) ^ (unsigned)V);
 }
@@ -1028,16 +984,6 @@ __global__ __launch_bounds__(512) void jh_dhx_kernel(const JhParams jp) {
     int pk = 0;
     int sb = 0;  // W2 stage of the chunk being multiplied (the A stage is kc & 3)
     bool first = true;
-#ifdef JH_TRACE
-    long long *tr = (wg == 200) ? jp.trace + (size_t)(kTraceBlocks * 8 + 8 + wave) * kTraceSlots : nullptr;
-    int tstep = 0;
-#define DT(k)                                                                                          \
-    do {                                                                                               \
-        if (tr && tstep < 22 && lane == 0) tr[7 * tstep + (k)] = (long long)__builtin_amdgcn_s_memtime(); \
-    } while (0)
-#else
-#define DT(k) do { } while (0)
-#endif
 
     for (int t_it = t_first; t_it < t_end;) {
         const bool has_next = t_n1 < t_end;                            // (t_n1: the next visited group, t_n2: the one after)
@@ -1090,14 +1036,11 @@ __global__ __launch_bounds__(512) void jh_dhx_kernel(const JhParams jp) {
                 // "at most NT + 2 outstanding" means everything up to two steps ago has landed.  The converted A pieces of the chunk:
                 // LDS writes of the last step.  The first step of an iteration follows an epilogue with ordinary loads and stores, the
                 // last steps of a workgroup issue less: drain there.
-                DT(0);
                 if (kc == 0 || (!has_next && last_group)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NT + 2) : "memory");
                 wait_lgkm();
-                DT(1);
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
-                DT(2);
                 const int sb1 = (sb == 2) ? 0 : sb + 1, sb2 = (sb1 == 2) ? 0 : sb1 + 1;
                 // the epilogue's first tile of inputs: a whole step ahead of their use (issued at the epilogue's start, their memory
                 // latency sat in front of the first tile; measured: no difference in the kernel's time, kept because the allocation it
@@ -1127,7 +1070,6 @@ __global__ __launch_bounds__(512) void jh_dhx_kernel(const JhParams jp) {
                     else a_store(o_pend, cur, t_it, pk);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                DT(5);
 #pragma unroll
                 for (int ni = 0; ni < NT; ++ni) {
                     if (e2) dma_b(k2, sb2, ni);
@@ -1141,14 +1083,12 @@ __global__ __launch_bounds__(512) void jh_dhx_kernel(const JhParams jp) {
                     else dma_a(cur, t_it, k3, (q + 3) & 3);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                DT(6);
 #pragma unroll
                 for (int ni = 0; ni < NT; ++ni) {
 #pragma unroll
                     for (int mi = 0; mi < 2; ++mi)
                         acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][mi], bf[ni], acc[mi][ni], 0, 0, 0);
                 }
-                DT(3);
                 // the conversion of the next chunk's A piece shares its scheduling region with the MFMAs of the second k-step (its
                 // LDS reads were issued with the fragment reads)
                 pend = e1, pend_next = x1, pk = k1;
@@ -1159,24 +1099,11 @@ __global__ __launch_bounds__(512) void jh_dhx_kernel(const JhParams jp) {
                     o_pend = a_finish(araw, cc, k1, (q + 1) & 3);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                DT(4);
-#ifdef JH_TRACE
-                ++tstep;
-#endif
                 sb = sb1;
             }
         }
         // ---- epilogue: acc[mi][ni][r] = S dh[row t_it + (r >> 2)][column u0 + 16 wm + 8 mi + 4 half + (r & 3)][unit JW wn + 32 ni + n]
         const bool last = !has_next;
-#ifdef JH_TRACE
-#define ET(k)                                                                                                   \
-    do {                                                                                                        \
-        if (tr && !first && tstep >= 22 && tstep < 70 && lane == 0) tr[154 + (k)] = (long long)__builtin_amdgcn_s_memtime();    \
-    } while (0)
-#else
-#define ET(k) do { } while (0)
-#endif
-        ET(0);
         const int ln3 = launder(tid) & 63, n3 = ln3 & 31, half3 = ln3 >> 5;
         load_idx(1);  // (tile 0: at the top of the iteration's last step)
 #pragma unroll
@@ -1242,9 +1169,6 @@ __global__ __launch_bounds__(512) void jh_dhx_kernel(const JhParams jp) {
                     if (t_it + rw < t_end)
                         (jp.dApart + (((size_t)ut * p.B + b) * p.T + t_it + rw) * J + jw)[(uint32_t)n3] = (rs[rw] + cb[rw * 128 + wn * 32 + n3]) * c4;
             }
-            if (ni == 0) ET(1);
-            if (ni == 1) ET(2);
-            if (ni == NT - 1) ET(3);
         }
         // the factors of the iteration after the next (its first chunk is converted in the last step of the next one).  (Their loads
         // issued two unit tiles earlier, the arithmetic here: 11 more live registers, spilled -- 13.7 against 13.1 ms at config 5.)
@@ -1253,7 +1177,6 @@ __global__ __launch_bounds__(512) void jh_dhx_kernel(const JhParams jp) {
             cell_place(nn, t_n2);
             cell_factors(nn, t_n2);
         }
-        ET(4);
         first = false;
         cur = nxt, nxt = nn;
         pend_next = false;  // (the piece converted in the last step belongs to what is now the current iteration)
@@ -1271,11 +1194,9 @@ __global__ __launch_bounds__(512) void jh_dhx_kernel(const JhParams jp) {
 // groups keep the workgroup's barriers, DMA pieces and h^T staging and skip their products (a separate instantiation: the
 // schedule of the full-tile kernel is left as it was tuned).
 // ---------------------------------------------------------------------------------------------
-#ifndef JH_K4_W256
-#define JH_K4_W256 4  // waves per SIMD the 256-column instantiation is compiled for (4 = two workgroups per CU)
-#endif
+constexpr int kK4W256 = 4;  // waves per SIMD the 256-column instantiation is compiled for (4 = two workgroups per CU)
 template <bool PARTIAL, int VT>
-__global__ __launch_bounds__(512, VT == 512 ? 1 : JH_K4_W256) void jh_dw_kernel(const JhParams jp) {
+__global__ __launch_bounds__(512, VT == 512 ? 1 : kK4W256) void jh_dw_kernel(const JhParams jp) {
     // VT = columns of a workgroup's V tile: 512 (one workgroup per CU, 126 KB of LDS), 256 or -- V = 128 only -- 128 (TWO per CU at 80 / 57 KB each: while one
     // sits in its barrier / fragment-read phase the other has the matrix pipe)
     constexpr int VB = VT / 128;       // 32-column accumulator blocks per wave
@@ -1316,10 +1237,6 @@ __global__ __launch_bounds__(512, VT == 512 ? 1 : JH_K4_W256) void jh_dw_kernel(
     const bool slow = jp.scal[2] != 0.f;  // kernel-uniform
     const float *Etab = slow ? jp.enc_proj : jp.expE, *Ptab = slow ? jp.pred_proj : jp.expP;
     char *ebuf = smem + 3 * kStage;  // [4][128] enc_proj values of the workgroup's joint units, one lattice row each
-#ifdef JH_TRACE
-    long long *tr = (blockIdx.x == 100) ? jp.trace + (size_t)(kTraceBlocks * 8 + wave) * kTraceSlots : nullptr;
-    int tstep = 0;
-#endif
     // the visited rows of the current unit, as byte offsets from its first row: [kTQ] bytes + a count, kept in the 64 padding bytes behind the
     // LAST dl row of the three stages (no DMA piece or h^T store touches them) -- NOT in extra LDS: the 256-column instantiation runs two
     // workgroups per CU at exactly 2 x 81,920 B, and 1 KB more per workgroup halved its occupancy (V = 256: 2.08 instead of 1.55 ms)
@@ -1438,18 +1355,11 @@ __global__ __launch_bounds__(512, VT == 512 ? 1 : JH_K4_W256) void jh_dw_kernel(
         }
         int c_s2 = row_of(2), c_s3 = row_of(3);
         for (int s = 0; s < nsteps; ++s) {
-#ifdef JH_TRACE
-            const bool tron = tr && tstep < 39;
-            if (tron && lane == 0) tr[4 * tstep] = (long long)__builtin_amdgcn_s_memtime();
-#endif
             if (s + 1 < nsteps) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // all but the newest stage's dl rows
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             wait_lgkm();
             __builtin_amdgcn_s_barrier();  // stage s complete (dl rows + h^T); stage (s+2)%3 free; enc_proj row s+2 visible
             asm volatile("" ::: "memory");
-#ifdef JH_TRACE
-            if (tron && lane == 0) tr[4 * tstep + 1] = (long long)__builtin_amdgcn_s_memtime();
-#endif
             // Stage s+2 is prepared WHILE stage s is multiplied: its five LDS-DMA pieces go out between the MFMA pairs of
             // the first k-step, its h^T values (8 tanh per thread) are computed between those of the second, and are
             // written to LDS at the end.  (Done up front, as a block, they cost 1100-1500 cycles per 32-cell step with
@@ -1459,11 +1369,6 @@ __global__ __launch_bounds__(512, VT == 512 ? 1 : JH_K4_W256) void jh_dw_kernel(
             char *stn = smem + ((s + 2) % 3) * kStage;
             float ejn = 0.f, hh[8];
             if (pf) ejn = ((const float *)(ebuf + ((s + 2) & 3) * 512))[jl];
-#ifdef JH_TRACE
-            if (tron && lane == 0) tr[4 * tstep + 2] = (long long)__builtin_amdgcn_s_memtime();
-            if (tron && lane == 0) tr[4 * tstep + 3] = (long long)__builtin_amdgcn_s_memtime();
-            ++tstep;
-#endif
             const char *D = smem + (s % 3) * kStage, *H = D + kDBytes;
             const int g4 = lane >> 4, pl = lane & 15;
             // all fragment reads of the step first (2 x (2 A + 8 transposed B)), then MFMA pairs with the staging work
@@ -1582,8 +1487,8 @@ static JhLayout make_jh_layout(int T, int U, int B, int J, int V) {
     L.n_ut = (U + 31) / 32;
     L.n_tt = (T + 7) / 8;
     // row splits of K3: its workgroups own (utterance, 32 columns, TS rows) x ALL joint units (round 6) -- as many splits as give about
-    // JH_DHX_WGS workgroups (ten rounds of one per CU; config 5: 16), strips of at least 16 rows (four iterations of four)
-    L.n_ts = (JH_DHX_WGS + B * L.n_ut - 1) / (B * L.n_ut);
+    // kDhxWgs workgroups (ten rounds of one per CU; config 5: 16), strips of at least 16 rows (four iterations of four)
+    L.n_ts = (kDhxWgs + B * L.n_ut - 1) / (B * L.n_ut);
     if (L.n_ts > (T + 15) / 16) L.n_ts = (T + 15) / 16;
     if (L.n_ts < 1) L.n_ts = 1;
     L.TS = ((T + L.n_ts - 1) / L.n_ts + 3) / 4 * 4;
@@ -1635,18 +1540,9 @@ hipError_t joint_f16_workspace_bytes(int T, int U, int B, int J, int V, size_t *
 bool fill_loss_params(LossParams &p, const float *acts, float *grads, const int *labels, const int *label_lengths,
                       const int *input_lengths, const float *cost_scale, int V, int B, float *costs, void *workspace,
                       int maxT, int maxU, int blank);
-hipError_t launch_reduce_partials(float *out, const float *in, int nparts, size_t n, hipStream_t s, unsigned *blockmax);
 hipError_t launch_reduce_f16_backward(float *d_enc, const float *dApart, int n_ut, const LossParams &lp, int J, unsigned *bm_enc, const uint8_t *live8,
                                       float *d_pred, const float *dCpart, int nC, unsigned *bm_pred, float *dW2, const float *dWpart, float *db2,
                                       const float *dbpart, int nR, int V, hipStream_t s);
-hipError_t launch_reduce_enc(float *out, const float *in, int n_ut, const LossParams &lp, int J, hipStream_t s, unsigned *blockmax,
-                             const uint8_t *live8);
-
-template <typename K>
-static hipError_t set_lds_f16(K kernel, size_t bytes) {
-    if (bytes <= 65536) return hipSuccess;
-    return hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
 
 template <int KS, int MODE>
 static hipError_t launch_logits_mode(const JhParams &jp, unsigned grid, hipStream_t s) {
@@ -1664,10 +1560,10 @@ static hipError_t launch_logits_mode(const JhParams &jp, unsigned grid, hipStrea
     }
     hipError_t e;
     if (jq.b2_lds_off >= 0) {
-        if ((e = set_lds_f16(jh_logits_kernel<KS, MODE, true>, shm)) != hipSuccess) return e;
+        if ((e = set_lds(jh_logits_kernel<KS, MODE, true>, shm)) != hipSuccess) return e;
         hipLaunchKernelGGL((jh_logits_kernel<KS, MODE, true>), dim3(grid), dim3(512), shm, s, jq);
     } else {
-        if ((e = set_lds_f16(jh_logits_kernel<KS, MODE, false>, shm)) != hipSuccess) return e;
+        if ((e = set_lds(jh_logits_kernel<KS, MODE, false>, shm)) != hipSuccess) return e;
         hipLaunchKernelGGL((jh_logits_kernel<KS, MODE, false>), dim3(grid), dim3(512), shm, s, jq);
     }
     return hipGetLastError();
@@ -1733,9 +1629,6 @@ static hipError_t jh_fill_params(JhParams &jp, const JhLayout &L, const float *e
     jp.n_units = L.n_units, jp.n_ranges = L.n_ranges;
     jp.logits_out = nullptr, jp.logits_only = 0;
     jp.b2_lds_off = -1;
-#ifdef JH_TRACE
-    jp.trace = nullptr;
-#endif
     return hipSuccess;
 }
 
@@ -1774,13 +1667,6 @@ hipError_t launch_joint_loss_f16(const float *enc_proj, const float *pred_proj, 
                                   blank, costs, workspace);
     if (e != hipSuccess) return e;
 
-#ifdef JH_TRACE
-    static long long *trace_dev = nullptr;
-    const size_t trace_bytes = (size_t)(kTraceBlocks + 2) * 8 * kTraceSlots * sizeof(long long);
-    if (!trace_dev) hipMalloc(&trace_dev, trace_bytes);
-    hipMemsetAsync(trace_dev, 0, trace_bytes, s);
-    jp.trace = trace_dev;
-#endif
     const unsigned tiles = (unsigned)B * L.n_tt * L.n_ut;
     auto logits = [&](int mode) -> hipError_t { return jh_launch_logits_for_J(jp, J, mode, tiles, s); };
     auto set_state = [&](int value) -> hipError_t {
@@ -1800,18 +1686,6 @@ hipError_t launch_joint_loss_f16(const float *enc_proj, const float *pred_proj, 
         if (launch_fill(jp.lp.W, kFillByte, L.w.A - L.w.W, s) != hipSuccess) return hipErrorUnknown;
         if ((e = logits(park ? 1 : 0)) != hipSuccess) return e;
         if (park && (e = set_state(1)) != hipSuccess) return e;
-#ifdef JH_TRACE
-        {
-            hipStreamSynchronize(s);
-            std::vector<long long> h(trace_bytes / sizeof(long long));
-            hipMemcpy(h.data(), trace_dev, trace_bytes, hipMemcpyDeviceToHost);
-            const char *path = getenv("JH_TRACE_FILE");
-            if (FILE *f = fopen(path ? path : "/tmp/jh_trace.bin", "wb")) {
-                fwrite(h.data(), 1, trace_bytes, f);
-                fclose(f);
-            }
-        }
-#endif
         if ((e = launch_sweeps(jp.lp, s)) != hipSuccess) return e;
     }
     if (!(phases & 2) || !d_enc_proj) return hipSuccess;
@@ -1823,7 +1697,7 @@ hipError_t launch_joint_loss_f16(const float *enc_proj, const float *pred_proj, 
     // was measured at config 5: the two kernels do overlap, and slow each other down by as much as the overlap hides.)
     // (a call that parked in its own forward phase knows the answer: the recompute kernel would read the state word and return)
     if (!((phases & 1) && park) && (e = logits(2)) != hipSuccess) return e;
-    // dC partials + the zero row + the row counters (the dA partials need no zero-fill: launch_reduce_enc reads only the rows K3 writes)
+    // dC partials + the zero row + the row counters (the dA partials need no zero-fill: reduce_f16_backward_kernel reads only the rows K3 writes)
     if (launch_fill(jp.dCpart, 0, L.live8 - L.dCpart, s) != hipSuccess) return hipErrorUnknown;
     // which lattice rows (x 32-column tiles) the backward visits: K3, K4 and the d enc_proj reduction follow these bits
     jp.visit_all = (phases & 8) ? 1 : 0;
@@ -1835,7 +1709,7 @@ hipError_t launch_joint_loss_f16(const float *enc_proj, const float *pred_proj, 
         const size_t shm = 3 * (size_t)(J * 64) + 4 * 8192 + 4 * 256 + 4096 + 128;  // W2 stages, A stages, reference tiles, hand-over rows, labels
         const unsigned grid = (unsigned)B * L.n_ut * L.n_ts;
         auto go = [&](auto kernel) -> hipError_t {
-            hipError_t e2 = set_lds_f16(kernel, shm);
+            hipError_t e2 = set_lds(kernel, shm);
             if (e2 != hipSuccess) return e2;
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), shm, s, jp);
             return hipGetLastError();
@@ -1855,7 +1729,7 @@ hipError_t launch_joint_loss_f16(const float *enc_proj, const float *pred_proj, 
         const size_t shm = 3 * (size_t)(32 * (2 * vt + 64) + 2 * 4 * 32 * 32) + 4 * 512;  // stages (the unit's row list in their padding), enc row slices
         const unsigned grid = (unsigned)L.n_ranges * (J / 128) * ((V + vt - 1) / vt);
         auto go = [&](auto kernel) -> hipError_t {
-            hipError_t e2 = set_lds_f16(kernel, shm);
+            hipError_t e2 = set_lds(kernel, shm);
             if (e2 != hipSuccess) return e2;
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), shm, s, jp);
             return hipGetLastError();
@@ -1869,18 +1743,6 @@ hipError_t launch_joint_loss_f16(const float *enc_proj, const float *pred_proj, 
     // d enc_proj, d pred_proj, dW2, db2 from their partials: one launch (joint_kernels.hip)
     e = launch_reduce_f16_backward(d_enc_proj, jp.dApart, L.n_ut, jp.lp, J, hooks ? hooks->dmax_enc : nullptr, jp.live8, d_pred_proj, jp.dCpart, L.n_ts,
                                    hooks ? hooks->dmax_pred : nullptr, dW2, jp.dWpart, db2, jp.dbpart, L.n_ranges, V, s);
-#ifdef JH_TRACE
-    {
-        hipStreamSynchronize(s);
-        std::vector<long long> h(trace_bytes / sizeof(long long));
-        hipMemcpy(h.data(), trace_dev, trace_bytes, hipMemcpyDeviceToHost);
-        const char *path = getenv("JH_TRACE_FILE");
-        if (FILE *f = fopen(path ? path : "/tmp/jh_trace.bin", "wb")) {
-            fwrite(h.data(), 1, trace_bytes, f);
-            fclose(f);
-        }
-    }
-#endif
     return e;
 }
 

@@ -33,10 +33,6 @@
 #include "rnnt_joint_math.h"
 
 #include <math.h>
-#ifdef JH_TRACE
-#include <stdio.h>
-#include <stdlib.h>
-#endif
 
 namespace rnnt {
 
@@ -52,15 +48,6 @@ __device__ __forceinline__ float jlg2(float x) { return __builtin_amdgcn_logf(x)
 // fast_tanh, tanh_from_exp, r_from_exp, fast_r: rnnt_joint_math.h
 // row of the 32x32 MFMA C/D tile held in register `reg` of a lane in half `half` (= lane >> 5)
 __device__ __forceinline__ constexpr int cd_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
-
-#ifdef JH_TRACE
-#define JT1(slot)                                                                   \
-    do {                                                                           \
-        if (trc && lane == 0) trc[(slot)] = (long long)__builtin_amdgcn_s_memtime(); \
-    } while (0)
-#else
-#define JT1(slot) do { } while (0)
-#endif
 
 struct JointParams {
     LossParams lp;  // lattice workspace, labels, lengths, costs, cost_scale (acts/grads unused)
@@ -88,9 +75,6 @@ struct JointParams {
                          // [3] == 1: the workspace holds the state of a whole-network forward call (JointHooks::prep_mode)
     jf16 *W2s;           // [VT][J/16][2 (hi, lo)][64 lanes][8]: s2 W2 as binary16 hi + lo parts in MFMA fragment order, per vocabulary tile
     float *b2s;          // [VT][2][32]: b2[v] + sum_j W2[j][v] as an f32 hi + lo pair (-1e30 / 0 beyond V), for joint_fwd_kernel
-#ifdef JH_TRACE
-    long long *trace;    // dev builds only: s_memtime stamps of one workgroup of phase 1 and one of phase 2
-#endif
     int J, n_ut, TR, n_tr, TS, n_ts;
     int VT, vt;       // vocabulary tiles of 32 symbols (1, or 2 for 32 < V <= 64: round 5) and the tile THIS launch works on; the
                       // parked logits are [cells][32 VT], W2s / b2s / dWpart / dbpart hold VT consecutive tile images
@@ -435,11 +419,7 @@ __global__ __launch_bounds__(kP1Waves * 64) void joint_phase1s_kernel(const Join
 constexpr int kFwdWaves = 16;
 constexpr int kFwdRows = 2 * kFwdWaves;  // lattice rows per item: one row pair per wave
 
-// lane (16-lane row R, position i) <- lane (R, E): the enc-side addends of a k-step sit one per lane (see joint_fwd_kernel)
-template <int E>
-__device__ __forceinline__ float row_bcast(const float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x150 + E /*row_newbcast:E*/, 0xf, 0xf, true));
-}
+// lane (16-lane row R, position i) <- lane (R, E): the enc-side addends of a k-step sit one per lane (see joint_fwd_kernel).
 // The two rows of a wave share every pred-side factor: their enc-side addends travel as a PAIR -- ONE 64-bit DPP broadcast per
 // joint unit (v_mov_b64_dpp takes row_newbcast and overlaps with the matrix pipe like any VALU move: probe_pk.hip) instead of two
 // 32-bit ones: -30 us of the kernel's 630 at B32 T600 U150 J640.  The multiply-adds stay scalar (see bwd_consumer on packed f32).
@@ -883,10 +863,8 @@ __global__ __launch_bounds__(256) void joint_dl_kernel(const JointParams jp) {
 // upstream gradients do not fall into binary16's subnormals; dh and the dW2 partial are divided by S_b again (exact).
 // LDS: Cs [64 j][36] | dlr [4][32 u][36] | red [4][32][33]
 // ---------------------------------------------------------------------------------------------
-#ifndef P2S_WG_PER_CU
-#define P2S_WG_PER_CU 2  // 227 VGPRs, no spills: 3.18 ms per fused step at C2; 3 (168 VGPRs, 57 spilled) 5.37 ms; 1 (284) 4.42 ms
-#endif
-__global__ __launch_bounds__(256, P2S_WG_PER_CU) void joint_phase2s_kernel(const JointParams jp) {
+constexpr int kP2sWgPerCu = 2;  // 227 VGPRs, no spills: 3.18 ms per fused step at C2; 3 (168 VGPRs, 57 spilled) 5.37 ms; 1 (284) 4.42 ms
+__global__ __launch_bounds__(256, kP2sWgPerCu) void joint_phase2s_kernel(const JointParams jp) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const LossParams &p = jp.lp;
     const int J = jp.J, V = p.V;
@@ -1102,10 +1080,7 @@ constexpr int kBwdRows = 32;
 // Round 6, late: the floor is 2^-40 -- and below it nothing is lost at all.  The products take dlogits as binary16 hi + lo parts of
 // S x dlogits with S |cost_scale| < 2^13 (bwd_scale), i.e. |S dl| <= 2^14 x occupancy: below an occupancy of 2^-40 that is under 2^-26, hi and
 // lo both round to zero (the smallest binary16 subnormal is 2^-24) -- the rows between 2^-50 and 2^-40 were visited to multiply and add exact zeros.
-#ifndef RNNT_OCC_FLOOR
-#define RNNT_OCC_FLOOR 40  // (dev builds: 100000 = visit every row, for same-box timing of the pruning)
-#endif
-constexpr int kOccFloor = RNNT_OCC_FLOOR;
+constexpr int kOccFloor = 40;  // (RNNT_VISIT_ALL visits every row)
 __device__ __forceinline__ uint32_t bwd_live_mask(const JointParams &jp, const int b, const int ut, const int tr, const int t_begin, const int t_end) {
     const int n_tr32 = (jp.lp.T + 31) >> 5;
     uint32_t m = ((const uint32_t *)jp.live8)[((size_t)b * jp.n_ut + ut) * n_tr32 + tr];
@@ -1188,15 +1163,6 @@ __device__ __forceinline__ bool lds_poll_ge(const uint32_t addr, const int need)
     return false;
 }
 
-// one dlogits value (scaled by sS = cost_scale * S) of symbol v for a cell with the given set-up
-__device__ __forceinline__ float bwd_dl(const float x, const int v, const int V, const int blank, const float c0, const float sS,
-                                        const float corr_b, const float corr_l, const int lab) {
-    float d = (v < V) ? sS * jex2(fmaf(x, kLog2e, c0)) : 0.f;
-    d -= (v == blank) ? corr_b : 0.f;
-    d -= (v == lab) ? corr_l : 0.f;
-    return d;
-}
-
 template <bool SLOW>
 __device__ void bwd_consumer(const JointParams &jp, char *ring, const uint32_t seq_a, const uint32_t use_a, const int cw,
                              const int j0, const int blk, const int nblk, const int lane, const int it_lo, const int it_hi,
@@ -1256,18 +1222,6 @@ __device__ void bwd_consumer(const JointParams &jp, char *ring, const uint32_t s
 
     // software pipeline, one row deep: the A fragments of dh for the NEXT row are polled for and read while the current
     // row's products run, so that neither the sequence-word round trip nor the LDS latency sits in front of the MFMA chain
-#ifdef JH_TRACE
-    // dev builds: s_memtime stamps of consumers 0, 4, 8 (one SIMD) of workgroup 20, rows 40..71, 6 stamps per row
-    long long *trc = (blockIdx.x == 20 && (cw & 3) == 0 && cw < 12) ? jp.trace + (cw >> 2) * 256 : nullptr;
-    int rc_count = 0;
-    const long long wg_t0 = (long long)__builtin_amdgcn_s_memtime();
-#define BT(k)                                                                                          \
-    do {                                                                                               \
-        if (trc && lane == 0 && row >= 40 && row < 72) trc[(row - 40) * 6 + (k)] = (long long)__builtin_amdgcn_s_memtime(); \
-    } while (0)
-#else
-#define BT(k) do { } while (0)
-#endif
     jh8 fa[2][2];
     float aj_next = 0.f;  // e^{2 enc_proj} (or enc_proj) of the next row for this lane's joint unit, delivered with the image
     if (rows_total > 0) {
@@ -1282,15 +1236,7 @@ __device__ void bwd_consumer(const JointParams &jp, char *ring, const uint32_t s
         const BwdItem it = bwd_item(jp, item, n_tr);
         if (!it.live) continue;
         if (it.col_first != cur_bu) {
-#ifdef JH_TRACE
-            int rc_slot = -1;
-            if (trc && lane == 0 && rc_count < 12) rc_slot = 192 + 5 * rc_count, trc[rc_slot] = (long long)__builtin_amdgcn_s_memtime(), trc[rc_slot + 4] = row;
-            ++rc_count;
-#endif
             flush_C();
-#ifdef JH_TRACE
-            if (rc_slot >= 0) trc[rc_slot + 1] = (long long)__builtin_amdgcn_s_memtime();
-#endif
             cur_bu = it.col_first, cur_u0 = it.u0;
             // which of the workgroups of my group that share this column am I?  (its d pred_proj slab)
             cur_slot = blk - bwd_blk_of(jp.plan, it.col_first, nblk);
@@ -1307,20 +1253,12 @@ __device__ void bwd_consumer(const JointParams &jp, char *ring, const uint32_t s
                 const int u = min(it.u0 + cd_row(r, half), p.U - 1);
                 ec[r] = Ptab[((size_t)it.b * p.U + u) * J + j0 + l31];
             }
-#ifdef JH_TRACE
-            if (rc_slot >= 0) {
-                trc[rc_slot + 2] = (long long)__builtin_amdgcn_s_memtime();
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                trc[rc_slot + 3] = (long long)__builtin_amdgcn_s_memtime();
-            }
-#endif
         }
         for (int t = it.t_begin; t < it.t_end; ++t) {
             if (!((it.mask >> (t - it.t_begin)) & 1u)) continue;  // (no cell of this row's tile carries mass: kOccFloor)
             const float aj = aj_next;
             const int slot = row % kBwdRing;
             const jh8 *frag = (const jh8 *)(ring + (size_t)slot * kBwdSlotBytes);
-            BT(0);
             // B fragments of dW2 for this row: issued now, needed after the dh chain
             jh8 fb[2][2];
 #pragma unroll
@@ -1333,7 +1271,6 @@ __device__ void bwd_consumer(const JointParams &jp, char *ring, const uint32_t s
             float h[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) h[r] = SLOW ? fast_tanh(aj + ec[r]) : tanh_from_exp(aj, ec[r]);
-            BT(1);
             // S dh[u][j] = sum_v (S dl[u][v]) W2[j][v]
             f32x16 dh;
 #pragma unroll
@@ -1352,7 +1289,6 @@ __device__ void bwd_consumer(const JointParams &jp, char *ring, const uint32_t s
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(h[r]));
-            BT(2);
             // next row's A fragments (its sequence word first)
             if (row + 1 < rows_total) {
                 const int nslot = (row + 1) % kBwdRing;
@@ -1362,7 +1298,6 @@ __device__ void bwd_consumer(const JointParams &jp, char *ring, const uint32_t s
                 for (int ks = 0; ks < 2; ++ks) fa[ks][0] = fn[(ks * 2 + 0) * 64 + lane], fa[ks][1] = fn[(ks * 2 + 1) * 64 + lane];
                 aj_next = *(const float *)((const char *)fn + 8192 + (cw * 32 + l31) * 4);
             }
-            BT(3);
             // S dW2[j][v] += sum_u h[u][j] (S dl[u][v]): k-slot (ks, half, e) <-> lattice column cd_row(8 ks + e, half)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
@@ -1372,7 +1307,6 @@ __device__ void bwd_consumer(const JointParams &jp, char *ring, const uint32_t s
                 split_h8(hk, hhi, hlo);
                 accW = mfma3(hhi, hlo, fb[ks][0], fb[ks][1], accW);
             }
-            BT(4);
             float colsum = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -1397,7 +1331,6 @@ __device__ void bwd_consumer(const JointParams &jp, char *ring, const uint32_t s
             }
             // every read of this row's slot has returned (fb above, fa one row earlier): hand it back to the loader
             if (lane == 0) asm volatile("ds_add_u32 %0, %1" ::"v"(use_a + 4u * slot), "v"(1) : "memory");
-            BT(5);
             if (lane < 32) {
                 float *dst = jp.dApart + (((size_t)it.ut * p.B + it.b) * p.T + t) * J + j0 + lane;
                 const float val = colsum * (invS * w2inv) + (jp.vt > 0 ? *dst : 0.f);
@@ -1407,12 +1340,6 @@ __device__ void bwd_consumer(const JointParams &jp, char *ring, const uint32_t s
         }
     }
     flush_C();
-#ifdef JH_TRACE
-    if (cw == 0 && lane == 0) {  // every workgroup: {clocks from the first poll to here, rows visited}
-        jp.trace[1024 + 2 * blockIdx.x] = (long long)__builtin_amdgcn_s_memtime() - wg_t0;
-        jp.trace[1024 + 2 * blockIdx.x + 1] = rows_total;
-    }
-#endif
     // this workgroup's dW2 partial: accW is [j rows][v cols]
 #pragma unroll
     for (int r = 0; r < 16; ++r)
@@ -1744,7 +1671,7 @@ __device__ __forceinline__ uint32_t lds_ld_u16(const uint32_t addr, const int im
 }
 
 // The two producers of a workgroup turn rows of parked logits + per-cell records into the dlogits operand images of the two
-// products, alternating rows.  Round 5 (late): a s_memtime trace (-DJH_TRACE, scripts/probes/bwd_trace.py) showed the kernel
+// products, alternating rows.  Round 5 (late): a s_memtime trace (an instrumented build, since removed) showed the kernel
 // PRODUCER-bound -- 7,470 clocks per own row against 3,736 per row for the consumers, which sat in their sequence-word poll for
 // 600 ... 1,500 of them: a producer evaluated every dlogits value TWICE (once per operand layout: 16 more scattered loads of the
 // logits, the per-cell records through an LDS scratch, 16 more exponentials) in ~1,100 instructions per row.  Now it evaluates
@@ -1779,27 +1706,14 @@ __device__ void bwd_producer(const JointParams &jp, char *ring, const uint32_t s
     iter.init(jp, it_lo, it_hi, n_tr);
     if (pw == 1 && iter.valid) iter.next(jp);
     int row = pw;
-#ifdef JH_TRACE
-    // producer stamps of workgroup 20, its rows 40..71: 0 = top of the iteration, 1 = next row's loads issued, 2 = slot free,
-    // 3 = row published
-    long long *ptrc = (blk == 10 && group == 0) ? jp.trace + 768 + pw * 64 : nullptr;
-#define PT(k)                                                                                                      \
-    do {                                                                                                           \
-        if (ptrc && lane == 0 && row >= 40 && row < 72) ptrc[((row - 40) >> 1) * 4 + (k)] = (long long)__builtin_amdgcn_s_memtime(); \
-    } while (0)
-#else
-#define PT(k) do { } while (0)
-#endif
     BwdRowLoads L;
     if (iter.valid) bwd_row_loads(jp, iter.it, iter.t, Etab, n_cons, group, lane, L);
     while (iter.valid) {
         // ---- my next row's loads go out before this row's arithmetic: a producer never sits behind a memory round trip
-        PT(0);
         iter.next(jp);
         if (iter.valid) iter.next(jp);
         BwdRowLoads Ln = L;
         if (iter.valid) bwd_row_loads(jp, iter.it, iter.t, Etab, n_cons, group, lane, Ln);
-        PT(1);
         if (L.b != cur_b) {
             float S;
             bwd_scale(p, L.b, S, invS);
@@ -1809,7 +1723,6 @@ __device__ void bwd_producer(const JointParams &jp, char *ring, const uint32_t s
         const bool valid = L.u0 + l31 < L.Ub;
         // ---- the slot must be free: every consumer has finished the row that used it kBwdRing rows ago
         if (row >= kBwdRing && !lds_poll_ge(use_a + 4u * slot, n_cons * (row / kBwdRing))) poisoned = true;
-        PT(2);
         char *slotp = ring + (size_t)slot * kBwdSlotBytes;
         jh8 *frag = (jh8 *)slotp;
         // ---- A fragments of dh (row = this lane's lattice column, k = symbol 16 ks + 8 half + e of the tile): the dlogits values
@@ -1874,7 +1787,6 @@ __device__ void bwd_producer(const JointParams &jp, char *ring, const uint32_t s
             }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the row's fragments and addends are in LDS
         if (lane == 0) asm volatile("ds_write_b32 %0, %1" ::"v"(seq_a + 4u * slot), "v"(row + 1) : "memory");
-        PT(3);
         L = Ln;
         row += 2;
     }
@@ -1921,9 +1833,6 @@ __global__ __launch_bounds__(768) void joint_bwd_kernel(const JointParams jp) {
         for (int i = tid; i < n_c; i += (int)blockDim.x) {
             const BwdItem it = bwd_item<false>(jp, it_lo + i, n_tr);
             bwd_item_cache[i].mask = it.mask, bwd_item_cache[i].Tb = it.Tb, bwd_item_cache[i].Ub = it.Ub;
-#ifdef JH_TRACE
-            if (blockIdx.x < 8 && (blockIdx.x & 1) == 0 && i < 24) jp.trace[1536 + 24 * (blockIdx.x >> 1) + i] = it.mask;
-#endif
         }
         if (tid == 0) bwd_item_cache_lo = it_lo, bwd_item_cache_n = n_c;
     }
@@ -1994,9 +1903,6 @@ __device__ __forceinline__ void reduce_partials_body(float *out, const float *in
     }
     if (bmslot) store_block_max(bm, bmslot);
 }
-__global__ __launch_bounds__(256) void reduce_partials_kernel(float *out, const float *in, int nparts, size_t n, unsigned *blockmax) {
-    reduce_partials_body(out, in, nparts, n, blockIdx.x, gridDim.x, blockmax ? blockmax + blockIdx.x : nullptr, 0.f);
-}
 
 // d enc_proj[b][t][:] = sum over the u-tiles of their partial rows, in u-tile order.  Every backward kernel writes the row
 // (ut, b, t) exactly when the u-tile starts inside the utterance's label range and t < T_b, and never otherwise: the reduction
@@ -2061,10 +1967,6 @@ __device__ __forceinline__ void reduce_enc_body(float *out, const float *in, con
         bm = max(bm, absbits4(s));
     }
     if (bmslot) store_block_max(bm, bmslot);
-}
-__global__ __launch_bounds__(256) void reduce_enc_kernel(float *out, const float *in, int n_ut, const LossParams p, int J,
-                                                         unsigned *blockmax, const uint8_t *live8) {
-    reduce_enc_body(out, in, n_ut, p, J, blockIdx.x, gridDim.x, blockmax ? blockmax + blockIdx.x : nullptr, 0.f, live8);
 }
 
 // d pred_proj[b][u][:] from the partial slabs of joint_bwd_kernel: an (utterance, u-tile) is written by the workgroups of a J
@@ -2242,14 +2144,6 @@ hipError_t launch_joint_loss_f16(const float *enc_proj, const float *pred_proj, 
                                  float *d_enc_proj, float *d_pred_proj, float *dW2, float *db2, int phases,
                                  void *workspace, hipStream_t s, const JointHooks *hooks);
 
-// d enc_proj from its [n_ut][B][T][J] partial rows (reduce_enc_kernel); shared with the f16 joint
-hipError_t launch_reduce_enc(float *out, const float *in, int n_ut, const LossParams &lp, int J, hipStream_t s, unsigned *blockmax,
-                             const uint8_t *live8) {
-    if ((unsigned long long)lp.B * lp.T * J >= (1ull << 32)) return hipErrorInvalidValue;  // 32-bit element indices in the kernel
-    hipLaunchKernelGGL(reduce_enc_kernel, dim3(kHookBlocks), dim3(256), 0, s, out, in, n_ut, lp, J, blockmax, live8);
-    return hipGetLastError();
-}
-
 // The four reductions behind the f16 joint's backward in ONE launch (round 6; four launches before, 23 us + a launch gap apiece at
 // the small end): blocks [0, kHookBlocks) d enc_proj from its u-tile partial rows, [kHookBlocks, 2 kHookBlocks) d pred_proj from its
 // row-strip slabs, then gW blocks of dW2 and gB blocks of db2 from K4's range partials.  The same bodies, the same association per
@@ -2273,13 +2167,6 @@ hipError_t launch_reduce_f16_backward(float *d_enc, const float *dApart, int n_u
     const unsigned gW = (unsigned)(nW < 1024 ? nW : 1024), gB = (unsigned)(nB < 1024 ? nB : 1024);
     hipLaunchKernelGGL(reduce_f16_backward_kernel, dim3(2u * kHookBlocks + gW + gB), dim3(256), 0, s, d_enc, dApart, n_ut, lp, J, bm_enc, live8, d_pred,
                        dCpart, nC, bm_pred, dW2, dWpart, db2, dbpart, nR, V, gW, gB);
-    return hipGetLastError();
-}
-
-hipError_t launch_reduce_partials(float *out, const float *in, int nparts, size_t n, hipStream_t s, unsigned *blockmax) {
-    // (a consumer of `blockmax` reads kHookBlocks entries: the grid is then exactly that, whatever n is)
-    const unsigned grid = blockmax ? (unsigned)kHookBlocks : (unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(grid), dim3(256), 0, s, out, in, nparts, n, blockmax);
     return hipGetLastError();
 }
 
@@ -2345,20 +2232,6 @@ hipError_t joint_workspace_bytes(int T, int U, int B, int J, int V, int joint_dt
 bool fill_loss_params(LossParams &p, const float *acts, float *grads, const int *labels, const int *label_lengths,
                       const int *input_lengths, const float *cost_scale, int V, int B, float *costs, void *workspace,
                       int maxT, int maxU, int blank);
-
-// compute units of the current device (persistent kernels launch one workgroup per CU)
-static int device_cu_count() {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 256;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 256;
-    return n;
-}
-
-template <typename K>
-static hipError_t set_lds(K kernel, size_t bytes) {
-    if (bytes <= 65536) return hipSuccess;
-    return hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
 
 // logits[c][0..V) <- the parked tiles dl[c][0..Vp) (bias included; Vp = 32 or 64)
 __global__ __launch_bounds__(256) void joint_logits_copy_kernel(float *out, const float *dl, const uint32_t cells, const int V, const int Vp) {
@@ -2430,9 +2303,6 @@ hipError_t launch_joint_logits(const float *enc_proj, const float *pred_proj, co
     jp.J = J;
     joint_bind(jp, L, ws);
     jp.d_enc_proj = jp.d_pred_proj = jp.dW2 = jp.db2 = nullptr;
-#ifdef JH_TRACE
-    jp.trace = nullptr;
-#endif
     jp.logits_only = 1, jp.tables_ready = 0;
     hipError_t e;
     if ((e = launch_fill2(jp.tflag, 0, 256, labels, 0, U > 1 ? (size_t)B * (U - 1) * sizeof(int) : 0, s)) != hipSuccess) return e;
@@ -2448,12 +2318,11 @@ hipError_t launch_joint_logits(const float *enc_proj, const float *pred_proj, co
 // the hand-back launch of the fused joint (joint_redo_kernel) with the chunk geometry of the utterance's sweeps
 template <int K, int G>
 static hipError_t launch_joint_redo_k(const JointParams &jp, const LossParams &q, const bool want_rec, hipStream_t s) {
-    constexpr int NB = ((size_t)4 * G * 2 * 64 * K * sizeof(float) + 16 <= 128 * 1024) ? 4 : 3;
-    constexpr size_t shm = (size_t)NB * G * 2 * 64 * K * sizeof(float) + 16;
-    hipError_t e = set_lds(joint_redo_kernel<K, G, NB>, shm);
+    using R = SweepRing<K, G>;
+    hipError_t e = set_lds(joint_redo_kernel<K, G, R::NB>, R::kBytes);
     if (e != hipSuccess) return e;
     const int team = redo_team_size(jp.lp.nb, jp.lp.T, jp.lp.U, device_cu_count());
-    hipLaunchKernelGGL((joint_redo_kernel<K, G, NB>), dim3(jp.lp.nb * team), dim3(kRedoThreads), shm, s, jp, q, want_rec ? 1 : 0, team);
+    hipLaunchKernelGGL((joint_redo_kernel<K, G, R::NB>), dim3(jp.lp.nb * team), dim3(kRedoThreads), R::kBytes, s, jp, q, want_rec ? 1 : 0, team);
     return hipGetLastError();
 }
 static hipError_t launch_joint_redo(const JointParams &jp, const bool want_rec, hipStream_t s) {
@@ -2461,17 +2330,7 @@ static hipError_t launch_joint_redo(const JointParams &jp, const bool want_rec, 
     LossParams q = jp.lp;
     q.acts = jp.dl, q.grads = nullptr, q.V = 32 * jp.VT;
     q.divV = make_fastdiv((uint32_t)q.V);
-    switch (sweep_K(jp.lp.U)) {
-        case 1: return launch_joint_redo_k<1, 16>(jp, q, want_rec, s);
-        case 2: return launch_joint_redo_k<2, 16>(jp, q, want_rec, s);
-        case 3: return launch_joint_redo_k<3, 16>(jp, q, want_rec, s);
-        case 4: return launch_joint_redo_k<4, 16>(jp, q, want_rec, s);
-        case 6: return launch_joint_redo_k<6, 8>(jp, q, want_rec, s);
-        case 8: return launch_joint_redo_k<8, 8>(jp, q, want_rec, s);
-        case 12: return launch_joint_redo_k<12, 4>(jp, q, want_rec, s);
-        case 16: return launch_joint_redo_k<16, 4>(jp, q, want_rec, s);
-        default: return hipErrorInvalidValue;
-    }
+    return sweep_dispatch(jp.lp.U, [&](auto K, auto G) { return launch_joint_redo_k<K, G>(jp, q, want_rec, s); });
 }
 
 hipError_t launch_joint_loss(const float *enc_proj, const float *pred_proj, const float *W2, const float *b2,
@@ -2499,13 +2358,6 @@ hipError_t launch_joint_loss(const float *enc_proj, const float *pred_proj, cons
     jp.J = J;
     joint_bind(jp, L, ws);
     jp.d_enc_proj = d_enc_proj, jp.d_pred_proj = d_pred_proj, jp.dW2 = dW2, jp.db2 = db2;
-#ifdef JH_TRACE
-    static long long *trace_dev = nullptr;
-    const size_t trace_bytes = 2048 * sizeof(long long);
-    if (!trace_dev) (void)hipMalloc(&trace_dev, trace_bytes);
-    (void)hipMemsetAsync(trace_dev, 0, trace_bytes, s);
-    jp.trace = trace_dev;
-#endif
     jp.logits_only = 0;
     jp.visit_all = (phases & 8) ? 1 : 0;
     const int prep_mode = hooks ? hooks->prep_mode : 0;
@@ -2578,18 +2430,6 @@ hipError_t launch_joint_loss(const float *enc_proj, const float *pred_proj, cons
     const unsigned nWblk = (unsigned)(J * V + 31) / 32u;
     hipLaunchKernelGGL(joint_reduce_kernel, dim3(2u * kHookBlocks + nWblk + (unsigned)L.VT), dim3(256), 0, s, jp, L.wide ? 0 : 1, nC, nW, nDb,
                        hooks ? hooks->dmax_enc : (unsigned *)nullptr, hooks ? hooks->dmax_pred : (unsigned *)nullptr);
-#ifdef JH_TRACE
-    {
-        (void)hipStreamSynchronize(s);
-        static long long h[2048];
-        (void)hipMemcpy(h, trace_dev, trace_bytes, hipMemcpyDeviceToHost);
-        const char *path = getenv("JH_TRACE_FILE32");
-        if (FILE *f = fopen(path ? path : "/tmp/j32_trace.bin", "wb")) {
-            fwrite(h, 1, trace_bytes, f);
-            fclose(f);
-        }
-    }
-#endif
     return hipGetLastError();
 }
 

@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace rnnt {
 
 constexpr float kNeg = -1.0e30f;      // "log zero" that survives additions without inf-inf
@@ -101,6 +103,33 @@ inline int sweep_K(int U) {
     for (int a : avail)
         if (k <= a) return a;
     return 0;
+}
+// The chunk ring in LDS of the register-resident sweeps and of the hand-back kernels that run them (NB chunks of G diagonals x
+// 2 x 64 lanes x K columns in float32, plus 16 bytes of flag words): four chunks where they fit in 128 KiB, else three.
+template <int K, int G>
+struct SweepRing {
+    static constexpr size_t kChunk = (size_t)G * 2 * 64 * K * sizeof(float);
+    static constexpr int NB = (4 * kChunk + 16 <= 128 * 1024) ? 4 : 3;
+    static constexpr size_t kBytes = NB * kChunk + 16;
+    static_assert(kBytes <= 160 * 1024, "chunk ring exceeds the LDS");
+};
+// Calls f(K, G) with the <K, G> pair (as std::integral_constant) of the register-resident sweeps for U lattice columns:
+// K = sweep_K(U), chunk length G = the longest whose ring fits the LDS (measured at C2: G = 16 beats 8 by 3 % of the step,
+// 4 loses 5 %).  hipErrorInvalidValue beyond 1024 columns.
+template <typename F>
+inline hipError_t sweep_dispatch(int U, F &&f) {
+    using std::integral_constant;
+    switch (sweep_K(U)) {
+        case 1: return f(integral_constant<int, 1>(), integral_constant<int, 16>());
+        case 2: return f(integral_constant<int, 2>(), integral_constant<int, 16>());
+        case 3: return f(integral_constant<int, 3>(), integral_constant<int, 16>());
+        case 4: return f(integral_constant<int, 4>(), integral_constant<int, 16>());
+        case 6: return f(integral_constant<int, 6>(), integral_constant<int, 8>());
+        case 8: return f(integral_constant<int, 8>(), integral_constant<int, 8>());
+        case 12: return f(integral_constant<int, 12>(), integral_constant<int, 4>());
+        case 16: return f(integral_constant<int, 16>(), integral_constant<int, 4>());
+        default: return hipErrorInvalidValue;
+    }
 }
 // Byte every W word is pre-filled with: 0xF1F1F1F1 = -2.39e30f, a finite "log zero".
 constexpr int kFillByte = 0xF1;
@@ -193,6 +222,21 @@ __device__ __forceinline__ void lds_dma16(const void *global, void *lds) {
     __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) const void *)global, (__attribute__((address_space(3))) void *)lds, 16, 0, 0);
 }
 #endif
+
+// Compute units of the current device (persistent kernels launch one workgroup per CU).  Asked on every call: a process may
+// drive several GPUs.
+inline int device_cu_count() {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 256;
+    return n;
+}
+// Lets `kernel` take `bytes` of dynamic LDS when that is more than 64 KiB.  Per device and cheap: set before every launch.
+template <typename Kernel>
+inline hipError_t set_lds(Kernel kernel, size_t bytes) {
+    if (bytes <= 64 * 1024) return hipSuccess;
+    return hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
 
 // Every fill the library enqueues goes through its own kernel, not hipMemsetAsync: a memset NODE recorded by stream capture
 // replayed a 16-byte garbage pattern instead of the 0xF1 bytes on this stack (ROCm 7.2, found by the HIP-graph tests) -- the

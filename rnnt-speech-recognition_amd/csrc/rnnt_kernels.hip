@@ -445,14 +445,10 @@ __global__ __launch_bounds__(128) void sweep_ld_kernel(const LossParams p) {
 
 template <int K, int G>
 static hipError_t launch_sweep_ld(const LossParams &p, hipStream_t s) {
-    constexpr int NB = ((size_t)4 * G * 2 * 64 * K * sizeof(float) + 16 <= 128 * 1024) ? 4 : 3;
-    constexpr size_t shm = (size_t)NB * G * 2 * 64 * K * sizeof(float) + 16;
-    static_assert(shm <= 160 * 1024, "chunk ring exceeds the LDS");
-    if (shm > 64 * 1024) {  // per device and cheap: set on every launch (a process may drive several GPUs)
-        hipError_t e = hipFuncSetAttribute((const void *)sweep_ld_kernel<K, G, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((sweep_ld_kernel<K, G, NB>), dim3(2 * p.nb), dim3(128), shm, s, p);
+    using R = SweepRing<K, G>;
+    hipError_t e = set_lds(sweep_ld_kernel<K, G, R::NB>, R::kBytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((sweep_ld_kernel<K, G, R::NB>), dim3(2 * p.nb), dim3(128), R::kBytes, s, p);
     return hipGetLastError();
 }
 
@@ -566,30 +562,17 @@ __global__ __launch_bounds__(1024) void sweep_wide_kernel(const LossParams p) {
 static hipError_t launch_sweep_wide(const LossParams &p, hipStream_t s) {
     const size_t shm = (size_t)2 * p.Up * sizeof(double) + (size_t)p.NG * sizeof(float);  // two diagonals in float64 + the groups' maxima
     hipError_t e;
-    if (shm > 64 * 1024) {
-        if ((e = hipFuncSetAttribute((const void *)sweep_wide_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)) != hipSuccess) return e;
-        if ((e = hipFuncSetAttribute((const void *)sweep_wide_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)) != hipSuccess) return e;
-    }
+    if ((e = set_lds(sweep_wide_kernel<false>, shm)) != hipSuccess) return e;
+    if ((e = set_lds(sweep_wide_kernel<true>, shm)) != hipSuccess) return e;
     hipLaunchKernelGGL((sweep_wide_kernel<false>), dim3(p.nb), dim3(1024), shm, s, p);
     hipLaunchKernelGGL((sweep_wide_kernel<true>), dim3(p.nb), dim3(1024), shm, s, p);  // (the gradient pass needs both; the
     // alpha launch is not a dependency of the beta launch, but one stream keeps the caller's ordering contract simple)
     return hipGetLastError();
 }
 
-// Chunk length G (diagonals per LDS-DMA batch): the longest whose ring fits the LDS (measured at C2: G = 16 beats 8 by
-// 3 % of the step, 4 loses 5 %).
 hipError_t launch_sweeps(const LossParams &p, hipStream_t s) {
-    switch (sweep_K(p.U)) {
-        case 1: return launch_sweep_ld<1, 16>(p, s);
-        case 2: return launch_sweep_ld<2, 16>(p, s);
-        case 3: return launch_sweep_ld<3, 16>(p, s);
-        case 4: return launch_sweep_ld<4, 16>(p, s);
-        case 6: return launch_sweep_ld<6, 8>(p, s);
-        case 8: return launch_sweep_ld<8, 8>(p, s);
-        case 12: return launch_sweep_ld<12, 4>(p, s);
-        case 16: return launch_sweep_ld<16, 4>(p, s);
-        default: return (p.U <= kMaxU) ? launch_sweep_wide(p, s) : hipErrorInvalidValue;  // 1024 < maxU <= 8192
-    }
+    if (sweep_K(p.U) == 0) return (p.U <= kMaxU) ? launch_sweep_wide(p, s) : hipErrorInvalidValue;  // 1024 < maxU <= 8192
+    return sweep_dispatch(p.U, [&](auto K, auto G) { return launch_sweep_ld<K, G>(p, s); });
 }
 
 }  // namespace rnnt

@@ -35,7 +35,6 @@ constexpr float kTinyEdge = 7.8886091e-31f;  // 2^-100: an edge the lattice owns
 enum { kFlagA = 0, kFlagB = 1, kFlagG = 2, kFlagState = 3 };  // state: 0 linear lattice, 2 log-domain lattice ready (after a redo)
 
 __device__ __forceinline__ void st_i32_wt(int *q, int v) { __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int ld_i32_sc1(const int *q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float frexp_m(float x) { return __builtin_amdgcn_frexp_mantf(x); }  // in [0.5, 1); 0 -> 0
 __device__ __forceinline__ int frexp_e(float x) { return __builtin_amdgcn_frexp_expf(x); }      // 0 for x == 0
 __device__ __forceinline__ float ldexp_f(float x, int e) { return __builtin_ldexpf(x, e); }     // v_ldexp_f32

@@ -491,13 +491,6 @@ __global__ __launch_bounds__(kRedoThreads) void lin_redo_kernel(const LossParams
     uint32_t lo, hi;
     redo_cell_range(p, b, tm, lo, hi);
     if (p.grads) redo_cells<true>(p, lo, hi, tid, lds, NB * chunkf);
-#ifdef RNNT_REDO_TRACE
-    REDO_STAMP(tm, 7);
-    if (redo && tid == 0 && blockIdx.x < 8)
-        printf("redo trace wg %d t0 %lld (clocks): fill %lld | sync %lld | lsm %lld | sync %lld | sweep %lld | sync %lld | grad %lld\n", (int)blockIdx.x, tm.ts[0] % 100000000ll,
-               tm.ts[1] - tm.ts[0], tm.ts[2] - tm.ts[1], tm.ts[3] - tm.ts[2], tm.ts[4] - tm.ts[3], tm.ts[5] - tm.ts[4], tm.ts[6] - tm.ts[5],
-               tm.ts[7] - tm.ts[6]);
-#endif
     if (!tm.ok) {  // a team member never arrived (bounded spin): the utterance's results must not look valid
         if (p.costs && tm.k == 0 && tid == 0) st_f32_wt(p.costs + b, NAN);
         if (p.grads)
@@ -512,68 +505,32 @@ __global__ __launch_bounds__(kRedoThreads) void lin_redo_kernel(const LossParams
 // sweeps cover (up to 1024 columns).  One frame per lane spans up to 16 columns there: lattices on which that is too coarse
 // (more label columns than frames, unstructured logits) fail the certificate and are redone in the log domain.
 // (V >= 2: the lsm pass parks a cell's two edge probabilities in the cell's own LDS slot of V floats)
-static int lin_cu_count() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t pr;
-        n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
-    }
-    return n;
-}
-
 bool lin_path_ok(const LossParams &p) { return p.V >= 2 && sweep_K(p.U) >= 1 && tile_path_ok(p, false); }
 
 template <int K, int G>
 static hipError_t launch_lin_sweep(const LossParams &p, hipStream_t s) {
-    constexpr int NB = ((size_t)4 * G * 2 * 64 * K * sizeof(float) + 16 <= 128 * 1024) ? 4 : 3;
-    constexpr size_t shm = (size_t)NB * G * 2 * 64 * K * sizeof(float) + 16;
-    static_assert(shm <= 160 * 1024 && 2 * kLinLoaders * sizeof(int) <= 16, "chunk ring exceeds the LDS");
-    if (shm > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)lin_sweep_kernel<K, G, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((lin_sweep_kernel<K, G, NB>), dim3(2 * p.nb), dim3(64 * (1 + kLinLoaders)), shm, s, p);
+    using R = SweepRing<K, G>;
+    static_assert(2 * kLinLoaders * sizeof(int) <= 16, "the loaders' flag words exceed the ring's 16 bytes");
+    hipError_t e = set_lds(lin_sweep_kernel<K, G, R::NB>, R::kBytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((lin_sweep_kernel<K, G, R::NB>), dim3(2 * p.nb), dim3(64 * (1 + kLinLoaders)), R::kBytes, s, p);
     return hipGetLastError();
 }
 template <int K, int G>
 static hipError_t launch_lin_redo(const LossParams &p, const bool force, hipStream_t s) {
-    constexpr int NB = ((size_t)4 * G * 2 * 64 * K * sizeof(float) + 16 <= 128 * 1024) ? 4 : 3;
-    constexpr size_t shm = (size_t)NB * G * 2 * 64 * K * sizeof(float) + 16;
-    if (shm > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)lin_redo_kernel<K, G, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return e;
-    }
-    const int team = redo_team_size(p.nb, p.T, p.U, lin_cu_count());
-    hipLaunchKernelGGL((lin_redo_kernel<K, G, NB>), dim3(p.nb * team), dim3(kRedoThreads), shm, s, p, force ? 1 : 0, team);
+    using R = SweepRing<K, G>;
+    hipError_t e = set_lds(lin_redo_kernel<K, G, R::NB>, R::kBytes);
+    if (e != hipSuccess) return e;
+    const int team = redo_team_size(p.nb, p.T, p.U, device_cu_count());
+    hipLaunchKernelGGL((lin_redo_kernel<K, G, R::NB>), dim3(p.nb * team), dim3(kRedoThreads), R::kBytes, s, p, force ? 1 : 0, team);
     return hipGetLastError();
 }
 
 hipError_t launch_sweeps_lin(const LossParams &p, hipStream_t s) {
-    switch (sweep_K(p.U)) {
-        case 1: return launch_lin_sweep<1, 16>(p, s);
-        case 2: return launch_lin_sweep<2, 16>(p, s);
-        case 3: return launch_lin_sweep<3, 16>(p, s);
-        case 4: return launch_lin_sweep<4, 16>(p, s);
-        case 6: return launch_lin_sweep<6, 8>(p, s);
-        case 8: return launch_lin_sweep<8, 8>(p, s);
-        case 12: return launch_lin_sweep<12, 4>(p, s);
-        case 16: return launch_lin_sweep<16, 4>(p, s);
-        default: return hipErrorInvalidValue;
-    }
+    return sweep_dispatch(p.U, [&](auto K, auto G) { return launch_lin_sweep<K, G>(p, s); });
 }
 hipError_t launch_redo_lin(const LossParams &p, const bool force, hipStream_t s) {
-    switch (sweep_K(p.U)) {
-        case 1: return launch_lin_redo<1, 16>(p, force, s);
-        case 2: return launch_lin_redo<2, 16>(p, force, s);
-        case 3: return launch_lin_redo<3, 16>(p, force, s);
-        case 4: return launch_lin_redo<4, 16>(p, force, s);
-        case 6: return launch_lin_redo<6, 8>(p, force, s);
-        case 8: return launch_lin_redo<8, 8>(p, force, s);
-        case 12: return launch_lin_redo<12, 4>(p, force, s);
-        case 16: return launch_lin_redo<16, 4>(p, force, s);
-        default: return hipErrorInvalidValue;
-    }
+    return sweep_dispatch(p.U, [&](auto K, auto G) { return launch_lin_redo<K, G>(p, force, s); });
 }
 
 }  // namespace rnnt

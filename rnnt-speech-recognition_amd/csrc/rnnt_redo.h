@@ -32,27 +32,14 @@ struct RedoTeam {
     int k, n;   // this workgroup's index in the team (only the LAST phase -- the caller's, which nobody waits for -- is dealt by it), team size
     int *bar;   // the utterance's counters (zeroed by the forward sweeps)
     bool ok;    // false once a bounded spin gave up: the caller poisons its outputs
-#ifdef RNNT_REDO_TRACE  // dev builds: s_memtime stamps of the phases (printed by member 0 of the launch's first utterance)
-    long long ts[8];
-#endif
 };
-#ifdef RNNT_REDO_TRACE
-#define REDO_STAMP(tm, i) ((tm).ts[i] = (long long)__builtin_amdgcn_s_memtime())
-#else
-#define REDO_STAMP(tm, i) ((void)0)
-#endif
 
 // Workgroups per flagged utterance: the whole chip for a small batch, at least ~1024 lattice cells per part.
 inline int redo_team_size(int nb, int T, int U, int cus) {
-#ifdef RNNT_REDO_TEAM  // dev builds: fixed team size (timing experiments)
-    (void)nb, (void)T, (void)U, (void)cus;
-    return RNNT_REDO_TEAM;
-#else
     int t = (cus > 0 ? cus : 256) / (nb > 0 ? nb : 1);
     const long long cells = (long long)T * U;
     if ((long long)t * 1024 > cells) t = (int)(cells / 1024);
     return t < 1 ? 1 : (t > 16 ? 16 : t);
-#endif
 }
 
 // A ticket of phase `ph`: the index of a part nobody else works on (>= the phase's part count: none left).  Workgroup-uniform.
@@ -218,14 +205,11 @@ __device__ __forceinline__ void redo_lattice(const LossParams &p, const int b, R
     uint32_t *Wb = (uint32_t *)(p.W + (size_t)b * p.Nr * 2 * p.Up);
     const uint32_t lz = (uint32_t)kFillByte * 0x01010101u;
     const size_t nW = (size_t)p.Nr * 2 * p.Up;
-    REDO_STAMP(tm, 0);
     for (int part = team_take(tm, 0, tid); part < tm.n; part = team_take(tm, 0, tid)) {
         for (size_t i = (size_t)part * kRedoThreads + tid; i < nW; i += (size_t)tm.n * kRedoThreads) st_i32_wt((int *)Wb + i, (int)lz);
         team_done(tm, 0, tid);
     }
-    REDO_STAMP(tm, 1);
     team_wait(tm, 0, tm.n, tid);
-    REDO_STAMP(tm, 2);
     // ---- phase 1: the cells' edge weights ----
     for (int part = team_take(tm, 1, tid); part < tm.n; part = team_take(tm, 1, tid)) {
         uint32_t lo, hi;
@@ -233,9 +217,7 @@ __device__ __forceinline__ void redo_lattice(const LossParams &p, const int b, R
         redo_cells<false>(p, lo, hi, tid, lds, NB * chunkf);
         team_done(tm, 1, tid);
     }
-    REDO_STAMP(tm, 3);
     team_wait(tm, 1, tm.n, tid);
-    REDO_STAMP(tm, 4);
     // ---- phase 2: the log-domain sweeps (float64 recurrence: whatever failed the certificate is a hard input), two parts:
     //      alpha and beta (side by side on two workgroups, or one after the other); waves 0 (sweeping) and 1 (loading) ----
     int *ctr = (int *)(lds + NB * chunkf);
@@ -258,9 +240,7 @@ __device__ __forceinline__ void redo_lattice(const LossParams &p, const int b, R
         }
         team_done(tm, 2, tid);
     }
-    REDO_STAMP(tm, 5);
     team_wait(tm, 2, 2, tid);
-    REDO_STAMP(tm, 6);
     if (tm.k == 0 && tid == 0) st_i32_wt(p.flags + 4 * b + kFlagState, 2);  // "log-domain lattice ready": later calls honour it
 }
 

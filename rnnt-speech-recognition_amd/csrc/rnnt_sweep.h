@@ -50,19 +50,6 @@ __device__ __forceinline__ void dma_rows(const float *g, float *l, int n16, int 
     }
 }
 
-// Re-basing reference of the WIDE sweep (1024 < U <= 8192; the register-resident sweeps re-base per lane, see rebase_lane):
-// the lattice cell on the straight line (0,0)->(T_b-1,U_b-1) -- NOT the row maximum: for near-uniform posteriors the
-// alpha-maximum of a diagonal sits at the binomial centre, ~e^(0.19 n) above the cells that matter.
-struct RidgeLine {
-    uint32_t slope_fx;  // (U_b-1)/(N_b-1) in 16.16 fixed point
-    __device__ __forceinline__ int u_at(int n) const { return (int)(((uint32_t)n * slope_fx + 32768u) >> 16); }
-};
-__device__ __forceinline__ RidgeLine make_ridge(int Ub, int Nb) {
-    RidgeLine r;
-    r.slope_fx = (Nb > 1) ? (((uint32_t)(Ub - 1) << 16) / (uint32_t)(Nb - 1)) : 0u;
-    return r;
-}
-
 // ---------------------------------------------------------------------------------------------
 // Precision control, per LANE.  Every lane keeps its own cumulative INTEGER offset (exact in f32) for the K lattice columns
 // it owns: true value = stored value + off[lane].  Every kRebase diagonals a lane re-bases against its own maximum, so the
@@ -108,9 +95,6 @@ __device__ __forceinline__ void rebase_lane(float (&v)[K], SweepState &st, const
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// number of store instructions store_diag<K, true> issues (pieces of 4 dwords, then one of 3, 2 or 1)
-constexpr int store_pieces(int K) { return K / 4 + ((K % 4) ? 1 : 0); }
 
 // Write one diagonal's K values of this lane: `row` is the wave-uniform row base (SGPR pair), `voff`
 // the lane's byte offset.  COUNTED: explicit instructions so that the number of VMEM operations per

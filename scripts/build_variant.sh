@@ -1,18 +1,18 @@
 #!/bin/bash
-# Dev tool: build an experimental variant of libwarprnnt.so with extra -D flags, e.g.
-#   scripts/build_variant.sh trace -DJH_TRACE      -> rnnt-speech-recognition_amd/lib/libwarprnnt_trace.so
+# Dev tool: build the library of another revision for same-box A/B, e.g.
+#   scripts/build_variant.sh base HEAD~1   -> rnnt-speech-recognition_amd/lib/libwarprnnt_base.so
 # and run anything with RNNT_LIBWARPRNNT=<that path> to load it instead of the product library.
-# (Same per-source flags as rnnt-speech-recognition_amd/build.py.)
-set -e
-NAME=$1; shift
-D=$(cd "$(dirname "$0")/.." && pwd)/rnnt-speech-recognition_amd
-F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wno-inline-asm"
+# The revision is exported into a scratch directory and built there by its own build.py (its sources, its flags).
+set -euo pipefail
+[ $# -eq 2 ] || { echo "usage: $0 NAME REV" >&2; exit 2; }
+NAME=$1
+REV=$2
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 T=$(mktemp -d)
-for s in rnnt_kernels rnnt_lin_kernels joint_kernels joint_f16_kernels dense_kernels rnnt_entrypoint; do
-  X="-fno-slp-vectorize"; [[ $s == rnnt_kernels || $s == rnnt_entrypoint ]] && X=""
-  /opt/rocm/bin/hipcc $F $X "$@" -c $D/csrc/$s.hip -o $T/$s.o &
-done
-wait
-/opt/rocm/bin/hipcc $F -shared $T/*.o -o $D/lib/libwarprnnt_$NAME.so
-rm -rf $T
-echo $D/lib/libwarprnnt_$NAME.so
+trap 'rm -rf "$T"' EXIT
+git -C "$ROOT" archive "$REV" | tar -x -C "$T"
+python "$T/rnnt-speech-recognition_amd/build.py" >/dev/null
+OUT=$ROOT/rnnt-speech-recognition_amd/lib/libwarprnnt_$NAME.so
+mkdir -p "$(dirname "$OUT")"
+cp "$T/rnnt-speech-recognition_amd/lib/libwarprnnt.so" "$OUT"
+echo "$OUT"
