@@ -411,6 +411,55 @@ RNNT_API rnntStatus_t compute_rnnt_greedy_step(const float *pred_proj, int *hyps
                                                int joint_size, int alphabet_size, int minibatch, int joint_dtype,
                                                void *workspace, rnntOptions options);
 
+/* Build-only extension: batched BEAM SEARCH ("modified" beam search: one symbol per frame, frame-synchronous, as the k2 /
+ * icefall recipes).  The caller steps the prediction network for every hypothesis row; the library evaluates the joint of
+ * every hypothesis (the greedy decoder's: every logit bitwise that of compute_rnnt_joint_logits for the hypothesis alone),
+ * ranks the candidates and keeps the beam, without writing logits.
+ *
+ * Per utterance b (T_b = frame_lengths[b] clamped into [0, maxT]; blank = options.blank_label): the beam holds up to `beam`
+ * hypotheses (y, s), y a token sequence, s a float64 log score; at the start [((), 0)].  Per frame t < T_b:
+ *   1. per hypothesis i: logits_i = tanh(enc_proj[b, t] + pred_proj[i]) @ W2 + b2 (f32), lse_i = logsumexp(logits_i) (f32
+ *      partial sums per 32-symbol chunk, combined in float64, as the greedy decoder forms it);
+ *   2. candidates (i, v), score s_i + ((double)logits_i[v] - lse_i) in float64, ranked by score descending, then i, then v
+ *      ascending; the first `beam` are taken; NaN and -inf candidates never are; nothing taken: the beam is carried over;
+ *   3. a taken candidate's sequence is y_i (v == blank) or y_i + (v,);
+ *   4. taken candidates with identical sequences merge: the first-ranked survives with score logaddexp(s_a, s_b) (float64);
+ *   5. the new beam is the merged list stably sorted by score, descending (it may hold fewer than `beam` hypotheses).
+ * Frames t >= T_b leave the beam as it is.  beam = 1 is greedy decoding with one symbol per frame.
+ *
+ *   enc_proj      device f32 [minibatch, maxT, joint_size] = enc @ W1 + b1
+ *   pred_proj     device f32 [minibatch * beam, joint_size]: row b * beam + k = pred @ W1 of slot k's current prediction output
+ *   W2, b2, joint_dtype, shapes: as for the greedy decoder (joint_dtype carries no flag bits); 1 <= beam <= 16
+ *   options       loc RNNT_GPU, stream, blank_label (< alphabet_size), maxT (> 0); the same for begin, every step and results
+ *
+ * compute_rnnt_beam_begin (once per decode) builds the tables and the W2 image and resets every beam to [((), 0)] and its frame
+ * counter to 0.  compute_rnnt_beam_step processes the next frame of every utterance:
+ *   parents  i32 [minibatch * beam]  the row whose prediction-network state slot r continues (a merged slot: the first-ranked
+ *            member's parent -- both have the same sequence); empty and frozen slots: their own row
+ *   emitted  i32 [minibatch * beam]  v when slot r's sequence grew by v, else -1: the caller gathers its prediction-network
+ *            output and state by `parents`, then advances the rows with emitted >= 0
+ *   topk_logits f32 [minibatch * beam, beam], topk_symbols i32 [minibatch * beam, beam], lse f32 [minibatch * beam]: optional
+ *            diagnostics (NULL: not written) -- this step's top-`beam` logits of each live hypothesis (logit descending, symbol
+ *            ascending; -inf / -1 where there are fewer) and its logsumexp
+ * compute_rnnt_beam_results writes the current beams: hyps i32 [minibatch, beam, maxT] (zero-padded), hyp_lengths i32
+ * [minibatch, beam], scores f32 [minibatch, beam] (empty slots: length 0, score -inf), best first.
+ * workspace: get_rnnt_beam_workspace_size(maxT, minibatch, beam, ...) bytes, 256-byte aligned, owned by one decode from its
+ * begin to its results.  No entry point synchronises the host.
+ */
+RNNT_API rnntStatus_t get_rnnt_beam_workspace_size(int maxT, int minibatch, int beam, int joint_size, int alphabet_size,
+                                                   int joint_dtype, size_t *size_bytes);
+
+RNNT_API rnntStatus_t compute_rnnt_beam_begin(const float *enc_proj, const int *frame_lengths, const float *W2, const float *b2,
+                                              int joint_size, int alphabet_size, int minibatch, int beam, int joint_dtype,
+                                              void *workspace, rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_beam_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits,
+                                             int *topk_symbols, float *lse, int joint_size, int alphabet_size, int minibatch,
+                                             int beam, int joint_dtype, void *workspace, rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_beam_results(int *hyps, int *hyp_lengths, float *scores, int joint_size, int alphabet_size,
+                                                int minibatch, int beam, int joint_dtype, void *workspace, rnntOptions options);
+
 #ifdef __cplusplus
 }
 #endif

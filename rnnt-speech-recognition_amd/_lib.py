@@ -38,6 +38,10 @@ SYMBOLS = [
     "get_rnnt_greedy_workspace_size",
     "compute_rnnt_greedy_begin",
     "compute_rnnt_greedy_step",
+    "get_rnnt_beam_workspace_size",
+    "compute_rnnt_beam_begin",
+    "compute_rnnt_beam_step",
+    "compute_rnnt_beam_results",
 ]
 
 
@@ -131,6 +135,15 @@ def load():
         lib.compute_rnnt_greedy_begin.argtypes = [vp] * 5 + [ci] * 5 + [vp, rnntOptions]
         lib.compute_rnnt_greedy_step.restype = ci
         lib.compute_rnnt_greedy_step.argtypes = [vp, vp, ci] + [vp] * 5 + [ci] * 4 + [vp, rnntOptions]
+    if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "compute_rnnt_beam_step"):
+        lib.get_rnnt_beam_workspace_size.restype = ci
+        lib.get_rnnt_beam_workspace_size.argtypes = [ci] * 6 + [ctypes.POINTER(ctypes.c_size_t)]
+        lib.compute_rnnt_beam_begin.restype = ci
+        lib.compute_rnnt_beam_begin.argtypes = [vp] * 4 + [ci] * 5 + [vp, rnntOptions]
+        lib.compute_rnnt_beam_step.restype = ci
+        lib.compute_rnnt_beam_step.argtypes = [vp] * 6 + [ci] * 5 + [vp, rnntOptions]
+        lib.compute_rnnt_beam_results.restype = ci
+        lib.compute_rnnt_beam_results.argtypes = [vp] * 3 + [ci] * 5 + [vp, rnntOptions]
     _lib = lib
     return lib
 
@@ -173,6 +186,13 @@ def greedy_workspace_bytes(maxT: int, minibatch: int, joint_size: int, alphabet_
     n = ctypes.c_size_t(0)
     check(load().get_rnnt_greedy_workspace_size(maxT, minibatch, joint_size, alphabet_size, joint_dtype, ctypes.byref(n)),
           "get_rnnt_greedy_workspace_size")
+    return int(n.value)
+
+
+def beam_workspace_bytes(maxT: int, minibatch: int, beam: int, joint_size: int, alphabet_size: int, joint_dtype: int) -> int:
+    n = ctypes.c_size_t(0)
+    check(load().get_rnnt_beam_workspace_size(maxT, minibatch, beam, joint_size, alphabet_size, joint_dtype, ctypes.byref(n)),
+          "get_rnnt_beam_workspace_size")
     return int(n.value)
 
 

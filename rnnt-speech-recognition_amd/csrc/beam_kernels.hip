@@ -1,0 +1,483 @@
+// beam_kernels.hip -- batched "modified" beam search (one symbol per frame, the k2 / icefall form) for every utterance of a batch.
+//
+// The beam of utterance b holds up to K hypotheses, rows b K + k of every per-hypothesis array.  Per decode step (= frame t_b of
+// every utterance that has one left), for every hypothesis of the beam:
+//   step    (beam_step_kernel<DT>)  the joint of greedy_step_kernel (rnnt_decode.h: the same h, operand images, MFMA chains, K
+//           order and epilogue, so every logit is bitwise that of compute_rnnt_joint_logits for the hypothesis alone) over tiles
+//           of 32 hypothesis rows; row r reads enc frame t_b of utterance b = r / K.  Epilogue per (vocabulary slice, row): the
+//           top-K (logit, symbol) list (logit descending, symbol ascending; NaN and -inf take no part) and greedy's (max, sum of
+//           exps).  Nothing of size [rows x V] is written.
+//   select  (beam_select_kernel)  one workgroup per utterance: the slice lists -> per-hypothesis top-K and logsumexp (f32 partial
+//           sums per chunk combined in float64, as greedy_update_kernel), the K x K candidates s_i + (logit - lse_i) ranked in
+//           float64 (score descending, then hypothesis, then symbol), the first K taken, identical sequences merged (logaddexp;
+//           the first-ranked survives), the new beam stably sorted by score.  Token rows are double-buffered [2][B][K][maxT] and
+//           gathered by parent; two sequences are compared by (length, 64-bit rolling hash) and confirmed on the token rows.
+// prepare (launch_greedy_prepare, then beam_begin_kernel): greedy's tables and W2 image, its per-utterance state (t, Tb: the
+// frame counter), and every beam reset to the empty sequence with score 0.
+#include "rnnt_decode.h"
+
+#include <limits.h>
+#include <math.h>
+
+namespace rnnt {
+
+constexpr int kBeamMax = 16;
+constexpr unsigned long long kHashMul = 0x9E3779B97F4A7C15ull;  // rolling hash of a prefix: h' = h kHashMul + (v + 1)
+
+struct BeamSlot {
+    double score;             // -inf: empty slot
+    unsigned long long hash;  // rolling hash of the token sequence
+    int len;                  // tokens
+    int pad;
+};
+
+struct BeamArgs {
+    GreedyArgs g;  // the joint's tables and image; g.st: per-utterance frame counter (t) and frames (Tb)
+    BeamSlot *slot;  // [B K]
+    int *nslot;      // [B] occupied slots (the first nslot[b] of the beam)
+    float *pl;       // [NS][B K][K] slice top-K logits
+    int *pv;         // [NS][B K][K] their symbols (-1: none)
+    int *tok;        // [2][B][K][T] token rows
+    int *parents, *emitted;
+    float *topl, *lse;  // diagnostics (NULL: not written)
+    int *tops;
+    int *hyps, *hyp_lengths;
+    float *scores;
+    int K, R;
+};
+
+__device__ __forceinline__ bool bm_better(float l, int v, float bl, int bv) { return l > bl || (l == bl && v < bv); }
+
+// ---------------------------------------------------------------------------------------------
+// prepare: every beam = [((), 0)]
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void beam_begin_kernel(const BeamArgs a) {
+    for (int r = blockIdx.x * 256 + threadIdx.x; r < a.R; r += gridDim.x * 256) {
+        BeamSlot s;
+        s.score = (r % a.K == 0) ? 0.0 : -INFINITY;
+        s.hash = 0, s.len = 0, s.pad = 0;
+        a.slot[r] = s;
+        if (r % a.K == 0) a.nslot[r / a.K] = 1;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// step: grid (NS vocabulary slices, ceil(B K / 32) row tiles), 4 waves; the same LDS image as greedy_step_kernel plus the
+// tile's logits of the slice, [32 rows][128 symbols] (+1 padding column)
+// ---------------------------------------------------------------------------------------------
+template <int DT>
+__global__ __launch_bounds__(kGrWaves * 64) void beam_step_kernel(const BeamArgs ba) {
+    const GreedyArgs &a = ba.g;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int s_t[32], s_live[32], s_slow[32];
+    __shared__ float r_m[kGrWaves * 64], r_s[kGrWaves * 64];
+    __shared__ float stage[DT == 2 ? 32 * 33 : 1];
+    __shared__ float lg[32 * (32 * kGrWaves + 1)];
+    constexpr int LW = 32 * kGrWaves + 1;
+    const int J = a.J, K = ba.K;
+    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, n31 = lane & 31;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int slice = blockIdx.x, r0 = blockIdx.y * 32;
+
+    bool live = false;
+    if (tid < 32) {
+        const int r = r0 + tid, b = r / K;
+        int t = 0, slow = 0;
+        if (r < ba.R) {
+            const GreedyState s = a.st[b];
+            live = s.t < s.Tb && r - b * K < ba.nslot[b];
+            t = min(max(s.t, 0), a.T - 1);
+            if (live) slow = a.rowflag[(size_t)b * a.T + t];
+        }
+        s_live[tid] = live ? 1 : 0, s_t[tid] = t, s_slow[tid] = slow;
+    }
+    if (!__syncthreads_or(live)) return;  // a tile without live hypotheses reads and writes nothing
+    dec_pred_route(a, J, r0, s_live, s_slow, tid);
+    __syncthreads();
+    gf16 *hA = (gf16 *)smem, *hL = hA + (size_t)J * 32;
+    const bool hform = DT == 0 && a.tflag[1] != 0.f;
+    dec_build_h<DT>(a, J, r0, s_live, s_slow, [&](int n) { return (size_t)((r0 + n) / K) * a.T + s_t[n]; }, hform, hA, hL, tid);
+    __syncthreads();
+
+    // ---- this wave's chunk of 32 symbols: greedy's (max, sum) per lane, and the logits into lg (NaN: takes no part)
+    const int vc = slice * kGrWaves + wave;
+    float bm = -INFINITY, bs = 0.f;
+    if (vc < a.NC) {
+        const gf32x16 acc = dec_chunk_acc<DT>(a, vc, hA, hL, stage, lane);
+        float m2inv, w2inv;
+        dec_logit_scales<DT>(a, hform, m2inv, w2inv);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int vv = gr_cdrow(r, half), v = 32 * vc + vv;
+            const float l = dec_logit<DT>(a, acc[r], vc, vv, v, m2inv, w2inv);
+            if (v < a.V) {  // padding columns take no part
+                if (l > bm) {
+                    bs = fmaf(bs, __builtin_amdgcn_exp2f((bm - l) * kLog2e), 1.0f);
+                    bm = l;
+                } else {
+                    bs += __builtin_amdgcn_exp2f((l - bm) * kLog2e);
+                }
+            }
+            lg[n31 * LW + 32 * wave + vv] = v < a.V ? l : __builtin_nanf("");
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) lg[n31 * LW + 32 * wave + gr_cdrow(r, half)] = __builtin_nanf("");
+    }
+    r_m[tid] = bm, r_s[tid] = bs;
+    __syncthreads();
+    if (tid < 32 && s_live[tid]) {  // the 2 kGrWaves partials of row tid, in greedy_step_kernel's order
+        float M = -INFINITY;
+        for (int q = 0; q < 2 * kGrWaves; ++q) {
+            const int src = (q >> 1) * 64 + tid + 32 * (q & 1);
+            if (r_m[src] > M) M = r_m[src];
+        }
+        float S = 0.f;
+        for (int q = 0; q < 2 * kGrWaves; ++q) {
+            const int src = (q >> 1) * 64 + tid + 32 * (q & 1);
+            if (r_s[src] > 0.f) S += r_s[src] * __builtin_amdgcn_exp2f((r_m[src] - M) * kLog2e);
+        }
+        const size_t o = (size_t)slice * ba.R + r0 + tid;
+        a.part_m[o] = M, a.part_s[o] = S;
+    }
+    // ---- the slice's top-K per row: 8 threads per row, 16 consecutive symbols each; K rounds of a best-untaken reduction
+    const int n = tid >> 3, q = tid & 7;
+    float val[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) val[i] = lg[n * LW + 16 * q + i];
+    const int sym0 = slice * 32 * kGrWaves + 16 * q;
+    const size_t lo = ((size_t)slice * ba.R + r0 + n) * K;
+    unsigned taken = 0;
+    for (int k = 0; k < K; ++k) {  // (uniform trip count: every lane takes part in the shuffles)
+        float bl = -INFINITY;
+        int bj = -1;
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            if (!((taken >> i) & 1) && val[i] > bl) bl = val[i], bj = i;  // ascending symbols: the lowest wins a tie
+        int bv = bj >= 0 ? sym0 + bj : INT_MAX;
+        const int mine = bv;
+#pragma unroll
+        for (int off = 1; off < 8; off <<= 1) {
+            const float ol = __shfl_xor(bl, off, 8);
+            const int ov = __shfl_xor(bv, off, 8);
+            if (bm_better(ol, ov, bl, bv)) bl = ol, bv = ov;
+        }
+        if (bv != INT_MAX && bv == mine) taken |= 1u << bj;
+        if (q == 0 && s_live[n]) {
+            ba.pl[lo + k] = bv != INT_MAX ? bl : -INFINITY;
+            ba.pv[lo + k] = bv != INT_MAX ? bv : -1;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// select: one workgroup (256 threads) per utterance
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int bm_token(const int *row, int len, int v, int p) {
+    return p < len ? row[p] : v;  // token p of y_i + (v,): row = y_i's token row, len = |y_i|
+}
+
+__global__ __launch_bounds__(256) void beam_select_kernel(const BeamArgs a) {
+    __shared__ float s_tl[kBeamMax * kBeamMax];  // per-hypothesis top-K
+    __shared__ int s_tv[kBeamMax * kBeamMax];
+    __shared__ double s_lse[kBeamMax], s_cs[kBeamMax * kBeamMax], s_term[kGrWaves][64];
+    __shared__ int s_rank[kBeamMax * kBeamMax], s_take[kBeamMax];
+    __shared__ int s_len[kBeamMax], s_par[kBeamMax], s_v[kBeamMax], s_same[kBeamMax * kBeamMax], s_ord[kBeamMax];
+    __shared__ unsigned long long s_hash[kBeamMax];
+    __shared__ double s_sc[kBeamMax];
+    __shared__ int s_m, s_n;
+    const GreedyArgs &g = a.g;
+    const int b = blockIdx.x, K = a.K, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, blank = g.blank;
+    const GreedyState st = g.st[b];
+    const int rb = b * K;
+    if (st.t >= st.Tb) {  // frozen: nothing changes
+        if (tid < K) a.parents[rb + tid] = rb + tid, a.emitted[rb + tid] = -1;
+        return;
+    }
+    const int nb = a.nslot[b], T = g.T, cur = st.t & 1;
+    const int *tok_cur = a.tok + ((size_t)cur * g.B + b) * K * T;
+    int *tok_nxt = a.tok + ((size_t)(cur ^ 1) * g.B + b) * K * T;
+
+    // ---- per hypothesis (one wave each): logsumexp as greedy_update_kernel, the slice lists merged into the top-K
+    for (int i = wave; i < nb; i += kGrWaves) {
+        const int r = rb + i;
+        const float pm = lane < g.NS ? g.part_m[(size_t)lane * a.R + r] : -INFINITY;
+        const float ps = lane < g.NS ? g.part_s[(size_t)lane * a.R + r] : 0.f;
+        float M = pm;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float o = __shfl_xor(M, off);
+            if (o > M) M = o;
+        }
+        s_term[wave][lane] = ps > 0.f ? (double)ps * exp((double)pm - (double)M) : 0.0;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (one wave: its LDS operations complete in order)
+        if (lane == 0) {
+            double S = 0.0;
+            for (int q = 0; q < g.NS; ++q) S += s_term[wave][q];  // slice order, as greedy_update_kernel
+            s_lse[i] = (double)M + log(S);
+            if (a.lse) a.lse[r] = (float)s_lse[i];
+        }
+        int h = 0;
+        for (int k = 0; k < K; ++k) {
+            float l = -INFINITY;
+            int v = INT_MAX;
+            if (lane < g.NS && h < K) {
+                const size_t o = ((size_t)lane * a.R + r) * K + h;
+                if (a.pv[o] >= 0) l = a.pl[o], v = a.pv[o];
+            }
+            const int mine = v;
+            float bl = l;
+            int bv = v;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const float ol = __shfl_xor(bl, off);
+                const int ov = __shfl_xor(bv, off);
+                if (bm_better(ol, ov, bl, bv)) bl = ol, bv = ov;
+            }
+            if (bv != INT_MAX && bv == mine) ++h;
+            if (lane == 0) {
+                s_tl[i * K + k] = bv != INT_MAX ? bl : -INFINITY;
+                s_tv[i * K + k] = bv != INT_MAX ? bv : -1;
+                if (a.topl) a.topl[(size_t)r * K + k] = bv != INT_MAX ? bl : -INFINITY;
+                if (a.tops) a.tops[(size_t)r * K + k] = bv != INT_MAX ? bv : -1;
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- the nb K candidates in float64, ranked by (score desc, hypothesis asc, symbol asc); NaN / -inf never taken
+    const int nc = nb * K;
+    if (tid < nc) {
+        const int i = tid / K;
+        const double sc = a.slot[rb + i].score + ((double)s_tl[tid] - s_lse[i]);
+        s_cs[tid] = (s_tv[tid] >= 0 && sc > -INFINITY) ? sc : __builtin_nan("");
+    }
+    if (tid == 0) s_m = 0;
+    __syncthreads();
+    if (tid < nc) {
+        const double sc = s_cs[tid];
+        int rank = -1;
+        if (sc == sc) {
+            rank = 0;
+            for (int c = 0; c < nc; ++c) {
+                const double o = s_cs[c];
+                if (o > sc || (o == sc && (c / K < tid / K || (c / K == tid / K && s_tv[c] < s_tv[tid])))) ++rank;
+            }
+        }
+        if (rank >= 0 && rank < K) s_take[rank] = tid, atomicAdd(&s_m, 1);
+    }
+    __syncthreads();
+    const int m = s_m;
+
+    // ---- the taken candidates' sequences: y_i, or y_i + (v,)
+    if (tid < m) {
+        const int c = s_take[tid], i = c / K, v = s_tv[c];
+        const BeamSlot p = a.slot[rb + i];
+        const bool emit = v != blank;
+        s_par[tid] = i, s_v[tid] = emit ? v : -1;
+        s_len[tid] = p.len + (emit ? 1 : 0);
+        s_hash[tid] = emit ? p.hash * kHashMul + (unsigned long long)(v + 1) : p.hash;
+        s_sc[tid] = s_cs[c];
+    } else if (m == 0 && tid < nb) {  // nothing can be taken: the beam is carried over unchanged
+        const BeamSlot p = a.slot[rb + tid];
+        s_par[tid] = tid, s_v[tid] = -1, s_len[tid] = p.len, s_hash[tid] = p.hash, s_sc[tid] = p.score;
+    }
+    __syncthreads();
+    const int nt = m > 0 ? m : nb;
+    // same (length, hash): confirmed on the token rows before a merge
+    if (tid < kBeamMax * kBeamMax) {
+        const int x = tid / kBeamMax, y = tid % kBeamMax;
+        s_same[tid] = (m > 0 && x < y && y < m && s_len[x] == s_len[y] && s_hash[x] == s_hash[y]) ? 1 : 0;
+    }
+    __syncthreads();
+    for (int x = 0; x < m; ++x)
+        for (int y = x + 1; y < m; ++y) {
+            if (!s_same[x * kBeamMax + y]) continue;  // (LDS, uniform)
+            const int *rx = tok_cur + (size_t)s_par[x] * T, *ry = tok_cur + (size_t)s_par[y] * T;
+            const int lx = a.slot[rb + s_par[x]].len, ly = a.slot[rb + s_par[y]].len;
+            bool diff = false;
+            for (int p = tid; p < s_len[x]; p += 256)
+                diff |= bm_token(rx, lx, s_v[x], p) != bm_token(ry, ly, s_v[y], p);
+            diff = __syncthreads_or(diff);
+            if (tid == 0 && diff) s_same[x * kBeamMax + y] = 0;
+        }
+    __syncthreads();
+    // merge (the first-ranked survives, logaddexp in float64), then a stable sort by score, descending
+    if (tid == 0) {
+        int alive = 0;
+        for (int x = 0; x < nt; ++x) {
+            if (s_sc[x] != s_sc[x]) continue;  // (merged away below)
+            for (int y = x + 1; y < nt; ++y)
+                if (s_same[x * kBeamMax + y] && s_sc[y] == s_sc[y]) {
+                    const double hi = fmax(s_sc[x], s_sc[y]), lo2 = fmin(s_sc[x], s_sc[y]);
+                    s_sc[x] = hi + log1p(exp(lo2 - hi));
+                    s_sc[y] = __builtin_nan("");
+                }
+            int p = alive++;
+            while (p > 0 && s_sc[s_ord[p - 1]] < s_sc[x]) s_ord[p] = s_ord[p - 1], --p;
+            s_ord[p] = x;
+        }
+        s_n = alive;
+    }
+    __syncthreads();
+    const int nn = s_n;
+    // ---- the new beam: slots, parents, emitted, token rows gathered by parent
+    if (tid < K) {
+        const int r = rb + tid;
+        BeamSlot s;
+        s.pad = 0;
+        if (tid < nn) {
+            const int x = s_ord[tid];
+            s.score = s_sc[x], s.hash = s_hash[x], s.len = s_len[x];
+            a.parents[r] = rb + s_par[x], a.emitted[r] = s_v[x];
+        } else {
+            s.score = -INFINITY, s.hash = 0, s.len = 0;
+            a.parents[r] = r, a.emitted[r] = -1;
+        }
+        a.slot[r] = s;
+    }
+    for (int k = 0; k < nn; ++k) {
+        const int x = s_ord[k], i = s_par[x], n = s_len[x];
+        const int li = n - (s_v[x] >= 0 ? 1 : 0);
+        for (int p = tid; p < n; p += 256) tok_nxt[(size_t)k * T + p] = bm_token(tok_cur + (size_t)i * T, li, s_v[x], p);
+    }
+    if (tid == 0) {
+        a.nslot[b] = nn;
+        GreedyState s2 = st;
+        s2.t = st.t + 1;
+        g.st[b] = s2;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// results: one workgroup per utterance; the current beams, zero-padded
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void beam_results_kernel(const BeamArgs a) {
+    const GreedyArgs &g = a.g;
+    const int b = blockIdx.x, K = a.K, T = g.T;
+    const int cur = g.st[b].t & 1, nb = a.nslot[b];
+    const int *tok = a.tok + ((size_t)cur * g.B + b) * K * T;
+    for (int k = 0; k < K; ++k) {
+        const int n = k < nb ? a.slot[b * K + k].len : 0;
+        for (int p = threadIdx.x; p < T; p += 256) a.hyps[((size_t)b * K + k) * T + p] = p < n ? tok[(size_t)k * T + p] : 0;
+        if (threadIdx.x == 0) {
+            a.hyp_lengths[b * K + k] = n;
+            a.scores[b * K + k] = k < nb ? (float)a.slot[b * K + k].score : -INFINITY;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+size_t joint_w2_image_bytes(int J, int V);
+
+struct BeamLayout {
+    size_t st, slot, nslot, pm, ps, pl, pv, tok, rowflag, expE, encraw, img, btab, tflag, total;
+    int NC, NS, DT;
+};
+
+static bool make_beam_layout(int T, int B, int K, int J, int V, int joint_dtype, BeamLayout &L) {
+    L.DT = greedy_dt(joint_dtype, J, V);
+    if (L.DT < 0 || T <= 0 || B <= 0 || K < 1 || K > kBeamMax) return false;
+    if ((unsigned long long)B * T * J >= (1ull << 31) || 2ull * B * K * T >= (1ull << 31)) return false;
+    L.NC = (V + 31) / 32;
+    L.NS = (L.NC + kGrWaves - 1) / kGrWaves;
+    const size_t R = (size_t)B * K;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + bytes, 256);
+        return o;
+    };
+    L.st = take((size_t)B * sizeof(GreedyState));
+    L.slot = take(R * sizeof(BeamSlot));
+    L.nslot = take((size_t)B * sizeof(int));
+    L.pm = take((size_t)L.NS * R * sizeof(float));
+    L.ps = take((size_t)L.NS * R * sizeof(float));
+    L.pl = take((size_t)L.NS * R * K * sizeof(float));
+    L.pv = take((size_t)L.NS * R * K * sizeof(int));
+    L.tok = take(2 * R * T * sizeof(int));
+    L.rowflag = take((size_t)B * T * sizeof(int));
+    L.expE = take((size_t)B * T * J * sizeof(float));
+    L.encraw = take((size_t)B * T * J * sizeof(float));
+    L.img = take(L.DT == 1 ? (size_t)L.NC * 32 * J * sizeof(gf16) : joint_w2_image_bytes(J, V));
+    L.btab = take((size_t)L.NC * 32 * sizeof(float));
+    L.tflag = take(256 + 1024);  // joint_prep_kernel's flag words + b2s (as greedy's layout)
+    L.total = off;
+    return true;
+}
+
+static bool beam_bind(BeamArgs &a, int T, int B, int K, int J, int V, int joint_dtype, void *workspace, BeamLayout &L) {
+    if (!make_beam_layout(T, B, K, J, V, joint_dtype, L)) return false;
+    char *ws = (char *)workspace;
+    GreedyArgs &g = a.g;
+    g.st = (GreedyState *)(ws + L.st);
+    g.part_m = (float *)(ws + L.pm), g.part_s = (float *)(ws + L.ps);
+    g.rowflag = (int *)(ws + L.rowflag);
+    g.expE = (float *)(ws + L.expE), g.encraw = (float *)(ws + L.encraw);
+    g.img = (gf16 *)(ws + L.img), g.btab = (float *)(ws + L.btab), g.tflag = (const float *)(ws + L.tflag);
+    g.NC = L.NC, g.NS = L.NS;
+    g.B = B, g.T = T, g.J = J, g.V = V;
+    a.slot = (BeamSlot *)(ws + L.slot), a.nslot = (int *)(ws + L.nslot);
+    a.pl = (float *)(ws + L.pl), a.pv = (int *)(ws + L.pv), a.tok = (int *)(ws + L.tok);
+    a.K = K, a.R = B * K;
+    return true;
+}
+
+hipError_t beam_workspace_bytes(int T, int B, int K, int J, int V, int joint_dtype, size_t *bytes) {
+    BeamLayout L;
+    if (!make_beam_layout(T, B, K, J, V, joint_dtype, L)) return hipErrorInvalidValue;
+    *bytes = L.total;
+    return hipSuccess;
+}
+
+hipError_t launch_beam_begin(const float *enc_proj, const int *frame_lengths, const float *W2, const float *b2, int J, int V, int B,
+                             int T, int K, int joint_dtype, void *workspace, hipStream_t s) {
+    BeamArgs a = {};
+    BeamLayout L;
+    if (!beam_bind(a, T, B, K, J, V, joint_dtype, workspace, L)) return hipErrorInvalidValue;
+    a.g.enc_proj = enc_proj, a.g.frame_lengths = frame_lengths, a.g.max_symbols = nullptr, a.g.max_per_frame = 0;
+    hipError_t e = launch_greedy_prepare(a.g, L.DT, W2, b2, s);
+    if (e != hipSuccess) return e;
+    const int grid = (a.R + 255) / 256;
+    hipLaunchKernelGGL(beam_begin_kernel, dim3(grid < 256 ? grid : 256), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+template <int DT>
+static hipError_t launch_beam_step_dt(const BeamArgs &a, size_t shm, hipStream_t s) {
+    const hipError_t e = set_lds(beam_step_kernel<DT>, shm);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(beam_step_kernel<DT>, dim3(a.g.NS, (a.R + 31) / 32), dim3(kGrWaves * 64), shm, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_beam_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits, int *topk_symbols, float *lse,
+                            int J, int V, int B, int T, int K, int blank, int joint_dtype, void *workspace, hipStream_t s) {
+    BeamArgs a = {};
+    BeamLayout L;
+    if (!beam_bind(a, T, B, K, J, V, joint_dtype, workspace, L)) return hipErrorInvalidValue;
+    a.g.pred_proj = pred_proj, a.g.blank = blank;
+    a.parents = parents, a.emitted = emitted, a.topl = topk_logits, a.tops = topk_symbols, a.lse = lse;
+    hipError_t e;
+    const size_t shm = (size_t)J * 32 * sizeof(gf16) * (L.DT == 1 ? 1 : 2);
+    if (L.DT == 1) e = launch_beam_step_dt<1>(a, shm, s);
+    else if (L.DT == 0) e = launch_beam_step_dt<0>(a, shm, s);
+    else e = launch_beam_step_dt<2>(a, shm, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_beam_results(int *hyps, int *hyp_lengths, float *scores, int J, int V, int B, int T, int K, int joint_dtype,
+                               void *workspace, hipStream_t s) {
+    BeamArgs a = {};
+    BeamLayout L;
+    if (!beam_bind(a, T, B, K, J, V, joint_dtype, workspace, L)) return hipErrorInvalidValue;
+    a.hyps = hyps, a.hyp_lengths = hyp_lengths, a.scores = scores;
+    hipLaunchKernelGGL(beam_results_kernel, dim3(B), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace rnnt

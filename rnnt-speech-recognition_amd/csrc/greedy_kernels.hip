@@ -26,50 +26,12 @@
 // The call-wide route switches of those kernels are decided PER HYPOTHESIS here: the direct-tanh route (some |x| beyond
 // kExpTabLimit) when this hypothesis's enc_proj row or pred_proj row leaves the table range -- exactly when the single-hypothesis
 // logits call would raise its flag.  The h / r form depends on W2 alone and is the same for every hypothesis.
-#include "rnnt_common.h"
-#include "rnnt_joint_math.h"
+#include "rnnt_decode.h"
 
 #include <limits.h>
 #include <math.h>
 
 namespace rnnt {
-
-typedef _Float16 gf16;
-typedef _Float16 gh8 __attribute__((ext_vector_type(8)));
-typedef float gf32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kGrWaves = 4;  // waves per step workgroup: wave w of slice s takes vocabulary chunk kGrWaves s + w
-
-// per-hypothesis decoder state (workspace)
-struct GreedyState {
-    int t;       // current frame
-    int n;       // symbols emitted
-    int nf;      // symbols emitted at the current frame
-    int done;    // 1: t >= Tb or n >= maxsym
-    int Tb;      // frames of the utterance (clamped to [0, maxT])
-    int maxsym;  // symbol budget (clamped to >= 0; INT_MAX: none)
-    int cap;     // symbols per frame at most (<= 0: no cap)
-    int pad;
-    double score;  // sum of the log-softmax of every decision taken
-};
-
-struct GreedyArgs {
-    const float *enc_proj, *W2, *b2;
-    const int *frame_lengths, *max_symbols;
-    const float *pred_proj;
-    int *hyps, *hyp_lengths, *emitted, *all_done;
-    float *scores, *stats;
-    GreedyState *st;
-    float *part_m, *part_s;
-    int *part_i;
-    int *rowflag;      // [B][T] 1: some |enc_proj| of the row beyond kExpTabLimit (or NaN)
-    float *expE;       // [B][T][J] e^{2 enc_proj}
-    float *encraw;     // [B][T][J] enc_proj (the direct-tanh route)
-    gf16 *img;         // W2 operand image: DT 1 [NC][J/16][2][32][8] binary16; DT 0 / 2 joint_prep_kernel's W2s
-    float *btab;       // DT 1: b2 log2 e [NC 32]; DT 2: b2 [32]
-    const float *tflag;  // DT 0 / 2: joint_prep_kernel's flag words (+ 64: b2s)
-    int B, T, J, V, NC, NS, blank, max_per_frame, max_hyp_len;
-};
 
 // ---------------------------------------------------------------------------------------------
 // prepare
@@ -124,8 +86,6 @@ __global__ __launch_bounds__(256) void greedy_w2_f16_kernel(const float *W2, con
 // step: grid (NS vocabulary slices, ceil(B / 32) hypothesis tiles), 4 waves.  LDS: the B-operand image of the tile's 32
 // hypotheses, [J/16 k-steps][64 lanes][8] binary16 (DT 0 / 2: hi, then lo).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ constexpr int gr_cdrow(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
-
 __device__ __forceinline__ bool gr_live(const GreedyState &s, const int max_hyp_len) {
     return !s.done && s.n < min(s.maxsym, max_hyp_len);  // (a full hyps buffer pauses a hypothesis: greedy_update_kernel)
 }
@@ -137,8 +97,8 @@ __global__ __launch_bounds__(kGrWaves * 64) void greedy_step_kernel(const Greedy
     __shared__ float r_m[kGrWaves * 64], r_s[kGrWaves * 64];
     __shared__ int r_i[kGrWaves * 64];
     __shared__ float stage[DT == 2 ? 32 * 33 : 1];
-    const int J = a.J, KS = J >> 4;
-    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, n31 = lane & 31;
+    const int J = a.J;
+    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int slice = blockIdx.x, b0 = blockIdx.y * 32;
 
@@ -155,38 +115,11 @@ __global__ __launch_bounds__(kGrWaves * 64) void greedy_step_kernel(const Greedy
         s_live[tid] = live ? 1 : 0, s_t[tid] = t, s_slow[tid] = slow;
     }
     if (!__syncthreads_or(live)) return;  // a tile of done hypotheses reads and writes nothing
-    {   // the pred-side half of the route switch: 8 threads per hypothesis scan its pred_proj row
-        const int n = tid >> 3, q = tid & 7;
-        bool big = false;
-        if (s_live[n])
-            for (int j = q; j < J; j += 8) big |= exp_tab_out_of_range(a.pred_proj[(size_t)(b0 + n) * J + j]);
-        if (big) s_slow[n] = 1;
-    }
+    dec_pred_route(a, J, b0, s_live, s_slow, tid);
     __syncthreads();
-    // h (DT 1) or r / h split into hi + lo (DT 0 / 2), in B-fragment order: lane n + 32 half of k-step ks holds units
-    // 16 ks + 8 half + 0..7 of hypothesis n
     gf16 *hA = (gf16 *)smem, *hL = hA + (size_t)J * 32;
     const bool hform = DT == 0 && a.tflag[1] != 0.f;
-    for (int i = tid; i < 32 * J; i += kGrWaves * 64) {
-        const int n = i / J, j = i - n * J;
-        float x = 0.f;
-        if (s_live[n]) {
-            const size_t er = ((size_t)(b0 + n) * a.T + s_t[n]) * J + j;
-            const float pv = a.pred_proj[(size_t)(b0 + n) * J + j];
-            if (!s_slow[n]) {
-                const float ea = a.expE[er], ec = exp_tab(pv);
-                x = DT == 0 ? r_from_exp(ea, ec) : tanh_from_exp(ea, ec);
-            } else {
-                const float ev = a.encraw[er];
-                x = DT == 0 ? fast_r(ev + pv) : fast_tanh(ev + pv);
-            }
-            if (hform) x = fmaf(x, -2.0f, 1.0f);
-        }
-        const int off = (((j >> 4) * 64 + n + 32 * ((j >> 3) & 1)) << 3) + (j & 7);
-        const gf16 hi = (gf16)x;
-        hA[off] = hi;
-        if (DT != 1) hL[off] = (gf16)(x - (float)hi);  // exact residual in f32, then rounded: split_pair's hi / lo
-    }
+    dec_build_h<DT>(a, J, b0, s_live, s_slow, [&](int n) { return (size_t)(b0 + n) * a.T + s_t[n]; }, hform, hA, hL, tid);
     __syncthreads();
 
     // ---- this wave's chunk of 32 symbols
@@ -194,54 +127,14 @@ __global__ __launch_bounds__(kGrWaves * 64) void greedy_step_kernel(const Greedy
     float bm = -INFINITY, bs = 0.f;
     int bi = INT_MAX;
     if (vc < a.NC) {
-        gf32x16 acc;
-        const gh8 *hb = (const gh8 *)hA + lane, *hl = (const gh8 *)hL + lane;
-        if (DT == 1) {
-            const gh8 *w = (const gh8 *)a.img + (size_t)vc * KS * 64 + lane;
-            gf32x16 acc0, acc1;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc0[r] = 0.f, acc1[r] = 0.f;
-            for (int ks = 0; ks < KS; ks += 2) {
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[ks * 64], hb[ks * 64], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[(ks + 1) * 64], hb[(ks + 1) * 64], acc1, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = acc0[r] + acc1[r];
-        } else {
-            const gh8 *w = (const gh8 *)a.img + (size_t)vc * J * 8 + lane;  // tile vc: [J/16][hi, lo][64 lanes] fragments
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-            for (int ks = 0; ks < KS; ++ks) {
-                const gh8 wh = w[(2 * ks) * 64], wl = w[(2 * ks + 1) * 64], bh = hb[ks * 64], bl = hl[ks * 64];
-                if (DT == 0) {
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, bh, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, bl, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, bh, acc, 0, 0, 0);
-                } else {  // h as the A operand: D[hypothesis][symbol]
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, wh, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl, wh, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, wl, acc, 0, 0, 0);
-                }
-            }
-        }
-        if (DT == 2) {  // transpose through LDS: afterwards lane n31 holds hypothesis n31, symbols gr_cdrow(r, half), as for DT 0 / 1
-#pragma unroll
-            for (int r = 0; r < 16; ++r) stage[gr_cdrow(r, half) * 33 + n31] = acc[r];
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (one wave: its LDS operations complete in order)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = stage[n31 * 33 + gr_cdrow(r, half)];
-        }
+        const gf32x16 acc = dec_chunk_acc<DT>(a, vc, hA, hL, stage, lane);
         // epilogue: logits of this lane's hypothesis, in increasing symbol order
-        float m2inv = 0.f;
-        if (DT == 0) m2inv = hform ? a.tflag[2] : -2.0f * a.tflag[2];
-        const float w2inv = DT == 2 ? a.tflag[2] : 0.f;
+        float m2inv, w2inv;
+        dec_logit_scales<DT>(a, hform, m2inv, w2inv);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int vv = gr_cdrow(r, half), v = 32 * vc + vv;
-            float l;
-            if (DT == 1) l = fmaf(acc[r], kLog2e, a.btab[v]) * kLn2;
-            else if (DT == 0) l = fmaf(acc[r], m2inv, a.tflag[64 + 64 * vc + vv]) + a.tflag[64 + 64 * vc + 32 + vv];
-            else l = fmaf(acc[r], w2inv, a.btab[v]);
+            const float l = dec_logit<DT>(a, acc[r], vc, vv, v, m2inv, w2inv);
             if (v < a.V) {  // padding columns take no part
                 if (l > bm) {
                     bs = fmaf(bs, __builtin_amdgcn_exp2f((bm - l) * kLog2e), 1.0f);
@@ -332,7 +225,7 @@ struct GreedyLayout {
 // DT of the step kernel for (joint_dtype, J, V), or -1 when the shape is not taken: joint_dtype 0 on the shapes of the f32-grade
 // joint (joint_dtype_supported), joint_dtype 1 on J a multiple of 128 up to 640 and 1 <= V <= 8192 (the vocabulary is padded to
 // whole chunks of 32 inside the image; the padding takes no part)
-static int greedy_dt(int joint_dtype, int J, int V) {
+int greedy_dt(int joint_dtype, int J, int V) {
     if (joint_dtype == 0) return joint_dtype_supported(0, J, V) ? (J > 640 ? 2 : 0) : -1;
     if (joint_dtype == 1) return (J >= 128 && J <= 640 && J % 128 == 0 && V >= 1 && V <= 8192) ? 1 : -1;
     return -1;
@@ -390,12 +283,20 @@ hipError_t launch_greedy_begin(const float *enc_proj, const int *frame_lengths, 
     greedy_bind(a, L, workspace);
     a.enc_proj = enc_proj, a.frame_lengths = frame_lengths, a.max_symbols = max_symbols;
     a.B = B, a.T = T, a.J = J, a.V = V, a.max_per_frame = max_per_frame;
-    a.b2 = L.DT == 2 ? b2 : nullptr;
+    return launch_greedy_prepare(a, L.DT, W2, b2, s);
+}
+
+// the W2 operand image and bias tables, the e^{2x} tables of enc_proj, the per-hypothesis state (a: bound to a workspace, with
+// enc_proj, frame_lengths, max_symbols, B, T, J, V, NC and max_per_frame set).  Shared with the beam decoder's begin.
+hipError_t launch_greedy_prepare(const GreedyArgs &ga, int DT, const float *W2, const float *b2, hipStream_t s) {
+    GreedyArgs a = ga;
+    const int J = a.J, V = a.V, B = a.B, T = a.T;
+    a.b2 = DT == 2 ? b2 : nullptr;
     hipError_t e;
-    if (L.DT == 1) {
-        const size_t n = (size_t)L.NC * 32 * J;
+    if (DT == 1) {
+        const size_t n = (size_t)a.NC * 32 * J;
         const unsigned grid = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-        hipLaunchKernelGGL(greedy_w2_f16_kernel, dim3(grid), dim3(256), 0, s, W2, b2, J, V, L.NC, a.img, a.btab);
+        hipLaunchKernelGGL(greedy_w2_f16_kernel, dim3(grid), dim3(256), 0, s, W2, b2, J, V, a.NC, a.img, a.btab);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     } else if ((e = launch_joint_w2_image(W2, b2, J, V, (float *)a.tflag, a.img, s)) != hipSuccess) {
         return e;

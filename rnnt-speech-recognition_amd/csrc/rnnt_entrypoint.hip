@@ -47,6 +47,14 @@ hipError_t launch_greedy_begin(const float *enc_proj, const int *frame_lengths, 
 hipError_t launch_greedy_step(const float *pred_proj, int *hyps, int max_hyp_len, int *hyp_lengths, float *scores, int *emitted,
                               int *all_done, float *stats, int J, int V, int B, int T, int blank, int joint_dtype, void *workspace,
                               hipStream_t s);
+// beam_kernels.hip (batched modified beam search)
+hipError_t beam_workspace_bytes(int T, int B, int K, int J, int V, int joint_dtype, size_t *bytes);
+hipError_t launch_beam_begin(const float *enc_proj, const int *frame_lengths, const float *W2, const float *b2, int J, int V, int B,
+                             int T, int K, int joint_dtype, void *workspace, hipStream_t s);
+hipError_t launch_beam_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits, int *topk_symbols, float *lse,
+                            int J, int V, int B, int T, int K, int blank, int joint_dtype, void *workspace, hipStream_t s);
+hipError_t launch_beam_results(int *hyps, int *hyp_lengths, float *scores, int J, int V, int B, int T, int K, int joint_dtype,
+                               void *workspace, hipStream_t s);
 }  // namespace rnnt
 
 static rnntStatus_t check_options(const rnntOptions &o) {
@@ -531,6 +539,59 @@ rnntStatus_t compute_rnnt_greedy_step(const float *pred_proj, int *hyps, int max
     return from_hip(launch_greedy_step(pred_proj, hyps, max_hyp_len, hyp_lengths, scores, emitted, all_done, logit_stats, joint_size,
                                        alphabet_size, minibatch, options.maxT, options.blank_label, joint_dtype, workspace,
                                        (hipStream_t)options.stream));
+}
+
+
+// Batched beam search (include/rnnt.h).  The checks of the greedy decoder, plus 1 <= beam <= 16; everything is checked before
+// anything is enqueued.
+static rnntStatus_t check_beam(int maxT, int joint_size, int alphabet_size, int minibatch, int beam, int joint_dtype,
+                               const void *workspace, const rnntOptions &o) {
+    if (!workspace || ((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
+    if (beam < 1 || beam > 16) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_greedy(maxT, joint_size, alphabet_size, minibatch, joint_dtype, o);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    size_t n = 0;
+    if (beam_workspace_bytes(maxT, minibatch, beam, joint_size, alphabet_size, joint_dtype, &n) != hipSuccess) return RNNT_STATUS_INVALID_VALUE;
+    return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t get_rnnt_beam_workspace_size(int maxT, int minibatch, int beam, int joint_size, int alphabet_size, int joint_dtype,
+                                          size_t *size_bytes) {
+    if (!size_bytes) return RNNT_STATUS_INVALID_VALUE;
+    if (joint_dtype != 0 && joint_dtype != 1) return RNNT_STATUS_INVALID_VALUE;
+    return beam_workspace_bytes(maxT, minibatch, beam, joint_size, alphabet_size, joint_dtype, size_bytes) == hipSuccess
+               ? RNNT_STATUS_SUCCESS
+               : RNNT_STATUS_INVALID_VALUE;
+}
+
+rnntStatus_t compute_rnnt_beam_begin(const float *enc_proj, const int *frame_lengths, const float *W2, const float *b2,
+                                     int joint_size, int alphabet_size, int minibatch, int beam, int joint_dtype, void *workspace,
+                                     rnntOptions options) {
+    if (!enc_proj || !frame_lengths || !W2 || !b2) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_begin(enc_proj, frame_lengths, W2, b2, joint_size, alphabet_size, minibatch, options.maxT, beam,
+                                      joint_dtype, workspace, (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_beam_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits, int *topk_symbols,
+                                    float *lse, int joint_size, int alphabet_size, int minibatch, int beam, int joint_dtype,
+                                    void *workspace, rnntOptions options) {
+    if (!pred_proj || !parents || !emitted) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size,
+                                     minibatch, options.maxT, beam, options.blank_label, joint_dtype, workspace,
+                                     (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_beam_results(int *hyps, int *hyp_lengths, float *scores, int joint_size, int alphabet_size, int minibatch,
+                                       int beam, int joint_dtype, void *workspace, rnntOptions options) {
+    if (!hyps || !hyp_lengths || !scores) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_results(hyps, hyp_lengths, scores, joint_size, alphabet_size, minibatch, options.maxT, beam,
+                                       joint_dtype, workspace, (hipStream_t)options.stream));
 }
 
 }  // extern "C"

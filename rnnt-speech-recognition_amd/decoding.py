@@ -23,7 +23,7 @@ from typing import List, Optional
 
 import torch
 
-from .joint import GreedyJoint
+from .joint import BeamJoint, GreedyJoint
 from .loss import reduced_lengths
 
 
@@ -190,4 +190,78 @@ def greedy_decode_batch_fn(model):
     """fn(inputs, max_length=None, spec_lengths=None) -> (ids, lengths, scores) of greedy_decode_batch."""
     def fn(inputs: torch.Tensor, max_length=None, spec_lengths: Optional[torch.Tensor] = None):
         return greedy_decode_batch(model, inputs, spec_lengths, max_length)
+    return fn
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Batched beam search
+# ---------------------------------------------------------------------------------------------------------------------------
+_BEAM_WORKSPACES = {}  # (device, stream) -> the beam workspace of the last decode there
+
+
+@torch.no_grad()
+def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, beam: int = 4):
+    """Modified beam search (one symbol per frame) over encoder outputs enc [B, T', H] with frame_lengths [B] (the model in eval
+    mode) -> (ids int32 [B, beam, T'] zero-padded, lengths int32 [B, beam], scores [B, beam]): every utterance's n-best, sorted
+    by score (empty slots: length 0, score -inf).  See include/rnnt.h for the algorithm; beam = 1 is greedy_search_batch with
+    max_symbols_per_frame = 1.
+
+    Runs enc.shape[1] steps without reading the host.  Per step the prediction network runs on all B beam rows; its output and
+    LSTM state are gathered by `parents`, and the rows that emitted a symbol advance."""
+    B, T = enc.shape[0], enc.shape[1]
+    K = int(beam)
+    dev = enc.device
+    jb = BeamJoint(model.joint, K)  # (the current weights: a model may be trained between two decodes)
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream) if enc.is_cuda else None
+    jb._ws = _BEAM_WORKSPACES.get(key)
+    jb.begin(enc, frame_lengths)
+    if jb._ws is not None:
+        _BEAM_WORKSPACES[key] = jb._ws
+    pred_net = model.prediction
+    g, states = _pred_step(pred_net, torch.zeros(B * K, dtype=torch.int32, device=dev), [None] * len(pred_net.blocks))
+    for t in range(T):
+        parents, emitted = jb.step(g)
+        if t + 1 == T:
+            break
+        idx = parents.long()
+        g = g[idx]
+        states = [(h[:, idx], c[:, idx]) for h, c in states]
+        mask = emitted >= 0
+        g2, states2 = _pred_step(pred_net, emitted.clamp(min=0), states)
+        g = torch.where(mask[:, None], g2, g)
+        states = [(torch.where(mask[None, :, None], h2, h), torch.where(mask[None, :, None], c2, c))
+                  for (h2, c2), (h, c) in zip(states2, states)]
+    return jb.results()
+
+
+@torch.no_grad()
+def beam_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[torch.Tensor] = None, beam: int = 4):
+    """Beam search of EVERY utterance of a batch -> the best hypothesis of each: (ids int32 [B, T'] zero-padded, lengths int32
+    [B], scores [B]).  spec_lengths are spectrogram frames, reduced as greedy_decode_batch reduces them; None: every frame."""
+    was_training = model.training
+    model.eval()
+    try:
+        enc = model.encoder(mel_specs)  # [B, T', H]
+        B, T = enc.shape[0], enc.shape[1]
+        if spec_lengths is None:
+            frames = torch.full((B,), T, dtype=torch.int32, device=enc.device)
+        else:
+            frames = reduced_lengths(spec_lengths.to(enc.device), model.hp.time_reduction_factor)
+        ids, lengths, scores = beam_search_batch(model, enc, frames, beam)
+        return ids[:, 0], lengths[:, 0], scores[:, 0]
+    finally:
+        model.train(was_training)
+
+
+def beam_decode_batch_fn(model, beam: int = 4):
+    """fn(inputs, max_length=None, spec_lengths=None) -> (ids, lengths, scores) of beam_decode_batch, for
+    metrics.build_batch_accuracy_fn / build_batch_wer_fn.  The search has no symbol budget: max_length (an int or an int tensor
+    [B]) truncates the best hypothesis afterwards."""
+    def fn(inputs: torch.Tensor, max_length=None, spec_lengths: Optional[torch.Tensor] = None):
+        ids, lengths, scores = beam_decode_batch(model, inputs, spec_lengths, beam)
+        if max_length is not None:
+            cap = torch.as_tensor(max_length, device=lengths.device).to(torch.int32)
+            lengths = torch.minimum(lengths, cap)
+            ids = torch.where(torch.arange(ids.shape[1], device=ids.device)[None, :] < lengths[:, None], ids, torch.zeros_like(ids))
+        return ids, lengths, scores
     return fn

@@ -511,3 +511,138 @@ class GreedyJoint:
         running, paused = ~self._done & (self._n < N), ~self._done & (self._n >= N)
         self.all_done.copy_(torch.where(running.any(), 0, torch.where(paused.any(), 2, 1)).to(torch.int32).reshape(1))
         return self.emitted
+
+
+class BeamJoint:
+    """The joint of the batched beam search (decoding.beam_search_batch): per frame, the joint of every hypothesis of every beam,
+    the candidate ranking, merging and the new beams in one pass ("modified" beam search, include/rnnt.h).
+
+    On an MI355X this is the ENGINE (compute_rnnt_beam_begin / _step / _results), with GreedyJoint's workspace ownership and
+    joint-unit padding.  CPU tensors and shapes the kernels do not take run the same state machine in torch on JointLoss.logits
+    (in the model's dtype; per-utterance bookkeeping on the host).
+
+    begin(enc [B, T, H], frame_lengths [B]); step(pred [B beam, H]) -> (parents, emitted) [B beam] int32; results() ->
+    (hyps [B, beam, T] int32 zero-padded, lengths [B, beam] int32, scores [B, beam]), best first."""
+
+    def __init__(self, joint: "JointLoss", beam: int = 4, joint_dtype: str = "auto"):
+        if not 1 <= int(beam) <= 16:
+            raise ValueError("BeamJoint: beam must be in 1 ... 16")
+        self.K = int(beam)
+        g = GreedyJoint(joint, joint_dtype)  # (the same engine / torch decision and padding)
+        self.joint, self.blank, self.V, self.engine = joint, g.blank, g.V, g.engine
+        if self.engine:
+            self.dtype, self.Jp, self.W1, self.b1, self.W2, self.b2 = g.dtype, g.Jp, g.W1, g.b1, g.W2, g.b2
+        self._ws = None
+
+    def begin(self, enc, frame_lengths):
+        B, T = enc.shape[0], enc.shape[1]
+        dev = enc.device
+        self.B, self.T = B, T
+        R = B * self.K
+        self.parents = torch.arange(R, dtype=torch.int32, device=dev)
+        self.emitted = torch.full((R,), -1, dtype=torch.int32, device=dev)
+        frames = frame_lengths.to(device=dev, dtype=torch.int32).contiguous()
+        if not self.engine:
+            return self._torch_begin(enc, frames)
+        ep = (torch.matmul(enc.float(), self.W1) + self.b1).contiguous()
+        self._keep = frames
+        with torch.cuda.device(dev):
+            nbytes = _lib.beam_workspace_bytes(T, B, self.K, self.Jp, self.V, self.dtype)
+            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
+                self._ws = _new_workspace(nbytes, dev)
+            elif _WORKSPACE_FILL is not None:
+                self._ws.fill_(int(_WORKSPACE_FILL))
+            self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
+            st = _lib.load().compute_rnnt_beam_begin(ep.data_ptr(), frames.data_ptr(), self.W2.data_ptr(), self.b2.data_ptr(),
+                                                     self.Jp, self.V, B, self.K, self.dtype, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_beam_begin")
+
+    def step(self, pred, topk_logits=None, topk_symbols=None, lse=None):
+        """pred [B beam, H]: the prediction network's output of every slot -> (parents, emitted), int32 [B beam]."""
+        if not self.engine:
+            return self._torch_step(pred)
+        pp = torch.matmul(pred.float(), self.W1).contiguous()
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        st = _lib.load().compute_rnnt_beam_step(pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(), ptr(topk_logits),
+                                                ptr(topk_symbols), ptr(lse), self.Jp, self.V, self.B, self.K, self.dtype,
+                                                self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_beam_step")
+        return self.parents, self.emitted
+
+    def results(self):
+        B, K, T = self.B, self.K, self.T
+        if not self.engine:
+            return self._torch_results()
+        dev = self.parents.device
+        hyps = torch.empty(B, K, T, dtype=torch.int32, device=dev)
+        lengths = torch.empty(B, K, dtype=torch.int32, device=dev)
+        scores = torch.empty(B, K, dtype=torch.float32, device=dev)
+        st = _lib.load().compute_rnnt_beam_results(hyps.data_ptr(), lengths.data_ptr(), scores.data_ptr(), self.Jp, self.V, B, K,
+                                                   self.dtype, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_beam_results")
+        return hyps, lengths, scores
+
+    # ---- torch composition: the same state machine (beam_select_kernel) on JointLoss.logits
+    def _torch_begin(self, enc, frames):
+        self._enc = enc
+        self._Tb = [int(x) for x in frames.clamp(0, enc.shape[1]).tolist()]
+        self._t = 0
+        self._beams = [[((), 0.0)] for _ in range(self.B)]  # (tokens, float64 score), best first
+        self._sdtype = torch.promote_types(enc.dtype, torch.float32)
+
+    def _torch_step(self, pred):
+        B, K, V, blank = self.B, self.K, self.V, self.blank
+        t = self._t
+        self._t += 1
+        parents = list(range(B * K))
+        emitted = [-1] * (B * K)
+        e = self._enc[:, min(t, self.T - 1)]  # [B, H]
+        logits = self.joint.logits(e.repeat_interleave(K, 0)[:, None, :], pred[:, None, :])[:, 0, 0, :]  # [B K, V]
+        lse = torch.logsumexp(logits, dim=-1)
+        top_l, top_v = torch.sort(logits, dim=-1, descending=True, stable=True)  # (logit descending, symbol ascending)
+        top_l, top_v, lse = top_l[:, :K].tolist(), top_v[:, :K].tolist(), lse.tolist()
+        for b in range(B):
+            if t >= self._Tb[b]:
+                continue
+            beam = self._beams[b]
+            cands = []
+            for i, (y, s) in enumerate(beam):
+                r = b * K + i
+                for l, v in zip(top_l[r], top_v[r]):
+                    sc = s + (float(l) - lse[r])
+                    if sc == sc and sc > -math.inf:
+                        cands.append((sc, i, v))
+            cands.sort(key=lambda c: (-c[0], c[1], c[2]))
+            taken = cands[:K]
+            if not taken:
+                continue  # the beam is carried over
+            merged = []  # [tokens, score, parent, emitted]
+            for sc, i, v in taken:
+                y = beam[i][0] if v == blank else beam[i][0] + (v,)
+                hit = next((m for m in merged if m[0] == y), None)
+                if hit is None:
+                    merged.append([y, sc, i, -1 if v == blank else v])
+                else:
+                    hi, lo = max(hit[1], sc), min(hit[1], sc)
+                    hit[1] = hi + math.log1p(math.exp(lo - hi))
+            merged.sort(key=lambda m: -m[1])  # (stable)
+            self._beams[b] = [(m[0], m[1]) for m in merged]
+            for k in range(K):
+                if k < len(merged):
+                    parents[b * K + k], emitted[b * K + k] = b * K + merged[k][2], merged[k][3]
+        dev = self.parents.device
+        self.parents = torch.tensor(parents, dtype=torch.int32, device=dev)
+        self.emitted = torch.tensor(emitted, dtype=torch.int32, device=dev)
+        return self.parents, self.emitted
+
+    def _torch_results(self):
+        B, K, T = self.B, self.K, self.T
+        hyps = torch.zeros(B, K, T, dtype=torch.int32)
+        lengths = torch.zeros(B, K, dtype=torch.int32)
+        scores = torch.full((B, K), -math.inf, dtype=torch.float64)
+        for b, beam in enumerate(self._beams):
+            for k, (y, s) in enumerate(beam):
+                hyps[b, k, : len(y)] = torch.tensor(y, dtype=torch.int32)
+                lengths[b, k], scores[b, k] = len(y), s
+        dev = self.parents.device
+        return hyps.to(dev), lengths.to(dev), scores.to(device=dev, dtype=self._sdtype)
