@@ -460,6 +460,69 @@ RNNT_API rnntStatus_t compute_rnnt_beam_step(const float *pred_proj, int *parent
 RNNT_API rnntStatus_t compute_rnnt_beam_results(int *hyps, int *hyp_lengths, float *scores, int joint_size, int alphabet_size,
                                                 int minibatch, int beam, int joint_dtype, void *workspace, rnntOptions options);
 
+/* Build-only extension: one PREDICTION-NETWORK step for every decoder row (model.py PredictionNetwork, inference only), so that
+ * a decode loop is library calls alone: prednet begin, then repeat {greedy / beam step, prednet step}.  The network is an
+ * embedding [vocab_size, embed_size] and num_blocks blocks of one single-layer LSTM (torch gate order i, f, g, o; optional
+ * bias-free projection) -> LayerNorm (biased variance; dropout is an eval no-op), followed by the joint's first Dense layer
+ * without its bias: pred_proj = x @ W1.
+ *
+ * Per row r = 0 ... rows-1 (rows = minibatch for greedy decoding, minibatch * beam for beam search), with
+ * src = parents ? parents[r] : r and tok = emitted[r]:
+ *   tok < 0:  row r takes row src's state and pred_proj unchanged (parents == NULL: nothing changes for the row);
+ *   tok >= 0: starting from row src's state, x = Emb[tok]; per block l:
+ *               gates = W_ih x + b_ih + W_hh r_prev + b_hh;  c = sigma(f) c_prev + sigma(i) tanh(g);  h = sigma(o) tanh(c);
+ *               r = W_hr h (projected block) or h;  x = LayerNorm_l(r)
+ *             pred_proj[r] = x @ W1.
+ * The state of block l is (r [rows, proj], c [rows, hidden]); r is the raw block output before the LayerNorm (torch's h of an
+ * LSTM with proj_size).  `emitted` and `parents` are exactly what compute_rnnt_greedy_step / compute_rnnt_beam_step write.
+ *
+ *   blocks      HOST array of num_blocks rnntPrednetBlock (below); the weight pointers are device f32, 16-byte aligned
+ *   embedding   device f32 [vocab_size, embed_size]
+ *   W1          device f32 [out, joint_size]: the joint's first Dense layer, zero-padded to joint_size columns (out = the last
+ *               block's output width); joint_size a multiple of 64 up to 704 (what the greedy / beam decoders take)
+ *   emitted     device i32 [rows]: tokens in [0, vocab_size) or negative (a PRECONDITION: the device does not check tokens)
+ *   parents     device i32 [rows] in [0, rows), or NULL
+ *   pred_proj_out device f32 [rows, joint_size]: the `pred_proj` of compute_rnnt_greedy_step / compute_rnnt_beam_step
+ *   options     loc RNNT_GPU, stream; the other fields are not used
+ * Limits: 1 <= rows <= 1024, 1 <= num_blocks <= 8, every width (embed, hidden, proj) in 1 ... 4096; anything else, a NULL
+ * pointer or a misaligned one: RNNT_STATUS_INVALID_VALUE, before anything is enqueued.
+ *
+ * compute_rnnt_prednet_begin (once per decode) packs embedding, every block's weights and W1 into the workspace (the caller may
+ * then free or change them), zeroes every row's state and runs the start token 0 (not blank_label) for every row, writing
+ * pred_proj_out.  compute_rnnt_prednet_step runs one step as above; the blocks' weight pointers are not read (only the widths
+ * and eps must match begin's).  The state and pred_proj are double-buffered in the workspace by step parity, so `parents` may
+ * name any row.  Arithmetic: float32, every sum in a fixed order: a row's results are bitwise independent of `rows`, of the
+ * other rows and of the run.
+ * Workspace: get_rnnt_prednet_workspace_size(...) bytes, 256-byte aligned, owned by one decode from its begin to its last step.
+ * It begins with the state: for slot s = (number of begin and step calls so far) & 1, and S = the sum over blocks of
+ * A(rows * proj_l) + A(rows * hidden_l) floats, A(n) = n rounded up to a multiple of 64: block l's r [rows, proj_l] sits at float
+ * s * S + sum_{m < l} (A(rows proj_m) + A(rows hidden_m)) and its c [rows, hidden_l] right after A(rows proj_l) floats.
+ * No entry point synchronises the host.
+ */
+typedef struct rnntPrednetBlock {
+    const float *W_ih;       /* [4 hidden, in]   in = embed_size for block 0, else the previous block's proj */
+    const float *W_hh;       /* [4 hidden, proj] */
+    const float *b_ih;       /* [4 hidden] */
+    const float *b_hh;       /* [4 hidden] */
+    const float *W_hr;       /* [proj, hidden], or NULL: no projection (proj must then equal hidden) */
+    const float *ln_weight;  /* [proj] LayerNorm gamma */
+    const float *ln_bias;    /* [proj] LayerNorm beta */
+    int hidden;
+    int proj;
+    float ln_eps;
+} rnntPrednetBlock;
+
+RNNT_API rnntStatus_t get_rnnt_prednet_workspace_size(const rnntPrednetBlock *blocks, int num_blocks, int embed_size,
+                                                      int vocab_size, int joint_size, int rows, size_t *size_bytes);
+
+RNNT_API rnntStatus_t compute_rnnt_prednet_begin(const float *embedding, const rnntPrednetBlock *blocks, int num_blocks,
+                                                 int embed_size, int vocab_size, const float *W1, int joint_size, int rows,
+                                                 float *pred_proj_out, void *workspace, rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_prednet_step(const int *emitted, const int *parents, float *pred_proj_out,
+                                                const rnntPrednetBlock *blocks, int num_blocks, int embed_size, int vocab_size,
+                                                int joint_size, int rows, void *workspace, rnntOptions options);
+
 #ifdef __cplusplus
 }
 #endif

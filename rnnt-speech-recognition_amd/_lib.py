@@ -42,6 +42,9 @@ SYMBOLS = [
     "compute_rnnt_beam_begin",
     "compute_rnnt_beam_step",
     "compute_rnnt_beam_results",
+    "get_rnnt_prednet_workspace_size",
+    "compute_rnnt_prednet_begin",
+    "compute_rnnt_prednet_step",
 ]
 
 
@@ -58,6 +61,22 @@ class rnntOptions(ctypes.Structure):
         ("maxT", ctypes.c_int),
         ("maxU", ctypes.c_int),
         ("batch_first", ctypes.c_bool),
+    ]
+
+
+class rnntPrednetBlock(ctypes.Structure):
+    """One LSTM block of the prediction network (include/rnnt.h): device pointers, widths and the LayerNorm epsilon."""
+    _fields_ = [
+        ("W_ih", ctypes.c_void_p),
+        ("W_hh", ctypes.c_void_p),
+        ("b_ih", ctypes.c_void_p),
+        ("b_hh", ctypes.c_void_p),
+        ("W_hr", ctypes.c_void_p),
+        ("ln_weight", ctypes.c_void_p),
+        ("ln_bias", ctypes.c_void_p),
+        ("hidden", ctypes.c_int),
+        ("proj", ctypes.c_int),
+        ("ln_eps", ctypes.c_float),
     ]
 
 
@@ -144,6 +163,14 @@ def load():
         lib.compute_rnnt_beam_step.argtypes = [vp] * 6 + [ci] * 5 + [vp, rnntOptions]
         lib.compute_rnnt_beam_results.restype = ci
         lib.compute_rnnt_beam_results.argtypes = [vp] * 3 + [ci] * 5 + [vp, rnntOptions]
+    if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "compute_rnnt_prednet_step"):
+        blk = ctypes.POINTER(rnntPrednetBlock)
+        lib.get_rnnt_prednet_workspace_size.restype = ci
+        lib.get_rnnt_prednet_workspace_size.argtypes = [blk] + [ci] * 5 + [ctypes.POINTER(ctypes.c_size_t)]
+        lib.compute_rnnt_prednet_begin.restype = ci
+        lib.compute_rnnt_prednet_begin.argtypes = [vp, blk, ci, ci, ci, vp, ci, ci, vp, vp, rnntOptions]
+        lib.compute_rnnt_prednet_step.restype = ci
+        lib.compute_rnnt_prednet_step.argtypes = [vp, vp, vp, blk] + [ci] * 5 + [vp, rnntOptions]
     _lib = lib
     return lib
 
@@ -193,6 +220,14 @@ def beam_workspace_bytes(maxT: int, minibatch: int, beam: int, joint_size: int, 
     n = ctypes.c_size_t(0)
     check(load().get_rnnt_beam_workspace_size(maxT, minibatch, beam, joint_size, alphabet_size, joint_dtype, ctypes.byref(n)),
           "get_rnnt_beam_workspace_size")
+    return int(n.value)
+
+
+def prednet_workspace_bytes(blocks, embed_size: int, vocab_size: int, joint_size: int, rows: int) -> int:
+    """blocks: a ctypes array of rnntPrednetBlock (only the widths are read)."""
+    n = ctypes.c_size_t(0)
+    check(load().get_rnnt_prednet_workspace_size(blocks, len(blocks), embed_size, vocab_size, joint_size, rows, ctypes.byref(n)),
+          "get_rnnt_prednet_workspace_size")
     return int(n.value)
 
 

@@ -55,6 +55,12 @@ hipError_t launch_beam_step(const float *pred_proj, int *parents, int *emitted, 
                             int J, int V, int B, int T, int K, int blank, int joint_dtype, void *workspace, hipStream_t s);
 hipError_t launch_beam_results(int *hyps, int *hyp_lengths, float *scores, int J, int V, int B, int T, int K, int joint_dtype,
                                void *workspace, hipStream_t s);
+// prednet_kernels.hip (the prediction-network step of the decoders)
+bool prednet_layout_ok(const rnntPrednetBlock *blocks, int L, int E, int V, int Jp, int R, size_t *bytes);
+hipError_t launch_prednet_begin(const float *emb, const rnntPrednetBlock *blocks, int L, int E, int V, const float *W1, int Jp, int R,
+                                float *out, void *workspace, hipStream_t s);
+hipError_t launch_prednet_step(const int *emitted, const int *parents, float *out, const rnntPrednetBlock *blocks, int L, int E,
+                               int V, int Jp, int R, void *workspace, hipStream_t s);
 }  // namespace rnnt
 
 static rnntStatus_t check_options(const rnntOptions &o) {
@@ -592,6 +598,57 @@ rnntStatus_t compute_rnnt_beam_results(int *hyps, int *hyp_lengths, float *score
     if (st != RNNT_STATUS_SUCCESS) return st;
     return from_hip(launch_beam_results(hyps, hyp_lengths, scores, joint_size, alphabet_size, minibatch, options.maxT, beam,
                                        joint_dtype, workspace, (hipStream_t)options.stream));
+}
+
+
+// The prediction-network step (include/rnnt.h).  Everything is checked before anything is enqueued.
+static bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
+
+static rnntStatus_t check_prednet(const rnntPrednetBlock *blocks, int num_blocks, int embed_size, int vocab_size, int joint_size,
+                                  int rows, const void *workspace, bool weights, const rnntOptions &o) {
+    if (!blocks || !workspace) return RNNT_STATUS_INVALID_VALUE;
+    if (o.loc != RNNT_GPU) return RNNT_STATUS_INVALID_VALUE;
+    if (((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
+    if (!prednet_layout_ok(blocks, num_blocks, embed_size, vocab_size, joint_size, rows, nullptr)) return RNNT_STATUS_INVALID_VALUE;
+    if (weights) {
+        for (int l = 0; l < num_blocks; ++l) {
+            const rnntPrednetBlock &b = blocks[l];
+            if (!b.W_ih || !b.W_hh || !b.b_ih || !b.b_hh || !b.ln_weight || !b.ln_bias) return RNNT_STATUS_INVALID_VALUE;
+            if (!aligned16(b.W_ih) || !aligned16(b.W_hh) || !aligned16(b.b_ih) || !aligned16(b.b_hh) || !aligned16(b.W_hr) ||
+                !aligned16(b.ln_weight) || !aligned16(b.ln_bias))
+                return RNNT_STATUS_INVALID_VALUE;
+        }
+    }
+    return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t get_rnnt_prednet_workspace_size(const rnntPrednetBlock *blocks, int num_blocks, int embed_size, int vocab_size,
+                                             int joint_size, int rows, size_t *size_bytes) {
+    if (!size_bytes) return RNNT_STATUS_INVALID_VALUE;
+    return prednet_layout_ok(blocks, num_blocks, embed_size, vocab_size, joint_size, rows, size_bytes) ? RNNT_STATUS_SUCCESS
+                                                                                                       : RNNT_STATUS_INVALID_VALUE;
+}
+
+rnntStatus_t compute_rnnt_prednet_begin(const float *embedding, const rnntPrednetBlock *blocks, int num_blocks, int embed_size,
+                                        int vocab_size, const float *W1, int joint_size, int rows, float *pred_proj_out,
+                                        void *workspace, rnntOptions options) {
+    if (!embedding || !W1 || !pred_proj_out) return RNNT_STATUS_INVALID_VALUE;
+    if (!aligned16(embedding) || !aligned16(W1) || !aligned16(pred_proj_out)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_prednet(blocks, num_blocks, embed_size, vocab_size, joint_size, rows, workspace, true, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_prednet_begin(embedding, blocks, num_blocks, embed_size, vocab_size, W1, joint_size, rows, pred_proj_out,
+                                         workspace, (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_prednet_step(const int *emitted, const int *parents, float *pred_proj_out, const rnntPrednetBlock *blocks,
+                                       int num_blocks, int embed_size, int vocab_size, int joint_size, int rows, void *workspace,
+                                       rnntOptions options) {
+    if (!emitted || !pred_proj_out) return RNNT_STATUS_INVALID_VALUE;
+    if (!aligned16(emitted) || !aligned16(parents) || !aligned16(pred_proj_out)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_prednet(blocks, num_blocks, embed_size, vocab_size, joint_size, rows, workspace, false, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_prednet_step(emitted, parents, pred_proj_out, blocks, num_blocks, embed_size, vocab_size, joint_size, rows,
+                                        workspace, (hipStream_t)options.stream));
 }
 
 }  // extern "C"

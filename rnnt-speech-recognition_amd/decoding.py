@@ -23,7 +23,7 @@ from typing import List, Optional
 
 import torch
 
-from .joint import BeamJoint, GreedyJoint
+from .joint import BeamJoint, GreedyJoint, PredictionStep
 from .loss import reduced_lengths
 
 
@@ -102,6 +102,27 @@ def read_flag(x: torch.Tensor) -> int:
             torch.cuda.set_sync_debug_mode(mode)
 
 
+_PRED_WORKSPACES = {}  # (device, stream) -> the prediction-network workspace of the last engine-route decode there
+PREDICTIONS = ("torch", "engine")
+
+
+def _prediction_step(model, joint, rows: int, dev):
+    """The engine route's PredictionStep for `joint` (a GreedyJoint / BeamJoint), begun for `rows` rows -> (step, pred_proj)."""
+    W1 = joint.W1 if joint.engine else model.joint.W1  # (the joint-unit padding of the engine joint; the torch joint takes J)
+    ps = PredictionStep(model.prediction, W1)
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream) if W1.is_cuda else None
+    ps._ws = _PRED_WORKSPACES.get(key)
+    pp = ps.begin(rows)
+    if ps._ws is not None:
+        _PRED_WORKSPACES[key] = ps._ws
+    return ps, pp
+
+
+def _check_prediction(prediction: str):
+    if prediction not in PREDICTIONS:
+        raise ValueError(f"prediction must be one of {PREDICTIONS}, got {prediction!r}")
+
+
 def _pred_step(pred_net, tokens: torch.Tensor, states):
     """One symbol through the prediction network for every row: tokens [B] -> (output [B, H], new states)."""
     y = pred_net.embed(tokens.long()[:, None])
@@ -115,9 +136,10 @@ def _pred_step(pred_net, tokens: torch.Tensor, states):
 
 @torch.no_grad()
 def greedy_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, max_length=None,
-                        max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY):
+                        max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY, prediction: str = "torch"):
     """Greedy search over encoder outputs enc [B, T', H] with frame_lengths [B] (the model in eval mode).  See greedy_decode_batch."""
     global LAST_STEPS
+    _check_prediction(prediction)
     B, T = enc.shape[0], enc.shape[1]
     dev = enc.device
     if max_length is None:
@@ -134,6 +156,21 @@ def greedy_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, m
     jg.begin(enc, frame_lengths, maxsym, int(max_symbols_per_frame or 0), N)
     if jg._ws is not None:
         _WORKSPACES[key] = jg._ws
+    if prediction == "engine":  # the loop body is library calls alone: the joint step, then the prediction-network step
+        ps, pp = _prediction_step(model, jg, B, dev)
+        steps = 0
+        while True:
+            emitted = jg.step(pred_proj=pp)
+            steps += 1
+            if steps % check_every == 0:
+                flag = read_flag(jg.all_done)
+                if flag == 1:
+                    break
+                if flag == 2:
+                    jg.grow_hyps()
+            pp = ps.step(emitted)
+        LAST_STEPS = steps
+        return jg.hyps, jg.lengths, jg.scores
     pred_net = model.prediction
     g, states = _pred_step(pred_net, torch.zeros(B, dtype=torch.int32, device=dev), [None] * len(pred_net.blocks))
     steps = 0
@@ -158,7 +195,7 @@ def greedy_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, m
 
 @torch.no_grad()
 def greedy_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[torch.Tensor] = None, max_length=None,
-                        max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY):
+                        max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY, prediction: str = "torch"):
     """Greedy decoding of EVERY utterance of a batch at once -> (ids int32 [B, N] zero-padded, lengths int32 [B], scores [B]).
 
     Per utterance the semantics of greedy_decode (utils/decoding.py:21-108): the hypothesis starts from token 0, symbols are
@@ -171,7 +208,9 @@ def greedy_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[t
 
     The prediction network steps all B rows at once (rows that emitted nothing keep their state), and on an MI355X the joint is
     the library's greedy step (GreedyJoint): no host synchronisation per step -- the all-done word is read every
-    `check_every` steps (read_flag)."""
+    `check_every` steps (read_flag).  prediction="engine" steps the prediction network in the library too (PredictionStep:
+    compute_rnnt_prednet_step, through W1 into the joint step), so that the loop body is library calls alone; "torch" (the
+    default) steps it with the model's own modules."""
     was_training = model.training
     model.eval()
     try:
@@ -181,15 +220,17 @@ def greedy_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[t
             frames = torch.full((B,), T, dtype=torch.int32, device=enc.device)
         else:
             frames = reduced_lengths(spec_lengths.to(enc.device), model.hp.time_reduction_factor)
-        return greedy_search_batch(model, enc, frames, max_length, max_symbols_per_frame, check_every)
+        return greedy_search_batch(model, enc, frames, max_length, max_symbols_per_frame, check_every, prediction)
     finally:
         model.train(was_training)
 
 
-def greedy_decode_batch_fn(model):
+def greedy_decode_batch_fn(model, prediction: str = "torch"):
     """fn(inputs, max_length=None, spec_lengths=None) -> (ids, lengths, scores) of greedy_decode_batch."""
+    _check_prediction(prediction)
+
     def fn(inputs: torch.Tensor, max_length=None, spec_lengths: Optional[torch.Tensor] = None):
-        return greedy_decode_batch(model, inputs, spec_lengths, max_length)
+        return greedy_decode_batch(model, inputs, spec_lengths, max_length, prediction=prediction)
     return fn
 
 
@@ -200,14 +241,16 @@ _BEAM_WORKSPACES = {}  # (device, stream) -> the beam workspace of the last deco
 
 
 @torch.no_grad()
-def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, beam: int = 4):
+def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, beam: int = 4, prediction: str = "torch"):
     """Modified beam search (one symbol per frame) over encoder outputs enc [B, T', H] with frame_lengths [B] (the model in eval
     mode) -> (ids int32 [B, beam, T'] zero-padded, lengths int32 [B, beam], scores [B, beam]): every utterance's n-best, sorted
     by score (empty slots: length 0, score -inf).  See include/rnnt.h for the algorithm; beam = 1 is greedy_search_batch with
     max_symbols_per_frame = 1.
 
     Runs enc.shape[1] steps without reading the host.  Per step the prediction network runs on all B beam rows; its output and
-    LSTM state are gathered by `parents`, and the rows that emitted a symbol advance."""
+    LSTM state are gathered by `parents`, and the rows that emitted a symbol advance.  prediction="engine": that step is the
+    library's (PredictionStep), as in greedy_search_batch."""
+    _check_prediction(prediction)
     B, T = enc.shape[0], enc.shape[1]
     K = int(beam)
     dev = enc.device
@@ -217,6 +260,14 @@ def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, bea
     jb.begin(enc, frame_lengths)
     if jb._ws is not None:
         _BEAM_WORKSPACES[key] = jb._ws
+    if prediction == "engine":
+        ps, pp = _prediction_step(model, jb, B * K, dev)
+        for t in range(T):
+            parents, emitted = jb.step(pred_proj=pp)
+            if t + 1 == T:
+                break
+            pp = ps.step(emitted, parents)
+        return jb.results()
     pred_net = model.prediction
     g, states = _pred_step(pred_net, torch.zeros(B * K, dtype=torch.int32, device=dev), [None] * len(pred_net.blocks))
     for t in range(T):
@@ -235,7 +286,8 @@ def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, bea
 
 
 @torch.no_grad()
-def beam_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[torch.Tensor] = None, beam: int = 4):
+def beam_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[torch.Tensor] = None, beam: int = 4,
+                      prediction: str = "torch"):
     """Beam search of EVERY utterance of a batch -> the best hypothesis of each: (ids int32 [B, T'] zero-padded, lengths int32
     [B], scores [B]).  spec_lengths are spectrogram frames, reduced as greedy_decode_batch reduces them; None: every frame."""
     was_training = model.training
@@ -247,18 +299,20 @@ def beam_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[tor
             frames = torch.full((B,), T, dtype=torch.int32, device=enc.device)
         else:
             frames = reduced_lengths(spec_lengths.to(enc.device), model.hp.time_reduction_factor)
-        ids, lengths, scores = beam_search_batch(model, enc, frames, beam)
+        ids, lengths, scores = beam_search_batch(model, enc, frames, beam, prediction)
         return ids[:, 0], lengths[:, 0], scores[:, 0]
     finally:
         model.train(was_training)
 
 
-def beam_decode_batch_fn(model, beam: int = 4):
+def beam_decode_batch_fn(model, beam: int = 4, prediction: str = "torch"):
     """fn(inputs, max_length=None, spec_lengths=None) -> (ids, lengths, scores) of beam_decode_batch, for
     metrics.build_batch_accuracy_fn / build_batch_wer_fn.  The search has no symbol budget: max_length (an int or an int tensor
     [B]) truncates the best hypothesis afterwards."""
+    _check_prediction(prediction)
+
     def fn(inputs: torch.Tensor, max_length=None, spec_lengths: Optional[torch.Tensor] = None):
-        ids, lengths, scores = beam_decode_batch(model, inputs, spec_lengths, beam)
+        ids, lengths, scores = beam_decode_batch(model, inputs, spec_lengths, beam, prediction)
         if max_length is not None:
             cap = torch.as_tensor(max_length, device=lengths.device).to(torch.int32)
             lengths = torch.minimum(lengths, cap)

@@ -384,6 +384,22 @@ class JointLoss(torch.nn.Module):
         return self.logits(enc, pred)
 
 
+def _projected_operand(pred_proj, Jp: int):
+    if pred_proj.dtype != torch.float32 or pred_proj.dim() != 2 or pred_proj.shape[1] != Jp:
+        raise ValueError(f"pred_proj must be float32 [rows, {Jp}] (the joint-unit padded pred @ W1)")
+    return pred_proj.contiguous()
+
+
+def _torch_cell_logits(joint: "JointLoss", e, pred, pred_proj):
+    """One joint cell per row on the torch route: e [R, H] against pred [R, H] (JointLoss.logits), or against pred_proj
+    [R, >= J] = pred @ W1 already (its first J columns): tanh(e W1 + b1 + pred_proj) W2 + b2 -> [R, V]."""
+    if pred_proj is None:
+        return joint.logits(e[:, None, :], pred[:, None, :])[:, 0, 0, :]
+    J = joint.W1.shape[1]
+    z = e @ joint.W1 + joint.b1 + pred_proj[:, :J].to(e.dtype)
+    return torch.tanh(z) @ joint.W2 + joint.b2
+
+
 class GreedyJoint:
     """The joint of the batched greedy decoder (decoding.greedy_decode_batch): one lattice cell per hypothesis and step, argmax,
     log-softmax of the decision and the decoder state in one pass.
@@ -453,11 +469,12 @@ class GreedyJoint:
                                                self.dtype, self._ws.data_ptr(), self._opts)
         _lib.check(st, "compute_rnnt_greedy_begin")
 
-    def step(self, pred, logit_stats=None):
-        """pred [B, H]: the prediction network's output of every row -> emitted [B] (int32, -1 where nothing was emitted)."""
+    def step(self, pred=None, logit_stats=None, *, pred_proj=None):
+        """pred [B, H]: the prediction network's output of every row -> emitted [B] (int32, -1 where nothing was emitted).
+        pred_proj [B, Jp] instead of pred: that output already through W1 (PredictionStep); the step skips its matmul."""
         if not self.engine:
-            return self._torch_step(pred)
-        pp = torch.matmul(pred.float(), self.W1).contiguous()
+            return self._torch_step(pred, pred_proj)
+        pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _projected_operand(pred_proj, self.Jp)
         st = _lib.load().compute_rnnt_greedy_step(pp.data_ptr(), self.hyps.data_ptr(), self.hyps.shape[1], self.lengths.data_ptr(),
                                                   self.scores.data_ptr(), self.emitted.data_ptr(), self.all_done.data_ptr(),
                                                   None if logit_stats is None else logit_stats.data_ptr(), self.Jp, self.V, self.B,
@@ -485,12 +502,12 @@ class GreedyJoint:
         self._nf = torch.zeros(B, dtype=torch.long, device=dev)
         self._done = (self._Tb == 0) | (self._maxsym == 0)
 
-    def _torch_step(self, pred):
+    def _torch_step(self, pred, pred_proj=None):
         B, T, N = self.B, self.T, self.hyps.shape[1]
-        ar = torch.arange(B, device=pred.device)
+        ar = torch.arange(B, device=self._enc.device)
         live = ~self._done & (self._n < self._maxsym.clamp(max=N))
         e = self._enc[ar, self._t.clamp(0, T - 1)]
-        logits = self.joint.logits(e[:, None, :], pred[:, None, :])[:, 0, 0, :]
+        logits = _torch_cell_logits(self.joint, e, pred, pred_proj)
         k = torch.argmax(logits, dim=-1)
         M = logits.gather(1, k[:, None])[:, 0]
         lse = torch.logsumexp(logits, dim=-1)
@@ -557,11 +574,12 @@ class BeamJoint:
                                                      self.Jp, self.V, B, self.K, self.dtype, self._ws.data_ptr(), self._opts)
         _lib.check(st, "compute_rnnt_beam_begin")
 
-    def step(self, pred, topk_logits=None, topk_symbols=None, lse=None):
-        """pred [B beam, H]: the prediction network's output of every slot -> (parents, emitted), int32 [B beam]."""
+    def step(self, pred=None, topk_logits=None, topk_symbols=None, lse=None, *, pred_proj=None):
+        """pred [B beam, H]: the prediction network's output of every slot -> (parents, emitted), int32 [B beam].
+        pred_proj [B beam, Jp] instead of pred: that output already through W1 (PredictionStep); the step skips its matmul."""
         if not self.engine:
-            return self._torch_step(pred)
-        pp = torch.matmul(pred.float(), self.W1).contiguous()
+            return self._torch_step(pred, pred_proj)
+        pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _projected_operand(pred_proj, self.Jp)
         ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         st = _lib.load().compute_rnnt_beam_step(pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(), ptr(topk_logits),
                                                 ptr(topk_symbols), ptr(lse), self.Jp, self.V, self.B, self.K, self.dtype,
@@ -590,14 +608,14 @@ class BeamJoint:
         self._beams = [[((), 0.0)] for _ in range(self.B)]  # (tokens, float64 score), best first
         self._sdtype = torch.promote_types(enc.dtype, torch.float32)
 
-    def _torch_step(self, pred):
+    def _torch_step(self, pred, pred_proj=None):
         B, K, V, blank = self.B, self.K, self.V, self.blank
         t = self._t
         self._t += 1
         parents = list(range(B * K))
         emitted = [-1] * (B * K)
         e = self._enc[:, min(t, self.T - 1)]  # [B, H]
-        logits = self.joint.logits(e.repeat_interleave(K, 0)[:, None, :], pred[:, None, :])[:, 0, 0, :]  # [B K, V]
+        logits = _torch_cell_logits(self.joint, e.repeat_interleave(K, 0), pred, pred_proj)  # [B K, V]
         lse = torch.logsumexp(logits, dim=-1)
         top_l, top_v = torch.sort(logits, dim=-1, descending=True, stable=True)  # (logit descending, symbol ascending)
         top_l, top_v, lse = top_l[:, :K].tolist(), top_v[:, :K].tolist(), lse.tolist()
@@ -646,3 +664,146 @@ class BeamJoint:
                 lengths[b, k], scores[b, k] = len(y), s
         dev = self.parents.device
         return hyps.to(dev), lengths.to(dev), scores.to(device=dev, dtype=self._sdtype)
+
+
+def _aligned16(x: torch.Tensor) -> torch.Tensor:
+    x = x.detach().contiguous()
+    return x if x.data_ptr() % 16 == 0 else x.clone()
+
+
+class PredictionStep:
+    """One prediction-network step for every decoder row, through the joint's first Dense layer: the `pred_proj` that
+    GreedyJoint.step / BeamJoint.step take as `pred_proj=`.
+
+    On an MI355X this is the ENGINE (include/rnnt.h compute_rnnt_prednet_begin / _step): begin packs the current weights into
+    the workspace (the object owns it; the next decode reuses it when it is large enough), zeroes every row's state and runs the
+    start token 0; each step advances the rows with emitted >= 0 from row parents[r]'s state (parents None: their own) and
+    carries the others over.  CPU tensors, models that are not float32 and shapes the kernels do not take run the same state
+    machine in torch (decoding._pred_step, then the parents gather and torch.where, then matmul(W1)).
+
+    pred_net: model.PredictionNetwork (embedding + single-layer LSTM blocks with LayerNorm); W1 [out, Jp]: the joint's first
+    Dense layer zero-padded to the decoder's joint units (GreedyJoint.W1 on the engine).  begin(rows) -> pred_proj [rows, Jp];
+    step(emitted [rows] int32, parents [rows] int32 or None) -> pred_proj (the same tensor, overwritten by the next step)."""
+
+    MAX_ROWS, MAX_BLOCKS, MAX_WIDTH = 1024, 8, 4096
+
+    def __init__(self, pred_net, W1: torch.Tensor):
+        self.net = pred_net
+        self.W1 = W1.detach()
+        self.Jp = int(W1.shape[1])
+        self.engine = self._engine_takes()
+        self._ws = None
+
+    def _engine_takes(self) -> bool:
+        net, W1 = self.net, self.W1
+        blocks = list(net.blocks)
+        if not W1.is_cuda or not 1 <= len(blocks) <= self.MAX_BLOCKS or self.Jp % 64 != 0 or not 64 <= self.Jp <= 704:
+            return False
+        tensors = [W1, net.embed.weight]
+        width = net.embed.embedding_dim
+        if width > self.MAX_WIDTH:
+            return False
+        for blk in blocks:
+            lstm, norm = blk.lstm, blk.norm
+            if lstm.num_layers != 1 or lstm.bidirectional or not lstm.bias or lstm.input_size != width:
+                return False
+            out = lstm.proj_size or lstm.hidden_size
+            if lstm.hidden_size > self.MAX_WIDTH or out > self.MAX_WIDTH or not norm.elementwise_affine or norm.bias is None:
+                return False
+            if tuple(norm.normalized_shape) != (out,):
+                return False
+            tensors += list(lstm.parameters()) + [norm.weight, norm.bias]
+            width = out
+        if W1.shape[0] != width:
+            return False
+        return all(t.dtype == torch.float32 and t.device == W1.device for t in tensors)
+
+    def begin(self, rows: int) -> torch.Tensor:
+        self.R = int(rows)
+        self._use_engine = self.engine and 1 <= self.R <= self.MAX_ROWS
+        dev = self.W1.device
+        if not self._use_engine:
+            from .decoding import _pred_step
+
+            self._g, self._states = _pred_step(self.net, torch.zeros(self.R, dtype=torch.int32, device=dev),
+                                               [None] * len(self.net.blocks))
+            return self._project()
+        net = self.net
+        keep = [_aligned16(net.embed.weight), _aligned16(self.W1)]
+        blocks = (_lib.rnntPrednetBlock * len(net.blocks))()
+        for b, blk in zip(blocks, net.blocks):
+            lstm, norm = blk.lstm, blk.norm
+            w = [_aligned16(x) for x in (lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, norm.weight, norm.bias)]
+            wr = _aligned16(lstm.weight_hr_l0) if lstm.proj_size else None
+            keep += w + ([wr] if wr is not None else [])
+            b.W_ih, b.W_hh, b.b_ih, b.b_hh = (x.data_ptr() for x in w[:4])
+            b.W_hr = None if wr is None else wr.data_ptr()
+            b.ln_weight, b.ln_bias = w[4].data_ptr(), w[5].data_ptr()
+            b.hidden, b.proj, b.ln_eps = lstm.hidden_size, lstm.proj_size or lstm.hidden_size, float(norm.eps)
+        self._blocks, self._keep = blocks, keep
+        self.E, self.V = net.embed.embedding_dim, net.embed.num_embeddings
+        self._n = 0
+        with torch.cuda.device(dev):
+            nbytes = _lib.prednet_workspace_bytes(blocks, self.E, self.V, self.Jp, self.R)
+            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
+                self._ws = _new_workspace(nbytes, dev)
+            elif _WORKSPACE_FILL is not None:
+                self._ws.fill_(int(_WORKSPACE_FILL))
+            self.pred_proj = torch.empty(self.R, self.Jp, dtype=torch.float32, device=dev)
+            self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, 0, 1, 1)
+            st = _lib.load().compute_rnnt_prednet_begin(keep[0].data_ptr(), blocks, len(blocks), self.E, self.V, keep[1].data_ptr(),
+                                                        self.Jp, self.R, self.pred_proj.data_ptr(), self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_prednet_begin")
+        self._n = 1
+        return self.pred_proj
+
+    def step(self, emitted: torch.Tensor, parents=None) -> torch.Tensor:
+        if not self._use_engine:
+            return self._torch_step(emitted, parents)
+        dev = self.pred_proj.device
+        em = emitted.to(device=dev, dtype=torch.int32).contiguous()
+        pa = None if parents is None else parents.to(device=dev, dtype=torch.int32).contiguous()
+        self._args = (em, pa)  # (alive until the launch has read them)
+        st = _lib.load().compute_rnnt_prednet_step(em.data_ptr(), None if pa is None else pa.data_ptr(), self.pred_proj.data_ptr(),
+                                                   self._blocks, len(self._blocks), self.E, self.V, self.Jp, self.R,
+                                                   self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_prednet_step")
+        self._n += 1
+        return self.pred_proj
+
+    def state(self):
+        """Every block's current (r [rows, proj], c [rows, hidden]): torch's (h, c) of the LSTM (views on the engine, valid until
+        the next step)."""
+        if not self._use_engine:
+            return [(h[0], c[0]) for h, c in self._states]
+        R = self.R
+        a64 = lambda n: (n + 63) // 64 * 64  # noqa: E731  (the workspace layout of include/rnnt.h)
+        sizes = [(R * b.proj, R * b.hidden) for b in self._blocks]
+        S = sum(a64(p) + a64(c) for p, c in sizes)
+        f = self._ws.view(torch.float32)
+        off = (self._n & 1) * S
+        out = []
+        for (p, c), b in zip(sizes, self._blocks):
+            out.append((f[off: off + p].view(R, b.proj), f[off + a64(p): off + a64(p) + c].view(R, b.hidden)))
+            off += a64(p) + a64(c)
+        return out
+
+    # ---- torch composition
+    def _project(self):
+        return torch.matmul(self._g.to(self.W1.dtype), self.W1)
+
+    def _torch_step(self, emitted, parents):
+        from .decoding import _pred_step
+
+        g, states = self._g, self._states
+        if parents is not None:
+            idx = parents.to(g.device).long()
+            g = g[idx]
+            states = [(h[:, idx], c[:, idx]) for h, c in states]
+        emitted = emitted.to(g.device)
+        mask = emitted >= 0
+        g2, states2 = _pred_step(self.net, emitted.clamp(min=0), states)
+        self._g = torch.where(mask[:, None], g2, g)
+        self._states = [(torch.where(mask[None, :, None], h2, h), torch.where(mask[None, :, None], c2, c))
+                        for (h2, c2), (h, c) in zip(states2, states)]
+        return self._project()
