@@ -523,6 +523,55 @@ RNNT_API rnntStatus_t compute_rnnt_prednet_step(const int *emitted, const int *p
                                                 const rnntPrednetBlock *blocks, int num_blocks, int embed_size, int vocab_size,
                                                 int joint_size, int rows, void *workspace, rnntOptions options);
 
+/* Build-only extension: the ENCODER's forward pass for every utterance of a batch (model.py Encoder, inference only), carrying
+ * its LSTM state from one run to the next, so that a long input may be encoded in chunks.  The network: a BatchNorm over the
+ * feat_size features with running statistics, x' = (x - bn_mean) * bn_weight / sqrt(bn_var + bn_eps) + bn_bias, then
+ * num_layers blocks of one single-layer LSTM (torch gate order i, f, g, o; optional bias-free projection) -> LayerNorm (biased
+ * variance; dropout is an eval no-op), described by the rnntPrednetBlock struct above (block 0's in = feat_size).  After block
+ * reduction_index, TimeReduction stacks reduction_factor = f consecutive frames of the LayerNorm output into one row of f times
+ * the width (block reduction_index + 1's in = f * proj); a frame past the end of the run's input reads as ZEROS (the pad comes
+ * after the LayerNorm).  Padded frames are run through, as in the reference.
+ *
+ * Per row r = 0 ... rows-1 (one utterance each) and block l with state (r_l [rows, proj_l], c_l [rows, hidden_l]):
+ *   for every frame t of the block's input:  gates = W_ih x_t + b_ih + W_hh r + b_hh;  c = sigma(f) c + sigma(i) tanh(g);
+ *                                            h = sigma(o) tanh(c);  r = W_hr h (projected block) or h
+ * r is the raw block output before the LayerNorm (torch's h of an LSTM with proj_size).
+ *
+ *   blocks       HOST array of num_layers rnntPrednetBlock; the weight pointers are device f32, 16-byte aligned
+ *   bn_*         device f32 [feat_size]
+ *   x            device f32 [rows, frames, feat_size], contiguous
+ *   out          device f32 [rows, ceil(frames / f), out_width]: the last block's LayerNorm output (out_width = its proj)
+ *   options      loc RNNT_GPU, stream; the other fields are not used
+ * Limits: 1 <= rows <= 1024, 1 <= num_layers <= 16, every width (feat, hidden, proj, f * proj at the reduction) in 1 ... 4096,
+ * 0 <= reduction_index < num_layers - 1, 1 <= reduction_factor <= 16, 1 <= frames <= max_frames <= 2^20; anything else, a NULL
+ * pointer or a misaligned one: RNNT_STATUS_INVALID_VALUE, before anything is enqueued.
+ *
+ * compute_rnnt_encoder_begin packs every block's weights and the BatchNorm into the workspace (the caller may then free or change
+ * them) and zeroes every row's state.  compute_rnnt_encoder_run encodes `frames` more frames of every row and advances the state;
+ * the blocks' weight pointers are not read (only the widths and eps must match begin's).
+ * Chunking: each run pads its own odd tail at the reduction, as TimeReduction does per call.  Runs whose lengths are multiples of
+ * f, except the last, give bit-identical output and state to one run over the concatenation.
+ * Arithmetic: float32, every sum in a fixed order: a row's results are bitwise independent of `rows`, of the other rows and of
+ * the run.
+ * Workspace: get_rnnt_encoder_workspace_size(...) bytes, 256-byte aligned, owned by one stream from begin to its last run.  It
+ * begins with the state: with A(n) = n rounded up to a multiple of 64, block l's r [rows, proj_l] sits at float
+ * sum_{m < l} (A(rows proj_m) + A(rows hidden_m)) and its c [rows, hidden_l] right after A(rows proj_l) floats.
+ * No entry point synchronises the host.
+ */
+RNNT_API rnntStatus_t get_rnnt_encoder_workspace_size(const rnntPrednetBlock *blocks, int num_layers, int feat_size,
+                                                      int reduction_index, int reduction_factor, int rows, int max_frames,
+                                                      size_t *size_bytes);
+
+RNNT_API rnntStatus_t compute_rnnt_encoder_begin(const rnntPrednetBlock *blocks, int num_layers, int feat_size,
+                                                 const float *bn_mean, const float *bn_var, const float *bn_weight,
+                                                 const float *bn_bias, float bn_eps, int reduction_index, int reduction_factor,
+                                                 int rows, int max_frames, void *workspace, rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_encoder_run(const float *x, int frames, float *out, const rnntPrednetBlock *blocks,
+                                               int num_layers, int feat_size, float bn_eps, int reduction_index,
+                                               int reduction_factor, int rows, int max_frames, void *workspace,
+                                               rnntOptions options);
+
 #ifdef __cplusplus
 }
 #endif

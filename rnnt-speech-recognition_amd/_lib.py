@@ -45,6 +45,9 @@ SYMBOLS = [
     "get_rnnt_prednet_workspace_size",
     "compute_rnnt_prednet_begin",
     "compute_rnnt_prednet_step",
+    "get_rnnt_encoder_workspace_size",
+    "compute_rnnt_encoder_begin",
+    "compute_rnnt_encoder_run",
 ]
 
 
@@ -171,6 +174,14 @@ def load():
         lib.compute_rnnt_prednet_begin.argtypes = [vp, blk, ci, ci, ci, vp, ci, ci, vp, vp, rnntOptions]
         lib.compute_rnnt_prednet_step.restype = ci
         lib.compute_rnnt_prednet_step.argtypes = [vp, vp, vp, blk] + [ci] * 5 + [vp, rnntOptions]
+    if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "compute_rnnt_encoder_run"):
+        blk, cf = ctypes.POINTER(rnntPrednetBlock), ctypes.c_float
+        lib.get_rnnt_encoder_workspace_size.restype = ci
+        lib.get_rnnt_encoder_workspace_size.argtypes = [blk] + [ci] * 6 + [ctypes.POINTER(ctypes.c_size_t)]
+        lib.compute_rnnt_encoder_begin.restype = ci
+        lib.compute_rnnt_encoder_begin.argtypes = [blk, ci, ci, vp, vp, vp, vp, cf, ci, ci, ci, ci, vp, rnntOptions]
+        lib.compute_rnnt_encoder_run.restype = ci
+        lib.compute_rnnt_encoder_run.argtypes = [vp, ci, vp, blk, ci, ci, cf, ci, ci, ci, ci, vp, rnntOptions]
     _lib = lib
     return lib
 
@@ -228,6 +239,15 @@ def prednet_workspace_bytes(blocks, embed_size: int, vocab_size: int, joint_size
     n = ctypes.c_size_t(0)
     check(load().get_rnnt_prednet_workspace_size(blocks, len(blocks), embed_size, vocab_size, joint_size, rows, ctypes.byref(n)),
           "get_rnnt_prednet_workspace_size")
+    return int(n.value)
+
+
+def encoder_workspace_bytes(blocks, feat_size: int, reduction_index: int, reduction_factor: int, rows: int,
+                            max_frames: int) -> int:
+    """blocks: a ctypes array of rnntPrednetBlock (only the widths are read)."""
+    n = ctypes.c_size_t(0)
+    check(load().get_rnnt_encoder_workspace_size(blocks, len(blocks), feat_size, reduction_index, reduction_factor, rows, max_frames,
+                                                 ctypes.byref(n)), "get_rnnt_encoder_workspace_size")
     return int(n.value)
 
 

@@ -61,6 +61,13 @@ hipError_t launch_prednet_begin(const float *emb, const rnntPrednetBlock *blocks
                                 float *out, void *workspace, hipStream_t s);
 hipError_t launch_prednet_step(const int *emitted, const int *parents, float *out, const rnntPrednetBlock *blocks, int L, int E,
                                int V, int Jp, int R, void *workspace, hipStream_t s);
+// encoder_kernels.hip (the encoder's forward pass, state carried across runs)
+bool encoder_layout_ok(const rnntPrednetBlock *blocks, int L, int F, float bn_eps, int ridx, int f, int R, int Tmax, size_t *bytes);
+hipError_t launch_encoder_begin(const rnntPrednetBlock *blocks, int L, int F, const float *bn_mean, const float *bn_var,
+                                const float *bn_weight, const float *bn_bias, float bn_eps, int ridx, int f, int R, int Tmax,
+                                void *workspace, hipStream_t s);
+hipError_t launch_encoder_run(const float *x, int T, float *out, const rnntPrednetBlock *blocks, int L, int F, float bn_eps, int ridx,
+                              int f, int R, int Tmax, void *workspace, hipStream_t s);
 }  // namespace rnnt
 
 static rnntStatus_t check_options(const rnntOptions &o) {
@@ -649,6 +656,61 @@ rnntStatus_t compute_rnnt_prednet_step(const int *emitted, const int *parents, f
     if (st != RNNT_STATUS_SUCCESS) return st;
     return from_hip(launch_prednet_step(emitted, parents, pred_proj_out, blocks, num_blocks, embed_size, vocab_size, joint_size, rows,
                                         workspace, (hipStream_t)options.stream));
+}
+
+
+// The encoder (include/rnnt.h).  Everything is checked before anything is enqueued.
+static rnntStatus_t check_encoder(const rnntPrednetBlock *blocks, int num_layers, int feat_size, float bn_eps, int reduction_index,
+                                  int reduction_factor, int rows, int max_frames, const void *workspace, bool weights,
+                                  const rnntOptions &o) {
+    if (!blocks || !workspace) return RNNT_STATUS_INVALID_VALUE;
+    if (o.loc != RNNT_GPU) return RNNT_STATUS_INVALID_VALUE;
+    if (((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
+    if (!encoder_layout_ok(blocks, num_layers, feat_size, bn_eps, reduction_index, reduction_factor, rows, max_frames, nullptr))
+        return RNNT_STATUS_INVALID_VALUE;
+    if (weights) {
+        for (int l = 0; l < num_layers; ++l) {
+            const rnntPrednetBlock &b = blocks[l];
+            if (!b.W_ih || !b.W_hh || !b.b_ih || !b.b_hh || !b.ln_weight || !b.ln_bias) return RNNT_STATUS_INVALID_VALUE;
+            if (!aligned16(b.W_ih) || !aligned16(b.W_hh) || !aligned16(b.b_ih) || !aligned16(b.b_hh) || !aligned16(b.W_hr) ||
+                !aligned16(b.ln_weight) || !aligned16(b.ln_bias))
+                return RNNT_STATUS_INVALID_VALUE;
+        }
+    }
+    return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t get_rnnt_encoder_workspace_size(const rnntPrednetBlock *blocks, int num_layers, int feat_size, int reduction_index,
+                                             int reduction_factor, int rows, int max_frames, size_t *size_bytes) {
+    if (!size_bytes) return RNNT_STATUS_INVALID_VALUE;
+    return encoder_layout_ok(blocks, num_layers, feat_size, 0.f, reduction_index, reduction_factor, rows, max_frames, size_bytes)
+               ? RNNT_STATUS_SUCCESS
+               : RNNT_STATUS_INVALID_VALUE;
+}
+
+rnntStatus_t compute_rnnt_encoder_begin(const rnntPrednetBlock *blocks, int num_layers, int feat_size, const float *bn_mean,
+                                        const float *bn_var, const float *bn_weight, const float *bn_bias, float bn_eps,
+                                        int reduction_index, int reduction_factor, int rows, int max_frames, void *workspace,
+                                        rnntOptions options) {
+    if (!bn_mean || !bn_var || !bn_weight || !bn_bias) return RNNT_STATUS_INVALID_VALUE;
+    if (!aligned16(bn_mean) || !aligned16(bn_var) || !aligned16(bn_weight) || !aligned16(bn_bias)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_encoder(blocks, num_layers, feat_size, bn_eps, reduction_index, reduction_factor, rows, max_frames,
+                                          workspace, true, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_encoder_begin(blocks, num_layers, feat_size, bn_mean, bn_var, bn_weight, bn_bias, bn_eps, reduction_index,
+                                         reduction_factor, rows, max_frames, workspace, (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_encoder_run(const float *x, int frames, float *out, const rnntPrednetBlock *blocks, int num_layers,
+                                      int feat_size, float bn_eps, int reduction_index, int reduction_factor, int rows, int max_frames,
+                                      void *workspace, rnntOptions options) {
+    if (!x || !out || !aligned16(x) || !aligned16(out)) return RNNT_STATUS_INVALID_VALUE;
+    if (frames < 1 || frames > max_frames) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_encoder(blocks, num_layers, feat_size, bn_eps, reduction_index, reduction_factor, rows, max_frames,
+                                          workspace, false, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_encoder_run(x, frames, out, blocks, num_layers, feat_size, bn_eps, reduction_index, reduction_factor, rows,
+                                       max_frames, workspace, (hipStream_t)options.stream));
 }
 
 }  // extern "C"

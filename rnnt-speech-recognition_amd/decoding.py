@@ -23,7 +23,7 @@ from typing import List, Optional
 
 import torch
 
-from .joint import BeamJoint, GreedyJoint, PredictionStep
+from .joint import BeamJoint, EncoderStream, GreedyJoint, PredictionStep
 from .loss import reduced_lengths
 
 
@@ -123,6 +123,31 @@ def _check_prediction(prediction: str):
         raise ValueError(f"prediction must be one of {PREDICTIONS}, got {prediction!r}")
 
 
+_ENC_WORKSPACES = {}  # (device, stream) -> the encoder workspace of the last engine-route decode there
+ENCODERS = ("torch", "engine")
+
+
+def _check_encoder(encoder: str):
+    if encoder not in ENCODERS:
+        raise ValueError(f"encoder must be one of {ENCODERS}, got {encoder!r}")
+
+
+def _encode(model, mel_specs: torch.Tensor, encoder: str) -> torch.Tensor:
+    """The encoder output of every row: model.encoder (encoder="torch") or one EncoderStream run (encoder="engine")."""
+    if encoder == "torch":
+        return model.encoder(mel_specs)
+    es = EncoderStream(model.encoder)
+    dev = mel_specs.device
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream) if (es.engine and mel_specs.is_cuda) else None
+    es._ws = _ENC_WORKSPACES.get(key)
+    B, T = mel_specs.shape[0], mel_specs.shape[1]
+    es.begin(B, T)
+    enc = es.run(mel_specs)
+    if key is not None and es._ws is not None:
+        _ENC_WORKSPACES[key] = es._ws
+    return enc
+
+
 def _pred_step(pred_net, tokens: torch.Tensor, states):
     """One symbol through the prediction network for every row: tokens [B] -> (output [B, H], new states)."""
     y = pred_net.embed(tokens.long()[:, None])
@@ -195,7 +220,8 @@ def greedy_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, m
 
 @torch.no_grad()
 def greedy_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[torch.Tensor] = None, max_length=None,
-                        max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY, prediction: str = "torch"):
+                        max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY, prediction: str = "torch",
+                        encoder: str = "torch"):
     """Greedy decoding of EVERY utterance of a batch at once -> (ids int32 [B, N] zero-padded, lengths int32 [B], scores [B]).
 
     Per utterance the semantics of greedy_decode (utils/decoding.py:21-108): the hypothesis starts from token 0, symbols are
@@ -210,11 +236,14 @@ def greedy_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[t
     the library's greedy step (GreedyJoint): no host synchronisation per step -- the all-done word is read every
     `check_every` steps (read_flag).  prediction="engine" steps the prediction network in the library too (PredictionStep:
     compute_rnnt_prednet_step, through W1 into the joint step), so that the loop body is library calls alone; "torch" (the
-    default) steps it with the model's own modules."""
+    default) steps it with the model's own modules.  encoder="engine" runs the encoder in the library (EncoderStream:
+    compute_rnnt_encoder_run, every row in one call); "torch" (the default) runs model.encoder."""
+    _check_prediction(prediction)
+    _check_encoder(encoder)
     was_training = model.training
     model.eval()
     try:
-        enc = model.encoder(mel_specs)  # [B, T', H]
+        enc = _encode(model, mel_specs, encoder)  # [B, T', H]
         B, T = enc.shape[0], enc.shape[1]
         if spec_lengths is None:
             frames = torch.full((B,), T, dtype=torch.int32, device=enc.device)
@@ -225,12 +254,13 @@ def greedy_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[t
         model.train(was_training)
 
 
-def greedy_decode_batch_fn(model, prediction: str = "torch"):
+def greedy_decode_batch_fn(model, prediction: str = "torch", encoder: str = "torch"):
     """fn(inputs, max_length=None, spec_lengths=None) -> (ids, lengths, scores) of greedy_decode_batch."""
     _check_prediction(prediction)
+    _check_encoder(encoder)
 
     def fn(inputs: torch.Tensor, max_length=None, spec_lengths: Optional[torch.Tensor] = None):
-        return greedy_decode_batch(model, inputs, spec_lengths, max_length, prediction=prediction)
+        return greedy_decode_batch(model, inputs, spec_lengths, max_length, prediction=prediction, encoder=encoder)
     return fn
 
 
@@ -287,13 +317,16 @@ def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, bea
 
 @torch.no_grad()
 def beam_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[torch.Tensor] = None, beam: int = 4,
-                      prediction: str = "torch"):
+                      prediction: str = "torch", encoder: str = "torch"):
     """Beam search of EVERY utterance of a batch -> the best hypothesis of each: (ids int32 [B, T'] zero-padded, lengths int32
-    [B], scores [B]).  spec_lengths are spectrogram frames, reduced as greedy_decode_batch reduces them; None: every frame."""
+    [B], scores [B]).  spec_lengths are spectrogram frames, reduced as greedy_decode_batch reduces them; None: every frame.
+    encoder= as in greedy_decode_batch."""
+    _check_prediction(prediction)
+    _check_encoder(encoder)
     was_training = model.training
     model.eval()
     try:
-        enc = model.encoder(mel_specs)  # [B, T', H]
+        enc = _encode(model, mel_specs, encoder)  # [B, T', H]
         B, T = enc.shape[0], enc.shape[1]
         if spec_lengths is None:
             frames = torch.full((B,), T, dtype=torch.int32, device=enc.device)
@@ -305,14 +338,15 @@ def beam_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[tor
         model.train(was_training)
 
 
-def beam_decode_batch_fn(model, beam: int = 4, prediction: str = "torch"):
+def beam_decode_batch_fn(model, beam: int = 4, prediction: str = "torch", encoder: str = "torch"):
     """fn(inputs, max_length=None, spec_lengths=None) -> (ids, lengths, scores) of beam_decode_batch, for
     metrics.build_batch_accuracy_fn / build_batch_wer_fn.  The search has no symbol budget: max_length (an int or an int tensor
     [B]) truncates the best hypothesis afterwards."""
     _check_prediction(prediction)
+    _check_encoder(encoder)
 
     def fn(inputs: torch.Tensor, max_length=None, spec_lengths: Optional[torch.Tensor] = None):
-        ids, lengths, scores = beam_decode_batch(model, inputs, spec_lengths, beam, prediction)
+        ids, lengths, scores = beam_decode_batch(model, inputs, spec_lengths, beam, prediction, encoder)
         if max_length is not None:
             cap = torch.as_tensor(max_length, device=lengths.device).to(torch.int32)
             lengths = torch.minimum(lengths, cap)

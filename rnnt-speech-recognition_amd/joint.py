@@ -807,3 +807,144 @@ class PredictionStep:
         self._states = [(torch.where(mask[None, :, None], h2, h), torch.where(mask[None, :, None], c2, c))
                         for (h2, c2), (h, c) in zip(states2, states)]
         return self._project()
+
+
+class EncoderStream:
+    """The encoder's forward pass (model.Encoder, inference) with its LSTM state carried from one run to the next, so that a long
+    input may be encoded in chunks: begin(rows, max_frames), then run(mel_chunk [rows, frames, feat]) -> enc_chunk [rows,
+    ceil(frames / f), out_width] any number of times.  Each run pads its own odd tail at the TimeReduction, as the module does
+    per call; chunks whose lengths are multiples of f, except the last, give the output of one run over the whole input.
+
+    On an MI355X this is the ENGINE (include/rnnt.h compute_rnnt_encoder_begin / _run): begin packs the current weights and the
+    BatchNorm's running statistics into the workspace (the object owns it; the next begin reuses it when it is large enough) and
+    zeroes every row's state.  CPU tensors, models that are not float32, a BatchNorm without running statistics, multi-layer or
+    bidirectional LSTMs and shapes the kernels do not take run the same state machine in torch: BatchNorm (eval) -> per block
+    nn.LSTM(x, (h, c)) with the carried state -> LayerNorm, TimeReduction of the chunk after block reduction_index."""
+
+    MAX_ROWS, MAX_LAYERS, MAX_WIDTH, MAX_FACTOR, MAX_FRAMES = 1024, 16, 4096, 16, 1 << 20
+
+    def __init__(self, encoder):
+        self.enc = encoder
+        self.factor = int(encoder.reduce.factor)
+        self.ridx = int(encoder.reduction_index)
+        self.engine = self._engine_takes()
+        self._ws = None
+
+    def _engine_takes(self) -> bool:
+        enc = self.enc
+        bn, blocks = enc.input_norm, list(enc.blocks)
+        if bn.running_mean is None or bn.running_var is None or bn.weight is None or bn.bias is None:
+            return False
+        dev = bn.weight.device
+        if dev.type != "cuda" or not 1 <= len(blocks) <= self.MAX_LAYERS or not 0 <= self.ridx < len(blocks) - 1:
+            return False
+        if not 1 <= self.factor <= self.MAX_FACTOR:
+            return False
+        width = bn.num_features
+        tensors = [bn.weight, bn.bias, bn.running_mean, bn.running_var]
+        for i, blk in enumerate(blocks):
+            lstm, norm = blk.lstm, blk.norm
+            if width > self.MAX_WIDTH:
+                return False
+            if lstm.num_layers != 1 or lstm.bidirectional or not lstm.bias or lstm.input_size != width or not lstm.batch_first:
+                return False
+            out = lstm.proj_size or lstm.hidden_size
+            if lstm.hidden_size > self.MAX_WIDTH or out > self.MAX_WIDTH or not norm.elementwise_affine or norm.bias is None:
+                return False
+            if tuple(norm.normalized_shape) != (out,):
+                return False
+            tensors += list(lstm.parameters()) + [norm.weight, norm.bias]
+            width = out * (self.factor if i == self.ridx else 1)
+        return all(t.dtype == torch.float32 and t.device == dev for t in tensors)
+
+    def begin(self, rows: int, max_frames: int) -> None:
+        self.R, self.Tmax = int(rows), int(max_frames)
+        self._use_engine = self.engine and 1 <= self.R <= self.MAX_ROWS and 1 <= self.Tmax <= self.MAX_FRAMES
+        enc = self.enc
+        if not self._use_engine:
+            dev = enc.input_norm.weight.device if enc.input_norm.weight is not None else next(enc.parameters()).device
+            dt = next(enc.blocks[0].lstm.parameters()).dtype
+            self._states = []
+            for blk in enc.blocks:
+                lstm = blk.lstm
+                self._states.append((torch.zeros(1, self.R, lstm.proj_size or lstm.hidden_size, dtype=dt, device=dev),
+                                     torch.zeros(1, self.R, lstm.hidden_size, dtype=dt, device=dev)))
+            return
+        bn = enc.input_norm
+        dev = bn.weight.device
+        keep = [_aligned16(x) for x in (bn.running_mean, bn.running_var, bn.weight, bn.bias)]
+        blocks = (_lib.rnntPrednetBlock * len(enc.blocks))()
+        for b, blk in zip(blocks, enc.blocks):
+            lstm, norm = blk.lstm, blk.norm
+            w = [_aligned16(x) for x in (lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, norm.weight, norm.bias)]
+            wr = _aligned16(lstm.weight_hr_l0) if lstm.proj_size else None
+            keep += w + ([wr] if wr is not None else [])
+            b.W_ih, b.W_hh, b.b_ih, b.b_hh = (x.data_ptr() for x in w[:4])
+            b.W_hr = None if wr is None else wr.data_ptr()
+            b.ln_weight, b.ln_bias = w[4].data_ptr(), w[5].data_ptr()
+            b.hidden, b.proj, b.ln_eps = lstm.hidden_size, lstm.proj_size or lstm.hidden_size, float(norm.eps)
+        self._blocks, self._keep = blocks, keep
+        self.F, self.bn_eps = bn.num_features, float(bn.eps)
+        with torch.cuda.device(dev):
+            nbytes = _lib.encoder_workspace_bytes(blocks, self.F, self.ridx, self.factor, self.R, self.Tmax)
+            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
+                self._ws = _new_workspace(nbytes, dev)
+            elif _WORKSPACE_FILL is not None:
+                self._ws.fill_(int(_WORKSPACE_FILL))
+            self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, 0, 1, 1)
+            st = _lib.load().compute_rnnt_encoder_begin(blocks, len(blocks), self.F, *(x.data_ptr() for x in keep[:4]), self.bn_eps,
+                                                        self.ridx, self.factor, self.R, self.Tmax, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_encoder_begin")
+
+    @torch.no_grad()
+    def run(self, mel_chunk: torch.Tensor) -> torch.Tensor:
+        """mel_chunk [rows, frames, feat] -> the encoder output of these frames [rows, ceil(frames / f), out_width]."""
+        if mel_chunk.dim() != 3 or mel_chunk.shape[0] != self.R:
+            raise ValueError(f"mel_chunk must be [{self.R}, frames, feat], got {tuple(mel_chunk.shape)}")
+        if not self._use_engine:
+            return self._torch_run(mel_chunk)
+        T = int(mel_chunk.shape[1])
+        if mel_chunk.shape[2] != self.F or not 1 <= T <= self.Tmax:
+            raise ValueError(f"mel_chunk must be [{self.R}, 1 ... {self.Tmax}, {self.F}], got {tuple(mel_chunk.shape)}")
+        dev = self._ws.device
+        x = _aligned16(mel_chunk.to(device=dev, dtype=torch.float32))
+        out = torch.empty(self.R, -(-T // self.factor), self._blocks[len(self._blocks) - 1].proj, dtype=torch.float32, device=dev)
+        self._x = x  # (alive until the launches have read it)
+        st = _lib.load().compute_rnnt_encoder_run(x.data_ptr(), T, out.data_ptr(), self._blocks, len(self._blocks), self.F,
+                                                  self.bn_eps, self.ridx, self.factor, self.R, self.Tmax, self._ws.data_ptr(),
+                                                  self._opts)
+        _lib.check(st, "compute_rnnt_encoder_run")
+        return out
+
+    def state(self):
+        """Every block's current (r [rows, proj], c [rows, hidden]): torch's (h, c) of the LSTM (views on the engine, valid until
+        the next run)."""
+        if not self._use_engine:
+            return [(h[0], c[0]) for h, c in self._states]
+        R = self.R
+        a64 = lambda n: (n + 63) // 64 * 64  # noqa: E731  (the workspace layout of include/rnnt.h)
+        f = self._ws.view(torch.float32)
+        off, out = 0, []
+        for b in self._blocks:
+            p, c = R * b.proj, R * b.hidden
+            out.append((f[off: off + p].view(R, b.proj), f[off + a64(p): off + a64(p) + c].view(R, b.hidden)))
+            off += a64(p) + a64(c)
+        return out
+
+    # ---- torch composition
+    def _torch_run(self, x):
+        enc = self.enc
+        bn = enc.input_norm
+        dt = self._states[0][0].dtype
+        x = x.to(device=self._states[0][0].device, dtype=dt)
+        x = torch.nn.functional.batch_norm(x.transpose(1, 2), bn.running_mean, bn.running_var, bn.weight, bn.bias,
+                                           bn.running_mean is None, 0.0, bn.eps).transpose(1, 2)
+        states = []
+        for i, (blk, st) in enumerate(zip(enc.blocks, self._states)):
+            y, st = blk.lstm(x, st)
+            states.append(st)
+            x = blk.norm(y)
+            if i == enc.reduction_index:
+                x = enc.reduce(x)
+        self._states = states
+        return x
