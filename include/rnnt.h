@@ -494,7 +494,7 @@ RNNT_API rnntStatus_t compute_rnnt_beam_results(int *hyps, int *hyp_lengths, flo
  * name any row.  Arithmetic: float32, every sum in a fixed order: a row's results are bitwise independent of `rows`, of the
  * other rows and of the run.
  * Workspace: get_rnnt_prednet_workspace_size(...) bytes, 256-byte aligned, owned by one decode from its begin to its last step.
- * It begins with the state: for slot s = (number of begin and step calls so far) & 1, and S = the sum over blocks of
+ * It begins with the state: for slot s = (number of begin, step and reset calls so far) & 1, and S = the sum over blocks of
  * A(rows * proj_l) + A(rows * hidden_l) floats, A(n) = n rounded up to a multiple of 64: block l's r [rows, proj_l] sits at float
  * s * S + sum_{m < l} (A(rows proj_m) + A(rows hidden_m)) and its c [rows, hidden_l] right after A(rows proj_l) floats.
  * No entry point synchronises the host.
@@ -571,6 +571,69 @@ RNNT_API rnntStatus_t compute_rnnt_encoder_run(const float *x, int frames, float
                                                int num_layers, int feat_size, float bn_eps, int reduction_index,
                                                int reduction_factor, int rows, int max_frames, void *workspace,
                                                rnntOptions options);
+
+/* The same over RAGGED rows with a per-row reset, for streams that start and end at different times.  Before the run, the rows
+ * with reset[r] != 0 start from zero state (reset NULL: none).  Row r then advances over its first row_frames[r] frames only
+ * (device i32 [rows], clamped into [0, frames]); a row with 0 frames keeps its state bit for bit.  At the reduction, a frame at or
+ * beyond row_frames[r] reads as ZEROS, and `out` is zero past the row's ceil(row_frames[r] / f) frames.  The saved state is that
+ * of the row's last valid frame.  The input GEMM may still compute the dead frames; nothing of them is kept.  With equal
+ * row_frames = frames and no reset this is compute_rnnt_encoder_run bit for bit; a row run alone gives bitwise the same output
+ * and state. */
+RNNT_API rnntStatus_t compute_rnnt_encoder_run_rows(const float *x, int frames, const int *row_frames, const int *reset, float *out,
+                                                    const rnntPrednetBlock *blocks, int num_layers, int feat_size, float bn_eps,
+                                                    int reduction_index, int reduction_factor, int rows, int max_frames,
+                                                    void *workspace, rnntOptions options);
+
+/* Build-only extension: STREAMING GREEDY DECODING over S slots (1 <= S <= 1024), each holding one live stream at a time.  The
+ * caller feeds every slot zero or more new spectrogram frames per call; the encoder (compute_rnnt_encoder_run_rows), the
+ * prediction network and the greedy search carry their state from one feed to the next.
+ *
+ * compute_rnnt_prednet_reset: one prediction-network step in which the rows with reset[r] != 0 (device i32 [rows]) get zero
+ * state and run the start token 0 -- bitwise what compute_rnnt_prednet_begin computes for them -- while the other rows keep
+ * their state and pred_proj.  It counts as a step for the parity slot of the workspace layout above (slot = the number of
+ * begin, step and reset calls so far, & 1), so the next compute_rnnt_prednet_step reads the right slot.
+ *
+ * The greedy stream: options.maxT = max_chunk_frames (the encoder frames one feed may bring per slot), minibatch = slots.
+ *   get_rnnt_greedy_stream_workspace_size(max_chunk_frames, slots, enc_width, ...): the greedy workspace of
+ *     get_rnnt_greedy_workspace_size(max_chunk_frames, slots, ...) followed by W1 [enc_width, joint_size] and b1 [joint_size];
+ *     compute_rnnt_greedy_step runs on it unchanged (with the same options and minibatch = slots).
+ *   compute_rnnt_greedy_stream_begin(W1, b1, W2, b2, ...) packs W1, b1 and the W2 image (the caller may then free them) and
+ *     leaves every slot FINISHED.
+ *   compute_rnnt_greedy_stream_feed(enc, enc_frames, chunk_frames, reset, final_chunk, max_symbols, max_per_frame, hyp_lengths,
+ *     scores, all_done, ...):
+ *       enc           device f32 [slots, enc_frames, enc_width] (0 <= enc_frames <= max_chunk_frames; NULL when 0): this feed's
+ *                     encoder frames; slot s uses its first chunk_frames[s] (device i32, clamped into [0, enc_frames])
+ *       reset         device i32 [slots] or NULL: reset[s] != 0 starts a new stream in slot s: no symbols, score 0, budget
+ *                     max_symbols[s] (NULL: none beyond the hyps buffer), per-frame cap max_per_frame (<= 0: none)
+ *       final_chunk   device i32 [slots] or NULL: final_chunk[s] != 0: the stream in slot s ends with this chunk
+ *     It projects the chunk's frames through W1 + b1 (one f32 FMA chain per output over enc_width in order, then + b1: a frame's
+ *     enc_proj is bitwise independent of the chunking, the slot and S), builds the e^{2x} tables and range flags of those frames,
+ *     and moves every slot on: a live slot gets frame cursor 0 over chunk_frames[s] frames and keeps its symbols, score and
+ *     budget; a finished slot (after its final chunk, or once its budget is spent) stays done until a reset.  It writes
+ *     hyp_lengths / scores of every slot and all_done (0: some slot has frames to decode, 1: none).
+ *   Then repeat {compute_rnnt_greedy_step, compute_rnnt_prednet_step} until all_done is 1 (2: grow `hyps` as for the batched
+ *   decoder).  `hyps` [slots, max_hyp_len] is the per-stream, append-only buffer of the batched decoder: symbol n of the stream
+ *   in slot s sits at hyps[s, n].  A slot that has used up its chunk is done for the step loop; the next feed brings it back.
+ * Equivalence: a stream fed through chunks whose lengths are multiples of the encoder's reduction factor (the last one
+ * excepted), in any slot, beside any other traffic, gives bitwise the ids, length and score of the same stream fed in one call
+ * to a 1-slot decoder.  No entry point synchronises the host; bad arguments give RNNT_STATUS_INVALID_VALUE before anything is
+ * enqueued. */
+RNNT_API rnntStatus_t compute_rnnt_prednet_reset(const int *reset, float *pred_proj_out, const rnntPrednetBlock *blocks,
+                                                 int num_blocks, int embed_size, int vocab_size, int joint_size, int rows,
+                                                 void *workspace, rnntOptions options);
+
+RNNT_API rnntStatus_t get_rnnt_greedy_stream_workspace_size(int max_chunk_frames, int slots, int enc_width, int joint_size,
+                                                            int alphabet_size, int joint_dtype, size_t *size_bytes);
+
+RNNT_API rnntStatus_t compute_rnnt_greedy_stream_begin(const float *W1, const float *b1, const float *W2, const float *b2,
+                                                       int enc_width, int joint_size, int alphabet_size, int slots,
+                                                       int joint_dtype, void *workspace, rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_greedy_stream_feed(const float *enc, int enc_frames, const int *chunk_frames, const int *reset,
+                                                      const int *final_chunk, const int *max_symbols, int max_per_frame,
+                                                      int *hyp_lengths, float *scores, int *all_done, int enc_width,
+                                                      int joint_size, int alphabet_size, int slots, int joint_dtype,
+                                                      void *workspace, rnntOptions options);
 
 #ifdef __cplusplus
 }

@@ -48,6 +48,11 @@ SYMBOLS = [
     "get_rnnt_encoder_workspace_size",
     "compute_rnnt_encoder_begin",
     "compute_rnnt_encoder_run",
+    "compute_rnnt_encoder_run_rows",
+    "compute_rnnt_prednet_reset",
+    "get_rnnt_greedy_stream_workspace_size",
+    "compute_rnnt_greedy_stream_begin",
+    "compute_rnnt_greedy_stream_feed",
 ]
 
 
@@ -182,6 +187,18 @@ def load():
         lib.compute_rnnt_encoder_begin.argtypes = [blk, ci, ci, vp, vp, vp, vp, cf, ci, ci, ci, ci, vp, rnntOptions]
         lib.compute_rnnt_encoder_run.restype = ci
         lib.compute_rnnt_encoder_run.argtypes = [vp, ci, vp, blk, ci, ci, cf, ci, ci, ci, ci, vp, rnntOptions]
+    if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "compute_rnnt_greedy_stream_feed"):
+        blk, cf = ctypes.POINTER(rnntPrednetBlock), ctypes.c_float
+        lib.compute_rnnt_encoder_run_rows.restype = ci
+        lib.compute_rnnt_encoder_run_rows.argtypes = [vp, ci, vp, vp, vp, blk, ci, ci, cf, ci, ci, ci, ci, vp, rnntOptions]
+        lib.compute_rnnt_prednet_reset.restype = ci
+        lib.compute_rnnt_prednet_reset.argtypes = [vp, vp, blk] + [ci] * 5 + [vp, rnntOptions]
+        lib.get_rnnt_greedy_stream_workspace_size.restype = ci
+        lib.get_rnnt_greedy_stream_workspace_size.argtypes = [ci] * 6 + [ctypes.POINTER(ctypes.c_size_t)]
+        lib.compute_rnnt_greedy_stream_begin.restype = ci
+        lib.compute_rnnt_greedy_stream_begin.argtypes = [vp] * 4 + [ci] * 5 + [vp, rnntOptions]
+        lib.compute_rnnt_greedy_stream_feed.restype = ci
+        lib.compute_rnnt_greedy_stream_feed.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp] + [ci] * 5 + [vp, rnntOptions]
     _lib = lib
     return lib
 
@@ -248,6 +265,14 @@ def encoder_workspace_bytes(blocks, feat_size: int, reduction_index: int, reduct
     n = ctypes.c_size_t(0)
     check(load().get_rnnt_encoder_workspace_size(blocks, len(blocks), feat_size, reduction_index, reduction_factor, rows, max_frames,
                                                  ctypes.byref(n)), "get_rnnt_encoder_workspace_size")
+    return int(n.value)
+
+
+def greedy_stream_workspace_bytes(max_chunk_frames: int, slots: int, enc_width: int, joint_size: int, alphabet_size: int,
+                                  joint_dtype: int) -> int:
+    n = ctypes.c_size_t(0)
+    check(load().get_rnnt_greedy_stream_workspace_size(max_chunk_frames, slots, enc_width, joint_size, alphabet_size, joint_dtype,
+                                                       ctypes.byref(n)), "get_rnnt_greedy_stream_workspace_size")
     return int(n.value)
 
 

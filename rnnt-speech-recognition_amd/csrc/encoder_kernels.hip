@@ -167,6 +167,11 @@ __global__ __launch_bounds__(256) void encoder_vec_kernel(float *d0, float *d1, 
 // ---------------------------------------------------------------------------------------------
 // run: BatchNorm in / LayerNorm out
 // ---------------------------------------------------------------------------------------------
+// ragged rows (compute_rnnt_encoder_run_rows): the frames row r has at a block whose frames are its input's reduced by div
+__device__ __forceinline__ int en_row_frames(const int *rf, const int r, const int div) {
+    return (max(rf[r], 0) + div - 1) / div;
+}
+
 __device__ __forceinline__ float en_wave_sum(float v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
@@ -180,6 +185,8 @@ struct EnNorm {
     const float *g, *b, *m;  // mode 0: scale, bias, mean; mode 1: gamma, beta
     float eps;
     int R, T, W, f, mode;
+    const int *rf;     // mode 1: row_frames of a ragged run (frames of row r: en_row_frames(rf, r, div)), or NULL: T each
+    int div;
 };
 
 // one wave per (row, frame) of the padded frame range; frames past T are written as zeros
@@ -190,7 +197,8 @@ __global__ __launch_bounds__(256) void enc_norm_kernel(const EnNorm a) {
     if (idx >= (long)a.R * Tp) return;
     const int r = (int)(idx / Tp), t = (int)(idx % Tp);
     float *d = a.dst + ((size_t)r * Tq + t / a.f) * ((size_t)a.f * a.W) + (size_t)(t % a.f) * a.W;
-    if (t >= a.T) {
+    const int Tr = (a.mode == 1 && a.rf) ? min(en_row_frames(a.rf, r, a.div), a.T) : a.T;  // the row's frames (its last: the state)
+    if (t >= Tr) {
         for (int k = lane; k < a.W; k += 64) d[k] = 0.f;
         return;
     }
@@ -209,7 +217,7 @@ __global__ __launch_bounds__(256) void enc_norm_kernel(const EnNorm a) {
     }
     const float rstd = 1.0f / sqrtf(en_wave_sum(q) / (float)a.W + a.eps);
     for (int k = lane; k < a.W; k += 64) d[k] = fmaf((s[k] - mean) * rstd, a.g[k], a.b[k]);
-    if (t == a.T - 1)
+    if (t == Tr - 1)
         for (int k = lane; k < a.W; k += 64) a.state[(size_t)r * a.W + k] = s[k];
 }
 
@@ -313,6 +321,9 @@ struct EnStep {
     float *out;
     size_t os;
     int N;
+    // ragged run: rows with frame t >= en_row_frames(rf, r, div) neither write nor update c (rf NULL: every row runs)
+    const int *rf;
+    int t, div;
 };
 
 __device__ __forceinline__ float en_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -385,6 +396,7 @@ __global__ __launch_bounds__(NKG * 8) void enc_step_kernel(const EnStep a) {
         for (int i = tid; i < TR * 8; i += NKG * 8) {
             const int t = i >> 3, u = i & 7, r = r0 + t, j = blockIdx.x * 8 + u;
             if (r >= a.R || j >= a.N) continue;
+            if (a.rf && a.t >= en_row_frames(a.rf, r, a.div)) continue;
             const float *s = red + t * 32, *p = a.pre + (size_t)r * a.ps + c0;
             const float gi = s[u] + p[u], gf = s[8 + u] + p[8 + u], gg = s[16 + u] + p[16 + u], go = s[24 + u] + p[24 + u];
             float *cp = a.c + (size_t)r * a.N + j;
@@ -396,6 +408,7 @@ __global__ __launch_bounds__(NKG * 8) void enc_step_kernel(const EnStep a) {
         for (int i = tid; i < TR * 32; i += NKG * 8) {
             const int t = i >> 5, n = c0 + (i & 31), r = r0 + t;
             if (r >= a.R || n >= a.N) continue;
+            if (a.rf && a.t >= en_row_frames(a.rf, r, a.div)) continue;
             a.out[(size_t)r * a.os + n] = red[i];
         }
     }
@@ -440,9 +453,39 @@ static hipError_t en_norm(const EnNorm &n, hipStream_t s) {
     return hipGetLastError();
 }
 
-static hipError_t en_run(const EnLayout &o, float *ws, const float *x, int T, float *out, hipStream_t s) {
+// ragged run: zero the state (r and c of every block) of the rows with reset[r] != 0; blockIdx.y = 2 l + (0: r, 1: c)
+struct EnReset {
+    float *base[2 * kEnMaxLayers];
+    int W[2 * kEnMaxLayers];
+    const int *reset;
+    int R;
+};
+
+__global__ __launch_bounds__(256) void enc_reset_kernel(const EnReset a) {
+    float *p = a.base[blockIdx.y];
+    const int W = a.W[blockIdx.y];
+    const size_t n = (size_t)a.R * W;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+        if (a.reset[i / W] != 0) p[i] = 0.f;
+}
+
+static hipError_t en_run(const EnLayout &o, float *ws, const float *x, int T, float *out, const int *rf, const int *reset,
+                         hipStream_t s) {
     hipError_t e;
     const int R = o.R;
+    if (reset) {
+        EnReset z = {};
+        size_t n = 0;
+        for (int l = 0; l < o.L; ++l) {
+            z.base[2 * l] = ws + o.r[l], z.W[2 * l] = o.P[l];
+            z.base[2 * l + 1] = ws + o.c[l], z.W[2 * l + 1] = o.H[l];
+            n = (size_t)R * (o.P[l] > o.H[l] ? o.P[l] : o.H[l]) > n ? (size_t)R * (o.P[l] > o.H[l] ? o.P[l] : o.H[l]) : n;
+        }
+        z.reset = reset, z.R = R;
+        const size_t g = (n + 255) / 256;
+        hipLaunchKernelGGL(enc_reset_kernel, dim3((unsigned)(g < 1024 ? g : 1024), 2 * o.L), dim3(256), 0, s, z);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
     {  // BatchNorm into X
         EnNorm n = {};
         n.src = x, n.dst = ws + o.X, n.g = ws + o.bn_scale, n.b = ws + o.bn_bias, n.m = ws + o.bn_mean;
@@ -466,6 +509,7 @@ static hipError_t en_run(const EnLayout &o, float *ws, const float *x, int T, fl
                 a.K = o.P[l];
                 a.pre = ws + o.pre + (size_t)(t - t0) * ld, a.ps = (size_t)wn * ld;
                 a.c = ws + o.c[l], a.N = o.H[l];
+                a.rf = rf, a.t = t, a.div = l > o.ridx ? o.f : 1;
                 if (o.proj[l]) a.out = ws + o.hbuf, a.os = o.H[l];
                 else a.out = Y + (size_t)t * o.P[l], a.os = (size_t)Tl * o.P[l];
                 if ((e = en_launch<EN_GATES, kEnGatesKg>(a, s)) != hipSuccess) return e;
@@ -474,6 +518,7 @@ static hipError_t en_run(const EnLayout &o, float *ws, const float *x, int T, fl
                     p.W = ws + o.wr[l], p.Kpad = o.Kr[l], p.ld = o.ldr[l], p.R = R;
                     p.x = ws + o.hbuf, p.xs = o.H[l], p.K = o.H[l];
                     p.out = Y + (size_t)t * o.P[l], p.os = (size_t)Tl * o.P[l], p.N = o.P[l];
+                    p.rf = rf, p.t = t, p.div = a.div;
                     if ((e = en_launch<EN_PROJ, kEnProjKg>(p, s)) != hipSuccess) return e;
                 }
             }
@@ -482,6 +527,7 @@ static hipError_t en_run(const EnLayout &o, float *ws, const float *x, int T, fl
         n.src = Y, n.dst = l + 1 < o.L ? ws + o.X : out, n.state = ws + o.r[l];
         n.g = ws + o.lng[l], n.b = ws + o.lnb[l], n.eps = o.eps[l];
         n.R = R, n.T = Tl, n.W = o.P[l], n.f = l == o.ridx ? o.f : 1, n.mode = 1;
+        n.rf = rf, n.div = l > o.ridx ? o.f : 1;
         if ((e = en_norm(n, s)) != hipSuccess) return e;
     }
     return hipSuccess;
@@ -535,7 +581,15 @@ hipError_t launch_encoder_run(const float *x, int T, float *out, const rnntPredn
                               int f, int R, int Tmax, void *workspace, hipStream_t s) {
     EnLayout o;
     if (!make_en_layout(blocks, L, F, bn_eps, ridx, f, R, Tmax, o) || T < 1 || T > Tmax) return hipErrorInvalidValue;
-    return en_run(o, (float *)workspace, x, T, out, s);
+    return en_run(o, (float *)workspace, x, T, out, nullptr, nullptr, s);
+}
+
+hipError_t launch_encoder_run_rows(const float *x, int T, const int *row_frames, const int *reset, float *out,
+                                   const rnntPrednetBlock *blocks, int L, int F, float bn_eps, int ridx, int f, int R, int Tmax,
+                                   void *workspace, hipStream_t s) {
+    EnLayout o;
+    if (!make_en_layout(blocks, L, F, bn_eps, ridx, f, R, Tmax, o) || T < 1 || T > Tmax || !row_frames) return hipErrorInvalidValue;
+    return en_run(o, (float *)workspace, x, T, out, row_frames, reset, s);
 }
 
 }  // namespace rnnt

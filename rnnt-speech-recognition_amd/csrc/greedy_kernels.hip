@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void greedy_begin_kernel(const GreedyArgs a) {
             s.Tb = min(max(a.frame_lengths[b], 0), a.T);  // out-of-range lengths: clamped into the tensor
             s.maxsym = a.max_symbols ? max(a.max_symbols[b], 0) : INT_MAX;
             s.done = (s.Tb == 0 || s.maxsym == 0) ? 1 : 0;
-            s.cap = a.max_per_frame, s.pad = 0;
+            s.cap = a.max_per_frame, s.fin = 0;
             s.score = 0.0;
             a.st[b] = s;
         }
@@ -288,19 +288,22 @@ hipError_t launch_greedy_begin(const float *enc_proj, const int *frame_lengths, 
 
 // the W2 operand image and bias tables, the e^{2x} tables of enc_proj, the per-hypothesis state (a: bound to a workspace, with
 // enc_proj, frame_lengths, max_symbols, B, T, J, V, NC and max_per_frame set).  Shared with the beam decoder's begin.
+static hipError_t launch_greedy_w2(const GreedyArgs &a, int DT, const float *W2, const float *b2, hipStream_t s) {
+    if (DT == 1) {
+        const size_t n = (size_t)a.NC * 32 * a.J;
+        const unsigned grid = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+        hipLaunchKernelGGL(greedy_w2_f16_kernel, dim3(grid), dim3(256), 0, s, W2, b2, a.J, a.V, a.NC, a.img, a.btab);
+        return hipGetLastError();
+    }
+    return launch_joint_w2_image(W2, b2, a.J, a.V, (float *)a.tflag, a.img, s);
+}
+
 hipError_t launch_greedy_prepare(const GreedyArgs &ga, int DT, const float *W2, const float *b2, hipStream_t s) {
     GreedyArgs a = ga;
-    const int J = a.J, V = a.V, B = a.B, T = a.T;
+    const int B = a.B, T = a.T;
     a.b2 = DT == 2 ? b2 : nullptr;
     hipError_t e;
-    if (DT == 1) {
-        const size_t n = (size_t)a.NC * 32 * J;
-        const unsigned grid = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-        hipLaunchKernelGGL(greedy_w2_f16_kernel, dim3(grid), dim3(256), 0, s, W2, b2, J, V, a.NC, a.img, a.btab);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    } else if ((e = launch_joint_w2_image(W2, b2, J, V, (float *)a.tflag, a.img, s)) != hipSuccess) {
-        return e;
-    }
+    if ((e = launch_greedy_w2(a, DT, W2, b2, s)) != hipSuccess) return e;
     const int rows = B * T;
     hipLaunchKernelGGL(greedy_begin_kernel, dim3(rows < 2048 ? rows : 2048), dim3(256), 0, s, a);
     return hipGetLastError();
@@ -331,6 +334,186 @@ hipError_t launch_greedy_step(const float *pred_proj, int *hyps, int max_hyp_len
     else e = launch_step_dt<2>(a, shm, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(greedy_update_kernel, dim3(1), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// stream: greedy search over a stream of chunks per slot (include/rnnt.h compute_rnnt_greedy_stream_*).  The workspace is the
+// greedy workspace with T = max_chunk_frames and B = slots, then W1 [H][J] and b1 [J]: greedy_step_kernel and
+// greedy_update_kernel run on it unchanged.  A feed refills the tables for the chunk's frames and resets every slot's frame
+// cursor; a slot that has used up its chunk is done for the step loop until the next feed.
+// ---------------------------------------------------------------------------------------------
+struct GreedyStreamArgs {
+    const float *enc;          // [S, Te, H]
+    const float *W1, *b1;      // workspace copies: [H][J], [J]
+    const int *chunk_frames, *reset, *final_, *max_symbols;
+    int *hyp_lengths, *all_done;
+    float *scores;
+    GreedyState *st;
+    int *rowflag;
+    float *expE, *encraw;
+    int S, Te, T, H, J, max_per_frame;
+};
+
+constexpr int kGsRows = 32, kGsKc = 64;
+
+__device__ __forceinline__ int gs_frames(const GreedyStreamArgs &a, const int s) { return min(max(a.chunk_frames[s], 0), a.Te); }
+
+// enc_proj = enc W1 + b1 for the chunk's frames: a workgroup owns 64 columns (one per lane) and 32 encoder rows (8 per wave);
+// every output is one FMA chain over k = 0 ... H-1 in order, then + b1, so it depends on the frame alone (not on the chunking,
+// the slot or S).  Out: the raw copy and the e^{2x} table of the frames t < chunk_frames[s].
+__global__ __launch_bounds__(256) void greedy_stream_proj_kernel(const GreedyStreamArgs a) {
+    __shared__ float xs[kGsRows][kGsKc];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int col = blockIdx.x * 64 + lane, m0 = blockIdx.y * kGsRows, M = a.S * a.Te;
+    float acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+    for (int k0 = 0; k0 < a.H; k0 += kGsKc) {
+        for (int i = tid; i < kGsRows * kGsKc; i += 256) {
+            const int rr = i / kGsKc, kk = i % kGsKc, m = m0 + rr, k = k0 + kk;
+            xs[rr][kk] = (m < M && k < a.H) ? a.enc[(size_t)m * a.H + k] : 0.f;
+        }
+        __syncthreads();
+        const int kn = min(kGsKc, a.H - k0);
+        const float *w = a.W1 + (size_t)k0 * a.J + min(col, a.J - 1);
+#pragma unroll 4
+        for (int kk = 0; kk < kn; ++kk) {
+            const float wv_ = w[(size_t)kk * a.J];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) acc[i] = fmaf(xs[wv + 4 * i][kk], wv_, acc[i]);
+        }
+        __syncthreads();
+    }
+    if (col >= a.J) return;
+    const float bias = a.b1[col];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int m = m0 + wv + 4 * i;
+        if (m >= M) continue;
+        const int s = m / a.Te, t = m - s * a.Te;
+        if (t >= gs_frames(a, s)) continue;
+        const float x = acc[i] + bias;
+        const size_t o = ((size_t)s * a.T + t) * a.J + col;
+        a.encraw[o] = x;
+        a.expE[o] = exp_tab(x);
+    }
+}
+
+// the per-frame range flags of the chunk's frames; workgroup 0 also moves every slot's state on to the chunk
+__global__ __launch_bounds__(256) void greedy_stream_feed_kernel(const GreedyStreamArgs a) {
+    const int rows = a.S * a.Te;
+    for (int r = blockIdx.x; r < rows; r += gridDim.x) {  // (block-uniform trip count and skip: the barrier below is safe)
+        const int s = r / a.Te, t = r - s * a.Te;
+        if (t >= gs_frames(a, s)) continue;
+        const size_t base = ((size_t)s * a.T + t) * a.J;
+        bool big = false;
+        for (int j = threadIdx.x; j < a.J; j += 256) big |= exp_tab_out_of_range(a.encraw[base + j]);  // also catches NaN
+        big = __syncthreads_or(big);
+        if (threadIdx.x == 0) a.rowflag[(size_t)s * a.T + t] = big ? 1 : 0;
+    }
+    if (blockIdx.x != 0) return;
+    bool running = false;
+    for (int b = threadIdx.x; b < a.S; b += 256) {
+        GreedyState s = a.st[b];
+        if (a.reset && a.reset[b] != 0) {
+            s.n = 0, s.fin = 0, s.score = 0.0;
+            s.maxsym = a.max_symbols ? max(a.max_symbols[b], 0) : INT_MAX;
+            s.cap = a.max_per_frame;
+        }
+        s.t = 0, s.nf = 0;
+        if (s.fin || s.n >= s.maxsym) {  // finished: nothing more until a reset
+            s.fin = 1, s.Tb = 0;
+        } else {
+            s.Tb = gs_frames(a, b);
+            if (a.final_ && a.final_[b] != 0) s.fin = 1;  // (after this chunk)
+        }
+        s.done = s.Tb == 0 ? 1 : 0;
+        a.st[b] = s;
+        a.hyp_lengths[b] = s.n;
+        a.scores[b] = (float)s.score;
+        running |= !s.done;
+    }
+    running = __syncthreads_or(running);
+    if (threadIdx.x == 0) a.all_done[0] = running ? 0 : 1;  // (a full hyps buffer: the next step reports 2)
+}
+
+// begin: W1 / b1 into the workspace, every slot finished
+__global__ __launch_bounds__(256) void greedy_stream_begin_kernel(const float *W1, const float *b1, float *w1, float *bb1, int H, int J,
+                                                                  GreedyState *st, int S, const float *b2, float *btab, int V) {
+    const size_t n = (size_t)H * J;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) w1[i] = W1[i];
+    if (blockIdx.x != 0) return;
+    for (int j = threadIdx.x; j < J; j += 256) bb1[j] = b1[j];
+    for (int b = threadIdx.x; b < S; b += 256) {
+        GreedyState s;
+        s.t = 0, s.n = 0, s.nf = 0, s.done = 1, s.Tb = 0, s.maxsym = 0, s.cap = 0, s.fin = 1;
+        s.score = 0.0;
+        st[b] = s;
+    }
+    if (b2 && btab)  // DT 2: the bias as joint_phase1s_kernel reads it
+        for (int v = threadIdx.x; v < V; v += 256) btab[v] = b2[v];
+}
+
+constexpr int kGsMaxSlots = 1024, kGsMaxWidth = 4096;
+
+static bool make_stream_layout(int Tc, int S, int H, int J, int V, int joint_dtype, GreedyLayout &L, size_t &w1, size_t &b1) {
+    if (S < 1 || S > kGsMaxSlots || H < 1 || H > kGsMaxWidth) return false;
+    if (!make_greedy_layout(Tc, S, J, V, joint_dtype, L)) return false;
+    w1 = L.total;
+    b1 = align_up(w1 + (size_t)H * J * sizeof(float), 256);
+    L.total = align_up(b1 + (size_t)J * sizeof(float), 256);
+    return true;
+}
+
+hipError_t greedy_stream_workspace_bytes(int Tc, int S, int H, int J, int V, int joint_dtype, size_t *bytes) {
+    GreedyLayout L;
+    size_t w1, b1;
+    if (!make_stream_layout(Tc, S, H, J, V, joint_dtype, L, w1, b1)) return hipErrorInvalidValue;
+    *bytes = L.total;
+    return hipSuccess;
+}
+
+hipError_t launch_greedy_stream_begin(const float *W1, const float *b1, const float *W2, const float *b2, int H, int J, int V, int S,
+                                      int Tc, int joint_dtype, void *workspace, hipStream_t s) {
+    GreedyLayout L;
+    size_t w1, bo;
+    if (!make_stream_layout(Tc, S, H, J, V, joint_dtype, L, w1, bo)) return hipErrorInvalidValue;
+    GreedyArgs a = {};
+    greedy_bind(a, L, workspace);
+    a.B = S, a.T = Tc, a.J = J, a.V = V;
+    hipError_t e;
+    if ((e = launch_greedy_w2(a, L.DT, W2, b2, s)) != hipSuccess) return e;
+    char *ws = (char *)workspace;
+    const size_t n = (size_t)H * J;
+    const unsigned grid = (unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
+    hipLaunchKernelGGL(greedy_stream_begin_kernel, dim3(grid), dim3(256), 0, s, W1, b1, (float *)(ws + w1), (float *)(ws + bo), H, J,
+                       a.st, S, L.DT == 2 ? b2 : nullptr, a.btab, V);
+    return hipGetLastError();
+}
+
+hipError_t launch_greedy_stream_feed(const float *enc, int Te, const int *chunk_frames, const int *reset, const int *final_,
+                                     const int *max_symbols, int max_per_frame, int *hyp_lengths, float *scores, int *all_done, int H,
+                                     int J, int V, int S, int Tc, int joint_dtype, void *workspace, hipStream_t s) {
+    GreedyLayout L;
+    size_t w1, bo;
+    if (!make_stream_layout(Tc, S, H, J, V, joint_dtype, L, w1, bo) || Te < 0 || Te > Tc) return hipErrorInvalidValue;
+    GreedyArgs g = {};
+    greedy_bind(g, L, workspace);
+    char *ws = (char *)workspace;
+    GreedyStreamArgs a = {};
+    a.enc = enc, a.W1 = (const float *)(ws + w1), a.b1 = (const float *)(ws + bo);
+    a.chunk_frames = chunk_frames, a.reset = reset, a.final_ = final_, a.max_symbols = max_symbols;
+    a.hyp_lengths = hyp_lengths, a.all_done = all_done, a.scores = scores;
+    a.st = g.st, a.rowflag = g.rowflag, a.expE = g.expE, a.encraw = g.encraw;
+    a.S = S, a.Te = Te, a.T = Tc, a.H = H, a.J = J, a.max_per_frame = max_per_frame;
+    const int rows = S * Te;
+    if (rows > 0) {
+        hipLaunchKernelGGL(greedy_stream_proj_kernel, dim3((J + 63) / 64, (rows + kGsRows - 1) / kGsRows), dim3(256), 0, s, a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(greedy_stream_feed_kernel, dim3(rows > 1 ? (rows < 2048 ? rows : 2048) : 1), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -154,6 +154,8 @@ struct PnArgs {
     int Kpad, ld, R, N;           // N: gates: hidden units; proj / out: real columns
     const int *emitted;           // NULL: token 0 for every row (begin)
     const int *parents;           // NULL: src = r
+    const int *reset;             // compute_rnnt_prednet_reset (emitted, parents NULL): reset[r] != 0 runs token 0 from zero
+                                  // state, the other rows carry over
     int *ctl;                     // [0] slot of the current state, [1] finished workgroups of the out launch
     size_t S;                     // state slot stride (floats)
     // staged x = [segment A (width A), segment B (width Bw)]
@@ -187,17 +189,18 @@ __global__ __launch_bounds__(NW * 64) void prednet_kernel(const PnArgs a) {
     extern __shared__ float pn_sm[];
     float *xs = pn_sm;                 // [TR][Kpad]
     float *red = pn_sm + TR * a.Kpad;  // [NW][TR][64]
-    __shared__ int s_tok[TR], s_src[TR], s_cur;
+    __shared__ int s_tok[TR], s_src[TR], s_zero[TR], s_cur;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int r0 = blockIdx.y * TR;
     if (tid < TR) {
         const int r = r0 + tid;
-        int tok = -1, src = 0;  // rows beyond R: staged as zeros, never stored
+        int tok = -1, src = 0, zero = 0;  // rows beyond R: staged as zeros, never stored
         if (r < a.R) {
             tok = a.emitted ? a.emitted[r] : 0;
             src = a.parents ? min(max(a.parents[r], 0), a.R - 1) : r;
+            if (a.reset) zero = a.reset[r] != 0, tok = zero ? 0 : -1;
         }
-        s_tok[tid] = tok, s_src[tid] = src;
+        s_tok[tid] = tok, s_src[tid] = src, s_zero[tid] = zero;
     }
     if (tid == 0) s_cur = __hip_atomic_load(a.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1;
     __syncthreads();
@@ -217,7 +220,7 @@ __global__ __launch_bounds__(NW * 64) void prednet_kernel(const PnArgs a) {
             }
             x[k] = v;
         }
-        for (int k = tid; k < a.Bw; k += NW * 64) x[a.A + k] = live ? a.b_base[cur * a.S + (size_t)src * a.Bw + k] : 0.f;
+        for (int k = tid; k < a.Bw; k += NW * 64) x[a.A + k] = (live && !s_zero[t]) ? a.b_base[cur * a.S + (size_t)src * a.Bw + k] : 0.f;
         for (int k = a.A + a.Bw + tid; k < a.Kpad; k += NW * 64) x[k] = 0.f;
     }
     __syncthreads();
@@ -276,7 +279,7 @@ __global__ __launch_bounds__(NW * 64) void prednet_kernel(const PnArgs a) {
             if (r >= a.R || j >= a.N) continue;
             const int tok = s_tok[t], src = s_src[t];
             float *cn = a.c_base + nxt * a.S + (size_t)r * a.N + j;
-            const float cp = a.c_base[cur * a.S + (size_t)src * a.N + j];
+            const float cp = s_zero[t] ? 0.f : a.c_base[cur * a.S + (size_t)src * a.N + j];
             float *hn = a.h_out + (a.h_state ? nxt * a.S : 0) + (size_t)r * a.N + j;
             if (tok < 0) {
                 *cn = cp;
@@ -350,11 +353,12 @@ static hipError_t pn_launch(const PnArgs &a, int col_tiles, int max_tr, hipStrea
 // workgroup: more weight loads in flight per CU, more workgroups.
 constexpr int kPnGatesWaves = 8, kPnDenseWaves = 16, kPnGatesRows = 16, kPnDenseRows = 4;
 
-static hipError_t pn_step(const PnLayout &o, float *ws, const int *emitted, const int *parents, float *out, hipStream_t s) {
+static hipError_t pn_step(const PnLayout &o, float *ws, const int *emitted, const int *parents, float *out, hipStream_t s,
+                          const int *reset = nullptr) {
     hipError_t e;
     for (int l = 0; l < o.L; ++l) {
         PnArgs a = {};
-        a.emitted = emitted, a.parents = parents, a.ctl = (int *)(ws + o.ctl), a.S = o.S, a.R = o.R;
+        a.emitted = emitted, a.parents = parents, a.reset = reset, a.ctl = (int *)(ws + o.ctl), a.S = o.S, a.R = o.R;
         a.W = ws + o.wg[l], a.bias_i = ws + o.bi[l], a.bias_h = ws + o.bh[l];
         a.Kpad = o.Kg[l], a.ld = 4 * o.Hpad[l], a.N = o.H[l];
         if (l == 0) {
@@ -370,7 +374,7 @@ static hipError_t pn_step(const PnLayout &o, float *ws, const int *emitted, cons
         if ((e = pn_launch<PN_GATES, kPnGatesWaves>(a, o.Hpad[l] / 16, kPnGatesRows, s)) != hipSuccess) return e;
         if (o.proj[l]) {
             PnArgs p = {};
-            p.emitted = emitted, p.parents = parents, p.ctl = (int *)(ws + o.ctl), p.S = o.S, p.R = o.R;
+            p.emitted = emitted, p.parents = parents, p.reset = reset, p.ctl = (int *)(ws + o.ctl), p.S = o.S, p.R = o.R;
             p.W = ws + o.wr[l], p.Kpad = o.Kp[l], p.ld = (int)a64(o.P[l]), p.N = o.P[l];
             p.mode_a = 2, p.a_base = ws + o.hbuf, p.A = o.H[l];
             p.o_base = ws + o.r[l], p.oS = o.S;
@@ -379,7 +383,7 @@ static hipError_t pn_step(const PnLayout &o, float *ws, const int *emitted, cons
     }
     const int l = o.L - 1;
     PnArgs q = {};
-    q.emitted = emitted, q.parents = parents, q.ctl = (int *)(ws + o.ctl), q.S = o.S, q.R = o.R;
+    q.emitted = emitted, q.parents = parents, q.reset = reset, q.ctl = (int *)(ws + o.ctl), q.S = o.S, q.R = o.R;
     q.W = ws + o.w1, q.Kpad = o.Kw1, q.ld = o.Jp, q.N = o.Jp;
     q.mode_a = 1, q.a_base = ws + o.r[l], q.A = o.P[l];
     q.ln_g = ws + o.lng[l], q.ln_b = ws + o.lnb[l], q.eps = o.eps[l];
@@ -439,6 +443,15 @@ hipError_t launch_prednet_step(const int *emitted, const int *parents, float *ou
     PnLayout o;
     if (!make_pn_layout(blocks, L, E, V, Jp, R, o)) return hipErrorInvalidValue;
     return pn_step(o, (float *)workspace, emitted, parents, out, s);
+}
+
+// one step in which the rows with reset[r] != 0 run the start token 0 from zero state (what begin runs for every row) and the
+// other rows carry their state and pred_proj over; it moves the parity slot on like any step
+hipError_t launch_prednet_reset(const int *reset, float *out, const rnntPrednetBlock *blocks, int L, int E, int V, int Jp, int R,
+                                void *workspace, hipStream_t s) {
+    PnLayout o;
+    if (!make_pn_layout(blocks, L, E, V, Jp, R, o) || !reset) return hipErrorInvalidValue;
+    return pn_step(o, (float *)workspace, nullptr, nullptr, out, s, reset);
 }
 
 }  // namespace rnnt

@@ -29,7 +29,7 @@ struct GreedyState {
     int Tb;      // frames of the utterance (clamped to [0, maxT])
     int maxsym;  // symbol budget (clamped to >= 0; INT_MAX: none)
     int cap;     // symbols per frame at most (<= 0: no cap)
-    int pad;
+    int fin;     // stream decoder: 1 once the stream has finished (its final chunk fed, or its budget spent) until a reset
     double score;  // sum of the log-softmax of every decision taken
 };
 

@@ -68,6 +68,18 @@ hipError_t launch_encoder_begin(const rnntPrednetBlock *blocks, int L, int F, co
                                 void *workspace, hipStream_t s);
 hipError_t launch_encoder_run(const float *x, int T, float *out, const rnntPrednetBlock *blocks, int L, int F, float bn_eps, int ridx,
                               int f, int R, int Tmax, void *workspace, hipStream_t s);
+hipError_t launch_encoder_run_rows(const float *x, int T, const int *row_frames, const int *reset, float *out,
+                                   const rnntPrednetBlock *blocks, int L, int F, float bn_eps, int ridx, int f, int R, int Tmax,
+                                   void *workspace, hipStream_t s);
+// prednet_kernels.hip / greedy_kernels.hip (streaming greedy decoding)
+hipError_t launch_prednet_reset(const int *reset, float *out, const rnntPrednetBlock *blocks, int L, int E, int V, int Jp, int R,
+                                void *workspace, hipStream_t s);
+hipError_t greedy_stream_workspace_bytes(int Tc, int S, int H, int J, int V, int joint_dtype, size_t *bytes);
+hipError_t launch_greedy_stream_begin(const float *W1, const float *b1, const float *W2, const float *b2, int H, int J, int V, int S,
+                                      int Tc, int joint_dtype, void *workspace, hipStream_t s);
+hipError_t launch_greedy_stream_feed(const float *enc, int Te, const int *chunk_frames, const int *reset, const int *final_,
+                                     const int *max_symbols, int max_per_frame, int *hyp_lengths, float *scores, int *all_done, int H,
+                                     int J, int V, int S, int Tc, int joint_dtype, void *workspace, hipStream_t s);
 }  // namespace rnnt
 
 static rnntStatus_t check_options(const rnntOptions &o) {
@@ -711,6 +723,76 @@ rnntStatus_t compute_rnnt_encoder_run(const float *x, int frames, float *out, co
     if (st != RNNT_STATUS_SUCCESS) return st;
     return from_hip(launch_encoder_run(x, frames, out, blocks, num_layers, feat_size, bn_eps, reduction_index, reduction_factor, rows,
                                        max_frames, workspace, (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_encoder_run_rows(const float *x, int frames, const int *row_frames, const int *reset, float *out,
+                                           const rnntPrednetBlock *blocks, int num_layers, int feat_size, float bn_eps,
+                                           int reduction_index, int reduction_factor, int rows, int max_frames, void *workspace,
+                                           rnntOptions options) {
+    if (!x || !out || !row_frames || !aligned16(x) || !aligned16(out)) return RNNT_STATUS_INVALID_VALUE;
+    if (frames < 1 || frames > max_frames) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_encoder(blocks, num_layers, feat_size, bn_eps, reduction_index, reduction_factor, rows, max_frames,
+                                          workspace, false, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_encoder_run_rows(x, frames, row_frames, reset, out, blocks, num_layers, feat_size, bn_eps, reduction_index,
+                                            reduction_factor, rows, max_frames, workspace, (hipStream_t)options.stream));
+}
+
+
+// Streaming greedy decoding (include/rnnt.h).  Everything is checked before anything is enqueued.
+rnntStatus_t compute_rnnt_prednet_reset(const int *reset, float *pred_proj_out, const rnntPrednetBlock *blocks, int num_blocks,
+                                        int embed_size, int vocab_size, int joint_size, int rows, void *workspace, rnntOptions options) {
+    if (!reset || !pred_proj_out || !aligned16(pred_proj_out)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_prednet(blocks, num_blocks, embed_size, vocab_size, joint_size, rows, workspace, false, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_prednet_reset(reset, pred_proj_out, blocks, num_blocks, embed_size, vocab_size, joint_size, rows, workspace,
+                                         (hipStream_t)options.stream));
+}
+
+static rnntStatus_t check_greedy_stream(int max_chunk_frames, int slots, int enc_width, int joint_size, int alphabet_size,
+                                        int joint_dtype, const void *workspace, const rnntOptions &o) {
+    if (!workspace || ((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_greedy(max_chunk_frames, joint_size, alphabet_size, slots, joint_dtype, o);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    size_t n = 0;
+    if (greedy_stream_workspace_bytes(max_chunk_frames, slots, enc_width, joint_size, alphabet_size, joint_dtype, &n) != hipSuccess)
+        return RNNT_STATUS_INVALID_VALUE;
+    return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t get_rnnt_greedy_stream_workspace_size(int max_chunk_frames, int slots, int enc_width, int joint_size, int alphabet_size,
+                                                   int joint_dtype, size_t *size_bytes) {
+    if (!size_bytes) return RNNT_STATUS_INVALID_VALUE;
+    if (joint_dtype != 0 && joint_dtype != 1) return RNNT_STATUS_INVALID_VALUE;
+    return greedy_stream_workspace_bytes(max_chunk_frames, slots, enc_width, joint_size, alphabet_size, joint_dtype, size_bytes) ==
+                   hipSuccess
+               ? RNNT_STATUS_SUCCESS
+               : RNNT_STATUS_INVALID_VALUE;
+}
+
+rnntStatus_t compute_rnnt_greedy_stream_begin(const float *W1, const float *b1, const float *W2, const float *b2, int enc_width,
+                                              int joint_size, int alphabet_size, int slots, int joint_dtype, void *workspace,
+                                              rnntOptions options) {
+    if (!W1 || !b1 || !W2 || !b2) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st =
+        check_greedy_stream(options.maxT, slots, enc_width, joint_size, alphabet_size, joint_dtype, workspace, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_greedy_stream_begin(W1, b1, W2, b2, enc_width, joint_size, alphabet_size, slots, options.maxT, joint_dtype,
+                                               workspace, (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_greedy_stream_feed(const float *enc, int enc_frames, const int *chunk_frames, const int *reset,
+                                             const int *final_chunk, const int *max_symbols, int max_per_frame, int *hyp_lengths,
+                                             float *scores, int *all_done, int enc_width, int joint_size, int alphabet_size, int slots,
+                                             int joint_dtype, void *workspace, rnntOptions options) {
+    if (!chunk_frames || !hyp_lengths || !scores || !all_done) return RNNT_STATUS_INVALID_VALUE;
+    if (enc_frames < 0 || enc_frames > options.maxT || (enc_frames > 0 && !enc)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st =
+        check_greedy_stream(options.maxT, slots, enc_width, joint_size, alphabet_size, joint_dtype, workspace, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_greedy_stream_feed(enc, enc_frames, chunk_frames, reset, final_chunk, max_symbols, max_per_frame,
+                                              hyp_lengths, scores, all_done, enc_width, joint_size, alphabet_size, slots, options.maxT,
+                                              joint_dtype, workspace, (hipStream_t)options.stream));
 }
 
 }  // extern "C"

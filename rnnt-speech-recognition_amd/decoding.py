@@ -23,7 +23,7 @@ from typing import List, Optional
 
 import torch
 
-from .joint import BeamJoint, EncoderStream, GreedyJoint, PredictionStep
+from .joint import BeamJoint, EncoderStream, GreedyJoint, GreedyStreamJoint, PredictionStep
 from .loss import reduced_lengths
 
 
@@ -353,3 +353,160 @@ def beam_decode_batch_fn(model, beam: int = 4, prediction: str = "torch", encode
             ids = torch.where(torch.arange(ids.shape[1], device=ids.device)[None, :] < lengths[:, None], ids, torch.zeros_like(ids))
         return ids, lengths, scores
     return fn
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Streaming greedy decoding
+# ---------------------------------------------------------------------------------------------------------------------------
+class StreamingGreedyDecoder:
+    """Greedy decoding of up to `slots` live audio streams at once, fed chunk by chunk (include/rnnt.h, streaming greedy
+    decoding).  Each slot holds one stream at a time; streams start and end at different times.
+
+    start(slots) (re)starts a stream in the given slots (indices, or a bool mask [slots]): zero encoder state, the prediction
+    network's start token 0 from zero state, no symbols, score 0, frame 0.  The other slots are untouched.
+
+    feed(mel_chunk [slots, Tc, F], frames [slots], final [slots]) -> (ids int32 [slots, N] zero-padded, counts int32 [slots]),
+    on the model's device: the symbols each stream emitted in this call.  Slot s consumes mel_chunk[s, :frames[s]] (stacked
+    log-mel rows, what model.Encoder takes); a slot with 0 frames and final False is left as it was.  In a non-final feed,
+    frames[s] must be a multiple of the encoder's reduction factor f; a final feed may have any length (its odd tail is
+    zero-padded after the LayerNorm, as one run over the whole input pads it).  frames and final are host data (lists, arrays
+    or CPU tensors).  Greedy search runs with greedy_decode_batch's per-frame semantics until every live slot has consumed
+    all encoder frames it has so far.  After its final feed, or once its max_length symbols are spent, a slot is finished: it
+    emits nothing more until the next start.
+
+    hypotheses() -> (ids [slots, N] zero-padded, lengths [slots], scores [slots]) of each slot's stream since its start.
+
+    A stream delivered through any chunking that follows the rule above, in any slot, beside any other traffic, ends with the
+    ids, length and score of the same stream fed in one call to a 1-slot decoder: bitwise on an MI355X (every kernel on the path
+    sums in a fixed order that depends on the shapes alone), and equal ids to greedy_decode_batch of the stream alone.
+
+    On an MI355X the encoder (EncoderStream, compute_rnnt_encoder_run_rows), the prediction network (PredictionStep) and the
+    joint (GreedyStreamJoint) run in the library, and a feed reads the host only for the all-done word every `check_every`
+    steps and once for N.  On CPU, or for models and shapes the kernels do not take, the same state machine runs in torch, with
+    the fallback rules of those three classes."""
+
+    def __init__(self, model, slots: int, max_chunk_frames: int, max_length: Optional[int] = None,
+                 max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY):
+        S, Tc = int(slots), int(max_chunk_frames)
+        if not 1 <= S <= EncoderStream.MAX_ROWS:
+            raise ValueError(f"slots must be in 1 ... {EncoderStream.MAX_ROWS}, got {slots}")
+        if Tc < 1:
+            raise ValueError(f"max_chunk_frames must be >= 1, got {max_chunk_frames}")
+        self.model, self.S, self.Tc, self.check_every = model, S, Tc, max(1, int(check_every))
+        self.max_length = None if max_length is None else int(max_length)
+        enc = model.encoder
+        self.f = int(enc.reduce.factor)
+        self.F = int(enc.input_norm.num_features)
+        last = enc.blocks[len(enc.blocks) - 1].lstm
+        self.H = int(last.proj_size or last.hidden_size)
+        self.Te = -(-Tc // self.f)
+        with self._eval():
+            self.es = EncoderStream(enc)
+            self.es.begin(S, Tc)
+            self.gj = GreedyStreamJoint(model.joint)
+            dev = next(model.parameters()).device
+            N = max(1, self.max_length) if self.max_length is not None else self.Te + 16
+            self.gj.begin(S, self.Te, int(max_symbols_per_frame or 0), N, device=dev)
+            W1 = self.gj.W1 if self.gj.engine else model.joint.W1
+            self.ps = PredictionStep(model.prediction, W1)
+            self.pp = self.ps.begin(S)
+        self.dev = self.gj.hyps.device
+        self._pending = [False] * S  # encoder resets waiting for the next run
+
+    class _EvalMode:
+        def __init__(self, model):
+            self.model = model
+
+        def __enter__(self):
+            self.was = self.model.training
+            self.model.eval()
+
+        def __exit__(self, *exc):
+            self.model.train(self.was)
+
+    def _eval(self):
+        return self._EvalMode(self.model)
+
+    def _mask(self, slots):
+        t = torch.as_tensor(slots)
+        if t.dtype == torch.bool:
+            if t.numel() != self.S:
+                raise ValueError(f"a slot mask must have {self.S} entries, got {t.numel()}")
+            return [bool(v) for v in t.reshape(-1).tolist()]
+        m = [False] * self.S
+        for s in t.reshape(-1).tolist():
+            if not 0 <= int(s) < self.S:
+                raise ValueError(f"slot {s} is not in 0 ... {self.S - 1}")
+            m[int(s)] = True
+        return m
+
+    @torch.no_grad()
+    def start(self, slots) -> None:
+        m = self._mask(slots)
+        if not any(m):
+            return
+        with self._eval():
+            self.pp = self.ps.reset(m)
+            ms = None if self.max_length is None else [self.max_length] * self.S
+            self.gj.feed(None, [0] * self.S, reset=m, final=None, max_symbols=ms)
+        self._pending = [p or q for p, q in zip(self._pending, m)]
+
+    @torch.no_grad()
+    def feed(self, mel_chunk: torch.Tensor, frames, final):
+        S, f = self.S, self.f
+        if mel_chunk.dim() != 3 or mel_chunk.shape[0] != S or mel_chunk.shape[2] != self.F:
+            raise ValueError(f"mel_chunk must be [{S}, frames, {self.F}], got {tuple(mel_chunk.shape)}")
+        Tc = int(mel_chunk.shape[1])
+        if Tc > self.Tc:
+            raise ValueError(f"mel_chunk has {Tc} frames; this decoder takes at most max_chunk_frames = {self.Tc}")
+        fr = [int(v) for v in torch.as_tensor(frames).reshape(-1).tolist()]
+        fi = [bool(v) for v in torch.as_tensor(final).reshape(-1).tolist()]
+        if len(fr) != S or len(fi) != S:
+            raise ValueError(f"frames and final must have {S} entries")
+        for s in range(S):
+            if not 0 <= fr[s] <= Tc:
+                raise ValueError(f"frames[{s}] = {fr[s]} is not in 0 ... {Tc}")
+            if not fi[s] and fr[s] % f != 0:
+                raise ValueError(f"frames[{s}] = {fr[s]}: a non-final feed must bring a multiple of the reduction factor {f}")
+        T = max(fr)
+        with self._eval():
+            enc = None
+            if T > 0:
+                reset = self._pending if any(self._pending) else None
+                enc = self.es.run(mel_chunk[:, :T], row_frames=fr, reset=reset)
+                self._pending = [False] * S
+            self.gj.feed(enc, [-(-v // f) for v in fr], reset=None, final=[int(v) for v in fi])
+            before = self.gj.lengths.clone()
+            if T > 0:
+                self._decode()
+            counts = self.gj.lengths - before
+            N = read_flag(counts.max().reshape(1)) if S > 0 else 0
+            ar = torch.arange(N, device=self.dev)
+            idx = (before.long()[:, None] + ar[None, :]).clamp(max=self.gj.hyps.shape[1] - 1)
+            ids = torch.where(ar[None, :] < counts[:, None], self.gj.hyps.gather(1, idx), 0).to(torch.int32)
+        return ids, counts
+
+    def _decode(self):
+        """Joint step, then prediction-network step, until every slot has consumed its chunk.  The prediction network always
+        takes the last step's symbols: the next feed goes on from them."""
+        global LAST_STEPS
+        gj, ps = self.gj, self.ps
+        pp, steps = self.pp, 0
+        while True:
+            emitted = gj.step(pred_proj=pp)
+            pp = ps.step(emitted)
+            steps += 1
+            if steps % self.check_every == 0:
+                flag = read_flag(gj.all_done)
+                if flag == 1:
+                    break
+                if flag == 2:
+                    gj.grow_hyps()
+        self.pp = pp
+        LAST_STEPS = steps
+
+    def hypotheses(self):
+        """(ids int32 [slots, N] zero-padded, lengths int32 [slots], scores [slots]) of each slot's stream since its start."""
+        h, n = self.gj.hyps, self.gj.lengths
+        ids = torch.where(torch.arange(h.shape[1], device=h.device)[None, :] < n[:, None], h, 0)
+        return ids, n.clone(), self.gj.scores.clone()

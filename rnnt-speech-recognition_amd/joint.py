@@ -530,6 +530,96 @@ class GreedyJoint:
         return self.emitted
 
 
+class GreedyStreamJoint(GreedyJoint):
+    """The joint of the streaming greedy decoder (decoding.StreamingGreedyDecoder): GreedyJoint's step over `slots` streams whose
+    encoder frames arrive chunk by chunk.
+
+    On an MI355X this is the ENGINE (include/rnnt.h compute_rnnt_greedy_stream_begin / _feed, then compute_rnnt_greedy_step on
+    the same workspace): the object owns the workspace (reused by the next begin when it is large enough) and W1 / b1 go into it,
+    so the encoder side's projection runs in the library with a fixed summation order.  CPU tensors and shapes the kernels do not
+    take run the same state machine in torch (GreedyJoint's torch step on JointLoss.logits).
+
+    begin(slots, max_chunk_frames (encoder frames per feed), max_per_frame, max_hyp_len) leaves every slot finished;
+    feed(enc [slots, Te, H], frames [slots], reset, final, max_symbols) hands every slot its chunk (device int32 vectors, or
+    None); then step(pred_proj=...) until all_done[0] is 1, as for GreedyJoint."""
+
+    def begin(self, slots: int, max_chunk_frames: int, max_per_frame: int, max_hyp_len: int, device=None):
+        S, T = int(slots), int(max_chunk_frames)
+        dev = self.W2.device if self.engine else (device if device is not None else self.joint.W2.device)
+        self.B, self.T, self.Tc = S, T, T
+        self.hyps = torch.zeros(S, max_hyp_len, dtype=torch.int32, device=dev)
+        self.lengths = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.emitted = torch.full((S,), -1, dtype=torch.int32, device=dev)
+        self.all_done = torch.ones(1, dtype=torch.int32, device=dev)
+        self._cap = int(max_per_frame)
+        if not self.engine:
+            self.scores = torch.zeros(S, dtype=torch.promote_types(self.joint.W2.dtype, torch.float32), device=dev)
+            z = torch.zeros(S, dtype=torch.long, device=dev)
+            self._t, self._n, self._nf, self._Tb, self._maxsym = z.clone(), z.clone(), z.clone(), z.clone(), z.clone()
+            self._done = torch.ones(S, dtype=torch.bool, device=dev)
+            self._fin = torch.ones(S, dtype=torch.bool, device=dev)
+            return
+        self.H = int(self.W1.shape[0])
+        self.scores = torch.zeros(S, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            nbytes = _lib.greedy_stream_workspace_bytes(T, S, self.H, self.Jp, self.V, self.dtype)
+            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
+                self._ws = _new_workspace(nbytes, dev)
+            elif _WORKSPACE_FILL is not None:
+                self._ws.fill_(int(_WORKSPACE_FILL))
+            self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
+            st = _lib.load().compute_rnnt_greedy_stream_begin(self.W1.data_ptr(), self.b1.data_ptr(), self.W2.data_ptr(),
+                                                              self.b2.data_ptr(), self.H, self.Jp, self.V, S, self.dtype,
+                                                              self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_greedy_stream_begin")
+
+    def feed(self, enc, frames, reset=None, final=None, max_symbols=None):
+        """enc [slots, Te, H] (None or Te = 0: no frames), frames [slots] encoder frames per slot, reset / final [slots] or None,
+        max_symbols [slots] or None (the budget of the streams reset here)."""
+        S = self.B
+        Te = 0 if enc is None else int(enc.shape[1])
+        if Te > self.Tc:
+            raise ValueError(f"a feed takes at most {self.Tc} encoder frames, got {Te}")
+        if not self.engine:
+            return self._torch_feed(enc, Te, frames, reset, final, max_symbols)
+        dev = self.hyps.device
+        if Te > 0:
+            enc = _aligned16(enc.to(device=dev, dtype=torch.float32))
+            if tuple(enc.shape) != (S, Te, self.H):
+                raise ValueError(f"enc must be [{S}, frames, {self.H}], got {tuple(enc.shape)}")
+        cv = lambda x: None if x is None else _device_i32(x, dev).reshape(S)  # noqa: E731
+        fr, rs, fi, ms = cv(frames), cv(reset), cv(final), cv(max_symbols)
+        self._feed_args = (enc, fr, rs, fi, ms)  # (alive until the launches have read them)
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        st = _lib.load().compute_rnnt_greedy_stream_feed(ptr(enc) if Te > 0 else None, Te, fr.data_ptr(), ptr(rs), ptr(fi), ptr(ms),
+                                                         self._cap, self.lengths.data_ptr(), self.scores.data_ptr(),
+                                                         self.all_done.data_ptr(), self.H, self.Jp, self.V, S, self.dtype,
+                                                         self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_greedy_stream_feed")
+
+    def _torch_feed(self, enc, Te, frames, reset, final, max_symbols):
+        S = self.B
+        dev = self.hyps.device
+        vec = lambda x, d: torch.full((S,), d, dtype=torch.long, device=dev) if x is None else torch.as_tensor(x).to(dev).reshape(S).long()  # noqa: E731
+        rs, fi = vec(reset, 0) != 0, vec(final, 0) != 0
+        ms = vec(max_symbols, 2**31 - 1).clamp(min=0)
+        self._n = torch.where(rs, 0, self._n)
+        self.scores = torch.where(rs, torch.zeros_like(self.scores), self.scores)
+        self._maxsym = torch.where(rs, ms, self._maxsym)
+        self._fin = self._fin & ~rs
+        finished = self._fin | (self._n >= self._maxsym)
+        self._Tb = torch.where(finished, 0, vec(frames, 0).clamp(0, Te))
+        self._fin = finished | fi
+        self._t = torch.zeros_like(self._t)
+        self._nf = torch.zeros_like(self._nf)
+        self._done = self._Tb == 0
+        H = self.joint.W1.shape[0]
+        self._enc = enc if Te > 0 else torch.zeros(S, 1, H, dtype=self.joint.W1.dtype, device=dev)
+        self.T = max(Te, 1)
+        self.lengths.copy_(self._n.to(torch.int32))
+        self.all_done.fill_(0 if bool((~self._done).any()) else 1)
+
+
 class BeamJoint:
     """The joint of the batched beam search (decoding.beam_search_batch): per frame, the joint of every hypothesis of every beam,
     the candidate ranking, merging and the new beams in one pass ("modified" beam search, include/rnnt.h).
@@ -671,6 +761,17 @@ def _aligned16(x: torch.Tensor) -> torch.Tensor:
     return x if x.data_ptr() % 16 == 0 else x.clone()
 
 
+def _device_i32(x, dev) -> torch.Tensor:
+    """x (a tensor, a list or an array) as a contiguous int32 tensor on dev; host data goes through pinned memory without a
+    host synchronisation."""
+    if isinstance(x, torch.Tensor) and x.device == dev:
+        return _aligned16(x.to(torch.int32))
+    t = torch.as_tensor(x).to(torch.int32).contiguous()
+    if t.device.type == "cpu" and dev.type == "cuda":
+        t = t.pin_memory()
+    return _aligned16(t.to(dev, non_blocking=True))
+
+
 class PredictionStep:
     """One prediction-network step for every decoder row, through the joint's first Dense layer: the `pred_proj` that
     GreedyJoint.step / BeamJoint.step take as `pred_proj=`.
@@ -768,6 +869,27 @@ class PredictionStep:
                                                    self._blocks, len(self._blocks), self.E, self.V, self.Jp, self.R,
                                                    self._ws.data_ptr(), self._opts)
         _lib.check(st, "compute_rnnt_prednet_step")
+        self._n += 1
+        return self.pred_proj
+
+    def reset(self, mask) -> torch.Tensor:
+        """Restart the rows where mask [rows] (bool or int) is set: zero state, then the start token 0 -- what begin runs for
+        every row (compute_rnnt_prednet_reset on the engine).  The other rows keep their state and pred_proj.  -> pred_proj."""
+        if not self._use_engine:
+            from .decoding import _pred_step
+
+            dev = self._g.device
+            m = torch.as_tensor(mask, device=dev).reshape(self.R).bool()
+            g0, st0 = _pred_step(self.net, torch.zeros(self.R, dtype=torch.int32, device=dev), [None] * len(self.net.blocks))
+            self._g = torch.where(m[:, None], g0, self._g)
+            self._states = [(torch.where(m[None, :, None], h0, h), torch.where(m[None, :, None], c0, c))
+                            for (h0, c0), (h, c) in zip(st0, self._states)]
+            return self._project()
+        m = _device_i32(mask, self.pred_proj.device).reshape(self.R)
+        self._args = (m,)
+        st = _lib.load().compute_rnnt_prednet_reset(m.data_ptr(), self.pred_proj.data_ptr(), self._blocks, len(self._blocks), self.E,
+                                                    self.V, self.Jp, self.R, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_prednet_reset")
         self._n += 1
         return self.pred_proj
 
@@ -897,12 +1019,17 @@ class EncoderStream:
         _lib.check(st, "compute_rnnt_encoder_begin")
 
     @torch.no_grad()
-    def run(self, mel_chunk: torch.Tensor) -> torch.Tensor:
-        """mel_chunk [rows, frames, feat] -> the encoder output of these frames [rows, ceil(frames / f), out_width]."""
+    def run(self, mel_chunk: torch.Tensor, row_frames=None, reset=None) -> torch.Tensor:
+        """mel_chunk [rows, frames, feat] -> the encoder output of these frames [rows, ceil(frames / f), out_width].
+
+        Ragged rows (compute_rnnt_encoder_run_rows): rows where reset [rows] is set start from zero state; row r advances over
+        its first row_frames[r] frames only (a row with 0 frames keeps its state), reads zeros beyond them at the reduction,
+        and its output is zero past ceil(row_frames[r] / f) frames.  Both None: every row runs every frame (today's run)."""
         if mel_chunk.dim() != 3 or mel_chunk.shape[0] != self.R:
             raise ValueError(f"mel_chunk must be [{self.R}, frames, feat], got {tuple(mel_chunk.shape)}")
+        rows = row_frames is not None or reset is not None
         if not self._use_engine:
-            return self._torch_run(mel_chunk)
+            return self._torch_run_rows(mel_chunk, row_frames, reset) if rows else self._torch_run(mel_chunk)
         T = int(mel_chunk.shape[1])
         if mel_chunk.shape[2] != self.F or not 1 <= T <= self.Tmax:
             raise ValueError(f"mel_chunk must be [{self.R}, 1 ... {self.Tmax}, {self.F}], got {tuple(mel_chunk.shape)}")
@@ -910,6 +1037,15 @@ class EncoderStream:
         x = _aligned16(mel_chunk.to(device=dev, dtype=torch.float32))
         out = torch.empty(self.R, -(-T // self.factor), self._blocks[len(self._blocks) - 1].proj, dtype=torch.float32, device=dev)
         self._x = x  # (alive until the launches have read it)
+        if rows:
+            rf = _device_i32([T] * self.R if row_frames is None else row_frames, dev).reshape(self.R)
+            rs = None if reset is None else _device_i32(reset, dev).reshape(self.R)
+            self._rows = (rf, rs)
+            st = _lib.load().compute_rnnt_encoder_run_rows(x.data_ptr(), T, rf.data_ptr(), None if rs is None else rs.data_ptr(),
+                                                           out.data_ptr(), self._blocks, len(self._blocks), self.F, self.bn_eps,
+                                                           self.ridx, self.factor, self.R, self.Tmax, self._ws.data_ptr(), self._opts)
+            _lib.check(st, "compute_rnnt_encoder_run_rows")
+            return out
         st = _lib.load().compute_rnnt_encoder_run(x.data_ptr(), T, out.data_ptr(), self._blocks, len(self._blocks), self.F,
                                                   self.bn_eps, self.ridx, self.factor, self.R, self.Tmax, self._ws.data_ptr(),
                                                   self._opts)
@@ -948,3 +1084,41 @@ class EncoderStream:
                 x = enc.reduce(x)
         self._states = states
         return x
+
+    def _torch_run_rows(self, x, row_frames, reset):
+        """The ragged run in torch: packed sequences give every row its own last frame's state."""
+        enc = self.enc
+        bn = enc.input_norm
+        R, T = x.shape[0], x.shape[1]
+        dt, dev = self._states[0][0].dtype, self._states[0][0].device
+        x = x.to(device=dev, dtype=dt)
+        if reset is not None:
+            m = torch.as_tensor(reset).to(dev).reshape(R).bool()
+            self._states = [(torch.where(m[None, :, None], 0.0, h), torch.where(m[None, :, None], 0.0, c)) for h, c in self._states]
+        rf = [T] * R if row_frames is None else [min(max(int(v), 0), T) for v in torch.as_tensor(row_frames).reshape(R).tolist()]
+        f = self.factor
+        width = enc.blocks[len(enc.blocks) - 1].lstm.proj_size or enc.blocks[len(enc.blocks) - 1].lstm.hidden_size
+        out = torch.zeros(R, -(-T // f), width, dtype=dt, device=dev)
+        live = [r for r in range(R) if rf[r] > 0]
+        if not live:
+            return out
+        idx = torch.tensor(live, device=dev)
+        lens = torch.tensor([rf[r] for r in live])
+        y = x[idx]
+        y = torch.nn.functional.batch_norm(y.transpose(1, 2), bn.running_mean, bn.running_var, bn.weight, bn.bias,
+                                           bn.running_mean is None, 0.0, bn.eps).transpose(1, 2)
+        pack = torch.nn.utils.rnn
+        states = []
+        for i, (blk, (h, c)) in enumerate(zip(enc.blocks, self._states)):
+            Tl = y.shape[1]
+            p, (h2, c2) = blk.lstm(pack.pack_padded_sequence(y, lens, batch_first=True, enforce_sorted=False),
+                                   (h[:, idx].contiguous(), c[:, idx].contiguous()))
+            y, _ = pack.pad_packed_sequence(p, batch_first=True, total_length=Tl)
+            y = blk.norm(y) * (torch.arange(Tl)[None, :] < lens[:, None]).to(device=dev, dtype=dt)[:, :, None]
+            states.append((h.index_copy(1, idx, h2), c.index_copy(1, idx, c2)))
+            if i == enc.reduction_index:
+                y = enc.reduce(y)
+                lens = (lens + f - 1) // f
+        self._states = states
+        out[idx] = y
+        return out
