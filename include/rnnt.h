@@ -635,6 +635,51 @@ RNNT_API rnntStatus_t compute_rnnt_greedy_stream_feed(const float *enc, int enc_
                                                       int joint_size, int alphabet_size, int slots, int joint_dtype,
                                                       void *workspace, rnntOptions options);
 
+/* Build-only extension: ONE LSTM LAYER FOR TRAINING -- a forward pass that keeps what the backward needs, and back-propagation
+ * through time.  rows R (the batch), frames T, hidden H, output width P: a projected layer (W_hr [P, H] given, P < H, bias-free)
+ * or an unprojected one (W_hr NULL, P = H).  torch's gate order i, f, g, o; zero initial state; no row lengths (padded frames
+ * are run through like any other).  Every buffer is device f32, 16-byte aligned and TIME-MAJOR: a frame's R rows are contiguous.
+ *
+ *   forward, t = 0 ... T-1:   a_t = pre_t + r_{t-1} W_hh^T;  i, f, o = sigma(a_i), sigma(a_f), sigma(a_o);  g = tanh(a_g);
+ *                             c_t = f c_{t-1} + i g;  h_t = o tanh(c_t);  r_t = h_t W_hr^T (projected) or h_t
+ *   backward, t = T-1 ... 0:  dr_t = dy_t + da_{t+1} W_hh;  dh_t = dr_t W_hr (projected) or dr_t;
+ *                             dc_t = dh_t o (1 - tanh^2 c_t) + dc_{t+1} f_{t+1};
+ *                             da_i = dc_t g i (1 - i);  da_f = dc_t c_{t-1} f (1 - f);  da_g = dc_t i (1 - g^2);
+ *                             da_o = dh_t tanh(c_t) o (1 - o)
+ *
+ * compute_rnnt_lstm_train_fwd(gates, W_hh, W_hr, y, c, h, ...):
+ *   gates  [T, R, 4H]  in: pre = x W_ih^T + b_ih + b_hh of every frame (the caller's GEMM), columns i | f | g | o as torch
+ *                      stores them; OVERWRITTEN by the activated gates i, f, g, o
+ *   W_hh   [4H, P], W_hr [P, H] or NULL: as torch stores them; packed into the workspace on every call (weights change every step)
+ *   y      [T, R, P]   out: r_t, the layer's output       c  [T, R, H]  out: every c_t
+ *   h      [T, R, H]   out, projected layers only (NULL otherwise): every h_t
+ * compute_rnnt_lstm_train_bwd(gates, c, dy, W_hh, W_hr, dr, ...):
+ *   gates  [T, R, 4H]  in: the forward's activated gates; OVERWRITTEN by da (same columns)
+ *   c      [T, R, H]   the forward's c                     dy [T, R, P]  the gradient of y
+ *   dr     [T, R, P]   out, projected layers only (NULL otherwise): every dr_t
+ * Everything that is not recurrent is then a sum over all frames at once and is left to the caller's GEMMs:
+ *   dW_ih = da^T x;  dW_hh = da[1:]^T y[:-1];  db_ih = db_hh = sum da;  dx = da W_ih;  dW_hr = dr^T h.
+ *
+ * Launches: one per frame for an unprojected layer and two for a projected one, in each direction, plus one pack per matrix and
+ * call.  No kernel waits for another workgroup; the frame-to-frame dependency is stream order.
+ * Arithmetic: float32, every sum in an order fixed by the shapes alone: a row's y, c, h, gates, da and dr are bitwise
+ * independent of `rows`, of the other rows and of the call.  Against a float64 LSTM the forward stays within
+ * 1e-4 max(1, max|ref|).
+ * Limits: 1 <= rows <= 1024, 1 <= frames <= 2^20, 1 <= proj <= hidden <= 4096, proj < hidden exactly when W_hr is given; anything
+ * else, a NULL or misaligned pointer, or options.loc != RNNT_GPU: RNNT_STATUS_INVALID_VALUE, before anything is enqueued.
+ * Workspace: get_rnnt_lstm_train_workspace_size(rows, frames, hidden, proj) bytes (a projected layer when proj < hidden),
+ * 256-byte aligned, owned by the call's stream for the call: the weight images and the backward's dc carry.  Nothing is kept in
+ * it between the forward and the backward.  No entry point synchronises the host. */
+RNNT_API rnntStatus_t get_rnnt_lstm_train_workspace_size(int rows, int frames, int hidden, int proj, size_t *size_bytes);
+
+RNNT_API rnntStatus_t compute_rnnt_lstm_train_fwd(float *gates, const float *W_hh, const float *W_hr, float *y, float *c, float *h,
+                                                  int rows, int frames, int hidden, int proj, void *workspace,
+                                                  rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_lstm_train_bwd(float *gates, const float *c, const float *dy, const float *W_hh,
+                                                  const float *W_hr, float *dr, int rows, int frames, int hidden, int proj,
+                                                  void *workspace, rnntOptions options);
+
 #ifdef __cplusplus
 }
 #endif

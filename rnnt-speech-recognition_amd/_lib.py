@@ -53,6 +53,9 @@ SYMBOLS = [
     "get_rnnt_greedy_stream_workspace_size",
     "compute_rnnt_greedy_stream_begin",
     "compute_rnnt_greedy_stream_feed",
+    "get_rnnt_lstm_train_workspace_size",
+    "compute_rnnt_lstm_train_fwd",
+    "compute_rnnt_lstm_train_bwd",
 ]
 
 
@@ -199,6 +202,13 @@ def load():
         lib.compute_rnnt_greedy_stream_begin.argtypes = [vp] * 4 + [ci] * 5 + [vp, rnntOptions]
         lib.compute_rnnt_greedy_stream_feed.restype = ci
         lib.compute_rnnt_greedy_stream_feed.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp] + [ci] * 5 + [vp, rnntOptions]
+    if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "compute_rnnt_lstm_train_fwd"):
+        lib.get_rnnt_lstm_train_workspace_size.restype = ci
+        lib.get_rnnt_lstm_train_workspace_size.argtypes = [ci] * 4 + [ctypes.POINTER(ctypes.c_size_t)]
+        lib.compute_rnnt_lstm_train_fwd.restype = ci
+        lib.compute_rnnt_lstm_train_fwd.argtypes = [vp] * 6 + [ci] * 4 + [vp, rnntOptions]
+        lib.compute_rnnt_lstm_train_bwd.restype = ci
+        lib.compute_rnnt_lstm_train_bwd.argtypes = [vp] * 6 + [ci] * 4 + [vp, rnntOptions]
     _lib = lib
     return lib
 
@@ -273,6 +283,12 @@ def greedy_stream_workspace_bytes(max_chunk_frames: int, slots: int, enc_width: 
     n = ctypes.c_size_t(0)
     check(load().get_rnnt_greedy_stream_workspace_size(max_chunk_frames, slots, enc_width, joint_size, alphabet_size, joint_dtype,
                                                        ctypes.byref(n)), "get_rnnt_greedy_stream_workspace_size")
+    return int(n.value)
+
+
+def lstm_train_workspace_bytes(rows: int, frames: int, hidden: int, proj: int) -> int:
+    n = ctypes.c_size_t(0)
+    check(load().get_rnnt_lstm_train_workspace_size(rows, frames, hidden, proj, ctypes.byref(n)), "get_rnnt_lstm_train_workspace_size")
     return int(n.value)
 
 

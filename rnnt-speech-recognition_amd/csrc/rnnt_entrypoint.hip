@@ -71,6 +71,12 @@ hipError_t launch_encoder_run(const float *x, int T, float *out, const rnntPredn
 hipError_t launch_encoder_run_rows(const float *x, int T, const int *row_frames, const int *reset, float *out,
                                    const rnntPrednetBlock *blocks, int L, int F, float bn_eps, int ridx, int f, int R, int Tmax,
                                    void *workspace, hipStream_t s);
+// lstm_train_kernels.hip (one LSTM layer for training: forward with saved activations, BPTT)
+bool lstm_train_layout_ok(int R, int T, int H, int P, bool proj, size_t *bytes);
+hipError_t launch_lstm_train_fwd(float *gates, const float *W_hh, const float *W_hr, float *y, float *c, float *h, int R, int T, int H,
+                                 int P, void *workspace, hipStream_t s);
+hipError_t launch_lstm_train_bwd(float *gates, const float *c, const float *dy, const float *W_hh, const float *W_hr, float *dr, int R,
+                                 int T, int H, int P, void *workspace, hipStream_t s);
 // prednet_kernels.hip / greedy_kernels.hip (streaming greedy decoding)
 hipError_t launch_prednet_reset(const int *reset, float *out, const rnntPrednetBlock *blocks, int L, int E, int V, int Jp, int R,
                                 void *workspace, hipStream_t s);
@@ -793,6 +799,41 @@ rnntStatus_t compute_rnnt_greedy_stream_feed(const float *enc, int enc_frames, c
     return from_hip(launch_greedy_stream_feed(enc, enc_frames, chunk_frames, reset, final_chunk, max_symbols, max_per_frame,
                                               hyp_lengths, scores, all_done, enc_width, joint_size, alphabet_size, slots, options.maxT,
                                               joint_dtype, workspace, (hipStream_t)options.stream));
+}
+
+// The LSTM layer for training (include/rnnt.h).  Everything is checked before anything is enqueued.
+static rnntStatus_t check_lstm_train(int rows, int frames, int hidden, int proj, const float *W_hh, const float *W_hr,
+                                     const void *workspace, const rnntOptions &o) {
+    if (!W_hh || !workspace || !aligned16(W_hh) || !aligned16(W_hr)) return RNNT_STATUS_INVALID_VALUE;
+    if (o.loc != RNNT_GPU) return RNNT_STATUS_INVALID_VALUE;
+    if (((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
+    return lstm_train_layout_ok(rows, frames, hidden, proj, W_hr != nullptr, nullptr) ? RNNT_STATUS_SUCCESS : RNNT_STATUS_INVALID_VALUE;
+}
+
+rnntStatus_t get_rnnt_lstm_train_workspace_size(int rows, int frames, int hidden, int proj, size_t *size_bytes) {
+    if (!size_bytes) return RNNT_STATUS_INVALID_VALUE;
+    return lstm_train_layout_ok(rows, frames, hidden, proj, proj < hidden, size_bytes) ? RNNT_STATUS_SUCCESS
+                                                                                       : RNNT_STATUS_INVALID_VALUE;
+}
+
+rnntStatus_t compute_rnnt_lstm_train_fwd(float *gates, const float *W_hh, const float *W_hr, float *y, float *c, float *h, int rows,
+                                         int frames, int hidden, int proj, void *workspace, rnntOptions options) {
+    if (!gates || !y || !c || (W_hr && !h)) return RNNT_STATUS_INVALID_VALUE;
+    if (!aligned16(gates) || !aligned16(y) || !aligned16(c) || !aligned16(h)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_lstm_train(rows, frames, hidden, proj, W_hh, W_hr, workspace, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_lstm_train_fwd(gates, W_hh, W_hr, y, c, h, rows, frames, hidden, proj, workspace,
+                                          (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_lstm_train_bwd(float *gates, const float *c, const float *dy, const float *W_hh, const float *W_hr,
+                                         float *dr, int rows, int frames, int hidden, int proj, void *workspace, rnntOptions options) {
+    if (!gates || !c || !dy || (W_hr && !dr)) return RNNT_STATUS_INVALID_VALUE;
+    if (!aligned16(gates) || !aligned16(c) || !aligned16(dy) || !aligned16(dr)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_lstm_train(rows, frames, hidden, proj, W_hh, W_hr, workspace, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_lstm_train_bwd(gates, c, dy, W_hh, W_hr, dr, rows, frames, hidden, proj, workspace,
+                                          (hipStream_t)options.stream));
 }
 
 }  // extern "C"

@@ -32,6 +32,15 @@ from torch import nn
 
 from .joint import JointLoss
 from .loss import reduced_lengths
+from .lstm import lstm_layer
+
+LSTM_ROUTES = ("torch", "engine")
+
+
+def _check_lstm_route(lstm: str) -> str:
+    if lstm not in LSTM_ROUTES:
+        raise ValueError(f"lstm must be one of {LSTM_ROUTES}, got {lstm!r}")
+    return lstm
 
 
 @dataclasses.dataclass
@@ -84,17 +93,25 @@ class TimeReduction(nn.Module):
 
 class _LSTMBlock(nn.Module):
     """RNN(LSTMCell(d, num_proj)) -> Dropout -> LayerNorm  (model.py:62-68 / :104-109).  The TF1 LSTMCell
-    projection has no bias, like torch's proj_size; padded frames are run through, as in the reference."""
+    projection has no bias, like torch's proj_size; padded frames are run through, as in the reference.
 
-    def __init__(self, in_size: int, hidden: int, proj: int, dropout: float):
+    `lstm` picks how forward runs the recurrent layer: "torch" is nn.LSTM; "engine" is lstm.LSTMLayerFunction (the library's
+    forward and BPTT step kernels on the GPU, the same equations in torch on the CPU).  The nn.LSTM holds the parameters on
+    both routes, so state_dict() keys, the initialisers and checkpoints are the same."""
+
+    def __init__(self, in_size: int, hidden: int, proj: int, dropout: float, lstm: str = "torch"):
         super().__init__()
+        self.lstm_route = _check_lstm_route(lstm)
         self.lstm = nn.LSTM(in_size, hidden, proj_size=proj if proj < hidden else 0, batch_first=True)
         self.drop = nn.Dropout(dropout)
         self.norm = nn.LayerNorm(proj if proj < hidden else hidden, eps=1e-3)  # Keras LayerNormalization epsilon
         init_lstm_like_tf1_(self.lstm)
 
     def forward(self, x):
-        y, _ = self.lstm(x)
+        if self.lstm_route == "engine":
+            y = lstm_layer(self.lstm, x)
+        else:
+            y, _ = self.lstm(x)
         return self.norm(self.drop(y))
 
 
@@ -156,7 +173,7 @@ def load_tf1_lstm_cell_(lstm: nn.LSTM, kernel, bias, projection_kernel=None, for
 
 
 class Encoder(nn.Module):
-    def __init__(self, hp: HParams):
+    def __init__(self, hp: HParams, lstm: str = "torch"):
         super().__init__()
         feat = hp.mel_bins * hp.downsample_factor  # model.py:124
         # model.py:55: Keras BatchNormalization over the feature axis, epsilon 1e-3, momentum 0.99 (= torch momentum 0.01)
@@ -166,7 +183,7 @@ class Encoder(nn.Module):
         self.reduce = TimeReduction(hp.time_reduction_factor)
         width = feat
         for i in range(hp.encoder_layers):
-            blk = _LSTMBlock(width, hp.encoder_size, hp.projection_size, hp.dropout)
+            blk = _LSTMBlock(width, hp.encoder_size, hp.projection_size, hp.dropout, lstm)
             self.blocks.append(blk)
             width = blk.norm.normalized_shape[0]
             if i == hp.time_reduction_index:
@@ -183,13 +200,13 @@ class Encoder(nn.Module):
 
 
 class PredictionNetwork(nn.Module):
-    def __init__(self, hp: HParams):
+    def __init__(self, hp: HParams, lstm: str = "torch"):
         super().__init__()
         self.embed = nn.Embedding(hp.vocab_size, hp.embedding_size)  # model.py:99
         self.blocks = nn.ModuleList()
         width = hp.embedding_size
         for _ in range(hp.pred_net_layers):
-            blk = _LSTMBlock(width, hp.pred_net_size, hp.projection_size, hp.dropout)
+            blk = _LSTMBlock(width, hp.pred_net_size, hp.projection_size, hp.dropout, lstm)
             self.blocks.append(blk)
             width = blk.norm.normalized_shape[0]
         self.out_width = width
@@ -202,13 +219,16 @@ class PredictionNetwork(nn.Module):
 
 
 class Transducer(nn.Module):
-    """build_keras_model (model.py:119-169) with the joint fused into the loss."""
+    """build_keras_model (model.py:119-169) with the joint fused into the loss.  `lstm="engine"` runs every LSTM layer of
+    `forward` (training included) through the library's step kernels instead of nn.LSTM; parameters, state_dict() and
+    checkpoints are the same on both routes, and the decoders' `encoder=` / `prediction=` options are independent of it."""
 
-    def __init__(self, hp: HParams, blank_label: int = 0):
+    def __init__(self, hp: HParams, blank_label: int = 0, lstm: str = "torch"):
         super().__init__()
         self.hp = hp
-        self.encoder = Encoder(hp)
-        self.prediction = PredictionNetwork(hp)
+        self.lstm_route = _check_lstm_route(lstm)
+        self.encoder = Encoder(hp, lstm)
+        self.prediction = PredictionNetwork(hp, lstm)
         if self.encoder.out_width != self.prediction.out_width:
             raise ValueError(
                 f"encoder output width {self.encoder.out_width} != prediction-network width "
