@@ -635,6 +635,69 @@ RNNT_API rnntStatus_t compute_rnnt_greedy_stream_feed(const float *enc, int enc_
                                                       int joint_size, int alphabet_size, int slots, int joint_dtype,
                                                       void *workspace, rnntOptions options);
 
+/* Build-only extension: STREAMING BEAM SEARCH over S slots: the beam search of compute_rnnt_beam_* fed chunk by chunk as the
+ * greedy stream is, each slot keeping its beam from one feed to the next.  S = slots, K = beam, N = max_hyp_len (the tokens one
+ * stream's hypothesis may hold); options.maxT = max_chunk_frames.  Limits: 1 <= K <= 16, 1 <= S, S K <= 1024 (the prediction
+ * network's rows), 1 <= N, 2 S K N < 2^31, 1 <= enc_width <= 4096; joint_size, alphabet_size, joint_dtype (no flag bits) and
+ * options (loc RNNT_GPU, stream, blank_label < alphabet_size, maxT > 0; the same for every call) as for the beam decoder.
+ *
+ *   get_rnnt_beam_stream_workspace_size(max_chunk_frames, slots, beam, max_hyp_len, enc_width, ...): the beam workspace for
+ *     (max_chunk_frames, S, K) with token rows of stride N instead of maxT, followed by W1 [enc_width, joint_size] and
+ *     b1 [joint_size].  256-byte aligned; it grows with N and K; it holds 2 S K N token words.
+ *   compute_rnnt_beam_stream_begin(W1, b1, W2, b2, ...) packs W1, b1 and the W2 image (the caller may then free them) and leaves
+ *     every slot FINISHED with an EMPTY beam (no hypothesis at all).
+ *   compute_rnnt_beam_stream_feed(enc, enc_frames, chunk_frames, reset, final_chunk, ...): enc, enc_frames, chunk_frames, reset
+ *     and final_chunk exactly as for compute_rnnt_greedy_stream_feed.  It projects the chunk's frames through W1 + b1 with the
+ *     greedy stream's projection (one f32 FMA chain per output: a frame's enc_proj is bitwise independent of the chunking, the
+ *     slot and S), builds the e^{2x} tables and range flags of those frames, and moves every slot on:
+ *       reset[s] != 0      the beam becomes [((), 0)], the slot's step count 0, and the slot is not finished;
+ *       a live slot        gets frame cursor 0 over chunk_frames[s] frames and keeps its beam and step count;
+ *       a finished slot    stays frozen (its beam readable) until a reset;
+ *       final_chunk[s]     != 0 finishes the slot after this chunk's frames.
+ *   compute_rnnt_beam_stream_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, ...): one frame of every slot that
+ *     has one left in its chunk, by rules 1 - 5 of compute_rnnt_beam_step (minibatch = slots), with the same outputs; slots
+ *     without a frame left are frozen: parents = own row, emitted = -1.  One rule is added: a hypothesis that already holds N
+ *     tokens offers only its blank candidate (i, blank), whatever rank blank has among its logits; its other candidates are never
+ *     taken, exactly like -inf candidates (topk_logits / topk_symbols still show its plain top-`beam`).  The rule cannot fire in
+ *     compute_rnnt_beam_step, where a hypothesis holds at most one token per frame of maxT.
+ *   compute_rnnt_beam_stream_results(hyps, hyp_lengths, scores, stable_lengths, ...): the current beams, best first: hyps i32
+ *     [S, K, N] zero-padded, hyp_lengths i32 [S, K], scores f32 [S, K]; stable_lengths i32 [S] or NULL: the length of the longest
+ *     common prefix of all occupied hypotheses of slot s -- the tokens no later frame can change (every later hypothesis extends
+ *     one of these).  It never exceeds the shortest occupied hypothesis.  An empty or never-started slot: lengths 0, scores
+ *     -inf, stable_lengths 0.  Callable between any two calls of the stream; it changes nothing.
+ *
+ * The loop, per chunk: feed; then max over s of chunk_frames[s] times {compute_rnnt_beam_stream_step;
+ * compute_rnnt_prednet_step(emitted, parents)}.  The number of steps is host data: nothing is polled.  The prediction network is
+ * stepped after the LAST frame of a feed too (the offline loop may skip that step; the stream must not), so that the next chunk
+ * starts from the state of the hypotheses it continues.  A new stream in slot s resets its K prediction-network rows
+ * s K ... s K + K-1 with compute_rnnt_prednet_reset and its encoder row with compute_rnnt_encoder_run_rows' reset.
+ * Equivalence: a stream fed through chunks whose lengths are multiples of the encoder's reduction factor (the last one excepted),
+ * in any slot, beside any other traffic, gives bitwise the n-best (ids, lengths, f32 scores) and stable_lengths of the same
+ * stream fed in one call to a 1-slot decoder.  Cost: the select kernel copies every surviving token row each frame, O(length).
+ * No entry point synchronises the host; the caller owns every buffer; a NULL (where not allowed above) or misaligned pointer
+ * (workspace: 256 bytes; every other: 4), a shape outside the limits, enc_frames > max_chunk_frames or options.loc != RNNT_GPU
+ * give RNNT_STATUS_INVALID_VALUE before anything is enqueued. */
+RNNT_API rnntStatus_t get_rnnt_beam_stream_workspace_size(int max_chunk_frames, int slots, int beam, int max_hyp_len, int enc_width,
+                                                          int joint_size, int alphabet_size, int joint_dtype, size_t *size_bytes);
+
+RNNT_API rnntStatus_t compute_rnnt_beam_stream_begin(const float *W1, const float *b1, const float *W2, const float *b2,
+                                                     int enc_width, int joint_size, int alphabet_size, int slots, int beam,
+                                                     int max_hyp_len, int joint_dtype, void *workspace, rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_beam_stream_feed(const float *enc, int enc_frames, const int *chunk_frames, const int *reset,
+                                                    const int *final_chunk, int enc_width, int joint_size, int alphabet_size,
+                                                    int slots, int beam, int max_hyp_len, int joint_dtype, void *workspace,
+                                                    rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_beam_stream_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits,
+                                                    int *topk_symbols, float *lse, int joint_size, int alphabet_size, int slots,
+                                                    int beam, int max_hyp_len, int joint_dtype, void *workspace,
+                                                    rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_beam_stream_results(int *hyps, int *hyp_lengths, float *scores, int *stable_lengths,
+                                                       int joint_size, int alphabet_size, int slots, int beam, int max_hyp_len,
+                                                       int joint_dtype, void *workspace, rnntOptions options);
+
 /* Build-only extension: ONE LSTM LAYER FOR TRAINING -- a forward pass that keeps what the backward needs, and back-propagation
  * through time.  rows R (the batch), frames T, hidden H, output width P: a projected layer (W_hr [P, H] given, P < H, bias-free)
  * or an unprojected one (W_hr NULL, P = H).  torch's gate order i, f, g, o; zero initial state; no row lengths (padded frames

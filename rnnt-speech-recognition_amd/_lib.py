@@ -56,6 +56,11 @@ SYMBOLS = [
     "get_rnnt_lstm_train_workspace_size",
     "compute_rnnt_lstm_train_fwd",
     "compute_rnnt_lstm_train_bwd",
+    "get_rnnt_beam_stream_workspace_size",
+    "compute_rnnt_beam_stream_begin",
+    "compute_rnnt_beam_stream_feed",
+    "compute_rnnt_beam_stream_step",
+    "compute_rnnt_beam_stream_results",
 ]
 
 
@@ -209,6 +214,17 @@ def load():
         lib.compute_rnnt_lstm_train_fwd.argtypes = [vp] * 6 + [ci] * 4 + [vp, rnntOptions]
         lib.compute_rnnt_lstm_train_bwd.restype = ci
         lib.compute_rnnt_lstm_train_bwd.argtypes = [vp] * 6 + [ci] * 4 + [vp, rnntOptions]
+    if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "compute_rnnt_beam_stream_feed"):
+        lib.get_rnnt_beam_stream_workspace_size.restype = ci
+        lib.get_rnnt_beam_stream_workspace_size.argtypes = [ci] * 8 + [ctypes.POINTER(ctypes.c_size_t)]
+        lib.compute_rnnt_beam_stream_begin.restype = ci
+        lib.compute_rnnt_beam_stream_begin.argtypes = [vp] * 4 + [ci] * 7 + [vp, rnntOptions]
+        lib.compute_rnnt_beam_stream_feed.restype = ci
+        lib.compute_rnnt_beam_stream_feed.argtypes = [vp, ci, vp, vp, vp] + [ci] * 7 + [vp, rnntOptions]
+        lib.compute_rnnt_beam_stream_step.restype = ci
+        lib.compute_rnnt_beam_stream_step.argtypes = [vp] * 6 + [ci] * 6 + [vp, rnntOptions]
+        lib.compute_rnnt_beam_stream_results.restype = ci
+        lib.compute_rnnt_beam_stream_results.argtypes = [vp] * 4 + [ci] * 6 + [vp, rnntOptions]
     _lib = lib
     return lib
 
@@ -283,6 +299,15 @@ def greedy_stream_workspace_bytes(max_chunk_frames: int, slots: int, enc_width: 
     n = ctypes.c_size_t(0)
     check(load().get_rnnt_greedy_stream_workspace_size(max_chunk_frames, slots, enc_width, joint_size, alphabet_size, joint_dtype,
                                                        ctypes.byref(n)), "get_rnnt_greedy_stream_workspace_size")
+    return int(n.value)
+
+
+def beam_stream_workspace_bytes(max_chunk_frames: int, slots: int, beam: int, max_hyp_len: int, enc_width: int, joint_size: int,
+                                alphabet_size: int, joint_dtype: int) -> int:
+    n = ctypes.c_size_t(0)
+    check(load().get_rnnt_beam_stream_workspace_size(max_chunk_frames, slots, beam, max_hyp_len, enc_width, joint_size,
+                                                     alphabet_size, joint_dtype, ctypes.byref(n)),
+          "get_rnnt_beam_stream_workspace_size")
     return int(n.value)
 
 

@@ -14,6 +14,11 @@
 //           gathered by parent; two sequences are compared by (length, 64-bit rolling hash) and confirmed on the token rows.
 // prepare (launch_greedy_prepare, then beam_begin_kernel): greedy's tables and W2 image, its per-utterance state (t, Tb: the
 // frame counter), and every beam reset to the empty sequence with score 0.
+//
+// Token rows have stride N (BeamArgs::N) and the double-buffer side is GreedyState::n & 1, n = the steps the beam has taken since
+// it was last reset.  Offline N = maxT and n == t.  The stream (beam_stream_*, at the end) keeps a beam across feeds: there t
+// counts the frames of the current chunk, N is the token capacity of a stream, n goes on counting, and a hypothesis that holds N
+// tokens offers only its blank candidate.
 #include "rnnt_decode.h"
 
 #include <limits.h>
@@ -37,13 +42,15 @@ struct BeamArgs {
     int *nslot;      // [B] occupied slots (the first nslot[b] of the beam)
     float *pl;       // [NS][B K][K] slice top-K logits
     int *pv;         // [NS][B K][K] their symbols (-1: none)
-    int *tok;        // [2][B][K][T] token rows
+    float *bl;       // [B K] the blank's logit (what a hypothesis with a full token row offers)
+    int *tok;        // [2][B][K][N] token rows
     int *parents, *emitted;
     float *topl, *lse;  // diagnostics (NULL: not written)
     int *tops;
-    int *hyps, *hyp_lengths;
+    int *hyps, *hyp_lengths, *stable;
     float *scores;
     int K, R;
+    int N;  // token row stride = tokens a hypothesis may hold (offline: maxT)
 };
 
 __device__ __forceinline__ bool bm_better(float l, int v, float bl, int bv) { return l > bl || (l == bl && v < bv); }
@@ -126,6 +133,7 @@ __global__ __launch_bounds__(kGrWaves * 64) void beam_step_kernel(const BeamArgs
     }
     r_m[tid] = bm, r_s[tid] = bs;
     __syncthreads();
+    if (tid < 32 && s_live[tid] && slice == a.blank / (32 * kGrWaves)) ba.bl[r0 + tid] = lg[tid * LW + a.blank % (32 * kGrWaves)];
     if (tid < 32 && s_live[tid]) {  // the 2 kGrWaves partials of row tid, in greedy_step_kernel's order
         float M = -INFINITY;
         for (int q = 0; q < 2 * kGrWaves; ++q) {
@@ -194,7 +202,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const BeamArgs a) {
         if (tid < K) a.parents[rb + tid] = rb + tid, a.emitted[rb + tid] = -1;
         return;
     }
-    const int nb = a.nslot[b], T = g.T, cur = st.t & 1;
+    const int nb = a.nslot[b], T = a.N, cur = st.n & 1;
     const int *tok_cur = a.tok + ((size_t)cur * g.B + b) * K * T;
     int *tok_nxt = a.tok + ((size_t)(cur ^ 1) * g.B + b) * K * T;
 
@@ -242,6 +250,12 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const BeamArgs a) {
                 if (a.tops) a.tops[(size_t)r * K + k] = bv != INT_MAX ? bv : -1;
             }
         }
+    }
+    __syncthreads();
+    // a hypothesis whose token row is full (N tokens; never offline) offers its blank candidate alone
+    if (tid < nb && a.slot[rb + tid].len >= a.N) {
+        for (int k = 0; k < K; ++k) s_tv[tid * K + k] = -1;
+        s_tv[tid * K] = blank, s_tl[tid * K] = a.bl[rb + tid];
     }
     __syncthreads();
 
@@ -344,27 +358,41 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const BeamArgs a) {
     if (tid == 0) {
         a.nslot[b] = nn;
         GreedyState s2 = st;
-        s2.t = st.t + 1;
+        s2.t = st.t + 1, s2.n = st.n + 1;
         g.st[b] = s2;
     }
 }
 
 // ---------------------------------------------------------------------------------------------
-// results: one workgroup per utterance; the current beams, zero-padded
+// results: one workgroup per utterance; the current beams, zero-padded; stable (NULL: not written): the length of the longest
+// common prefix of the occupied hypotheses (rows 1 ... nb-1 against row 0, position by position; an integer minimum in LDS)
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void beam_results_kernel(const BeamArgs a) {
+    __shared__ int s_first;
     const GreedyArgs &g = a.g;
-    const int b = blockIdx.x, K = a.K, T = g.T;
-    const int cur = g.st[b].t & 1, nb = a.nslot[b];
+    const int b = blockIdx.x, K = a.K, T = a.N;
+    const int cur = g.st[b].n & 1, nb = min(max(a.nslot[b], 0), K);
     const int *tok = a.tok + ((size_t)cur * g.B + b) * K * T;
+    int shortest = nb > 0 ? INT_MAX : 0;
     for (int k = 0; k < K; ++k) {
-        const int n = k < nb ? a.slot[b * K + k].len : 0;
+        const int n = k < nb ? min(max(a.slot[b * K + k].len, 0), T) : 0;
+        if (k < nb) shortest = min(shortest, n);
         for (int p = threadIdx.x; p < T; p += 256) a.hyps[((size_t)b * K + k) * T + p] = p < n ? tok[(size_t)k * T + p] : 0;
         if (threadIdx.x == 0) {
             a.hyp_lengths[b * K + k] = n;
             a.scores[b * K + k] = k < nb ? (float)a.slot[b * K + k].score : -INFINITY;
         }
     }
+    if (!a.stable) return;  // (uniform)
+    if (threadIdx.x == 0) s_first = shortest;
+    __syncthreads();
+    int first = shortest;
+    for (int p = threadIdx.x; p < shortest && first == shortest; p += 256)
+        for (int k = 1; k < nb; ++k)
+            if (tok[(size_t)k * T + p] != tok[p]) first = p;
+    if (first < shortest) atomicMin(&s_first, first);
+    __syncthreads();
+    if (threadIdx.x == 0) a.stable[b] = s_first;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -373,14 +401,15 @@ __global__ __launch_bounds__(256) void beam_results_kernel(const BeamArgs a) {
 size_t joint_w2_image_bytes(int J, int V);
 
 struct BeamLayout {
-    size_t st, slot, nslot, pm, ps, pl, pv, tok, rowflag, expE, encraw, img, btab, tflag, total;
+    size_t st, slot, nslot, pm, ps, pl, pv, bl, tok, rowflag, expE, encraw, img, btab, tflag, total;
     int NC, NS, DT;
 };
 
-static bool make_beam_layout(int T, int B, int K, int J, int V, int joint_dtype, BeamLayout &L) {
+// N: the token row stride (offline: T)
+static bool make_beam_layout(int T, int B, int K, int N, int J, int V, int joint_dtype, BeamLayout &L) {
     L.DT = greedy_dt(joint_dtype, J, V);
-    if (L.DT < 0 || T <= 0 || B <= 0 || K < 1 || K > kBeamMax) return false;
-    if ((unsigned long long)B * T * J >= (1ull << 31) || 2ull * B * K * T >= (1ull << 31)) return false;
+    if (L.DT < 0 || T <= 0 || B <= 0 || K < 1 || K > kBeamMax || N < 1) return false;
+    if ((unsigned long long)B * T * J >= (1ull << 31) || 2ull * B * K * N >= (1ull << 31)) return false;
     L.NC = (V + 31) / 32;
     L.NS = (L.NC + kGrWaves - 1) / kGrWaves;
     const size_t R = (size_t)B * K;
@@ -397,19 +426,20 @@ static bool make_beam_layout(int T, int B, int K, int J, int V, int joint_dtype,
     L.ps = take((size_t)L.NS * R * sizeof(float));
     L.pl = take((size_t)L.NS * R * K * sizeof(float));
     L.pv = take((size_t)L.NS * R * K * sizeof(int));
-    L.tok = take(2 * R * T * sizeof(int));
+    L.tok = take(2 * R * (size_t)N * sizeof(int));
     L.rowflag = take((size_t)B * T * sizeof(int));
     L.expE = take((size_t)B * T * J * sizeof(float));
     L.encraw = take((size_t)B * T * J * sizeof(float));
     L.img = take(L.DT == 1 ? (size_t)L.NC * 32 * J * sizeof(gf16) : joint_w2_image_bytes(J, V));
     L.btab = take((size_t)L.NC * 32 * sizeof(float));
     L.tflag = take(256 + 1024);  // joint_prep_kernel's flag words + b2s (as greedy's layout)
+    L.bl = take(R * sizeof(float));
     L.total = off;
     return true;
 }
 
-static bool beam_bind(BeamArgs &a, int T, int B, int K, int J, int V, int joint_dtype, void *workspace, BeamLayout &L) {
-    if (!make_beam_layout(T, B, K, J, V, joint_dtype, L)) return false;
+static bool beam_bind(BeamArgs &a, int T, int B, int K, int N, int J, int V, int joint_dtype, void *workspace, BeamLayout &L) {
+    if (!make_beam_layout(T, B, K, N, J, V, joint_dtype, L)) return false;
     char *ws = (char *)workspace;
     GreedyArgs &g = a.g;
     g.st = (GreedyState *)(ws + L.st);
@@ -420,14 +450,14 @@ static bool beam_bind(BeamArgs &a, int T, int B, int K, int J, int V, int joint_
     g.NC = L.NC, g.NS = L.NS;
     g.B = B, g.T = T, g.J = J, g.V = V;
     a.slot = (BeamSlot *)(ws + L.slot), a.nslot = (int *)(ws + L.nslot);
-    a.pl = (float *)(ws + L.pl), a.pv = (int *)(ws + L.pv), a.tok = (int *)(ws + L.tok);
-    a.K = K, a.R = B * K;
+    a.pl = (float *)(ws + L.pl), a.pv = (int *)(ws + L.pv), a.bl = (float *)(ws + L.bl), a.tok = (int *)(ws + L.tok);
+    a.K = K, a.R = B * K, a.N = N;
     return true;
 }
 
 hipError_t beam_workspace_bytes(int T, int B, int K, int J, int V, int joint_dtype, size_t *bytes) {
     BeamLayout L;
-    if (!make_beam_layout(T, B, K, J, V, joint_dtype, L)) return hipErrorInvalidValue;
+    if (!make_beam_layout(T, B, K, T, J, V, joint_dtype, L)) return hipErrorInvalidValue;
     *bytes = L.total;
     return hipSuccess;
 }
@@ -436,7 +466,7 @@ hipError_t launch_beam_begin(const float *enc_proj, const int *frame_lengths, co
                              int T, int K, int joint_dtype, void *workspace, hipStream_t s) {
     BeamArgs a = {};
     BeamLayout L;
-    if (!beam_bind(a, T, B, K, J, V, joint_dtype, workspace, L)) return hipErrorInvalidValue;
+    if (!beam_bind(a, T, B, K, T, J, V, joint_dtype, workspace, L)) return hipErrorInvalidValue;
     a.g.enc_proj = enc_proj, a.g.frame_lengths = frame_lengths, a.g.max_symbols = nullptr, a.g.max_per_frame = 0;
     hipError_t e = launch_greedy_prepare(a.g, L.DT, W2, b2, s);
     if (e != hipSuccess) return e;
@@ -453,11 +483,12 @@ static hipError_t launch_beam_step_dt(const BeamArgs &a, size_t shm, hipStream_t
     return hipGetLastError();
 }
 
+// N: the token row stride the workspace was laid out with (offline: T; the stream: max_hyp_len)
 hipError_t launch_beam_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits, int *topk_symbols, float *lse,
-                            int J, int V, int B, int T, int K, int blank, int joint_dtype, void *workspace, hipStream_t s) {
+                            int J, int V, int B, int T, int K, int N, int blank, int joint_dtype, void *workspace, hipStream_t s) {
     BeamArgs a = {};
     BeamLayout L;
-    if (!beam_bind(a, T, B, K, J, V, joint_dtype, workspace, L)) return hipErrorInvalidValue;
+    if (!beam_bind(a, T, B, K, N, J, V, joint_dtype, workspace, L)) return hipErrorInvalidValue;
     a.g.pred_proj = pred_proj, a.g.blank = blank;
     a.parents = parents, a.emitted = emitted, a.topl = topk_logits, a.tops = topk_symbols, a.lse = lse;
     hipError_t e;
@@ -470,13 +501,123 @@ hipError_t launch_beam_step(const float *pred_proj, int *parents, int *emitted, 
     return hipGetLastError();
 }
 
-hipError_t launch_beam_results(int *hyps, int *hyp_lengths, float *scores, int J, int V, int B, int T, int K, int joint_dtype,
-                               void *workspace, hipStream_t s) {
+hipError_t launch_beam_results(int *hyps, int *hyp_lengths, float *scores, int *stable_lengths, int J, int V, int B, int T, int K,
+                               int N, int joint_dtype, void *workspace, hipStream_t s) {
     BeamArgs a = {};
     BeamLayout L;
-    if (!beam_bind(a, T, B, K, J, V, joint_dtype, workspace, L)) return hipErrorInvalidValue;
-    a.hyps = hyps, a.hyp_lengths = hyp_lengths, a.scores = scores;
+    if (!beam_bind(a, T, B, K, N, J, V, joint_dtype, workspace, L)) return hipErrorInvalidValue;
+    a.hyps = hyps, a.hyp_lengths = hyp_lengths, a.scores = scores, a.stable = stable_lengths;
     hipLaunchKernelGGL(beam_results_kernel, dim3(B), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// stream: beam search over a stream of chunks per slot (include/rnnt.h compute_rnnt_beam_stream_*).  The workspace is the beam
+// workspace with T = max_chunk_frames, B = slots and token rows of stride N = max_hyp_len, then W1 [H][J] and b1 [J] as the
+// greedy stream lays them out: beam_step_kernel, beam_select_kernel and beam_results_kernel run on it unchanged.  A feed refills
+// the tables for the chunk's frames (greedy_stream_proj_kernel: the one FMA chain the chunking equivalence rests on) and sets
+// every slot's frame cursor; GreedyState::n (the step count) and the beam live on until a reset.
+// ---------------------------------------------------------------------------------------------
+// begin: every beam empty (the slots' states were set finished by launch_greedy_stream_pack)
+__global__ __launch_bounds__(256) void beam_stream_begin_kernel(const BeamArgs a) {
+    for (int r = blockIdx.x * 256 + threadIdx.x; r < a.R; r += gridDim.x * 256) {
+        BeamSlot s;
+        s.score = -INFINITY, s.hash = 0, s.len = 0, s.pad = 0;
+        a.slot[r] = s;
+        if (r % a.K == 0) a.nslot[r / a.K] = 0;
+    }
+}
+
+// the per-frame range flags of the chunk's frames (as greedy_stream_feed_kernel forms them); workgroup 0 also moves every slot on
+__global__ __launch_bounds__(256) void beam_stream_feed_kernel(const GreedyStreamArgs a, BeamSlot *slot, int *nslot, const int K) {
+    const int rows = a.S * a.Te;
+    for (int r = blockIdx.x; r < rows; r += gridDim.x) {  // (block-uniform trip count and skip: the barrier below is safe)
+        const int s = r / a.Te, t = r - s * a.Te;
+        if (t >= gs_frames(a, s)) continue;
+        const size_t base = ((size_t)s * a.T + t) * a.J;
+        bool big = false;
+        for (int j = threadIdx.x; j < a.J; j += 256) big |= exp_tab_out_of_range(a.encraw[base + j]);  // also catches NaN
+        big = __syncthreads_or(big);
+        if (threadIdx.x == 0) a.rowflag[(size_t)s * a.T + t] = big ? 1 : 0;
+    }
+    if (blockIdx.x != 0) return;
+    for (int b = threadIdx.x; b < a.S; b += 256) {
+        GreedyState s = a.st[b];
+        if (a.reset && a.reset[b] != 0) {  // a new stream: the beam [((), 0)], no steps taken
+            s.n = 0, s.fin = 0;
+            for (int k = 0; k < K; ++k) {
+                BeamSlot e;
+                e.score = k == 0 ? 0.0 : -INFINITY, e.hash = 0, e.len = 0, e.pad = 0;
+                slot[b * K + k] = e;
+            }
+            nslot[b] = 1;
+        }
+        s.t = 0, s.nf = 0, s.maxsym = INT_MAX, s.cap = 0, s.score = 0.0;
+        if (s.fin) {  // finished: frozen until a reset
+            s.Tb = 0;
+        } else {
+            s.Tb = gs_frames(a, b);
+            if (a.final_ && a.final_[b] != 0) s.fin = 1;  // (after this chunk)
+        }
+        s.done = s.Tb == 0 ? 1 : 0;
+        a.st[b] = s;
+    }
+}
+
+static bool make_beam_stream_layout(int Tc, int S, int K, int N, int H, int J, int V, int joint_dtype, BeamLayout &L, size_t &w1,
+                                    size_t &b1) {
+    if (S < 1 || K < 1 || K > kBeamMax || (long long)S * K > 1024 || H < 1 || H > 4096) return false;  // (the prediction network's rows)
+    if (!make_beam_layout(Tc, S, K, N, J, V, joint_dtype, L)) return false;
+    w1 = L.total;
+    b1 = align_up(w1 + (size_t)H * J * sizeof(float), 256);
+    L.total = align_up(b1 + (size_t)J * sizeof(float), 256);
+    return true;
+}
+
+hipError_t beam_stream_workspace_bytes(int Tc, int S, int K, int N, int H, int J, int V, int joint_dtype, size_t *bytes) {
+    BeamLayout L;
+    size_t w1, b1;
+    if (!make_beam_stream_layout(Tc, S, K, N, H, J, V, joint_dtype, L, w1, b1)) return hipErrorInvalidValue;
+    *bytes = L.total;
+    return hipSuccess;
+}
+
+hipError_t launch_beam_stream_begin(const float *W1, const float *b1, const float *W2, const float *b2, int H, int J, int V, int S,
+                                    int Tc, int K, int N, int joint_dtype, void *workspace, hipStream_t s) {
+    BeamLayout L;
+    size_t w1, bo;
+    if (!make_beam_stream_layout(Tc, S, K, N, H, J, V, joint_dtype, L, w1, bo)) return hipErrorInvalidValue;
+    BeamArgs a = {};
+    if (!beam_bind(a, Tc, S, K, N, J, V, joint_dtype, workspace, L)) return hipErrorInvalidValue;
+    hipError_t e;
+    if ((e = launch_greedy_w2(a.g, L.DT, W2, b2, s)) != hipSuccess) return e;
+    char *ws = (char *)workspace;
+    e = launch_greedy_stream_pack(W1, b1, (float *)(ws + w1), (float *)(ws + bo), H, J, a.g.st, S, L.DT == 2 ? b2 : nullptr, a.g.btab,
+                                  V, s);
+    if (e != hipSuccess) return e;
+    const int grid = (a.R + 255) / 256;
+    hipLaunchKernelGGL(beam_stream_begin_kernel, dim3(grid), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_beam_stream_feed(const float *enc, int Te, const int *chunk_frames, const int *reset, const int *final_, int H, int J,
+                                   int V, int S, int Tc, int K, int N, int joint_dtype, void *workspace, hipStream_t s) {
+    BeamLayout L;
+    size_t w1, bo;
+    if (!make_beam_stream_layout(Tc, S, K, N, H, J, V, joint_dtype, L, w1, bo) || Te < 0 || Te > Tc) return hipErrorInvalidValue;
+    BeamArgs b = {};
+    if (!beam_bind(b, Tc, S, K, N, J, V, joint_dtype, workspace, L)) return hipErrorInvalidValue;
+    char *ws = (char *)workspace;
+    GreedyStreamArgs a = {};
+    a.enc = enc, a.W1 = (const float *)(ws + w1), a.b1 = (const float *)(ws + bo);
+    a.chunk_frames = chunk_frames, a.reset = reset, a.final_ = final_;
+    a.st = b.g.st, a.rowflag = b.g.rowflag, a.expE = b.g.expE, a.encraw = b.g.encraw;
+    a.S = S, a.Te = Te, a.T = Tc, a.H = H, a.J = J;
+    const hipError_t e = launch_greedy_stream_proj(a, s);
+    if (e != hipSuccess) return e;
+    const int rows = S * Te;
+    hipLaunchKernelGGL(beam_stream_feed_kernel, dim3(rows > 1 ? (rows < 2048 ? rows : 2048) : 1), dim3(256), 0, s, a, b.slot, b.nslot,
+                       K);
     return hipGetLastError();
 }
 

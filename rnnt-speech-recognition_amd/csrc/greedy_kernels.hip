@@ -288,7 +288,7 @@ hipError_t launch_greedy_begin(const float *enc_proj, const int *frame_lengths, 
 
 // the W2 operand image and bias tables, the e^{2x} tables of enc_proj, the per-hypothesis state (a: bound to a workspace, with
 // enc_proj, frame_lengths, max_symbols, B, T, J, V, NC and max_per_frame set).  Shared with the beam decoder's begin.
-static hipError_t launch_greedy_w2(const GreedyArgs &a, int DT, const float *W2, const float *b2, hipStream_t s) {
+hipError_t launch_greedy_w2(const GreedyArgs &a, int DT, const float *W2, const float *b2, hipStream_t s) {
     if (DT == 1) {
         const size_t n = (size_t)a.NC * 32 * a.J;
         const unsigned grid = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
@@ -343,21 +343,7 @@ hipError_t launch_greedy_step(const float *pred_proj, int *hyps, int max_hyp_len
 // greedy_update_kernel run on it unchanged.  A feed refills the tables for the chunk's frames and resets every slot's frame
 // cursor; a slot that has used up its chunk is done for the step loop until the next feed.
 // ---------------------------------------------------------------------------------------------
-struct GreedyStreamArgs {
-    const float *enc;          // [S, Te, H]
-    const float *W1, *b1;      // workspace copies: [H][J], [J]
-    const int *chunk_frames, *reset, *final_, *max_symbols;
-    int *hyp_lengths, *all_done;
-    float *scores;
-    GreedyState *st;
-    int *rowflag;
-    float *expE, *encraw;
-    int S, Te, T, H, J, max_per_frame;
-};
-
 constexpr int kGsRows = 32, kGsKc = 64;
-
-__device__ __forceinline__ int gs_frames(const GreedyStreamArgs &a, const int s) { return min(max(a.chunk_frames[s], 0), a.Te); }
 
 // enc_proj = enc W1 + b1 for the chunk's frames: a workgroup owns 64 columns (one per lane) and 32 encoder rows (8 per wave);
 // every output is one FMA chain over k = 0 ... H-1 in order, then + b1, so it depends on the frame alone (not on the chunking,
@@ -455,6 +441,23 @@ __global__ __launch_bounds__(256) void greedy_stream_begin_kernel(const float *W
         for (int v = threadIdx.x; v < V; v += 256) btab[v] = b2[v];
 }
 
+// the launches the beam stream shares (beam_kernels.hip): W1 / b1 into a workspace with every slot's state finished, and the
+// chunk projection
+hipError_t launch_greedy_stream_pack(const float *W1, const float *b1, float *w1, float *bb1, int H, int J, GreedyState *st, int S,
+                                     const float *b2, float *btab, int V, hipStream_t s) {
+    const size_t n = (size_t)H * J;
+    const unsigned grid = (unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
+    hipLaunchKernelGGL(greedy_stream_begin_kernel, dim3(grid), dim3(256), 0, s, W1, b1, w1, bb1, H, J, st, S, b2, btab, V);
+    return hipGetLastError();
+}
+
+hipError_t launch_greedy_stream_proj(const GreedyStreamArgs &a, hipStream_t s) {
+    const int rows = a.S * a.Te;
+    if (rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(greedy_stream_proj_kernel, dim3((a.J + 63) / 64, (rows + kGsRows - 1) / kGsRows), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 constexpr int kGsMaxSlots = 1024, kGsMaxWidth = 4096;
 
 static bool make_stream_layout(int Tc, int S, int H, int J, int V, int joint_dtype, GreedyLayout &L, size_t &w1, size_t &b1) {
@@ -485,11 +488,8 @@ hipError_t launch_greedy_stream_begin(const float *W1, const float *b1, const fl
     hipError_t e;
     if ((e = launch_greedy_w2(a, L.DT, W2, b2, s)) != hipSuccess) return e;
     char *ws = (char *)workspace;
-    const size_t n = (size_t)H * J;
-    const unsigned grid = (unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
-    hipLaunchKernelGGL(greedy_stream_begin_kernel, dim3(grid), dim3(256), 0, s, W1, b1, (float *)(ws + w1), (float *)(ws + bo), H, J,
-                       a.st, S, L.DT == 2 ? b2 : nullptr, a.btab, V);
-    return hipGetLastError();
+    return launch_greedy_stream_pack(W1, b1, (float *)(ws + w1), (float *)(ws + bo), H, J, a.st, S, L.DT == 2 ? b2 : nullptr, a.btab,
+                                     V, s);
 }
 
 hipError_t launch_greedy_stream_feed(const float *enc, int Te, const int *chunk_frames, const int *reset, const int *final_,
@@ -508,11 +508,8 @@ hipError_t launch_greedy_stream_feed(const float *enc, int Te, const int *chunk_
     a.st = g.st, a.rowflag = g.rowflag, a.expE = g.expE, a.encraw = g.encraw;
     a.S = S, a.Te = Te, a.T = Tc, a.H = H, a.J = J, a.max_per_frame = max_per_frame;
     const int rows = S * Te;
-    if (rows > 0) {
-        hipLaunchKernelGGL(greedy_stream_proj_kernel, dim3((J + 63) / 64, (rows + kGsRows - 1) / kGsRows), dim3(256), 0, s, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e = launch_greedy_stream_proj(a, s);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(greedy_stream_feed_kernel, dim3(rows > 1 ? (rows < 2048 ? rows : 2048) : 1), dim3(256), 0, s, a);
     return hipGetLastError();
 }

@@ -153,9 +153,30 @@ __device__ __forceinline__ float dec_logit(const GreedyArgs &a, const float acc,
     return fmaf(acc, w2inv, a.btab[v]);
 }
 
+// the stream decoders' feed (greedy_kernels.hip greedy_stream_*, beam_kernels.hip beam_stream_*): a chunk of encoder frames per slot
+struct GreedyStreamArgs {
+    const float *enc;          // [S, Te, H]
+    const float *W1, *b1;      // workspace copies: [H][J], [J]
+    const int *chunk_frames, *reset, *final_, *max_symbols;
+    int *hyp_lengths, *all_done;
+    float *scores;
+    GreedyState *st;
+    int *rowflag;
+    float *expE, *encraw;
+    int S, Te, T, H, J, max_per_frame;
+};
+
+__device__ __forceinline__ int gs_frames(const GreedyStreamArgs &a, const int s) { return min(max(a.chunk_frames[s], 0), a.Te); }
+
 // host side: the prepare path (greedy_kernels.hip) both decoders run in their begin.  DT: 0 / 1 / 2 of the step kernels.
 // greedy_dt: DT for (joint_dtype, J, V), or -1 when the shape is not taken.
 int greedy_dt(int joint_dtype, int J, int V);
 hipError_t launch_greedy_prepare(const GreedyArgs &a, int DT, const float *W2, const float *b2, hipStream_t s);
+// the pieces of the greedy stream that the beam stream runs unchanged (greedy_kernels.hip): the W2 image alone; W1 [H][J] / b1 [J]
+// copied to w1 / bb1 with st[0 .. S) set finished (b2 / btab: DT 2's bias table, else NULL); greedy_stream_proj_kernel over a.enc
+hipError_t launch_greedy_w2(const GreedyArgs &a, int DT, const float *W2, const float *b2, hipStream_t s);
+hipError_t launch_greedy_stream_pack(const float *W1, const float *b1, float *w1, float *bb1, int H, int J, GreedyState *st, int S,
+                                     const float *b2, float *btab, int V, hipStream_t s);
+hipError_t launch_greedy_stream_proj(const GreedyStreamArgs &a, hipStream_t s);
 
 }  // namespace rnnt

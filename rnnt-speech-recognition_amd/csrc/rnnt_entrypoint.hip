@@ -52,9 +52,14 @@ hipError_t beam_workspace_bytes(int T, int B, int K, int J, int V, int joint_dty
 hipError_t launch_beam_begin(const float *enc_proj, const int *frame_lengths, const float *W2, const float *b2, int J, int V, int B,
                              int T, int K, int joint_dtype, void *workspace, hipStream_t s);
 hipError_t launch_beam_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits, int *topk_symbols, float *lse,
-                            int J, int V, int B, int T, int K, int blank, int joint_dtype, void *workspace, hipStream_t s);
-hipError_t launch_beam_results(int *hyps, int *hyp_lengths, float *scores, int J, int V, int B, int T, int K, int joint_dtype,
-                               void *workspace, hipStream_t s);
+                            int J, int V, int B, int T, int K, int N, int blank, int joint_dtype, void *workspace, hipStream_t s);
+hipError_t launch_beam_results(int *hyps, int *hyp_lengths, float *scores, int *stable_lengths, int J, int V, int B, int T, int K,
+                               int N, int joint_dtype, void *workspace, hipStream_t s);
+hipError_t beam_stream_workspace_bytes(int Tc, int S, int K, int N, int H, int J, int V, int joint_dtype, size_t *bytes);
+hipError_t launch_beam_stream_begin(const float *W1, const float *b1, const float *W2, const float *b2, int H, int J, int V, int S,
+                                    int Tc, int K, int N, int joint_dtype, void *workspace, hipStream_t s);
+hipError_t launch_beam_stream_feed(const float *enc, int Te, const int *chunk_frames, const int *reset, const int *final_, int H, int J,
+                                   int V, int S, int Tc, int K, int N, int joint_dtype, void *workspace, hipStream_t s);
 // prednet_kernels.hip (the prediction-network step of the decoders)
 bool prednet_layout_ok(const rnntPrednetBlock *blocks, int L, int E, int V, int Jp, int R, size_t *bytes);
 hipError_t launch_prednet_begin(const float *emb, const rnntPrednetBlock *blocks, int L, int E, int V, const float *W1, int Jp, int R,
@@ -612,7 +617,7 @@ rnntStatus_t compute_rnnt_beam_step(const float *pred_proj, int *parents, int *e
     const rnntStatus_t st = check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
     return from_hip(launch_beam_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size,
-                                     minibatch, options.maxT, beam, options.blank_label, joint_dtype, workspace,
+                                     minibatch, options.maxT, beam, options.maxT, options.blank_label, joint_dtype, workspace,
                                      (hipStream_t)options.stream));
 }
 
@@ -621,8 +626,8 @@ rnntStatus_t compute_rnnt_beam_results(int *hyps, int *hyp_lengths, float *score
     if (!hyps || !hyp_lengths || !scores) return RNNT_STATUS_INVALID_VALUE;
     const rnntStatus_t st = check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
-    return from_hip(launch_beam_results(hyps, hyp_lengths, scores, joint_size, alphabet_size, minibatch, options.maxT, beam,
-                                       joint_dtype, workspace, (hipStream_t)options.stream));
+    return from_hip(launch_beam_results(hyps, hyp_lengths, scores, nullptr, joint_size, alphabet_size, minibatch, options.maxT, beam,
+                                       options.maxT, joint_dtype, workspace, (hipStream_t)options.stream));
 }
 
 
@@ -799,6 +804,84 @@ rnntStatus_t compute_rnnt_greedy_stream_feed(const float *enc, int enc_frames, c
     return from_hip(launch_greedy_stream_feed(enc, enc_frames, chunk_frames, reset, final_chunk, max_symbols, max_per_frame,
                                               hyp_lengths, scores, all_done, enc_width, joint_size, alphabet_size, slots, options.maxT,
                                               joint_dtype, workspace, (hipStream_t)options.stream));
+}
+
+// The beam stream (include/rnnt.h).  enc_width 1: step and results do not reach W1 / b1, which follow the beam workspace.
+static bool aligned4(const void *p) { return (((uintptr_t)p) & 3) == 0; }
+
+static rnntStatus_t check_beam_stream(int max_chunk_frames, int slots, int beam, int max_hyp_len, int enc_width, int joint_size,
+                                      int alphabet_size, int joint_dtype, const void *workspace, const rnntOptions &o) {
+    if (!workspace || ((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
+    if (beam < 1 || beam > 16 || slots < 1 || (long long)slots * beam > 1024 || max_hyp_len < 1) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_greedy(max_chunk_frames, joint_size, alphabet_size, slots, joint_dtype, o);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    size_t n = 0;
+    if (beam_stream_workspace_bytes(max_chunk_frames, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype,
+                                    &n) != hipSuccess)
+        return RNNT_STATUS_INVALID_VALUE;
+    return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t get_rnnt_beam_stream_workspace_size(int max_chunk_frames, int slots, int beam, int max_hyp_len, int enc_width,
+                                                 int joint_size, int alphabet_size, int joint_dtype, size_t *size_bytes) {
+    if (!size_bytes) return RNNT_STATUS_INVALID_VALUE;
+    if (joint_dtype != 0 && joint_dtype != 1) return RNNT_STATUS_INVALID_VALUE;
+    return beam_stream_workspace_bytes(max_chunk_frames, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype,
+                                       size_bytes) == hipSuccess
+               ? RNNT_STATUS_SUCCESS
+               : RNNT_STATUS_INVALID_VALUE;
+}
+
+rnntStatus_t compute_rnnt_beam_stream_begin(const float *W1, const float *b1, const float *W2, const float *b2, int enc_width,
+                                            int joint_size, int alphabet_size, int slots, int beam, int max_hyp_len, int joint_dtype,
+                                            void *workspace, rnntOptions options) {
+    if (!W1 || !b1 || !W2 || !b2 || !aligned4(W1) || !aligned4(b1) || !aligned4(W2) || !aligned4(b2)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_beam_stream(options.maxT, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype,
+                                              workspace, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_stream_begin(W1, b1, W2, b2, enc_width, joint_size, alphabet_size, slots, options.maxT, beam,
+                                             max_hyp_len, joint_dtype, workspace, (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_beam_stream_feed(const float *enc, int enc_frames, const int *chunk_frames, const int *reset,
+                                           const int *final_chunk, int enc_width, int joint_size, int alphabet_size, int slots,
+                                           int beam, int max_hyp_len, int joint_dtype, void *workspace, rnntOptions options) {
+    if (!chunk_frames || !aligned4(enc) || !aligned4(chunk_frames) || !aligned4(reset) || !aligned4(final_chunk))
+        return RNNT_STATUS_INVALID_VALUE;
+    if (enc_frames < 0 || enc_frames > options.maxT || (enc_frames > 0 && !enc)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_beam_stream(options.maxT, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype,
+                                              workspace, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_stream_feed(enc, enc_frames, chunk_frames, reset, final_chunk, enc_width, joint_size, alphabet_size,
+                                            slots, options.maxT, beam, max_hyp_len, joint_dtype, workspace,
+                                            (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_beam_stream_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits, int *topk_symbols,
+                                           float *lse, int joint_size, int alphabet_size, int slots, int beam, int max_hyp_len,
+                                           int joint_dtype, void *workspace, rnntOptions options) {
+    if (!pred_proj || !parents || !emitted) return RNNT_STATUS_INVALID_VALUE;
+    if (!aligned4(pred_proj) || !aligned4(parents) || !aligned4(emitted) || !aligned4(topk_logits) || !aligned4(topk_symbols) ||
+        !aligned4(lse))
+        return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st =
+        check_beam_stream(options.maxT, slots, beam, max_hyp_len, 1, joint_size, alphabet_size, joint_dtype, workspace, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, slots,
+                                     options.maxT, beam, max_hyp_len, options.blank_label, joint_dtype, workspace,
+                                     (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_beam_stream_results(int *hyps, int *hyp_lengths, float *scores, int *stable_lengths, int joint_size,
+                                              int alphabet_size, int slots, int beam, int max_hyp_len, int joint_dtype,
+                                              void *workspace, rnntOptions options) {
+    if (!hyps || !hyp_lengths || !scores) return RNNT_STATUS_INVALID_VALUE;
+    if (!aligned4(hyps) || !aligned4(hyp_lengths) || !aligned4(scores) || !aligned4(stable_lengths)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st =
+        check_beam_stream(options.maxT, slots, beam, max_hyp_len, 1, joint_size, alphabet_size, joint_dtype, workspace, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_results(hyps, hyp_lengths, scores, stable_lengths, joint_size, alphabet_size, slots, options.maxT, beam,
+                                        max_hyp_len, joint_dtype, workspace, (hipStream_t)options.stream));
 }
 
 // The LSTM layer for training (include/rnnt.h).  Everything is checked before anything is enqueued.

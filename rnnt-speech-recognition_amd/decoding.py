@@ -23,7 +23,7 @@ from typing import List, Optional
 
 import torch
 
-from .joint import BeamJoint, EncoderStream, GreedyJoint, GreedyStreamJoint, PredictionStep
+from .joint import BeamJoint, BeamStreamJoint, EncoderStream, GreedyJoint, GreedyStreamJoint, PredictionStep
 from .loss import reduced_lengths
 
 
@@ -358,42 +358,16 @@ def beam_decode_batch_fn(model, beam: int = 4, prediction: str = "torch", encode
 # ---------------------------------------------------------------------------------------------------------------------------
 # Streaming greedy decoding
 # ---------------------------------------------------------------------------------------------------------------------------
-class StreamingGreedyDecoder:
-    """Greedy decoding of up to `slots` live audio streams at once, fed chunk by chunk (include/rnnt.h, streaming greedy
-    decoding).  Each slot holds one stream at a time; streams start and end at different times.
+class _StreamingSlots:
+    """What the streaming decoders share: the slots' encoder stream, the slot masks of start() and the argument checks of feed()."""
 
-    start(slots) (re)starts a stream in the given slots (indices, or a bool mask [slots]): zero encoder state, the prediction
-    network's start token 0 from zero state, no symbols, score 0, frame 0.  The other slots are untouched.
-
-    feed(mel_chunk [slots, Tc, F], frames [slots], final [slots]) -> (ids int32 [slots, N] zero-padded, counts int32 [slots]),
-    on the model's device: the symbols each stream emitted in this call.  Slot s consumes mel_chunk[s, :frames[s]] (stacked
-    log-mel rows, what model.Encoder takes); a slot with 0 frames and final False is left as it was.  In a non-final feed,
-    frames[s] must be a multiple of the encoder's reduction factor f; a final feed may have any length (its odd tail is
-    zero-padded after the LayerNorm, as one run over the whole input pads it).  frames and final are host data (lists, arrays
-    or CPU tensors).  Greedy search runs with greedy_decode_batch's per-frame semantics until every live slot has consumed
-    all encoder frames it has so far.  After its final feed, or once its max_length symbols are spent, a slot is finished: it
-    emits nothing more until the next start.
-
-    hypotheses() -> (ids [slots, N] zero-padded, lengths [slots], scores [slots]) of each slot's stream since its start.
-
-    A stream delivered through any chunking that follows the rule above, in any slot, beside any other traffic, ends with the
-    ids, length and score of the same stream fed in one call to a 1-slot decoder: bitwise on an MI355X (every kernel on the path
-    sums in a fixed order that depends on the shapes alone), and equal ids to greedy_decode_batch of the stream alone.
-
-    On an MI355X the encoder (EncoderStream, compute_rnnt_encoder_run_rows), the prediction network (PredictionStep) and the
-    joint (GreedyStreamJoint) run in the library, and a feed reads the host only for the all-done word every `check_every`
-    steps and once for N.  On CPU, or for models and shapes the kernels do not take, the same state machine runs in torch, with
-    the fallback rules of those three classes."""
-
-    def __init__(self, model, slots: int, max_chunk_frames: int, max_length: Optional[int] = None,
-                 max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY):
+    def _init_slots(self, model, slots: int, max_chunk_frames: int) -> None:
         S, Tc = int(slots), int(max_chunk_frames)
         if not 1 <= S <= EncoderStream.MAX_ROWS:
             raise ValueError(f"slots must be in 1 ... {EncoderStream.MAX_ROWS}, got {slots}")
         if Tc < 1:
             raise ValueError(f"max_chunk_frames must be >= 1, got {max_chunk_frames}")
-        self.model, self.S, self.Tc, self.check_every = model, S, Tc, max(1, int(check_every))
-        self.max_length = None if max_length is None else int(max_length)
+        self.model, self.S, self.Tc = model, S, Tc
         enc = model.encoder
         self.f = int(enc.reduce.factor)
         self.F = int(enc.input_norm.num_features)
@@ -403,14 +377,6 @@ class StreamingGreedyDecoder:
         with self._eval():
             self.es = EncoderStream(enc)
             self.es.begin(S, Tc)
-            self.gj = GreedyStreamJoint(model.joint)
-            dev = next(model.parameters()).device
-            N = max(1, self.max_length) if self.max_length is not None else self.Te + 16
-            self.gj.begin(S, self.Te, int(max_symbols_per_frame or 0), N, device=dev)
-            W1 = self.gj.W1 if self.gj.engine else model.joint.W1
-            self.ps = PredictionStep(model.prediction, W1)
-            self.pp = self.ps.begin(S)
-        self.dev = self.gj.hyps.device
         self._pending = [False] * S  # encoder resets waiting for the next run
 
     class _EvalMode:
@@ -440,19 +406,8 @@ class StreamingGreedyDecoder:
             m[int(s)] = True
         return m
 
-    @torch.no_grad()
-    def start(self, slots) -> None:
-        m = self._mask(slots)
-        if not any(m):
-            return
-        with self._eval():
-            self.pp = self.ps.reset(m)
-            ms = None if self.max_length is None else [self.max_length] * self.S
-            self.gj.feed(None, [0] * self.S, reset=m, final=None, max_symbols=ms)
-        self._pending = [p or q for p, q in zip(self._pending, m)]
-
-    @torch.no_grad()
-    def feed(self, mel_chunk: torch.Tensor, frames, final):
+    def _check_feed(self, mel_chunk, frames, final):
+        """feed()'s arguments -> (frames, final) as host lists of ints / bools."""
         S, f = self.S, self.f
         if mel_chunk.dim() != 3 or mel_chunk.shape[0] != S or mel_chunk.shape[2] != self.F:
             raise ValueError(f"mel_chunk must be [{S}, frames, {self.F}], got {tuple(mel_chunk.shape)}")
@@ -468,13 +423,80 @@ class StreamingGreedyDecoder:
                 raise ValueError(f"frames[{s}] = {fr[s]} is not in 0 ... {Tc}")
             if not fi[s] and fr[s] % f != 0:
                 raise ValueError(f"frames[{s}] = {fr[s]}: a non-final feed must bring a multiple of the reduction factor {f}")
+        return fr, fi
+
+    def _encode_chunk(self, mel_chunk, fr):
+        """The encoder over every slot's new frames (inside _eval()) -> enc [slots, ceil(max(fr) / f), H], or None without frames."""
+        T = max(fr)
+        if T == 0:
+            return None
+        reset = self._pending if any(self._pending) else None
+        enc = self.es.run(mel_chunk[:, :T], row_frames=fr, reset=reset)
+        self._pending = [False] * self.S
+        return enc
+
+
+class StreamingGreedyDecoder(_StreamingSlots):
+    """Greedy decoding of up to `slots` live audio streams at once, fed chunk by chunk (include/rnnt.h, streaming greedy
+    decoding).  Each slot holds one stream at a time; streams start and end at different times.
+
+    start(slots) (re)starts a stream in the given slots (indices, or a bool mask [slots]): zero encoder state, the prediction
+    network's start token 0 from zero state, no symbols, score 0, frame 0.  The other slots are untouched.
+
+    feed(mel_chunk [slots, Tc, F], frames [slots], final [slots]) -> (ids int32 [slots, N] zero-padded, counts int32 [slots]),
+    on the model's device: the symbols each stream emitted in this call.  Slot s consumes mel_chunk[s, :frames[s]] (stacked
+    log-mel rows, what model.Encoder takes); a slot with 0 frames and final False is left as it was.  In a non-final feed,
+    frames[s] must be a multiple of the encoder's reduction factor f; a final feed may have any length (its odd tail is
+    zero-padded after the LayerNorm, as one run over the whole input pads it).  frames and final are host data (lists, arrays
+    or CPU tensors).  Greedy search runs with greedy_decode_batch's per-frame semantics until every live slot has consumed
+    all encoder frames it has so far.  After its final feed, or once its max_length symbols are spent, a slot is finished: it
+    emits nothing more until the next start.
+
+    hypotheses() -> (ids [slots, N] zero-padded, lengths [slots], scores [slots]) of each slot's stream since its start.
+
+    A stream delivered through any chunking that follows the rule above, in any slot, beside any other traffic, ends with the
+    ids, length and score of the same stream fed in one call to a 1-slot decoder: bitwise on an MI355X (every kernel on the path
+    sums in a fixed order that depends on the shapes alone), and equal ids to greedy_decode_batch of the stream alone.
+
+    On an MI355X the encoder (EncoderStream, compute_rnnt_encoder_run_rows), the prediction network (PredictionStep) and the
+    joint (GreedyStreamJoint) run in the library, and a feed reads the host only for the all-done word every `check_every`
+    steps and once for N.  On CPU, or for models and shapes the kernels do not take, the same state machine runs in torch, with
+    the fallback rules of those three classes."""
+
+    def __init__(self, model, slots: int, max_chunk_frames: int, max_length: Optional[int] = None,
+                 max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY):
+        self._init_slots(model, slots, max_chunk_frames)
+        S = self.S
+        self.check_every = max(1, int(check_every))
+        self.max_length = None if max_length is None else int(max_length)
+        with self._eval():
+            self.gj = GreedyStreamJoint(model.joint)
+            dev = next(model.parameters()).device
+            N = max(1, self.max_length) if self.max_length is not None else self.Te + 16
+            self.gj.begin(S, self.Te, int(max_symbols_per_frame or 0), N, device=dev)
+            W1 = self.gj.W1 if self.gj.engine else model.joint.W1
+            self.ps = PredictionStep(model.prediction, W1)
+            self.pp = self.ps.begin(S)
+        self.dev = self.gj.hyps.device
+
+    @torch.no_grad()
+    def start(self, slots) -> None:
+        m = self._mask(slots)
+        if not any(m):
+            return
+        with self._eval():
+            self.pp = self.ps.reset(m)
+            ms = None if self.max_length is None else [self.max_length] * self.S
+            self.gj.feed(None, [0] * self.S, reset=m, final=None, max_symbols=ms)
+        self._pending = [p or q for p, q in zip(self._pending, m)]
+
+    @torch.no_grad()
+    def feed(self, mel_chunk: torch.Tensor, frames, final):
+        S, f = self.S, self.f
+        fr, fi = self._check_feed(mel_chunk, frames, final)
         T = max(fr)
         with self._eval():
-            enc = None
-            if T > 0:
-                reset = self._pending if any(self._pending) else None
-                enc = self.es.run(mel_chunk[:, :T], row_frames=fr, reset=reset)
-                self._pending = [False] * S
+            enc = self._encode_chunk(mel_chunk, fr)
             self.gj.feed(enc, [-(-v // f) for v in fr], reset=None, final=[int(v) for v in fi])
             before = self.gj.lengths.clone()
             if T > 0:
@@ -510,3 +532,104 @@ class StreamingGreedyDecoder:
         h, n = self.gj.hyps, self.gj.lengths
         ids = torch.where(torch.arange(h.shape[1], device=h.device)[None, :] < n[:, None], h, 0)
         return ids, n.clone(), self.gj.scores.clone()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Streaming beam search
+# ---------------------------------------------------------------------------------------------------------------------------
+class StreamingBeamDecoder(_StreamingSlots):
+    """Modified beam search (one symbol per frame, include/rnnt.h) of up to `slots` live audio streams at once, fed chunk by
+    chunk; the streaming counterpart of beam_decode_batch, with the slot handling of StreamingGreedyDecoder.
+
+    start(slots) (re)starts a stream in the given slots: zero encoder state, the beam [((), 0)], its `beam` prediction-network
+    rows from the start token.  The other slots are untouched.
+
+    feed(mel_chunk [slots, Tc, F], frames [slots], final [slots]) -> (ids int32 [slots, N] zero-padded, lengths int32 [slots],
+    stable int32 [slots]) on the model's device: the CURRENT BEST hypothesis of every slot and how much of it is final.  A later
+    frame may rewrite a beam's best hypothesis, so a feed returns the whole of it, not a delta; its first stable[s] tokens are
+    shared by every hypothesis of the beam and can no longer change.  frames and final follow StreamingGreedyDecoder.feed's rules
+    (host data; a non-final feed brings a multiple of the reduction factor; frames <= max_chunk_frames).  After its final feed a
+    slot is finished: further feeds leave it as it is until the next start.
+
+    hypotheses() -> the best (ids [slots, N], lengths [slots], scores [slots]); nbest() -> (ids [slots, beam, N], lengths
+    [slots, beam], scores [slots, beam]), best first (empty places: length 0, score -inf).
+
+    max_length is N, the tokens one stream's hypothesis may hold; the default is 512.  The search emits at most one token per
+    encoder frame, so no stream can reach 512 tokens in fewer than 512 encoder frames: 30.7 s of audio at the reference's 60 ms
+    encoder frame (10 ms step, downsample 3, time reduction 2).  Speech fills a small part of its frames with tokens, so 512
+    tokens are some minutes of it; how many depends on the vocabulary and is not measured here.  A hypothesis that holds N tokens
+    is NOT reported as full: it goes on through the later frames on blanks alone and emits nothing more, silently.  lengths[s] ==
+    N is the only sign; a caller that may meet it restarts the slot (start) or builds the decoder with a larger max_length.  The
+    workspace holds 2 slots beam N ints and every frame copies each surviving token row, so N costs memory and time.
+    slots * beam <= 1024 (the prediction network's rows).
+
+    A stream delivered through any chunking that follows the rule above, in any slot, beside any other traffic, ends with the
+    n-best (ids, lengths, scores) and stable of the same stream fed in one call to a 1-slot decoder: bitwise on an MI355X.  beam
+    = 1 gives the ids of StreamingGreedyDecoder with max_symbols_per_frame = 1.
+
+    On an MI355X the encoder (EncoderStream), the prediction network (PredictionStep) and the joint (BeamStreamJoint) run in the
+    library and a feed reads nothing from the host: a chunk of n encoder frames is exactly n steps.  On CPU, or for models and
+    shapes the kernels do not take, the same state machine runs in torch, with the fallback rules of those three classes."""
+
+    DEFAULT_MAX_LENGTH = 512
+
+    def __init__(self, model, slots: int, max_chunk_frames: int, beam: int = 4, max_length: Optional[int] = None):
+        K = int(beam)
+        if not 1 <= K <= 16:
+            raise ValueError(f"beam must be in 1 ... 16, got {beam}")
+        if int(slots) * K > BeamStreamJoint.MAX_ROWS:
+            raise ValueError(f"slots * beam must be in 1 ... {BeamStreamJoint.MAX_ROWS}, got {slots} * {beam}")
+        N = self.DEFAULT_MAX_LENGTH if max_length is None else int(max_length)
+        if N < 1:
+            raise ValueError(f"max_length must be >= 1, got {max_length}")
+        self._init_slots(model, slots, max_chunk_frames)
+        S = self.S
+        self.K, self.max_length = K, N
+        with self._eval():
+            self.bj = BeamStreamJoint(model.joint, K)
+            dev = next(model.parameters()).device
+            self.bj.begin(S, self.Te, N, device=dev)
+            W1 = self.bj.W1 if self.bj.engine else model.joint.W1
+            self.ps = PredictionStep(model.prediction, W1)
+            self.pp = self.ps.begin(S * K)
+        self.dev = self.bj.parents.device
+
+    @torch.no_grad()
+    def start(self, slots) -> None:
+        m = self._mask(slots)
+        if not any(m):
+            return
+        with self._eval():
+            self.pp = self.ps.reset([v for v in m for _ in range(self.K)])
+            self.bj.feed(None, [0] * self.S, reset=[int(v) for v in m], final=None)
+        self._pending = [p or q for p, q in zip(self._pending, m)]
+
+    @torch.no_grad()
+    def feed(self, mel_chunk: torch.Tensor, frames, final):
+        global LAST_STEPS
+        f = self.f
+        fr, fi = self._check_feed(mel_chunk, frames, final)
+        T = max(fr)
+        with self._eval():
+            enc = self._encode_chunk(mel_chunk, fr)
+            self.bj.feed(enc, [-(-v // f) for v in fr], reset=None, final=[int(v) for v in fi])
+            steps = -(-T // f)  # (host data: the search is frame-synchronous, so nothing is polled)
+            pp = self.pp
+            for _ in range(steps):
+                parents, emitted = self.bj.step(pred_proj=pp)
+                pp = self.ps.step(emitted, parents)  # (after the last frame too: the next feed goes on from it)
+            self.pp = pp
+            LAST_STEPS = steps
+            ids, lengths, _, stable = self.bj.results()
+        return ids[:, 0], lengths[:, 0], stable
+
+    def hypotheses(self):
+        """The best hypothesis of each slot's stream since its start: (ids int32 [slots, N] zero-padded, lengths int32 [slots],
+        scores [slots])."""
+        ids, lengths, scores, _ = self.bj.results()
+        return ids[:, 0], lengths[:, 0], scores[:, 0]
+
+    def nbest(self):
+        """(ids int32 [slots, beam, N] zero-padded, lengths int32 [slots, beam], scores [slots, beam]), best first."""
+        ids, lengths, scores, _ = self.bj.results()
+        return ids, lengths, scores

@@ -11,6 +11,7 @@ through torch.matmul + autograd around compute_rnnt_joint_loss_* (first_layer="t
 """
 from __future__ import annotations
 
+import ctypes
 import math
 
 import torch
@@ -710,38 +711,43 @@ class BeamJoint:
         top_l, top_v = torch.sort(logits, dim=-1, descending=True, stable=True)  # (logit descending, symbol ascending)
         top_l, top_v, lse = top_l[:, :K].tolist(), top_v[:, :K].tolist(), lse.tolist()
         for b in range(B):
-            if t >= self._Tb[b]:
-                continue
-            beam = self._beams[b]
-            cands = []
-            for i, (y, s) in enumerate(beam):
-                r = b * K + i
-                for l, v in zip(top_l[r], top_v[r]):
-                    sc = s + (float(l) - lse[r])
-                    if sc == sc and sc > -math.inf:
-                        cands.append((sc, i, v))
-            cands.sort(key=lambda c: (-c[0], c[1], c[2]))
-            taken = cands[:K]
-            if not taken:
-                continue  # the beam is carried over
-            merged = []  # [tokens, score, parent, emitted]
-            for sc, i, v in taken:
-                y = beam[i][0] if v == blank else beam[i][0] + (v,)
-                hit = next((m for m in merged if m[0] == y), None)
-                if hit is None:
-                    merged.append([y, sc, i, -1 if v == blank else v])
-                else:
-                    hi, lo = max(hit[1], sc), min(hit[1], sc)
-                    hit[1] = hi + math.log1p(math.exp(lo - hi))
-            merged.sort(key=lambda m: -m[1])  # (stable)
-            self._beams[b] = [(m[0], m[1]) for m in merged]
-            for k in range(K):
-                if k < len(merged):
-                    parents[b * K + k], emitted[b * K + k] = b * K + merged[k][2], merged[k][3]
+            if t < self._Tb[b]:
+                self._torch_rank(b, top_l, top_v, lse, parents, emitted)
         dev = self.parents.device
         self.parents = torch.tensor(parents, dtype=torch.int32, device=dev)
         self.emitted = torch.tensor(emitted, dtype=torch.int32, device=dev)
         return self.parents, self.emitted
+
+    def _torch_rank(self, b, top_l, top_v, lse, parents, emitted, blank_l=None, cap=None):
+        """One frame of beam b (rules 2 - 5 of include/rnnt.h) from every row's top-K lists and logsumexp; parents / emitted of
+        its rows are filled in.  cap (the stream): a hypothesis of cap tokens offers its blank candidate (logit blank_l[r]) alone."""
+        K, blank = self.K, self.blank
+        beam = self._beams[b]
+        cands = []
+        for i, (y, s) in enumerate(beam):
+            r = b * K + i
+            offers = zip(top_l[r], top_v[r]) if cap is None or len(y) < cap else [(blank_l[r], blank)]
+            for l, v in offers:
+                sc = s + (float(l) - lse[r])
+                if sc == sc and sc > -math.inf:
+                    cands.append((sc, i, v))
+        cands.sort(key=lambda c: (-c[0], c[1], c[2]))
+        taken = cands[:K]
+        if not taken:
+            return  # the beam is carried over
+        merged = []  # [tokens, score, parent, emitted]
+        for sc, i, v in taken:
+            y = beam[i][0] if v == blank else beam[i][0] + (v,)
+            hit = next((m for m in merged if m[0] == y), None)
+            if hit is None:
+                merged.append([y, sc, i, -1 if v == blank else v])
+            else:
+                hi, lo = max(hit[1], sc), min(hit[1], sc)
+                hit[1] = hi + math.log1p(math.exp(lo - hi))
+        merged.sort(key=lambda m: -m[1])  # (stable)
+        self._beams[b] = [(m[0], m[1]) for m in merged]
+        for k in range(len(merged)):
+            parents[b * K + k], emitted[b * K + k] = b * K + merged[k][2], merged[k][3]
 
     def _torch_results(self):
         B, K, T = self.B, self.K, self.T
@@ -754,6 +760,161 @@ class BeamJoint:
                 lengths[b, k], scores[b, k] = len(y), s
         dev = self.parents.device
         return hyps.to(dev), lengths.to(dev), scores.to(device=dev, dtype=self._sdtype)
+
+
+class BeamStreamJoint(BeamJoint):
+    """The joint of the streaming beam search (decoding.StreamingBeamDecoder): BeamJoint's step over `slots` streams whose encoder
+    frames arrive chunk by chunk, each slot keeping its beam from one feed to the next.
+
+    On an MI355X this is the ENGINE (include/rnnt.h compute_rnnt_beam_stream_begin / _feed / _step / _results): the object owns
+    the workspace and W1 / b1 go into it, so the encoder side's projection runs in the library with a fixed summation order.  CPU
+    tensors and shapes the kernels do not take run the same state machine in torch, the capacity rule and `stable` included:
+    the joint shapes GreedyJoint refuses, and what only the stream refuses at begin (an encoder width beyond 4096, or a workspace
+    beyond the library's 2^31 index limits: 2 slots beam max_hyp_len tokens, slots max_chunk_frames joint units).
+
+    begin(slots, max_chunk_frames (encoder frames per feed), max_hyp_len (the tokens a stream's hypothesis may hold)) leaves every
+    slot finished with an empty beam; feed(enc [slots, Te, H], frames [slots], reset, final) hands every slot its chunk (int
+    vectors, or None); then step(pred_proj=...) once per encoder frame of the longest chunk (host data: nothing is polled), each
+    followed by a prediction-network step -- after the last frame too.  results() -> (hyps [slots, beam, max_hyp_len] zero-padded,
+    lengths [slots, beam], scores [slots, beam], stable [slots]) at any time: stable = the common prefix of a slot's hypotheses,
+    the tokens no later frame can change."""
+
+    MAX_ROWS = 1024  # slots * beam: the prediction network's rows
+
+    def begin(self, slots: int, max_chunk_frames: int, max_hyp_len: int, device=None):
+        S, T, N, K = int(slots), int(max_chunk_frames), int(max_hyp_len), self.K
+        if S < 1 or S * K > self.MAX_ROWS:
+            raise ValueError(f"slots * beam must be in 1 ... {self.MAX_ROWS}, got {S} * {K}")
+        if T < 1 or N < 1:
+            raise ValueError("max_chunk_frames and max_hyp_len must be >= 1")
+        dev = self.W2.device if self.engine else (device if device is not None else self.joint.W2.device)
+        self.B, self.T, self.Tc, self.N = S, T, T, N
+        self.parents = torch.arange(S * K, dtype=torch.int32, device=dev)
+        self.emitted = torch.full((S * K,), -1, dtype=torch.int32, device=dev)
+        if self.engine:  # (the library's own answer: a size it refuses is a shape the stream kernels do not take)
+            n = ctypes.c_size_t(0)
+            self.engine = _lib.load().get_rnnt_beam_stream_workspace_size(T, S, K, N, int(self.W1.shape[0]), self.Jp, self.V,
+                                                                          self.dtype, ctypes.byref(n)) == _lib.STATUS_SUCCESS
+        if not self.engine:
+            self._beams = [[] for _ in range(S)]
+            self._fin, self._Tb, self._tc = [True] * S, [0] * S, [0] * S
+            self._enc = None
+            self._sdtype = torch.promote_types(self.joint.W2.dtype, torch.float32)
+            return
+        self.H = int(self.W1.shape[0])
+        with torch.cuda.device(dev):
+            nbytes = _lib.beam_stream_workspace_bytes(T, S, K, N, self.H, self.Jp, self.V, self.dtype)
+            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
+                self._ws = _new_workspace(nbytes, dev)
+            elif _WORKSPACE_FILL is not None:
+                self._ws.fill_(int(_WORKSPACE_FILL))
+            self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
+            st = _lib.load().compute_rnnt_beam_stream_begin(self.W1.data_ptr(), self.b1.data_ptr(), self.W2.data_ptr(),
+                                                            self.b2.data_ptr(), self.H, self.Jp, self.V, S, K, N, self.dtype,
+                                                            self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_beam_stream_begin")
+
+    def feed(self, enc, frames, reset=None, final=None):
+        """enc [slots, Te, H] (None or Te = 0: no frames), frames [slots] encoder frames per slot, reset / final [slots] or None."""
+        S = self.B
+        Te = 0 if enc is None else int(enc.shape[1])
+        if Te > self.Tc:
+            raise ValueError(f"a feed takes at most {self.Tc} encoder frames, got {Te}")
+        if not self.engine:
+            return self._torch_feed(enc, Te, frames, reset, final)
+        dev = self.parents.device
+        if Te > 0:
+            enc = _aligned16(enc.to(device=dev, dtype=torch.float32))
+            if tuple(enc.shape) != (S, Te, self.H):
+                raise ValueError(f"enc must be [{S}, frames, {self.H}], got {tuple(enc.shape)}")
+        cv = lambda x: None if x is None else _device_i32(x, dev).reshape(S)  # noqa: E731
+        fr, rs, fi = cv(frames), cv(reset), cv(final)
+        self._feed_args = (enc, fr, rs, fi)  # (alive until the launches have read them)
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        st = _lib.load().compute_rnnt_beam_stream_feed(ptr(enc) if Te > 0 else None, Te, fr.data_ptr(), ptr(rs), ptr(fi), self.H,
+                                                       self.Jp, self.V, S, self.K, self.N, self.dtype, self._ws.data_ptr(),
+                                                       self._opts)
+        _lib.check(st, "compute_rnnt_beam_stream_feed")
+
+    def step(self, pred=None, topk_logits=None, topk_symbols=None, lse=None, *, pred_proj=None):
+        """One frame of every slot that has one left -> (parents, emitted), int32 [slots beam]; as BeamJoint.step."""
+        if not self.engine:
+            return self._torch_step(pred, pred_proj)
+        pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _projected_operand(pred_proj, self.Jp)
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        st = _lib.load().compute_rnnt_beam_stream_step(pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(),
+                                                       ptr(topk_logits), ptr(topk_symbols), ptr(lse), self.Jp, self.V, self.B, self.K,
+                                                       self.N, self.dtype, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_beam_stream_step")
+        return self.parents, self.emitted
+
+    def results(self):
+        S, K, N = self.B, self.K, self.N
+        if not self.engine:
+            return self._torch_results()
+        dev = self.parents.device
+        hyps = torch.empty(S, K, N, dtype=torch.int32, device=dev)
+        lengths = torch.empty(S, K, dtype=torch.int32, device=dev)
+        scores = torch.empty(S, K, dtype=torch.float32, device=dev)
+        stable = torch.empty(S, dtype=torch.int32, device=dev)
+        st = _lib.load().compute_rnnt_beam_stream_results(hyps.data_ptr(), lengths.data_ptr(), scores.data_ptr(), stable.data_ptr(),
+                                                          self.Jp, self.V, S, K, N, self.dtype, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_beam_stream_results")
+        return hyps, lengths, scores, stable
+
+    # ---- torch composition: the same state machine (beam_stream_feed_kernel, beam_select_kernel, beam_results_kernel)
+    def _torch_feed(self, enc, Te, frames, reset, final):
+        S = self.B
+        vec = lambda x: [0] * S if x is None else [int(v) for v in torch.as_tensor(x).reshape(S).tolist()]  # noqa: E731
+        fr, rs, fi = vec(frames), vec(reset), vec(final)
+        for s in range(S):
+            if rs[s]:
+                self._beams[s], self._fin[s] = [((), 0.0)], False
+            self._tc[s] = 0
+            if self._fin[s]:
+                self._Tb[s] = 0
+            else:
+                self._Tb[s] = min(max(fr[s], 0), Te)
+                self._fin[s] = fi[s] != 0
+        self._enc = enc if Te > 0 else None
+
+    def _torch_step(self, pred, pred_proj=None):
+        S, K = self.B, self.K
+        parents, emitted = list(range(S * K)), [-1] * (S * K)
+        dev = self.parents.device
+        live = [s for s in range(S) if self._tc[s] < self._Tb[s]]
+        if live:
+            Te = self._enc.shape[1]
+            cur = torch.tensor([min(self._tc[s], Te - 1) for s in range(S)], device=self._enc.device)
+            e = self._enc[torch.arange(S, device=self._enc.device), cur]  # [S, H]
+            logits = _torch_cell_logits(self.joint, e.repeat_interleave(K, 0), pred, pred_proj)  # [S K, V]
+            lse = torch.logsumexp(logits, dim=-1).tolist()
+            top_l, top_v = torch.sort(logits, dim=-1, descending=True, stable=True)  # (logit descending, symbol ascending)
+            top_l, top_v, blank_l = top_l[:, :K].tolist(), top_v[:, :K].tolist(), logits[:, self.blank].tolist()
+            for s in live:
+                self._torch_rank(s, top_l, top_v, lse, parents, emitted, blank_l, self.N)
+                self._tc[s] += 1
+        self.parents = torch.tensor(parents, dtype=torch.int32, device=dev)
+        self.emitted = torch.tensor(emitted, dtype=torch.int32, device=dev)
+        return self.parents, self.emitted
+
+    def _torch_results(self):
+        S, K, N = self.B, self.K, self.N
+        hyps = torch.zeros(S, K, N, dtype=torch.int32)
+        lengths = torch.zeros(S, K, dtype=torch.int32)
+        scores = torch.full((S, K), -math.inf, dtype=torch.float64)
+        stable = torch.zeros(S, dtype=torch.int32)
+        for s, beam in enumerate(self._beams):
+            for k, (y, sc) in enumerate(beam):
+                hyps[s, k, : len(y)] = torch.tensor(y, dtype=torch.int32)
+                lengths[s, k], scores[s, k] = len(y), sc
+            if beam:
+                n = 0
+                while all(n < len(y) for y, _ in beam) and all(y[n] == beam[0][0][n] for y, _ in beam):
+                    n += 1
+                stable[s] = n
+        dev = self.parents.device
+        return hyps.to(dev), lengths.to(dev), scores.to(device=dev, dtype=self._sdtype), stable.to(dev)
 
 
 def _aligned16(x: torch.Tensor) -> torch.Tensor:
