@@ -743,6 +743,61 @@ RNNT_API rnntStatus_t compute_rnnt_lstm_train_bwd(float *gates, const float *c, 
                                                   const float *W_hr, float *dr, int rows, int frames, int hidden, int proj,
                                                   void *workspace, rnntOptions options);
 
+/* Build-only extension: the STREAMING LOG-MEL FRONT END over S slots (1 <= S <= 1024): raw audio chunks in, stacked log-mel rows
+ * out -- what compute_rnnt_encoder_run_rows and the streaming decoders take -- with the state of every stream kept in the
+ * workspace.  The spectral definitions are those of tf.signal.stft / linear_to_mel_weight_matrix as the offline front end
+ * restates them: L = frame_len samples per frame, frame_step <= L samples between frames, nfft = the next power of two >= L
+ * (256, 512, 1024 or 2048), magnitude of the one-sided spectrum, mel = |X| @ mel_weights summed per filter over its band (first
+ * to last non-zero weight) in ascending bin order, x = log(mel + 1e-6) (the sum in float32; the log in float64, rounded once).
+ * stack = the frames side by side in one row (downsample_spec), row_multiple = the encoder's reduction factor, G = stack *
+ * row_multiple, M = mel_bins.
+ *
+ * State per slot: c < L carried samples, n frames made so far, the running per-bin sum m [M], h < G held frames, a finished flag.
+ * Feed of k new samples (0 <= k <= chunk_samples <= max_chunk_samples; samples[s] is clamped into that range) to a live slot:
+ *   avail = c + k;  nf = avail < L ? 0 : 1 + (avail - L) / frame_step;  c' = avail - nf frame_step
+ *   (frame i of a stream always covers its samples i frame_step ... i frame_step + L - 1)
+ *   each new frame, in stream order:  norm 0: y = x;   norm 1: n += 1; m += x; y = x - (m / n + 1e-8)   (float32, per bin)
+ *   not final:  (h + nf) / G * row_multiple rows leave, (h + nf) % G frames are held
+ *   final:      (h + nf) / stack rows leave; the other frames and the carried samples are dropped; the slot is FINISHED
+ * A finished slot ignores feeds (0 rows, nothing changes) until reset[s] != 0, which zeroes its state and makes it live BEFORE the
+ * call's samples are taken.  Row r of a slot is its frames r stack ... r stack + stack-1 side by side, [M * stack].
+ *
+ *   max_rows = (G - 1 + NF) / stack with NF = 1 + (max_chunk_samples - 1) / frame_step: a feed completes at most NF frames
+ *   (avail <= L - 1 + max_chunk_samples) beside at most G - 1 held ones.  row_counts are a function of the sample counts alone:
+ *   a caller mirrors them in integers and need never read them back.
+ *
+ *   window        device f32 [frame_len] (the periodic Hann window; formed in float64, rounded once)
+ *   mel_weights   device f32 [nfft / 2 + 1, mel_bins] (formed in float64, rounded once)
+ *   audio         device f32 [slots, chunk_samples], contiguous (NULL when chunk_samples is 0)
+ *   samples       device i32 [slots];  reset, final_chunk: device i32 [slots] or NULL (none)
+ *   rows_out      device f32 [slots, max_rows, mel_bins * stack]: rows past a slot's count are written as ZEROS
+ *   row_counts    device i32 [slots]
+ *   options       loc RNNT_GPU, stream; the other fields are not used
+ * compute_rnnt_frontend_begin copies the window, packs the mel matrix (transposed, with every filter's band) and the FFT's
+ * twiddles (float64, rounded once) into the workspace -- the caller may then free them -- and leaves every slot FINISHED.
+ * compute_rnnt_frontend_feed is two launches: the new frames of every slot (one wave per frame: gather, window, FFT in LDS,
+ * magnitude, band sum, log), then per slot the scan in stream order, the rows, the held frames and the new carry, which is
+ * written only there, after every frame has been read.
+ * Equivalence: every sum has an order fixed by the shapes alone, so a frame is bitwise independent of the chunking, the slot, S
+ * and the other slots' traffic: a stream fed through any chunks (zero-sample feeds and chunks shorter than a step included) gives
+ * bitwise the rows, in the same total number, of the same stream fed in one call to a 1-slot front end.
+ * Limits: 1 <= max_chunk_samples <= 2^20, 1 <= frame_step <= frame_len, 129 <= frame_len <= 2048, 1 <= mel_bins <= 1024,
+ * 1 <= stack, row_multiple <= 16, norm 0 or 1; anything else, chunk_samples outside 0 ... max_chunk_samples, a NULL (where not
+ * allowed above) or misaligned pointer (workspace: 256 bytes; every other: 4) or options.loc != RNNT_GPU:
+ * RNNT_STATUS_INVALID_VALUE, before anything is enqueued.  Workspace: get_rnnt_frontend_workspace_size(...) bytes, owned by the
+ * S streams from begin on.  No entry point synchronises the host. */
+RNNT_API rnntStatus_t get_rnnt_frontend_workspace_size(int max_chunk_samples, int slots, int frame_len, int frame_step,
+                                                       int mel_bins, int stack, int row_multiple, size_t *size_bytes);
+
+RNNT_API rnntStatus_t compute_rnnt_frontend_begin(const float *window, const float *mel_weights, int max_chunk_samples, int slots,
+                                                  int frame_len, int frame_step, int mel_bins, int stack, int row_multiple,
+                                                  void *workspace, rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_frontend_feed(const float *audio, int chunk_samples, const int *samples, const int *reset,
+                                                 const int *final_chunk, int norm, float *rows_out, int *row_counts,
+                                                 int max_chunk_samples, int slots, int frame_len, int frame_step, int mel_bins,
+                                                 int stack, int row_multiple, void *workspace, rnntOptions options);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,9 @@ SYMBOLS = [
     "compute_rnnt_beam_stream_feed",
     "compute_rnnt_beam_stream_step",
     "compute_rnnt_beam_stream_results",
+    "get_rnnt_frontend_workspace_size",
+    "compute_rnnt_frontend_begin",
+    "compute_rnnt_frontend_feed",
 ]
 
 
@@ -225,6 +228,13 @@ def load():
         lib.compute_rnnt_beam_stream_step.argtypes = [vp] * 6 + [ci] * 6 + [vp, rnntOptions]
         lib.compute_rnnt_beam_stream_results.restype = ci
         lib.compute_rnnt_beam_stream_results.argtypes = [vp] * 4 + [ci] * 6 + [vp, rnntOptions]
+    if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "compute_rnnt_frontend_feed"):
+        lib.get_rnnt_frontend_workspace_size.restype = ci
+        lib.get_rnnt_frontend_workspace_size.argtypes = [ci] * 7 + [ctypes.POINTER(ctypes.c_size_t)]
+        lib.compute_rnnt_frontend_begin.restype = ci
+        lib.compute_rnnt_frontend_begin.argtypes = [vp, vp] + [ci] * 7 + [vp, rnntOptions]
+        lib.compute_rnnt_frontend_feed.restype = ci
+        lib.compute_rnnt_frontend_feed.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp] + [ci] * 7 + [vp, rnntOptions]
     _lib = lib
     return lib
 
@@ -308,6 +318,14 @@ def beam_stream_workspace_bytes(max_chunk_frames: int, slots: int, beam: int, ma
     check(load().get_rnnt_beam_stream_workspace_size(max_chunk_frames, slots, beam, max_hyp_len, enc_width, joint_size,
                                                      alphabet_size, joint_dtype, ctypes.byref(n)),
           "get_rnnt_beam_stream_workspace_size")
+    return int(n.value)
+
+
+def frontend_workspace_bytes(max_chunk_samples: int, slots: int, frame_len: int, frame_step: int, mel_bins: int, stack: int,
+                             row_multiple: int) -> int:
+    n = ctypes.c_size_t(0)
+    check(load().get_rnnt_frontend_workspace_size(max_chunk_samples, slots, frame_len, frame_step, mel_bins, stack, row_multiple,
+                                                  ctypes.byref(n)), "get_rnnt_frontend_workspace_size")
     return int(n.value)
 
 

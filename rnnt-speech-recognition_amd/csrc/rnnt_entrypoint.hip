@@ -91,6 +91,13 @@ hipError_t launch_greedy_stream_begin(const float *W1, const float *b1, const fl
 hipError_t launch_greedy_stream_feed(const float *enc, int Te, const int *chunk_frames, const int *reset, const int *final_,
                                      const int *max_symbols, int max_per_frame, int *hyp_lengths, float *scores, int *all_done, int H,
                                      int J, int V, int S, int Tc, int joint_dtype, void *workspace, hipStream_t s);
+// frontend_kernels.hip (the streaming log-mel front end)
+bool frontend_layout_ok(int K, int S, int L, int step, int M, int stack, int rm, size_t *bytes, int *max_rows);
+hipError_t launch_frontend_begin(const float *window, const float *mel_weights, int K, int S, int L, int step, int M, int stack,
+                                 int rm, void *workspace, hipStream_t s);
+hipError_t launch_frontend_feed(const float *audio, int cs, const int *samples, const int *reset, const int *final_, int norm,
+                                float *rows, int *counts, int K, int S, int L, int step, int M, int stack, int rm, void *workspace,
+                                hipStream_t s);
 }  // namespace rnnt
 
 static rnntStatus_t check_options(const rnntOptions &o) {
@@ -917,6 +924,53 @@ rnntStatus_t compute_rnnt_lstm_train_bwd(float *gates, const float *c, const flo
     if (st != RNNT_STATUS_SUCCESS) return st;
     return from_hip(launch_lstm_train_bwd(gates, c, dy, W_hh, W_hr, dr, rows, frames, hidden, proj, workspace,
                                           (hipStream_t)options.stream));
+}
+
+// The streaming log-mel front end (include/rnnt.h).  Everything is checked before anything is enqueued.
+static rnntStatus_t check_frontend(int max_chunk_samples, int slots, int frame_len, int frame_step, int mel_bins, int stack,
+                                   int row_multiple, const void *workspace, const rnntOptions &o) {
+    if (!workspace || ((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
+    if (o.loc != RNNT_GPU) return RNNT_STATUS_INVALID_VALUE;
+    return frontend_layout_ok(max_chunk_samples, slots, frame_len, frame_step, mel_bins, stack, row_multiple, nullptr, nullptr)
+               ? RNNT_STATUS_SUCCESS
+               : RNNT_STATUS_INVALID_VALUE;
+}
+
+rnntStatus_t get_rnnt_frontend_workspace_size(int max_chunk_samples, int slots, int frame_len, int frame_step, int mel_bins,
+                                              int stack, int row_multiple, size_t *size_bytes) {
+    if (!size_bytes) return RNNT_STATUS_INVALID_VALUE;
+    return frontend_layout_ok(max_chunk_samples, slots, frame_len, frame_step, mel_bins, stack, row_multiple, size_bytes, nullptr)
+               ? RNNT_STATUS_SUCCESS
+               : RNNT_STATUS_INVALID_VALUE;
+}
+
+rnntStatus_t compute_rnnt_frontend_begin(const float *window, const float *mel_weights, int max_chunk_samples, int slots,
+                                         int frame_len, int frame_step, int mel_bins, int stack, int row_multiple, void *workspace,
+                                         rnntOptions options) {
+    if (!window || !mel_weights || !aligned4(window) || !aligned4(mel_weights)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st =
+        check_frontend(max_chunk_samples, slots, frame_len, frame_step, mel_bins, stack, row_multiple, workspace, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_frontend_begin(window, mel_weights, max_chunk_samples, slots, frame_len, frame_step, mel_bins, stack,
+                                          row_multiple, workspace, (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_frontend_feed(const float *audio, int chunk_samples, const int *samples, const int *reset,
+                                        const int *final_chunk, int norm, float *rows_out, int *row_counts, int max_chunk_samples,
+                                        int slots, int frame_len, int frame_step, int mel_bins, int stack, int row_multiple,
+                                        void *workspace, rnntOptions options) {
+    if (!samples || !rows_out || !row_counts) return RNNT_STATUS_INVALID_VALUE;
+    if (!aligned4(audio) || !aligned4(samples) || !aligned4(reset) || !aligned4(final_chunk) || !aligned4(rows_out) ||
+        !aligned4(row_counts))
+        return RNNT_STATUS_INVALID_VALUE;
+    if (chunk_samples < 0 || chunk_samples > max_chunk_samples || (chunk_samples > 0 && !audio)) return RNNT_STATUS_INVALID_VALUE;
+    if (norm != 0 && norm != 1) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st =
+        check_frontend(max_chunk_samples, slots, frame_len, frame_step, mel_bins, stack, row_multiple, workspace, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_frontend_feed(audio, chunk_samples, samples, reset, final_chunk, norm, rows_out, row_counts,
+                                         max_chunk_samples, slots, frame_len, frame_step, mel_bins, stack, row_multiple, workspace,
+                                         (hipStream_t)options.stream));
 }
 
 }  // extern "C"

@@ -633,3 +633,46 @@ class StreamingBeamDecoder(_StreamingSlots):
         """(ids int32 [slots, beam, N] zero-padded, lengths int32 [slots, beam], scores [slots, beam]), best first."""
         ids, lengths, scores, _ = self.bj.results()
         return ids, lengths, scores
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Streaming transcription from raw audio
+# ---------------------------------------------------------------------------------------------------------------------------
+class StreamingTranscriber:
+    """Raw audio in, hypotheses out, for up to `slots` live streams: a features.StreamingFrontEnd (its row_multiple the encoder's
+    reduction factor, so that every non-final feed hands the decoder a multiple of it) in front of a StreamingGreedyDecoder, or
+    of a StreamingBeamDecoder when `beam` is given.  The decoder is sized by the front end's max_rows; decoder_kwargs go to it
+    (max_length, max_symbols_per_frame, check_every for greedy; max_length for beam).
+
+    start(slots) starts a stream in the given slots of both; feed(audio [slots, N], samples [slots], final [slots]) (N <=
+    max_chunk_samples; samples and final are host data) returns what the decoder's feed returns for the rows this audio
+    completed; hypotheses() and nbest() (beam only) are the decoder's.  norm is the front end's: the default "running" subtracts
+    the mean of the frames so far, which is NOT the per-utterance mean the reference trains on -- train the model on
+    features.running_mean_log_mel for it.  A stream's result is bitwise independent of how its audio was chunked."""
+
+    def __init__(self, model, hp, sample_rate, slots: int, max_chunk_samples: int, beam: Optional[int] = None,
+                 norm: str = "running", **decoder_kwargs):
+        from .features import StreamingFrontEnd
+
+        dev = next(model.parameters()).device
+        self.front = StreamingFrontEnd(hp, sample_rate, slots, max_chunk_samples, int(model.encoder.reduce.factor), norm, device=dev)
+        if beam is None:
+            self.decoder = StreamingGreedyDecoder(model, slots, self.front.max_rows, **decoder_kwargs)
+        else:
+            self.decoder = StreamingBeamDecoder(model, slots, self.front.max_rows, beam=beam, **decoder_kwargs)
+
+    def start(self, slots) -> None:
+        self.front.start(slots)
+        self.decoder.start(slots)
+
+    def feed(self, audio: torch.Tensor, samples, final):
+        rows, counts = self.front.feed(audio, samples, final)
+        return self.decoder.feed(rows, counts, final)
+
+    def hypotheses(self):
+        return self.decoder.hypotheses()
+
+    def nbest(self):
+        if not hasattr(self.decoder, "nbest"):
+            raise RuntimeError("nbest() needs beam search: build the StreamingTranscriber with beam=")
+        return self.decoder.nbest()
