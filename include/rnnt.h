@@ -798,6 +798,61 @@ RNNT_API rnntStatus_t compute_rnnt_frontend_feed(const float *audio, int chunk_s
                                                  int max_chunk_samples, int slots, int frame_len, int frame_step, int mel_bins,
                                                  int stack, int row_multiple, void *workspace, rnntOptions options);
 
+/* ------------------------------------------------------------------------------------------
+ * Build-only extension (no upstream counterpart): FORCED ALIGNMENT -- the maximum-probability monotone path through the
+ * T x (U+1) lattice the loss sums over, and the frame at which it emits every label.
+ *
+ * Convention of compute_rnnt_loss: acts f32 [minibatch, maxT, maxU, alphabet_size] RAW LOGITS, maxU = longest label sequence + 1,
+ * T_b = input_lengths[b], U_b = label_lengths[b], flat_labels [minibatch, maxU-1], blank = options.blank_label.  Per utterance:
+ *   lpb[t,u] = log_softmax(acts[b,t,u,:])[blank]
+ *   lpl[t,u] = log_softmax(acts[b,t,u,:])[label_b[u]]            u < U_b
+ *   v(0,0)   = 0
+ *   v(t,u)   = max( v(t-1,u) + lpb[t-1,u] , v(t,u-1) + lpl[t,u-1] )
+ *   score_b  = v(T_b-1, U_b) + lpb[T_b-1, U_b]
+ * Tie rule (part of the contract): a cell with two predecessors takes the label arrival, from (t, u-1), only if its value is
+ * STRICTLY greater; on an exact tie it takes the blank arrival, from (t-1, u).  A cell with one predecessor takes that one.
+ * Outputs, from the back-trace that starts at (T_b-1, U_b):
+ *   token_frames  device i32 [minibatch, maxU-1]  the frame t at which label u is emitted on the best path; -1 for u >= U_b.
+ *                                                 Non-decreasing in u; several labels may share a frame.
+ *   token_logp    device f32 [minibatch, maxU-1]  lpl[token_frames[b,u], u], the per-token confidence; 0 for u >= U_b
+ *   scores        device f32 [minibatch]          the best path's log-probability (natural log)
+ * U_b = 0 is valid: the path is all blanks, every token_frames entry is -1.  Out-of-range lengths (T_b < 1, T_b > maxT, U_b < 0,
+ * U_b > maxU-1) are device data, as in the op: they are clamped into the tensor and THAT utterance comes back with a NaN score,
+ * -1 frames and 0 confidences; nothing else in the batch is affected.  Labels outside [0, alphabet_size) are clamped into range.
+ * Arithmetic: the normaliser of every cell in float32 from the float32 logits (running max / sum of exponentials); the sweep
+ * carries v in float64, so the T_b + U_b additions along a path add no error of their own.  Every sum has an order fixed by the
+ * shapes alone (the normaliser's by alphabet_size, the sweep's by the utterance's own cells): an utterance's three outputs are
+ * BITWISE independent of the rest of the batch, of minibatch and of how the frames were cut into slabs.  Cells outside an
+ * utterance's T_b x (U_b+1) lattice are neither read from acts nor from the workspace.
+ *
+ *   get_rnnt_align_workspace_size  bytes for (maxT, maxU, minibatch): two f32 per lattice cell on a row stride of maxU rounded up
+ *                                  to the sweep's width (64 x columns per lane; 1024 x columns per thread above 1024 columns), one
+ *                                  decision BIT per cell.  Never depends on alphabet_size.
+ *   compute_rnnt_align_cells       acts_slab f32 [minibatch, slab_frames, maxU, alphabet_size] = the logits of frames
+ *                                  frame_offset ... frame_offset + slab_frames - 1 of every utterance: writes their lpb / lpl
+ *                                  into the workspace.  A caller that produces logits slab by slab (alphabet_size 4096) never
+ *                                  holds [B, T, U, V]: it reduces each slab to two floats per cell and reuses the slab buffer.
+ *   compute_rnnt_align_path        the sweep and the back-trace on what a sequence of _cells calls covering frames 0 ... maxT-1
+ *                                  (in any order, any slab sizes) has left in the workspace.
+ *   compute_rnnt_align             = _cells on the whole tensor (slab_frames = maxT, frame_offset 0) followed by _path.
+ * Domain: the op's -- maxU <= 8192, minibatch * maxT * maxU < 2^31, any alphabet_size >= 2, 0 <= blank_label < alphabet_size,
+ * options.loc == RNNT_GPU, batch_first; 1 <= slab_frames, 0 <= frame_offset, frame_offset + slab_frames <= maxT.  Pointers:
+ * none may be NULL; workspace 256-byte aligned, every other 4-byte aligned (acts_slab 16-byte aligned with alphabet_size a
+ * multiple of 4 takes the wide loads; results do not depend on it).  Anything else: RNNT_STATUS_INVALID_VALUE before anything is
+ * enqueued.  No entry point synchronises the host. */
+RNNT_API rnntStatus_t get_rnnt_align_workspace_size(int maxT, int maxU, int minibatch, size_t *size_bytes);
+
+RNNT_API rnntStatus_t compute_rnnt_align_cells(const float *acts_slab, int slab_frames, int frame_offset, const int *flat_labels,
+                                               const int *label_lengths, const int *input_lengths, int alphabet_size,
+                                               int minibatch, void *workspace, rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_align_path(int *token_frames, float *token_logp, float *scores, const int *label_lengths,
+                                              const int *input_lengths, int minibatch, void *workspace, rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_align(const float *acts, const int *flat_labels, const int *label_lengths,
+                                         const int *input_lengths, int alphabet_size, int minibatch, int *token_frames,
+                                         float *token_logp, float *scores, void *workspace, rnntOptions options);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,10 @@ SYMBOLS = [
     "get_rnnt_frontend_workspace_size",
     "compute_rnnt_frontend_begin",
     "compute_rnnt_frontend_feed",
+    "get_rnnt_align_workspace_size",
+    "compute_rnnt_align_cells",
+    "compute_rnnt_align_path",
+    "compute_rnnt_align",
 ]
 
 
@@ -235,6 +239,15 @@ def load():
         lib.compute_rnnt_frontend_begin.argtypes = [vp, vp] + [ci] * 7 + [vp, rnntOptions]
         lib.compute_rnnt_frontend_feed.restype = ci
         lib.compute_rnnt_frontend_feed.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp] + [ci] * 7 + [vp, rnntOptions]
+    if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "compute_rnnt_align"):
+        lib.get_rnnt_align_workspace_size.restype = ci
+        lib.get_rnnt_align_workspace_size.argtypes = [ci, ci, ci, ctypes.POINTER(ctypes.c_size_t)]
+        lib.compute_rnnt_align_cells.restype = ci
+        lib.compute_rnnt_align_cells.argtypes = [vp, ci, ci, vp, vp, vp, ci, ci, vp, rnntOptions]
+        lib.compute_rnnt_align_path.restype = ci
+        lib.compute_rnnt_align_path.argtypes = [vp, vp, vp, vp, vp, ci, vp, rnntOptions]
+        lib.compute_rnnt_align.restype = ci
+        lib.compute_rnnt_align.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, rnntOptions]
     _lib = lib
     return lib
 
@@ -326,6 +339,12 @@ def frontend_workspace_bytes(max_chunk_samples: int, slots: int, frame_len: int,
     n = ctypes.c_size_t(0)
     check(load().get_rnnt_frontend_workspace_size(max_chunk_samples, slots, frame_len, frame_step, mel_bins, stack, row_multiple,
                                                   ctypes.byref(n)), "get_rnnt_frontend_workspace_size")
+    return int(n.value)
+
+
+def align_workspace_bytes(maxT: int, maxU: int, minibatch: int) -> int:
+    n = ctypes.c_size_t(0)
+    check(load().get_rnnt_align_workspace_size(maxT, maxU, minibatch, ctypes.byref(n)), "get_rnnt_align_workspace_size")
     return int(n.value)
 
 

@@ -15,7 +15,7 @@ LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libwarprnnt.so")
 SOURCES = ["rnnt_kernels.hip", "rnnt_lin_kernels.hip", "joint_kernels.hip", "joint_f16_kernels.hip", "dense_kernels.hip", "greedy_kernels.hip",
            "beam_kernels.hip", "prednet_kernels.hip", "encoder_kernels.hip", "lstm_train_kernels.hip", "frontend_kernels.hip",
-           "rnnt_entrypoint.hip"]
+           "align_kernels.hip", "rnnt_entrypoint.hip"]
 # -fvisibility=hidden: the library exports exactly the entry points include/rnnt.h marks RNNT_API (tests/test_abi.py)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-inline-asm"]
 # per-source extras.  -fno-slp-vectorize: no packed-f32 instructions (v_pk_fma_f32 ...) from the compiler -- in the linear sweeps

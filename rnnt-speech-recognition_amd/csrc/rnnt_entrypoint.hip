@@ -7,6 +7,7 @@
 #include "../../include/rnnt.h"
 #include "rnnt_common.h"
 #include "rnnt_lin.h"
+#include "rnnt_align.h"
 
 using namespace rnnt;
 
@@ -971,6 +972,83 @@ rnntStatus_t compute_rnnt_frontend_feed(const float *audio, int chunk_samples, c
     return from_hip(launch_frontend_feed(audio, chunk_samples, samples, reset, final_chunk, norm, rows_out, row_counts,
                                          max_chunk_samples, slots, frame_len, frame_step, mel_bins, stack, row_multiple, workspace,
                                          (hipStream_t)options.stream));
+}
+
+// Forced alignment (include/rnnt.h).  Everything is checked before anything is enqueued.
+static rnntStatus_t check_align(const void *labels, const void *ll, const void *il, const void *ws, int V, int B,
+                                const rnntOptions &o) {
+    if (!labels || !ll || !il || !ws) return RNNT_STATUS_INVALID_VALUE;
+    if (V < 2 || B <= 0) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_options(o);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (o.blank_label >= V) return RNNT_STATUS_INVALID_VALUE;
+    const long long cells = (long long)B * o.maxT * o.maxU;
+    if (cells >= (1ll << 31)) return RNNT_STATUS_INVALID_VALUE;
+    if (((uintptr_t)ws & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
+    if (!aligned4(labels) || !aligned4(ll) || !aligned4(il)) return RNNT_STATUS_INVALID_VALUE;
+    return RNNT_STATUS_SUCCESS;
+}
+
+static void fill_align(AlignParams &p, const int *labels, const int *ll, const int *il, int V, int B, void *ws,
+                       const rnntOptions &o) {
+    const AlignLayout w = make_align_layout(o.maxT, o.maxU, B);
+    p = AlignParams{};
+    p.labels = labels, p.label_lengths = ll, p.input_lengths = il;
+    p.cells = (float2 *)((char *)ws + w.cells);
+    p.bits = (uint32_t *)((char *)ws + w.bits);
+    p.B = B, p.T = o.maxT, p.U = o.maxU, p.V = V, p.blank = o.blank_label;
+    p.Up = w.Up, p.NB = w.NB;
+    p.divU = make_fastdiv((uint32_t)o.maxU);
+}
+
+rnntStatus_t get_rnnt_align_workspace_size(int maxT, int maxU, int minibatch, size_t *size_bytes) {
+    if (!size_bytes || maxT <= 0 || maxU <= 0 || maxU > kMaxU || minibatch <= 0) return RNNT_STATUS_INVALID_VALUE;
+    if ((long long)minibatch * maxT * maxU >= (1ll << 31)) return RNNT_STATUS_INVALID_VALUE;
+    *size_bytes = make_align_layout(maxT, maxU, minibatch).total;
+    return RNNT_STATUS_SUCCESS;
+}
+
+rnntStatus_t compute_rnnt_align_cells(const float *acts_slab, int slab_frames, int frame_offset, const int *flat_labels,
+                                      const int *label_lengths, const int *input_lengths, int alphabet_size, int minibatch,
+                                      void *workspace, rnntOptions options) {
+    if (!acts_slab || !aligned4(acts_slab)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_align(flat_labels, label_lengths, input_lengths, workspace, alphabet_size, minibatch, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (slab_frames < 1 || frame_offset < 0 || (long long)frame_offset + slab_frames > options.maxT) return RNNT_STATUS_INVALID_VALUE;
+    AlignParams p;
+    fill_align(p, flat_labels, label_lengths, input_lengths, alphabet_size, minibatch, workspace, options);
+    p.acts = acts_slab, p.S = slab_frames, p.t0 = frame_offset;
+    p.divS = make_fastdiv((uint32_t)slab_frames);
+    return from_hip(launch_align_cells(p, (hipStream_t)options.stream));
+}
+
+// alphabet_size does not enter the sweep; the entry point takes none
+rnntStatus_t compute_rnnt_align_path(int *token_frames, float *token_logp, float *scores, const int *label_lengths,
+                                     const int *input_lengths, int minibatch, void *workspace, rnntOptions options) {
+    if (!token_frames || !token_logp || !scores || !aligned4(token_frames) || !aligned4(token_logp) || !aligned4(scores))
+        return RNNT_STATUS_INVALID_VALUE;
+    // (the blank's range was checked against the vocabulary by the _cells calls that filled the workspace)
+    const rnntStatus_t st =
+        check_align(label_lengths, label_lengths, input_lengths, workspace, options.blank_label + 2, minibatch, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    AlignParams p;
+    fill_align(p, nullptr, label_lengths, input_lengths, 0, minibatch, workspace, options);
+    p.token_frames = token_frames, p.token_logp = token_logp, p.scores = scores;
+    return from_hip(launch_align_path(p, (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_align(const float *acts, const int *flat_labels, const int *label_lengths, const int *input_lengths,
+                                int alphabet_size, int minibatch, int *token_frames, float *token_logp, float *scores,
+                                void *workspace, rnntOptions options) {
+    if (!acts || !aligned4(acts)) return RNNT_STATUS_INVALID_VALUE;
+    if (!token_frames || !token_logp || !scores || !aligned4(token_frames) || !aligned4(token_logp) || !aligned4(scores))
+        return RNNT_STATUS_INVALID_VALUE;
+    rnntStatus_t st = check_align(flat_labels, label_lengths, input_lengths, workspace, alphabet_size, minibatch, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    st = compute_rnnt_align_cells(acts, options.maxT, 0, flat_labels, label_lengths, input_lengths, alphabet_size, minibatch,
+                                  workspace, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return compute_rnnt_align_path(token_frames, token_logp, scores, label_lengths, input_lengths, minibatch, workspace, options);
 }
 
 }  // extern "C"

@@ -251,6 +251,16 @@ class Transducer(nn.Module):
         enc, pred = self(mel_specs, pred_inp)
         return self.joint.logits(enc, pred)
 
+    @torch.no_grad()
+    def align(self, mel_specs, pred_inp, spec_lengths, label_lengths, labels, slab_frames=None):
+        """Forced alignment of `labels` with the loss's argument set: (token_frames, token_logp, scores) of alignment.align_joint,
+        frames counted after the encoder's time reduction (alignment.token_times turns them into seconds)."""
+        from .alignment import align_joint
+
+        enc, pred = self(mel_specs, pred_inp)
+        t_len = reduced_lengths(spec_lengths, self.hp.time_reduction_factor)
+        return align_joint(self.joint, enc, pred, labels, t_len, label_lengths, slab_frames=slab_frames)
+
 
 def save_weights(model: nn.Module, path: str) -> None:
     """Weights-only checkpoint, like model.save_weights (run_rnnt.py:326-329): no optimizer state, step or RNG."""
