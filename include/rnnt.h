@@ -698,6 +698,97 @@ RNNT_API rnntStatus_t compute_rnnt_beam_stream_results(int *hyps, int *hyp_lengt
                                                        int joint_size, int alphabet_size, int slots, int beam, int max_hyp_len,
                                                        int joint_dtype, void *workspace, rnntOptions options);
 
+/* Build-only extension: PER-TOKEN EMISSION FRAMES AND LOG-PROBABILITIES from the four decoders above ("timed" decoding).  New
+ * entry points only: every function above keeps its signature, its results bit for bit and what its size query returns; the
+ * timed calls compute ids, lengths and scores bitwise equal to the untimed ones.  joint_dtype carries no flag bits here either.
+ *
+ * Definitions.
+ *   emission frame of a token  the 0-based encoder frame t whose joint evaluation made the decision that appended the token
+ *                    (token_frames of compute_rnnt_align has the same convention).  Offline t counts from the utterance's first
+ *                    frame; on a stream it counts from the slot's reset, across every chunk fed since.
+ *   log-probability of a token (double)logit[v] - lse of that decision -- the float64 term the decision added to the hypothesis
+ *                    score -- rounded once to f32.
+ *   beam merges      when rule 4 of compute_rnnt_beam_step merges taken candidates with identical token sequences, the
+ *                    first-ranked survivor keeps ITS OWN frames and log-probabilities; the merged score stays the logaddexp of
+ *                    the members.  Frames and log-probabilities describe one path; the score may sum several.
+ *   timed stable length (beam stream)  the length of the longest prefix on which all occupied hypotheses of a slot agree in
+ *                    token AND in emission frame.  Every later hypothesis descends from one of the current ones and a merge
+ *                    keeps one member's rows, so nothing in this prefix, times included, can change any more.  It never exceeds
+ *                    stable_lengths, which compares tokens only.
+ *
+ * Greedy, batched and streaming (they share the step):
+ *   compute_rnnt_greedy_step_timed is compute_rnnt_greedy_step plus hyp_frames i32 [minibatch, max_hyp_len] and hyp_logp f32
+ *     [minibatch, max_hyp_len], caller-owned, append-only, written at the position of hyps[b, n_b] and nowhere else.  A caller that
+ *     grows hyps after all_done == 2 grows and copies all three buffers.  frame_base i32 [minibatch] or NULL (0): added to the
+ *     frame of every token of row b; the batched decoder passes NULL.  Timed and untimed steps may be mixed on one workspace.
+ *   compute_rnnt_greedy_stream_feed_timed is compute_rnnt_greedy_stream_feed plus frame_base i32 [slots], caller-owned state the
+ *     feed keeps: a reset sets frame_base[s] = 0, every other feed adds the frames of the chunk the slot had before this one.
+ *     Passed to compute_rnnt_greedy_step_timed, it makes the frames absolute since the slot's reset.  Its content means nothing
+ *     before a slot's first reset (the slot emits nothing then).  The workspace is that of
+ *     get_rnnt_greedy_stream_workspace_size, unchanged; a stream uses the timed feed for all its feeds or for none.
+ * Beam, batched: get_rnnt_beam_timed_workspace_size, compute_rnnt_beam_timed_begin / _step / _results are the untimed four on a
+ *   workspace that holds, beside the double-buffered token rows, a double-buffered row of {frame, log-probability} pairs (8
+ *   bytes per token) per hypothesis, gathered by parent exactly as the tokens.  _results adds hyp_frames i32 [minibatch, beam,
+ *   maxT] (padded with -1) and hyp_logp f32 [minibatch, beam, maxT] (padded with 0), as compute_rnnt_align pads them.
+ * Beam, streaming: get_rnnt_beam_stream_timed_workspace_size, compute_rnnt_beam_stream_timed_begin / _feed / _step / _results
+ *   likewise ([slots, beam, max_hyp_len]); _results also writes timed_stable_lengths i32 [slots] (NULL: not written).
+ *   A workspace is used by the timed calls or by the untimed ones, never both.
+ * Limits: the untimed beam workspace holds 2 S K N token words (2 S K N < 2^31); the timed one adds 4 S K N words, and
+ *   6 S K N < 2^31 is required (S = minibatch or slots, K = beam, N = maxT or max_hyp_len).
+ * Equivalence: the guarantee of the streams extends to hyp_frames, hyp_logp and timed_stable_lengths, bitwise.
+ * Validation as everywhere: a NULL (where not allowed) or misaligned pointer (workspace: 256 bytes; every other: 4), a shape
+ * outside the limits or flag bits in joint_dtype give RNNT_STATUS_INVALID_VALUE before anything is enqueued.  No entry point
+ * synchronises the host. */
+RNNT_API rnntStatus_t compute_rnnt_greedy_step_timed(const float *pred_proj, int *hyps, int *hyp_frames, float *hyp_logp,
+                                                     int max_hyp_len, int *hyp_lengths, float *scores, int *emitted, int *all_done,
+                                                     float *logit_stats, const int *frame_base, int joint_size, int alphabet_size,
+                                                     int minibatch, int joint_dtype, void *workspace, rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_greedy_stream_feed_timed(const float *enc, int enc_frames, const int *chunk_frames,
+                                                            const int *reset, const int *final_chunk, const int *max_symbols,
+                                                            int max_per_frame, int *hyp_lengths, float *scores, int *all_done,
+                                                            int *frame_base, int enc_width, int joint_size, int alphabet_size,
+                                                            int slots, int joint_dtype, void *workspace, rnntOptions options);
+
+RNNT_API rnntStatus_t get_rnnt_beam_timed_workspace_size(int maxT, int minibatch, int beam, int joint_size, int alphabet_size,
+                                                         int joint_dtype, size_t *size_bytes);
+
+RNNT_API rnntStatus_t compute_rnnt_beam_timed_begin(const float *enc_proj, const int *frame_lengths, const float *W2,
+                                                    const float *b2, int joint_size, int alphabet_size, int minibatch, int beam,
+                                                    int joint_dtype, void *workspace, rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_beam_timed_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits,
+                                                   int *topk_symbols, float *lse, int joint_size, int alphabet_size, int minibatch,
+                                                   int beam, int joint_dtype, void *workspace, rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_beam_timed_results(int *hyps, int *hyp_lengths, float *scores, int *hyp_frames, float *hyp_logp,
+                                                      int joint_size, int alphabet_size, int minibatch, int beam, int joint_dtype,
+                                                      void *workspace, rnntOptions options);
+
+RNNT_API rnntStatus_t get_rnnt_beam_stream_timed_workspace_size(int max_chunk_frames, int slots, int beam, int max_hyp_len,
+                                                                int enc_width, int joint_size, int alphabet_size, int joint_dtype,
+                                                                size_t *size_bytes);
+
+RNNT_API rnntStatus_t compute_rnnt_beam_stream_timed_begin(const float *W1, const float *b1, const float *W2, const float *b2,
+                                                           int enc_width, int joint_size, int alphabet_size, int slots, int beam,
+                                                           int max_hyp_len, int joint_dtype, void *workspace, rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_beam_stream_timed_feed(const float *enc, int enc_frames, const int *chunk_frames,
+                                                          const int *reset, const int *final_chunk, int enc_width, int joint_size,
+                                                          int alphabet_size, int slots, int beam, int max_hyp_len, int joint_dtype,
+                                                          void *workspace, rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_beam_stream_timed_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits,
+                                                          int *topk_symbols, float *lse, int joint_size, int alphabet_size,
+                                                          int slots, int beam, int max_hyp_len, int joint_dtype, void *workspace,
+                                                          rnntOptions options);
+
+RNNT_API rnntStatus_t compute_rnnt_beam_stream_timed_results(int *hyps, int *hyp_lengths, float *scores, int *stable_lengths,
+                                                             int *hyp_frames, float *hyp_logp, int *timed_stable_lengths,
+                                                             int joint_size, int alphabet_size, int slots, int beam,
+                                                             int max_hyp_len, int joint_dtype, void *workspace,
+                                                             rnntOptions options);
+
 /* Build-only extension: ONE LSTM LAYER FOR TRAINING -- a forward pass that keeps what the backward needs, and back-propagation
  * through time.  rows R (the batch), frames T, hidden H, output width P: a projected layer (W_hr [P, H] given, P < H, bias-free)
  * or an unprojected one (W_hr NULL, P = H).  torch's gate order i, f, g, o; zero initial state; no row lengths (padded frames

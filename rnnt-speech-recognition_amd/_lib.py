@@ -68,6 +68,17 @@ SYMBOLS = [
     "compute_rnnt_align_cells",
     "compute_rnnt_align_path",
     "compute_rnnt_align",
+    "compute_rnnt_greedy_step_timed",
+    "compute_rnnt_greedy_stream_feed_timed",
+    "get_rnnt_beam_timed_workspace_size",
+    "compute_rnnt_beam_timed_begin",
+    "compute_rnnt_beam_timed_step",
+    "compute_rnnt_beam_timed_results",
+    "get_rnnt_beam_stream_timed_workspace_size",
+    "compute_rnnt_beam_stream_timed_begin",
+    "compute_rnnt_beam_stream_timed_feed",
+    "compute_rnnt_beam_stream_timed_step",
+    "compute_rnnt_beam_stream_timed_results",
 ]
 
 
@@ -248,6 +259,29 @@ def load():
         lib.compute_rnnt_align_path.argtypes = [vp, vp, vp, vp, vp, ci, vp, rnntOptions]
         lib.compute_rnnt_align.restype = ci
         lib.compute_rnnt_align.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, rnntOptions]
+    if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "compute_rnnt_greedy_step_timed"):
+        lib.compute_rnnt_greedy_step_timed.restype = ci
+        lib.compute_rnnt_greedy_step_timed.argtypes = [vp] * 4 + [ci] + [vp] * 6 + [ci] * 4 + [vp, rnntOptions]
+        lib.compute_rnnt_greedy_stream_feed_timed.restype = ci
+        lib.compute_rnnt_greedy_stream_feed_timed.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp] + [ci] * 5 + [vp, rnntOptions]
+        lib.get_rnnt_beam_timed_workspace_size.restype = ci
+        lib.get_rnnt_beam_timed_workspace_size.argtypes = [ci] * 6 + [ctypes.POINTER(ctypes.c_size_t)]
+        lib.compute_rnnt_beam_timed_begin.restype = ci
+        lib.compute_rnnt_beam_timed_begin.argtypes = [vp] * 4 + [ci] * 5 + [vp, rnntOptions]
+        lib.compute_rnnt_beam_timed_step.restype = ci
+        lib.compute_rnnt_beam_timed_step.argtypes = [vp] * 6 + [ci] * 5 + [vp, rnntOptions]
+        lib.compute_rnnt_beam_timed_results.restype = ci
+        lib.compute_rnnt_beam_timed_results.argtypes = [vp] * 5 + [ci] * 5 + [vp, rnntOptions]
+        lib.get_rnnt_beam_stream_timed_workspace_size.restype = ci
+        lib.get_rnnt_beam_stream_timed_workspace_size.argtypes = [ci] * 8 + [ctypes.POINTER(ctypes.c_size_t)]
+        lib.compute_rnnt_beam_stream_timed_begin.restype = ci
+        lib.compute_rnnt_beam_stream_timed_begin.argtypes = [vp] * 4 + [ci] * 7 + [vp, rnntOptions]
+        lib.compute_rnnt_beam_stream_timed_feed.restype = ci
+        lib.compute_rnnt_beam_stream_timed_feed.argtypes = [vp, ci, vp, vp, vp] + [ci] * 7 + [vp, rnntOptions]
+        lib.compute_rnnt_beam_stream_timed_step.restype = ci
+        lib.compute_rnnt_beam_stream_timed_step.argtypes = [vp] * 6 + [ci] * 6 + [vp, rnntOptions]
+        lib.compute_rnnt_beam_stream_timed_results.restype = ci
+        lib.compute_rnnt_beam_stream_timed_results.argtypes = [vp] * 7 + [ci] * 6 + [vp, rnntOptions]
     _lib = lib
     return lib
 
@@ -331,6 +365,22 @@ def beam_stream_workspace_bytes(max_chunk_frames: int, slots: int, beam: int, ma
     check(load().get_rnnt_beam_stream_workspace_size(max_chunk_frames, slots, beam, max_hyp_len, enc_width, joint_size,
                                                      alphabet_size, joint_dtype, ctypes.byref(n)),
           "get_rnnt_beam_stream_workspace_size")
+    return int(n.value)
+
+
+def beam_timed_workspace_bytes(maxT: int, minibatch: int, beam: int, joint_size: int, alphabet_size: int, joint_dtype: int) -> int:
+    n = ctypes.c_size_t(0)
+    check(load().get_rnnt_beam_timed_workspace_size(maxT, minibatch, beam, joint_size, alphabet_size, joint_dtype, ctypes.byref(n)),
+          "get_rnnt_beam_timed_workspace_size")
+    return int(n.value)
+
+
+def beam_stream_timed_workspace_bytes(max_chunk_frames: int, slots: int, beam: int, max_hyp_len: int, enc_width: int,
+                                      joint_size: int, alphabet_size: int, joint_dtype: int) -> int:
+    n = ctypes.c_size_t(0)
+    check(load().get_rnnt_beam_stream_timed_workspace_size(max_chunk_frames, slots, beam, max_hyp_len, enc_width, joint_size,
+                                                           alphabet_size, joint_dtype, ctypes.byref(n)),
+          "get_rnnt_beam_stream_timed_workspace_size")
     return int(n.value)
 
 

@@ -19,6 +19,11 @@
 // it was last reset.  Offline N = maxT and n == t.  The stream (beam_stream_*, at the end) keeps a beam across feeds: there t
 // counts the frames of the current chunk, N is the token capacity of a stream, n goes on counting, and a hypothesis that holds N
 // tokens offers only its blank candidate.
+//
+// The timed route (compute_rnnt_beam_timed_* / _stream_timed_*: beam_select_timed_kernel, beam_results_timed_kernel) keeps, beside
+// the token rows, a double-buffered row of {frame, log-probability} pairs per hypothesis (BeamArgs::tt, one 8-byte element per
+// token), gathered by parent exactly as the tokens are; an emission appends {n, logit - lse of the taken candidate}.  A merge
+// keeps the first-ranked survivor's row.  The workspace is the untimed one with the pair rows appended.
 #include "rnnt_decode.h"
 
 #include <limits.h>
@@ -44,6 +49,9 @@ struct BeamArgs {
     int *pv;         // [NS][B K][K] their symbols (-1: none)
     float *bl;       // [B K] the blank's logit (what a hypothesis with a full token row offers)
     int *tok;        // [2][B][K][N] token rows
+    int2 *tt;        // timed: [2][B][K][N] {emission frame, f32 bits of the log-probability} of every token
+    int *hyp_frames, *tstable;  // timed results: [B][K][N] (-1 padded), [B] (NULL: not written)
+    float *hyp_logp;            // timed results: [B][K][N] (0 padded)
     int *parents, *emitted;
     float *topl, *lse;  // diagnostics (NULL: not written)
     int *tops;
@@ -185,189 +193,38 @@ __device__ __forceinline__ int bm_token(const int *row, int len, int v, int p) {
     return p < len ? row[p] : v;  // token p of y_i + (v,): row = y_i's token row, len = |y_i|
 }
 
-__global__ __launch_bounds__(256) void beam_select_kernel(const BeamArgs a) {
-    __shared__ float s_tl[kBeamMax * kBeamMax];  // per-hypothesis top-K
-    __shared__ int s_tv[kBeamMax * kBeamMax];
-    __shared__ double s_lse[kBeamMax], s_cs[kBeamMax * kBeamMax], s_term[kGrWaves][64];
-    __shared__ int s_rank[kBeamMax * kBeamMax], s_take[kBeamMax];
-    __shared__ int s_len[kBeamMax], s_par[kBeamMax], s_v[kBeamMax], s_same[kBeamMax * kBeamMax], s_ord[kBeamMax];
-    __shared__ unsigned long long s_hash[kBeamMax];
-    __shared__ double s_sc[kBeamMax];
-    __shared__ int s_m, s_n;
-    const GreedyArgs &g = a.g;
-    const int b = blockIdx.x, K = a.K, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, blank = g.blank;
-    const GreedyState st = g.st[b];
-    const int rb = b * K;
-    if (st.t >= st.Tb) {  // frozen: nothing changes
-        if (tid < K) a.parents[rb + tid] = rb + tid, a.emitted[rb + tid] = -1;
-        return;
-    }
-    const int nb = a.nslot[b], T = a.N, cur = st.n & 1;
-    const int *tok_cur = a.tok + ((size_t)cur * g.B + b) * K * T;
-    int *tok_nxt = a.tok + ((size_t)(cur ^ 1) * g.B + b) * K * T;
-
-    // ---- per hypothesis (one wave each): logsumexp as greedy_update_kernel, the slice lists merged into the top-K
-    for (int i = wave; i < nb; i += kGrWaves) {
-        const int r = rb + i;
-        const float pm = lane < g.NS ? g.part_m[(size_t)lane * a.R + r] : -INFINITY;
-        const float ps = lane < g.NS ? g.part_s[(size_t)lane * a.R + r] : 0.f;
-        float M = pm;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float o = __shfl_xor(M, off);
-            if (o > M) M = o;
-        }
-        s_term[wave][lane] = ps > 0.f ? (double)ps * exp((double)pm - (double)M) : 0.0;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (one wave: its LDS operations complete in order)
-        if (lane == 0) {
-            double S = 0.0;
-            for (int q = 0; q < g.NS; ++q) S += s_term[wave][q];  // slice order, as greedy_update_kernel
-            s_lse[i] = (double)M + log(S);
-            if (a.lse) a.lse[r] = (float)s_lse[i];
-        }
-        int h = 0;
-        for (int k = 0; k < K; ++k) {
-            float l = -INFINITY;
-            int v = INT_MAX;
-            if (lane < g.NS && h < K) {
-                const size_t o = ((size_t)lane * a.R + r) * K + h;
-                if (a.pv[o] >= 0) l = a.pl[o], v = a.pv[o];
-            }
-            const int mine = v;
-            float bl = l;
-            int bv = v;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const float ol = __shfl_xor(bl, off);
-                const int ov = __shfl_xor(bv, off);
-                if (bm_better(ol, ov, bl, bv)) bl = ol, bv = ov;
-            }
-            if (bv != INT_MAX && bv == mine) ++h;
-            if (lane == 0) {
-                s_tl[i * K + k] = bv != INT_MAX ? bl : -INFINITY;
-                s_tv[i * K + k] = bv != INT_MAX ? bv : -1;
-                if (a.topl) a.topl[(size_t)r * K + k] = bv != INT_MAX ? bl : -INFINITY;
-                if (a.tops) a.tops[(size_t)r * K + k] = bv != INT_MAX ? bv : -1;
-            }
-        }
-    }
-    __syncthreads();
-    // a hypothesis whose token row is full (N tokens; never offline) offers its blank candidate alone
-    if (tid < nb && a.slot[rb + tid].len >= a.N) {
-        for (int k = 0; k < K; ++k) s_tv[tid * K + k] = -1;
-        s_tv[tid * K] = blank, s_tl[tid * K] = a.bl[rb + tid];
-    }
-    __syncthreads();
-
-    // ---- the nb K candidates in float64, ranked by (score desc, hypothesis asc, symbol asc); NaN / -inf never taken
-    const int nc = nb * K;
-    if (tid < nc) {
-        const int i = tid / K;
-        const double sc = a.slot[rb + i].score + ((double)s_tl[tid] - s_lse[i]);
-        s_cs[tid] = (s_tv[tid] >= 0 && sc > -INFINITY) ? sc : __builtin_nan("");
-    }
-    if (tid == 0) s_m = 0;
-    __syncthreads();
-    if (tid < nc) {
-        const double sc = s_cs[tid];
-        int rank = -1;
-        if (sc == sc) {
-            rank = 0;
-            for (int c = 0; c < nc; ++c) {
-                const double o = s_cs[c];
-                if (o > sc || (o == sc && (c / K < tid / K || (c / K == tid / K && s_tv[c] < s_tv[tid])))) ++rank;
-            }
-        }
-        if (rank >= 0 && rank < K) s_take[rank] = tid, atomicAdd(&s_m, 1);
-    }
-    __syncthreads();
-    const int m = s_m;
-
-    // ---- the taken candidates' sequences: y_i, or y_i + (v,)
-    if (tid < m) {
-        const int c = s_take[tid], i = c / K, v = s_tv[c];
-        const BeamSlot p = a.slot[rb + i];
-        const bool emit = v != blank;
-        s_par[tid] = i, s_v[tid] = emit ? v : -1;
-        s_len[tid] = p.len + (emit ? 1 : 0);
-        s_hash[tid] = emit ? p.hash * kHashMul + (unsigned long long)(v + 1) : p.hash;
-        s_sc[tid] = s_cs[c];
-    } else if (m == 0 && tid < nb) {  // nothing can be taken: the beam is carried over unchanged
-        const BeamSlot p = a.slot[rb + tid];
-        s_par[tid] = tid, s_v[tid] = -1, s_len[tid] = p.len, s_hash[tid] = p.hash, s_sc[tid] = p.score;
-    }
-    __syncthreads();
-    const int nt = m > 0 ? m : nb;
-    // same (length, hash): confirmed on the token rows before a merge
-    if (tid < kBeamMax * kBeamMax) {
-        const int x = tid / kBeamMax, y = tid % kBeamMax;
-        s_same[tid] = (m > 0 && x < y && y < m && s_len[x] == s_len[y] && s_hash[x] == s_hash[y]) ? 1 : 0;
-    }
-    __syncthreads();
-    for (int x = 0; x < m; ++x)
-        for (int y = x + 1; y < m; ++y) {
-            if (!s_same[x * kBeamMax + y]) continue;  // (LDS, uniform)
-            const int *rx = tok_cur + (size_t)s_par[x] * T, *ry = tok_cur + (size_t)s_par[y] * T;
-            const int lx = a.slot[rb + s_par[x]].len, ly = a.slot[rb + s_par[y]].len;
-            bool diff = false;
-            for (int p = tid; p < s_len[x]; p += 256)
-                diff |= bm_token(rx, lx, s_v[x], p) != bm_token(ry, ly, s_v[y], p);
-            diff = __syncthreads_or(diff);
-            if (tid == 0 && diff) s_same[x * kBeamMax + y] = 0;
-        }
-    __syncthreads();
-    // merge (the first-ranked survives, logaddexp in float64), then a stable sort by score, descending
-    if (tid == 0) {
-        int alive = 0;
-        for (int x = 0; x < nt; ++x) {
-            if (s_sc[x] != s_sc[x]) continue;  // (merged away below)
-            for (int y = x + 1; y < nt; ++y)
-                if (s_same[x * kBeamMax + y] && s_sc[y] == s_sc[y]) {
-                    const double hi = fmax(s_sc[x], s_sc[y]), lo2 = fmin(s_sc[x], s_sc[y]);
-                    s_sc[x] = hi + log1p(exp(lo2 - hi));
-                    s_sc[y] = __builtin_nan("");
-                }
-            int p = alive++;
-            while (p > 0 && s_sc[s_ord[p - 1]] < s_sc[x]) s_ord[p] = s_ord[p - 1], --p;
-            s_ord[p] = x;
-        }
-        s_n = alive;
-    }
-    __syncthreads();
-    const int nn = s_n;
-    // ---- the new beam: slots, parents, emitted, token rows gathered by parent
-    if (tid < K) {
-        const int r = rb + tid;
-        BeamSlot s;
-        s.pad = 0;
-        if (tid < nn) {
-            const int x = s_ord[tid];
-            s.score = s_sc[x], s.hash = s_hash[x], s.len = s_len[x];
-            a.parents[r] = rb + s_par[x], a.emitted[r] = s_v[x];
-        } else {
-            s.score = -INFINITY, s.hash = 0, s.len = 0;
-            a.parents[r] = r, a.emitted[r] = -1;
-        }
-        a.slot[r] = s;
-    }
-    for (int k = 0; k < nn; ++k) {
-        const int x = s_ord[k], i = s_par[x], n = s_len[x];
-        const int li = n - (s_v[x] >= 0 ? 1 : 0);
-        for (int p = tid; p < n; p += 256) tok_nxt[(size_t)k * T + p] = bm_token(tok_cur + (size_t)i * T, li, s_v[x], p);
-    }
-    if (tid == 0) {
-        a.nslot[b] = nn;
-        GreedyState s2 = st;
-        s2.t = st.t + 1, s2.n = st.n + 1;
-        g.st[b] = s2;
-    }
-}
+#define BEAM_SELECT_KERNEL beam_select_kernel
+#define BEAM_SELECT_TIMED 0
+#include "beam_select_body.h"
+#undef BEAM_SELECT_KERNEL
+#undef BEAM_SELECT_TIMED
+#define BEAM_SELECT_KERNEL beam_select_timed_kernel
+#define BEAM_SELECT_TIMED 1
+#include "beam_select_body.h"
+#undef BEAM_SELECT_KERNEL
+#undef BEAM_SELECT_TIMED
 
 // ---------------------------------------------------------------------------------------------
 // results: one workgroup per utterance; the current beams, zero-padded; stable (NULL: not written): the length of the longest
 // common prefix of the occupied hypotheses (rows 1 ... nb-1 against row 0, position by position; an integer minimum in LDS)
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void beam_results_kernel(const BeamArgs a) {
+// FR: positions agree only when the emission frames agree too (the timed stable length)
+template <bool FR>
+__device__ __forceinline__ int bm_common_prefix(const int *tok, const int2 *tt, const int T, const int nb, const int shortest,
+                                                int *s_first) {
+    if (threadIdx.x == 0) *s_first = shortest;
+    __syncthreads();
+    int first = shortest;
+    for (int p = threadIdx.x; p < shortest && first == shortest; p += 256)
+        for (int k = 1; k < nb; ++k)
+            if (tok[(size_t)k * T + p] != tok[p] || (FR && tt[(size_t)k * T + p].x != tt[p].x)) first = p;
+    if (first < shortest) atomicMin(s_first, first);
+    __syncthreads();
+    return *s_first;
+}
+
+template <bool TIMED>
+__device__ __forceinline__ void beam_results_body(const BeamArgs a) {
     __shared__ int s_first;
     const GreedyArgs &g = a.g;
     const int b = blockIdx.x, K = a.K, T = a.N;
@@ -378,22 +235,32 @@ __global__ __launch_bounds__(256) void beam_results_kernel(const BeamArgs a) {
         const int n = k < nb ? min(max(a.slot[b * K + k].len, 0), T) : 0;
         if (k < nb) shortest = min(shortest, n);
         for (int p = threadIdx.x; p < T; p += 256) a.hyps[((size_t)b * K + k) * T + p] = p < n ? tok[(size_t)k * T + p] : 0;
+        if (TIMED) {
+            const int2 *tt = a.tt + (((size_t)cur * g.B + b) * K + k) * T;
+            for (int p = threadIdx.x; p < T; p += 256) {
+                const int2 e = p < n ? tt[p] : make_int2(-1, 0);
+                a.hyp_frames[((size_t)b * K + k) * T + p] = e.x;
+                a.hyp_logp[((size_t)b * K + k) * T + p] = __int_as_float(e.y);
+            }
+        }
         if (threadIdx.x == 0) {
             a.hyp_lengths[b * K + k] = n;
             a.scores[b * K + k] = k < nb ? (float)a.slot[b * K + k].score : -INFINITY;
         }
     }
-    if (!a.stable) return;  // (uniform)
-    if (threadIdx.x == 0) s_first = shortest;
-    __syncthreads();
-    int first = shortest;
-    for (int p = threadIdx.x; p < shortest && first == shortest; p += 256)
-        for (int k = 1; k < nb; ++k)
-            if (tok[(size_t)k * T + p] != tok[p]) first = p;
-    if (first < shortest) atomicMin(&s_first, first);
-    __syncthreads();
-    if (threadIdx.x == 0) a.stable[b] = s_first;
+    if (a.stable) {  // (uniform)
+        const int n = bm_common_prefix<false>(tok, nullptr, T, nb, shortest, &s_first);
+        if (threadIdx.x == 0) a.stable[b] = n;
+    }
+    if (TIMED && a.tstable) {  // (uniform)
+        __syncthreads();
+        const int n = bm_common_prefix<true>(tok, a.tt + ((size_t)cur * g.B + b) * K * T, T, nb, shortest, &s_first);
+        if (threadIdx.x == 0) a.tstable[b] = n;
+    }
 }
+
+__global__ __launch_bounds__(256) void beam_results_kernel(const BeamArgs a) { beam_results_body<false>(a); }
+__global__ __launch_bounds__(256) void beam_results_timed_kernel(const BeamArgs a) { beam_results_body<true>(a); }
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -401,15 +268,16 @@ __global__ __launch_bounds__(256) void beam_results_kernel(const BeamArgs a) {
 size_t joint_w2_image_bytes(int J, int V);
 
 struct BeamLayout {
-    size_t st, slot, nslot, pm, ps, pl, pv, bl, tok, rowflag, expE, encraw, img, btab, tflag, total;
+    size_t st, slot, nslot, pm, ps, pl, pv, bl, tok, rowflag, expE, encraw, img, btab, tflag, tt, total;
     int NC, NS, DT;
 };
 
-// N: the token row stride (offline: T)
-static bool make_beam_layout(int T, int B, int K, int N, int J, int V, int joint_dtype, BeamLayout &L) {
+// N: the token row stride (offline: T).  timed: the {frame, log-probability} rows follow the untimed layout, which stays as it
+// is; the token and pair rows together are 6 B K N words, and that count must stay below 2^31
+static bool make_beam_layout(int T, int B, int K, int N, int J, int V, int joint_dtype, bool timed, BeamLayout &L) {
     L.DT = greedy_dt(joint_dtype, J, V);
     if (L.DT < 0 || T <= 0 || B <= 0 || K < 1 || K > kBeamMax || N < 1) return false;
-    if ((unsigned long long)B * T * J >= (1ull << 31) || 2ull * B * K * N >= (1ull << 31)) return false;
+    if ((unsigned long long)B * T * J >= (1ull << 31) || (timed ? 6ull : 2ull) * B * K * N >= (1ull << 31)) return false;
     L.NC = (V + 31) / 32;
     L.NS = (L.NC + kGrWaves - 1) / kGrWaves;
     const size_t R = (size_t)B * K;
@@ -434,12 +302,14 @@ static bool make_beam_layout(int T, int B, int K, int N, int J, int V, int joint
     L.btab = take((size_t)L.NC * 32 * sizeof(float));
     L.tflag = take(256 + 1024);  // joint_prep_kernel's flag words + b2s (as greedy's layout)
     L.bl = take(R * sizeof(float));
+    L.tt = timed ? take(2 * R * (size_t)N * sizeof(int2)) : off;
     L.total = off;
     return true;
 }
 
-static bool beam_bind(BeamArgs &a, int T, int B, int K, int N, int J, int V, int joint_dtype, void *workspace, BeamLayout &L) {
-    if (!make_beam_layout(T, B, K, N, J, V, joint_dtype, L)) return false;
+static bool beam_bind(BeamArgs &a, int T, int B, int K, int N, int J, int V, int joint_dtype, bool timed, void *workspace,
+                      BeamLayout &L) {
+    if (!make_beam_layout(T, B, K, N, J, V, joint_dtype, timed, L)) return false;
     char *ws = (char *)workspace;
     GreedyArgs &g = a.g;
     g.st = (GreedyState *)(ws + L.st);
@@ -451,22 +321,23 @@ static bool beam_bind(BeamArgs &a, int T, int B, int K, int N, int J, int V, int
     g.B = B, g.T = T, g.J = J, g.V = V;
     a.slot = (BeamSlot *)(ws + L.slot), a.nslot = (int *)(ws + L.nslot);
     a.pl = (float *)(ws + L.pl), a.pv = (int *)(ws + L.pv), a.bl = (float *)(ws + L.bl), a.tok = (int *)(ws + L.tok);
+    a.tt = timed ? (int2 *)(ws + L.tt) : nullptr;
     a.K = K, a.R = B * K, a.N = N;
     return true;
 }
 
-hipError_t beam_workspace_bytes(int T, int B, int K, int J, int V, int joint_dtype, size_t *bytes) {
+hipError_t beam_workspace_bytes(int T, int B, int K, int J, int V, int joint_dtype, bool timed, size_t *bytes) {
     BeamLayout L;
-    if (!make_beam_layout(T, B, K, T, J, V, joint_dtype, L)) return hipErrorInvalidValue;
+    if (!make_beam_layout(T, B, K, T, J, V, joint_dtype, timed, L)) return hipErrorInvalidValue;
     *bytes = L.total;
     return hipSuccess;
 }
 
 hipError_t launch_beam_begin(const float *enc_proj, const int *frame_lengths, const float *W2, const float *b2, int J, int V, int B,
-                             int T, int K, int joint_dtype, void *workspace, hipStream_t s) {
+                             int T, int K, int joint_dtype, bool timed, void *workspace, hipStream_t s) {
     BeamArgs a = {};
     BeamLayout L;
-    if (!beam_bind(a, T, B, K, T, J, V, joint_dtype, workspace, L)) return hipErrorInvalidValue;
+    if (!beam_bind(a, T, B, K, T, J, V, joint_dtype, timed, workspace, L)) return hipErrorInvalidValue;
     a.g.enc_proj = enc_proj, a.g.frame_lengths = frame_lengths, a.g.max_symbols = nullptr, a.g.max_per_frame = 0;
     hipError_t e = launch_greedy_prepare(a.g, L.DT, W2, b2, s);
     if (e != hipSuccess) return e;
@@ -485,10 +356,11 @@ static hipError_t launch_beam_step_dt(const BeamArgs &a, size_t shm, hipStream_t
 
 // N: the token row stride the workspace was laid out with (offline: T; the stream: max_hyp_len)
 hipError_t launch_beam_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits, int *topk_symbols, float *lse,
-                            int J, int V, int B, int T, int K, int N, int blank, int joint_dtype, void *workspace, hipStream_t s) {
+                            int J, int V, int B, int T, int K, int N, int blank, int joint_dtype, bool timed, void *workspace,
+                            hipStream_t s) {
     BeamArgs a = {};
     BeamLayout L;
-    if (!beam_bind(a, T, B, K, N, J, V, joint_dtype, workspace, L)) return hipErrorInvalidValue;
+    if (!beam_bind(a, T, B, K, N, J, V, joint_dtype, timed, workspace, L)) return hipErrorInvalidValue;
     a.g.pred_proj = pred_proj, a.g.blank = blank;
     a.parents = parents, a.emitted = emitted, a.topl = topk_logits, a.tops = topk_symbols, a.lse = lse;
     hipError_t e;
@@ -497,17 +369,23 @@ hipError_t launch_beam_step(const float *pred_proj, int *parents, int *emitted, 
     else if (L.DT == 0) e = launch_beam_step_dt<0>(a, shm, s);
     else e = launch_beam_step_dt<2>(a, shm, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(256), 0, s, a);
+    if (timed) hipLaunchKernelGGL(beam_select_timed_kernel, dim3(B), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_beam_results(int *hyps, int *hyp_lengths, float *scores, int *stable_lengths, int J, int V, int B, int T, int K,
-                               int N, int joint_dtype, void *workspace, hipStream_t s) {
+// hyp_frames != NULL: the timed results (hyp_logp too; timed_stable_lengths or NULL) of a workspace laid out timed
+hipError_t launch_beam_results(int *hyps, int *hyp_lengths, float *scores, int *stable_lengths, int *hyp_frames, float *hyp_logp,
+                               int *timed_stable_lengths, int J, int V, int B, int T, int K, int N, int joint_dtype, void *workspace,
+                               hipStream_t s) {
     BeamArgs a = {};
     BeamLayout L;
-    if (!beam_bind(a, T, B, K, N, J, V, joint_dtype, workspace, L)) return hipErrorInvalidValue;
+    const bool timed = hyp_frames != nullptr;
+    if (!beam_bind(a, T, B, K, N, J, V, joint_dtype, timed, workspace, L)) return hipErrorInvalidValue;
     a.hyps = hyps, a.hyp_lengths = hyp_lengths, a.scores = scores, a.stable = stable_lengths;
-    hipLaunchKernelGGL(beam_results_kernel, dim3(B), dim3(256), 0, s, a);
+    a.hyp_frames = hyp_frames, a.hyp_logp = hyp_logp, a.tstable = timed_stable_lengths;
+    if (timed) hipLaunchKernelGGL(beam_results_timed_kernel, dim3(B), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(beam_results_kernel, dim3(B), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -564,31 +442,31 @@ __global__ __launch_bounds__(256) void beam_stream_feed_kernel(const GreedyStrea
     }
 }
 
-static bool make_beam_stream_layout(int Tc, int S, int K, int N, int H, int J, int V, int joint_dtype, BeamLayout &L, size_t &w1,
-                                    size_t &b1) {
+static bool make_beam_stream_layout(int Tc, int S, int K, int N, int H, int J, int V, int joint_dtype, bool timed, BeamLayout &L,
+                                    size_t &w1, size_t &b1) {
     if (S < 1 || K < 1 || K > kBeamMax || (long long)S * K > 1024 || H < 1 || H > 4096) return false;  // (the prediction network's rows)
-    if (!make_beam_layout(Tc, S, K, N, J, V, joint_dtype, L)) return false;
+    if (!make_beam_layout(Tc, S, K, N, J, V, joint_dtype, timed, L)) return false;
     w1 = L.total;
     b1 = align_up(w1 + (size_t)H * J * sizeof(float), 256);
     L.total = align_up(b1 + (size_t)J * sizeof(float), 256);
     return true;
 }
 
-hipError_t beam_stream_workspace_bytes(int Tc, int S, int K, int N, int H, int J, int V, int joint_dtype, size_t *bytes) {
+hipError_t beam_stream_workspace_bytes(int Tc, int S, int K, int N, int H, int J, int V, int joint_dtype, bool timed, size_t *bytes) {
     BeamLayout L;
     size_t w1, b1;
-    if (!make_beam_stream_layout(Tc, S, K, N, H, J, V, joint_dtype, L, w1, b1)) return hipErrorInvalidValue;
+    if (!make_beam_stream_layout(Tc, S, K, N, H, J, V, joint_dtype, timed, L, w1, b1)) return hipErrorInvalidValue;
     *bytes = L.total;
     return hipSuccess;
 }
 
 hipError_t launch_beam_stream_begin(const float *W1, const float *b1, const float *W2, const float *b2, int H, int J, int V, int S,
-                                    int Tc, int K, int N, int joint_dtype, void *workspace, hipStream_t s) {
+                                    int Tc, int K, int N, int joint_dtype, bool timed, void *workspace, hipStream_t s) {
     BeamLayout L;
     size_t w1, bo;
-    if (!make_beam_stream_layout(Tc, S, K, N, H, J, V, joint_dtype, L, w1, bo)) return hipErrorInvalidValue;
+    if (!make_beam_stream_layout(Tc, S, K, N, H, J, V, joint_dtype, timed, L, w1, bo)) return hipErrorInvalidValue;
     BeamArgs a = {};
-    if (!beam_bind(a, Tc, S, K, N, J, V, joint_dtype, workspace, L)) return hipErrorInvalidValue;
+    if (!beam_bind(a, Tc, S, K, N, J, V, joint_dtype, timed, workspace, L)) return hipErrorInvalidValue;
     hipError_t e;
     if ((e = launch_greedy_w2(a.g, L.DT, W2, b2, s)) != hipSuccess) return e;
     char *ws = (char *)workspace;
@@ -601,12 +479,12 @@ hipError_t launch_beam_stream_begin(const float *W1, const float *b1, const floa
 }
 
 hipError_t launch_beam_stream_feed(const float *enc, int Te, const int *chunk_frames, const int *reset, const int *final_, int H, int J,
-                                   int V, int S, int Tc, int K, int N, int joint_dtype, void *workspace, hipStream_t s) {
+                                   int V, int S, int Tc, int K, int N, int joint_dtype, bool timed, void *workspace, hipStream_t s) {
     BeamLayout L;
     size_t w1, bo;
-    if (!make_beam_stream_layout(Tc, S, K, N, H, J, V, joint_dtype, L, w1, bo) || Te < 0 || Te > Tc) return hipErrorInvalidValue;
+    if (!make_beam_stream_layout(Tc, S, K, N, H, J, V, joint_dtype, timed, L, w1, bo) || Te < 0 || Te > Tc) return hipErrorInvalidValue;
     BeamArgs b = {};
-    if (!beam_bind(b, Tc, S, K, N, J, V, joint_dtype, workspace, L)) return hipErrorInvalidValue;
+    if (!beam_bind(b, Tc, S, K, N, J, V, joint_dtype, timed, workspace, L)) return hipErrorInvalidValue;
     char *ws = (char *)workspace;
     GreedyStreamArgs a = {};
     a.enc = enc, a.W1 = (const float *)(ws + w1), a.b1 = (const float *)(ws + bo);

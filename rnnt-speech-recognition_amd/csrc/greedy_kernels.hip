@@ -10,7 +10,9 @@
 //           (slice, hypothesis).  Nothing of size [B x V] is written.
 //   update  (greedy_update_kernel)  one workgroup: the partials of each hypothesis -> (argmax, max, logsumexp) in float64, the
 //           state update (emit / advance the frame / done), the all-done word.  A second launch: the kernel boundary makes the
-//           partials visible (no inter-workgroup protocol; DESIGN.md "Batched greedy decoding").
+//           partials visible (no inter-workgroup protocol; DESIGN.md "Batched greedy decoding").  greedy_update_timed_kernel
+//           (compute_rnnt_greedy_step_timed) also stores, beside every token, the frame that emitted it and the log-softmax
+//           of that decision.
 // prepare (greedy_begin_kernel, greedy_w2_f16_kernel or joint_prep_kernel via launch_joint_w2_image), once per decode: e^{2x}
 //           tables of enc_proj for all frames, a raw copy of it (the direct-tanh route), the per-frame table-range flag, the W2
 //           operand image and bias tables, the per-hypothesis state.
@@ -167,7 +169,8 @@ __global__ __launch_bounds__(kGrWaves * 64) void greedy_step_kernel(const Greedy
 // ---------------------------------------------------------------------------------------------
 // update: one workgroup over all hypotheses
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void greedy_update_kernel(const GreedyArgs a) {
+template <bool TIMED>
+__device__ __forceinline__ void greedy_update_body(const GreedyArgs a) {
     bool running = false, paused = false;
     for (int b = threadIdx.x; b < a.B; b += 256) {
         GreedyState s = a.st[b];
@@ -192,6 +195,10 @@ __global__ __launch_bounds__(256) void greedy_update_kernel(const GreedyArgs a) 
                 s.t += 1, s.nf = 0;
             } else {
                 a.hyps[(size_t)b * a.max_hyp_len + s.n] = k;
+                if (TIMED) {  // (s.t: the frame of this decision, before the state moves on)
+                    a.hyp_frames[(size_t)b * a.max_hyp_len + s.n] = (a.frame_base ? a.frame_base[b] : 0) + s.t;
+                    a.hyp_logp[(size_t)b * a.max_hyp_len + s.n] = (float)((double)M - lse);
+                }
                 s.n += 1, s.nf += 1, em = k;
                 if (s.cap > 0 && s.nf >= s.cap) s.t += 1, s.nf = 0;
             }
@@ -209,6 +216,10 @@ __global__ __launch_bounds__(256) void greedy_update_kernel(const GreedyArgs a) 
     const int any_running = __syncthreads_or(running), any_paused = __syncthreads_or(paused);
     if (threadIdx.x == 0) a.all_done[0] = any_running ? 0 : (any_paused ? 2 : 1);
 }
+
+// (two kernels with names of their own: the code-object audits look a kernel up by its name and expect one)
+__global__ __launch_bounds__(256) void greedy_update_kernel(const GreedyArgs a) { greedy_update_body<false>(a); }
+__global__ __launch_bounds__(256) void greedy_update_timed_kernel(const GreedyArgs a) { greedy_update_body<true>(a); }
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -317,15 +328,17 @@ static hipError_t launch_step_dt(const GreedyArgs &a, size_t shm, hipStream_t s)
     return hipGetLastError();
 }
 
+// hyp_frames != NULL: the timed step (hyp_logp too; frame_base [B] or NULL)
 hipError_t launch_greedy_step(const float *pred_proj, int *hyps, int max_hyp_len, int *hyp_lengths, float *scores, int *emitted,
-                              int *all_done, float *stats, int J, int V, int B, int T, int blank, int joint_dtype, void *workspace,
-                              hipStream_t s) {
+                              int *all_done, float *stats, int *hyp_frames, float *hyp_logp, const int *frame_base, int J, int V,
+                              int B, int T, int blank, int joint_dtype, void *workspace, hipStream_t s) {
     GreedyLayout L;
     if (!make_greedy_layout(T, B, J, V, joint_dtype, L)) return hipErrorInvalidValue;
     GreedyArgs a = {};
     greedy_bind(a, L, workspace);
     a.pred_proj = pred_proj, a.hyps = hyps, a.hyp_lengths = hyp_lengths, a.scores = scores, a.emitted = emitted;
     a.all_done = all_done, a.stats = stats;
+    a.hyp_frames = hyp_frames, a.hyp_logp = hyp_logp, a.frame_base = frame_base;
     a.B = B, a.T = T, a.J = J, a.V = V, a.blank = blank, a.max_hyp_len = max_hyp_len;
     hipError_t e;
     const size_t shm = (size_t)J * 32 * sizeof(gf16) * (L.DT == 1 ? 1 : 2);
@@ -333,7 +346,8 @@ hipError_t launch_greedy_step(const float *pred_proj, int *hyps, int max_hyp_len
     else if (L.DT == 0) e = launch_step_dt<0>(a, shm, s);
     else e = launch_step_dt<2>(a, shm, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(greedy_update_kernel, dim3(1), dim3(256), 0, s, a);
+    if (hyp_frames) hipLaunchKernelGGL(greedy_update_timed_kernel, dim3(1), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(greedy_update_kernel, dim3(1), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -386,43 +400,16 @@ __global__ __launch_bounds__(256) void greedy_stream_proj_kernel(const GreedyStr
     }
 }
 
-// the per-frame range flags of the chunk's frames; workgroup 0 also moves every slot's state on to the chunk
-__global__ __launch_bounds__(256) void greedy_stream_feed_kernel(const GreedyStreamArgs a) {
-    const int rows = a.S * a.Te;
-    for (int r = blockIdx.x; r < rows; r += gridDim.x) {  // (block-uniform trip count and skip: the barrier below is safe)
-        const int s = r / a.Te, t = r - s * a.Te;
-        if (t >= gs_frames(a, s)) continue;
-        const size_t base = ((size_t)s * a.T + t) * a.J;
-        bool big = false;
-        for (int j = threadIdx.x; j < a.J; j += 256) big |= exp_tab_out_of_range(a.encraw[base + j]);  // also catches NaN
-        big = __syncthreads_or(big);
-        if (threadIdx.x == 0) a.rowflag[(size_t)s * a.T + t] = big ? 1 : 0;
-    }
-    if (blockIdx.x != 0) return;
-    bool running = false;
-    for (int b = threadIdx.x; b < a.S; b += 256) {
-        GreedyState s = a.st[b];
-        if (a.reset && a.reset[b] != 0) {
-            s.n = 0, s.fin = 0, s.score = 0.0;
-            s.maxsym = a.max_symbols ? max(a.max_symbols[b], 0) : INT_MAX;
-            s.cap = a.max_per_frame;
-        }
-        s.t = 0, s.nf = 0;
-        if (s.fin || s.n >= s.maxsym) {  // finished: nothing more until a reset
-            s.fin = 1, s.Tb = 0;
-        } else {
-            s.Tb = gs_frames(a, b);
-            if (a.final_ && a.final_[b] != 0) s.fin = 1;  // (after this chunk)
-        }
-        s.done = s.Tb == 0 ? 1 : 0;
-        a.st[b] = s;
-        a.hyp_lengths[b] = s.n;
-        a.scores[b] = (float)s.score;
-        running |= !s.done;
-    }
-    running = __syncthreads_or(running);
-    if (threadIdx.x == 0) a.all_done[0] = running ? 0 : 1;  // (a full hyps buffer: the next step reports 2)
-}
+#define GREEDY_STREAM_FEED_KERNEL greedy_stream_feed_kernel
+#define GREEDY_STREAM_FEED_TIMED 0
+#include "greedy_stream_feed_body.h"
+#undef GREEDY_STREAM_FEED_KERNEL
+#undef GREEDY_STREAM_FEED_TIMED
+#define GREEDY_STREAM_FEED_KERNEL greedy_stream_feed_timed_kernel
+#define GREEDY_STREAM_FEED_TIMED 1
+#include "greedy_stream_feed_body.h"
+#undef GREEDY_STREAM_FEED_KERNEL
+#undef GREEDY_STREAM_FEED_TIMED
 
 // begin: W1 / b1 into the workspace, every slot finished
 __global__ __launch_bounds__(256) void greedy_stream_begin_kernel(const float *W1, const float *b1, float *w1, float *bb1, int H, int J,
@@ -493,8 +480,9 @@ hipError_t launch_greedy_stream_begin(const float *W1, const float *b1, const fl
 }
 
 hipError_t launch_greedy_stream_feed(const float *enc, int Te, const int *chunk_frames, const int *reset, const int *final_,
-                                     const int *max_symbols, int max_per_frame, int *hyp_lengths, float *scores, int *all_done, int H,
-                                     int J, int V, int S, int Tc, int joint_dtype, void *workspace, hipStream_t s) {
+                                     const int *max_symbols, int max_per_frame, int *hyp_lengths, float *scores, int *all_done,
+                                     int *frame_base, int H, int J, int V, int S, int Tc, int joint_dtype, void *workspace,
+                                     hipStream_t s) {
     GreedyLayout L;
     size_t w1, bo;
     if (!make_stream_layout(Tc, S, H, J, V, joint_dtype, L, w1, bo) || Te < 0 || Te > Tc) return hipErrorInvalidValue;
@@ -507,10 +495,13 @@ hipError_t launch_greedy_stream_feed(const float *enc, int Te, const int *chunk_
     a.hyp_lengths = hyp_lengths, a.all_done = all_done, a.scores = scores;
     a.st = g.st, a.rowflag = g.rowflag, a.expE = g.expE, a.encraw = g.encraw;
     a.S = S, a.Te = Te, a.T = Tc, a.H = H, a.J = J, a.max_per_frame = max_per_frame;
+    a.frame_base = frame_base;  // (NULL: the untimed feed)
     const int rows = S * Te;
     const hipError_t e = launch_greedy_stream_proj(a, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(greedy_stream_feed_kernel, dim3(rows > 1 ? (rows < 2048 ? rows : 2048) : 1), dim3(256), 0, s, a);
+    const dim3 grid(rows > 1 ? (rows < 2048 ? rows : 2048) : 1);
+    if (frame_base) hipLaunchKernelGGL(greedy_stream_feed_timed_kernel, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(greedy_stream_feed_kernel, grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

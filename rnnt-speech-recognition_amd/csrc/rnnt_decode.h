@@ -49,6 +49,11 @@ struct GreedyArgs {
     float *btab;       // DT 1: b2 log2 e [NC 32]; DT 2: b2 [32]
     const float *tflag;  // DT 0 / 2: joint_prep_kernel's flag words (+ 64: b2s)
     int B, T, J, V, NC, NS, blank, max_per_frame, max_hyp_len;
+    // the timed step (greedy_update_timed_kernel): per token the frame that emitted it and the log-softmax of that decision,
+    // at the token's position in hyps
+    int *hyp_frames;        // [B][max_hyp_len]
+    float *hyp_logp;        // [B][max_hyp_len]
+    const int *frame_base;  // [B] frames of the stream's earlier chunks (NULL: 0)
 };
 
 __device__ __forceinline__ constexpr int gr_cdrow(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
@@ -164,6 +169,7 @@ struct GreedyStreamArgs {
     int *rowflag;
     float *expE, *encraw;
     int S, Te, T, H, J, max_per_frame;
+    int *frame_base;  // the timed feed (greedy_stream_feed_timed_kernel): [S] frames of the chunks fed before this one
 };
 
 __device__ __forceinline__ int gs_frames(const GreedyStreamArgs &a, const int s) { return min(max(a.chunk_frames[s], 0), a.Te); }

@@ -46,21 +46,24 @@ hipError_t launch_greedy_begin(const float *enc_proj, const int *frame_lengths, 
                                const float *b2, int J, int V, int B, int T, int max_per_frame, int joint_dtype, void *workspace,
                                hipStream_t s);
 hipError_t launch_greedy_step(const float *pred_proj, int *hyps, int max_hyp_len, int *hyp_lengths, float *scores, int *emitted,
-                              int *all_done, float *stats, int J, int V, int B, int T, int blank, int joint_dtype, void *workspace,
-                              hipStream_t s);
+                              int *all_done, float *stats, int *hyp_frames, float *hyp_logp, const int *frame_base, int J, int V,
+                              int B, int T, int blank, int joint_dtype, void *workspace, hipStream_t s);
 // beam_kernels.hip (batched modified beam search)
-hipError_t beam_workspace_bytes(int T, int B, int K, int J, int V, int joint_dtype, size_t *bytes);
+// (timed: the workspace layout with the {frame, log-probability} rows, and the kernels that keep them)
+hipError_t beam_workspace_bytes(int T, int B, int K, int J, int V, int joint_dtype, bool timed, size_t *bytes);
 hipError_t launch_beam_begin(const float *enc_proj, const int *frame_lengths, const float *W2, const float *b2, int J, int V, int B,
-                             int T, int K, int joint_dtype, void *workspace, hipStream_t s);
+                             int T, int K, int joint_dtype, bool timed, void *workspace, hipStream_t s);
 hipError_t launch_beam_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits, int *topk_symbols, float *lse,
-                            int J, int V, int B, int T, int K, int N, int blank, int joint_dtype, void *workspace, hipStream_t s);
-hipError_t launch_beam_results(int *hyps, int *hyp_lengths, float *scores, int *stable_lengths, int J, int V, int B, int T, int K,
-                               int N, int joint_dtype, void *workspace, hipStream_t s);
-hipError_t beam_stream_workspace_bytes(int Tc, int S, int K, int N, int H, int J, int V, int joint_dtype, size_t *bytes);
+                            int J, int V, int B, int T, int K, int N, int blank, int joint_dtype, bool timed, void *workspace,
+                            hipStream_t s);
+hipError_t launch_beam_results(int *hyps, int *hyp_lengths, float *scores, int *stable_lengths, int *hyp_frames, float *hyp_logp,
+                               int *timed_stable_lengths, int J, int V, int B, int T, int K, int N, int joint_dtype, void *workspace,
+                               hipStream_t s);
+hipError_t beam_stream_workspace_bytes(int Tc, int S, int K, int N, int H, int J, int V, int joint_dtype, bool timed, size_t *bytes);
 hipError_t launch_beam_stream_begin(const float *W1, const float *b1, const float *W2, const float *b2, int H, int J, int V, int S,
-                                    int Tc, int K, int N, int joint_dtype, void *workspace, hipStream_t s);
+                                    int Tc, int K, int N, int joint_dtype, bool timed, void *workspace, hipStream_t s);
 hipError_t launch_beam_stream_feed(const float *enc, int Te, const int *chunk_frames, const int *reset, const int *final_, int H, int J,
-                                   int V, int S, int Tc, int K, int N, int joint_dtype, void *workspace, hipStream_t s);
+                                   int V, int S, int Tc, int K, int N, int joint_dtype, bool timed, void *workspace, hipStream_t s);
 // prednet_kernels.hip (the prediction-network step of the decoders)
 bool prednet_layout_ok(const rnntPrednetBlock *blocks, int L, int E, int V, int Jp, int R, size_t *bytes);
 hipError_t launch_prednet_begin(const float *emb, const rnntPrednetBlock *blocks, int L, int E, int V, const float *W1, int Jp, int R,
@@ -90,8 +93,9 @@ hipError_t greedy_stream_workspace_bytes(int Tc, int S, int H, int J, int V, int
 hipError_t launch_greedy_stream_begin(const float *W1, const float *b1, const float *W2, const float *b2, int H, int J, int V, int S,
                                       int Tc, int joint_dtype, void *workspace, hipStream_t s);
 hipError_t launch_greedy_stream_feed(const float *enc, int Te, const int *chunk_frames, const int *reset, const int *final_,
-                                     const int *max_symbols, int max_per_frame, int *hyp_lengths, float *scores, int *all_done, int H,
-                                     int J, int V, int S, int Tc, int joint_dtype, void *workspace, hipStream_t s);
+                                     const int *max_symbols, int max_per_frame, int *hyp_lengths, float *scores, int *all_done,
+                                     int *frame_base, int H, int J, int V, int S, int Tc, int joint_dtype, void *workspace,
+                                     hipStream_t s);
 // frontend_kernels.hip (the streaming log-mel front end)
 bool frontend_layout_ok(int K, int S, int L, int step, int M, int stack, int rm, size_t *bytes, int *max_rows);
 hipError_t launch_frontend_begin(const float *window, const float *mel_weights, int K, int S, int L, int step, int M, int stack,
@@ -580,22 +584,40 @@ rnntStatus_t compute_rnnt_greedy_step(const float *pred_proj, int *hyps, int max
     const rnntStatus_t st = check_greedy(options.maxT, joint_size, alphabet_size, minibatch, joint_dtype, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
     if (((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
-    return from_hip(launch_greedy_step(pred_proj, hyps, max_hyp_len, hyp_lengths, scores, emitted, all_done, logit_stats, joint_size,
-                                       alphabet_size, minibatch, options.maxT, options.blank_label, joint_dtype, workspace,
-                                       (hipStream_t)options.stream));
+    return from_hip(launch_greedy_step(pred_proj, hyps, max_hyp_len, hyp_lengths, scores, emitted, all_done, logit_stats, nullptr,
+                                       nullptr, nullptr, joint_size, alphabet_size, minibatch, options.maxT, options.blank_label,
+                                       joint_dtype, workspace, (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_greedy_step_timed(const float *pred_proj, int *hyps, int *hyp_frames, float *hyp_logp, int max_hyp_len,
+                                            int *hyp_lengths, float *scores, int *emitted, int *all_done, float *logit_stats,
+                                            const int *frame_base, int joint_size, int alphabet_size, int minibatch, int joint_dtype,
+                                            void *workspace, rnntOptions options) {
+    if (!pred_proj || !hyps || !hyp_frames || !hyp_logp || !hyp_lengths || !scores || !emitted || !all_done || !workspace)
+        return RNNT_STATUS_INVALID_VALUE;
+    if ((((uintptr_t)hyps | (uintptr_t)hyp_frames | (uintptr_t)hyp_logp | (uintptr_t)frame_base) & 3) != 0)
+        return RNNT_STATUS_INVALID_VALUE;
+    if (max_hyp_len <= 0 || (long long)max_hyp_len * minibatch >= (1ll << 31)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_greedy(options.maxT, joint_size, alphabet_size, minibatch, joint_dtype, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
+    return from_hip(launch_greedy_step(pred_proj, hyps, max_hyp_len, hyp_lengths, scores, emitted, all_done, logit_stats, hyp_frames,
+                                       hyp_logp, frame_base, joint_size, alphabet_size, minibatch, options.maxT, options.blank_label,
+                                       joint_dtype, workspace, (hipStream_t)options.stream));
 }
 
 
 // Batched beam search (include/rnnt.h).  The checks of the greedy decoder, plus 1 <= beam <= 16; everything is checked before
 // anything is enqueued.
 static rnntStatus_t check_beam(int maxT, int joint_size, int alphabet_size, int minibatch, int beam, int joint_dtype,
-                               const void *workspace, const rnntOptions &o) {
+                               const void *workspace, const rnntOptions &o, bool timed = false) {
     if (!workspace || ((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
     if (beam < 1 || beam > 16) return RNNT_STATUS_INVALID_VALUE;
     const rnntStatus_t st = check_greedy(maxT, joint_size, alphabet_size, minibatch, joint_dtype, o);
     if (st != RNNT_STATUS_SUCCESS) return st;
     size_t n = 0;
-    if (beam_workspace_bytes(maxT, minibatch, beam, joint_size, alphabet_size, joint_dtype, &n) != hipSuccess) return RNNT_STATUS_INVALID_VALUE;
+    if (beam_workspace_bytes(maxT, minibatch, beam, joint_size, alphabet_size, joint_dtype, timed, &n) != hipSuccess)
+        return RNNT_STATUS_INVALID_VALUE;
     return RNNT_STATUS_SUCCESS;
 }
 
@@ -603,7 +625,7 @@ rnntStatus_t get_rnnt_beam_workspace_size(int maxT, int minibatch, int beam, int
                                           size_t *size_bytes) {
     if (!size_bytes) return RNNT_STATUS_INVALID_VALUE;
     if (joint_dtype != 0 && joint_dtype != 1) return RNNT_STATUS_INVALID_VALUE;
-    return beam_workspace_bytes(maxT, minibatch, beam, joint_size, alphabet_size, joint_dtype, size_bytes) == hipSuccess
+    return beam_workspace_bytes(maxT, minibatch, beam, joint_size, alphabet_size, joint_dtype, false, size_bytes) == hipSuccess
                ? RNNT_STATUS_SUCCESS
                : RNNT_STATUS_INVALID_VALUE;
 }
@@ -615,7 +637,7 @@ rnntStatus_t compute_rnnt_beam_begin(const float *enc_proj, const int *frame_len
     const rnntStatus_t st = check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
     return from_hip(launch_beam_begin(enc_proj, frame_lengths, W2, b2, joint_size, alphabet_size, minibatch, options.maxT, beam,
-                                      joint_dtype, workspace, (hipStream_t)options.stream));
+                                      joint_dtype, false, workspace, (hipStream_t)options.stream));
 }
 
 rnntStatus_t compute_rnnt_beam_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits, int *topk_symbols,
@@ -625,7 +647,7 @@ rnntStatus_t compute_rnnt_beam_step(const float *pred_proj, int *parents, int *e
     const rnntStatus_t st = check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
     return from_hip(launch_beam_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size,
-                                     minibatch, options.maxT, beam, options.maxT, options.blank_label, joint_dtype, workspace,
+                                     minibatch, options.maxT, beam, options.maxT, options.blank_label, joint_dtype, false, workspace,
                                      (hipStream_t)options.stream));
 }
 
@@ -634,8 +656,9 @@ rnntStatus_t compute_rnnt_beam_results(int *hyps, int *hyp_lengths, float *score
     if (!hyps || !hyp_lengths || !scores) return RNNT_STATUS_INVALID_VALUE;
     const rnntStatus_t st = check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
-    return from_hip(launch_beam_results(hyps, hyp_lengths, scores, nullptr, joint_size, alphabet_size, minibatch, options.maxT, beam,
-                                       options.maxT, joint_dtype, workspace, (hipStream_t)options.stream));
+    return from_hip(launch_beam_results(hyps, hyp_lengths, scores, nullptr, nullptr, nullptr, nullptr, joint_size, alphabet_size,
+                                        minibatch, options.maxT, beam, options.maxT, joint_dtype, workspace,
+                                        (hipStream_t)options.stream));
 }
 
 
@@ -810,22 +833,39 @@ rnntStatus_t compute_rnnt_greedy_stream_feed(const float *enc, int enc_frames, c
         check_greedy_stream(options.maxT, slots, enc_width, joint_size, alphabet_size, joint_dtype, workspace, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
     return from_hip(launch_greedy_stream_feed(enc, enc_frames, chunk_frames, reset, final_chunk, max_symbols, max_per_frame,
-                                              hyp_lengths, scores, all_done, enc_width, joint_size, alphabet_size, slots, options.maxT,
-                                              joint_dtype, workspace, (hipStream_t)options.stream));
+                                              hyp_lengths, scores, all_done, nullptr, enc_width, joint_size, alphabet_size, slots,
+                                              options.maxT, joint_dtype, workspace, (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_greedy_stream_feed_timed(const float *enc, int enc_frames, const int *chunk_frames, const int *reset,
+                                                   const int *final_chunk, const int *max_symbols, int max_per_frame,
+                                                   int *hyp_lengths, float *scores, int *all_done, int *frame_base, int enc_width,
+                                                   int joint_size, int alphabet_size, int slots, int joint_dtype, void *workspace,
+                                                   rnntOptions options) {
+    if (!chunk_frames || !hyp_lengths || !scores || !all_done || !frame_base || ((uintptr_t)frame_base & 3) != 0)
+        return RNNT_STATUS_INVALID_VALUE;
+    if (enc_frames < 0 || enc_frames > options.maxT || (enc_frames > 0 && !enc)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st =
+        check_greedy_stream(options.maxT, slots, enc_width, joint_size, alphabet_size, joint_dtype, workspace, options);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_greedy_stream_feed(enc, enc_frames, chunk_frames, reset, final_chunk, max_symbols, max_per_frame,
+                                              hyp_lengths, scores, all_done, frame_base, enc_width, joint_size, alphabet_size, slots,
+                                              options.maxT, joint_dtype, workspace, (hipStream_t)options.stream));
 }
 
 // The beam stream (include/rnnt.h).  enc_width 1: step and results do not reach W1 / b1, which follow the beam workspace.
 static bool aligned4(const void *p) { return (((uintptr_t)p) & 3) == 0; }
 
 static rnntStatus_t check_beam_stream(int max_chunk_frames, int slots, int beam, int max_hyp_len, int enc_width, int joint_size,
-                                      int alphabet_size, int joint_dtype, const void *workspace, const rnntOptions &o) {
+                                      int alphabet_size, int joint_dtype, const void *workspace, const rnntOptions &o,
+                                      bool timed = false) {
     if (!workspace || ((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
     if (beam < 1 || beam > 16 || slots < 1 || (long long)slots * beam > 1024 || max_hyp_len < 1) return RNNT_STATUS_INVALID_VALUE;
     const rnntStatus_t st = check_greedy(max_chunk_frames, joint_size, alphabet_size, slots, joint_dtype, o);
     if (st != RNNT_STATUS_SUCCESS) return st;
     size_t n = 0;
     if (beam_stream_workspace_bytes(max_chunk_frames, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype,
-                                    &n) != hipSuccess)
+                                    timed, &n) != hipSuccess)
         return RNNT_STATUS_INVALID_VALUE;
     return RNNT_STATUS_SUCCESS;
 }
@@ -835,7 +875,7 @@ rnntStatus_t get_rnnt_beam_stream_workspace_size(int max_chunk_frames, int slots
     if (!size_bytes) return RNNT_STATUS_INVALID_VALUE;
     if (joint_dtype != 0 && joint_dtype != 1) return RNNT_STATUS_INVALID_VALUE;
     return beam_stream_workspace_bytes(max_chunk_frames, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype,
-                                       size_bytes) == hipSuccess
+                                       false, size_bytes) == hipSuccess
                ? RNNT_STATUS_SUCCESS
                : RNNT_STATUS_INVALID_VALUE;
 }
@@ -848,7 +888,7 @@ rnntStatus_t compute_rnnt_beam_stream_begin(const float *W1, const float *b1, co
                                               workspace, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
     return from_hip(launch_beam_stream_begin(W1, b1, W2, b2, enc_width, joint_size, alphabet_size, slots, options.maxT, beam,
-                                             max_hyp_len, joint_dtype, workspace, (hipStream_t)options.stream));
+                                             max_hyp_len, joint_dtype, false, workspace, (hipStream_t)options.stream));
 }
 
 rnntStatus_t compute_rnnt_beam_stream_feed(const float *enc, int enc_frames, const int *chunk_frames, const int *reset,
@@ -861,7 +901,7 @@ rnntStatus_t compute_rnnt_beam_stream_feed(const float *enc, int enc_frames, con
                                               workspace, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
     return from_hip(launch_beam_stream_feed(enc, enc_frames, chunk_frames, reset, final_chunk, enc_width, joint_size, alphabet_size,
-                                            slots, options.maxT, beam, max_hyp_len, joint_dtype, workspace,
+                                            slots, options.maxT, beam, max_hyp_len, joint_dtype, false, workspace,
                                             (hipStream_t)options.stream));
 }
 
@@ -876,7 +916,7 @@ rnntStatus_t compute_rnnt_beam_stream_step(const float *pred_proj, int *parents,
         check_beam_stream(options.maxT, slots, beam, max_hyp_len, 1, joint_size, alphabet_size, joint_dtype, workspace, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
     return from_hip(launch_beam_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, slots,
-                                     options.maxT, beam, max_hyp_len, options.blank_label, joint_dtype, workspace,
+                                     options.maxT, beam, max_hyp_len, options.blank_label, joint_dtype, false, workspace,
                                      (hipStream_t)options.stream));
 }
 
@@ -888,8 +928,126 @@ rnntStatus_t compute_rnnt_beam_stream_results(int *hyps, int *hyp_lengths, float
     const rnntStatus_t st =
         check_beam_stream(options.maxT, slots, beam, max_hyp_len, 1, joint_size, alphabet_size, joint_dtype, workspace, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
-    return from_hip(launch_beam_results(hyps, hyp_lengths, scores, stable_lengths, joint_size, alphabet_size, slots, options.maxT, beam,
-                                        max_hyp_len, joint_dtype, workspace, (hipStream_t)options.stream));
+    return from_hip(launch_beam_results(hyps, hyp_lengths, scores, stable_lengths, nullptr, nullptr, nullptr, joint_size, alphabet_size,
+                                        slots, options.maxT, beam, max_hyp_len, joint_dtype, workspace, (hipStream_t)options.stream));
+}
+
+// The timed beam searches (include/rnnt.h): the same checks and launches on the workspace layout that also holds the
+// {frame, log-probability} rows.
+rnntStatus_t get_rnnt_beam_timed_workspace_size(int maxT, int minibatch, int beam, int joint_size, int alphabet_size, int joint_dtype,
+                                                size_t *size_bytes) {
+    if (!size_bytes) return RNNT_STATUS_INVALID_VALUE;
+    if (joint_dtype != 0 && joint_dtype != 1) return RNNT_STATUS_INVALID_VALUE;
+    return beam_workspace_bytes(maxT, minibatch, beam, joint_size, alphabet_size, joint_dtype, true, size_bytes) == hipSuccess
+               ? RNNT_STATUS_SUCCESS
+               : RNNT_STATUS_INVALID_VALUE;
+}
+
+rnntStatus_t compute_rnnt_beam_timed_begin(const float *enc_proj, const int *frame_lengths, const float *W2, const float *b2,
+                                           int joint_size, int alphabet_size, int minibatch, int beam, int joint_dtype,
+                                           void *workspace, rnntOptions options) {
+    if (!enc_proj || !frame_lengths || !W2 || !b2 || !aligned4(enc_proj) || !aligned4(frame_lengths) || !aligned4(W2) || !aligned4(b2))
+        return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st =
+        check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options, true);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_begin(enc_proj, frame_lengths, W2, b2, joint_size, alphabet_size, minibatch, options.maxT, beam,
+                                      joint_dtype, true, workspace, (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_beam_timed_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits, int *topk_symbols,
+                                          float *lse, int joint_size, int alphabet_size, int minibatch, int beam, int joint_dtype,
+                                          void *workspace, rnntOptions options) {
+    if (!pred_proj || !parents || !emitted) return RNNT_STATUS_INVALID_VALUE;
+    if (!aligned4(pred_proj) || !aligned4(parents) || !aligned4(emitted) || !aligned4(topk_logits) || !aligned4(topk_symbols) ||
+        !aligned4(lse))
+        return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st =
+        check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options, true);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size,
+                                     minibatch, options.maxT, beam, options.maxT, options.blank_label, joint_dtype, true, workspace,
+                                     (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_beam_timed_results(int *hyps, int *hyp_lengths, float *scores, int *hyp_frames, float *hyp_logp,
+                                             int joint_size, int alphabet_size, int minibatch, int beam, int joint_dtype,
+                                             void *workspace, rnntOptions options) {
+    if (!hyps || !hyp_lengths || !scores || !hyp_frames || !hyp_logp) return RNNT_STATUS_INVALID_VALUE;
+    if (!aligned4(hyps) || !aligned4(hyp_lengths) || !aligned4(scores) || !aligned4(hyp_frames) || !aligned4(hyp_logp))
+        return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st =
+        check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options, true);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_results(hyps, hyp_lengths, scores, nullptr, hyp_frames, hyp_logp, nullptr, joint_size, alphabet_size,
+                                        minibatch, options.maxT, beam, options.maxT, joint_dtype, workspace,
+                                        (hipStream_t)options.stream));
+}
+
+rnntStatus_t get_rnnt_beam_stream_timed_workspace_size(int max_chunk_frames, int slots, int beam, int max_hyp_len, int enc_width,
+                                                       int joint_size, int alphabet_size, int joint_dtype, size_t *size_bytes) {
+    if (!size_bytes) return RNNT_STATUS_INVALID_VALUE;
+    if (joint_dtype != 0 && joint_dtype != 1) return RNNT_STATUS_INVALID_VALUE;
+    return beam_stream_workspace_bytes(max_chunk_frames, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype,
+                                       true, size_bytes) == hipSuccess
+               ? RNNT_STATUS_SUCCESS
+               : RNNT_STATUS_INVALID_VALUE;
+}
+
+rnntStatus_t compute_rnnt_beam_stream_timed_begin(const float *W1, const float *b1, const float *W2, const float *b2, int enc_width,
+                                                  int joint_size, int alphabet_size, int slots, int beam, int max_hyp_len,
+                                                  int joint_dtype, void *workspace, rnntOptions options) {
+    if (!W1 || !b1 || !W2 || !b2 || !aligned4(W1) || !aligned4(b1) || !aligned4(W2) || !aligned4(b2)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_beam_stream(options.maxT, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype,
+                                              workspace, options, true);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_stream_begin(W1, b1, W2, b2, enc_width, joint_size, alphabet_size, slots, options.maxT, beam,
+                                             max_hyp_len, joint_dtype, true, workspace, (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_beam_stream_timed_feed(const float *enc, int enc_frames, const int *chunk_frames, const int *reset,
+                                                 const int *final_chunk, int enc_width, int joint_size, int alphabet_size, int slots,
+                                                 int beam, int max_hyp_len, int joint_dtype, void *workspace, rnntOptions options) {
+    if (!chunk_frames || !aligned4(enc) || !aligned4(chunk_frames) || !aligned4(reset) || !aligned4(final_chunk))
+        return RNNT_STATUS_INVALID_VALUE;
+    if (enc_frames < 0 || enc_frames > options.maxT || (enc_frames > 0 && !enc)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_beam_stream(options.maxT, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype,
+                                              workspace, options, true);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_stream_feed(enc, enc_frames, chunk_frames, reset, final_chunk, enc_width, joint_size, alphabet_size,
+                                            slots, options.maxT, beam, max_hyp_len, joint_dtype, true, workspace,
+                                            (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_beam_stream_timed_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits,
+                                                 int *topk_symbols, float *lse, int joint_size, int alphabet_size, int slots, int beam,
+                                                 int max_hyp_len, int joint_dtype, void *workspace, rnntOptions options) {
+    if (!pred_proj || !parents || !emitted) return RNNT_STATUS_INVALID_VALUE;
+    if (!aligned4(pred_proj) || !aligned4(parents) || !aligned4(emitted) || !aligned4(topk_logits) || !aligned4(topk_symbols) ||
+        !aligned4(lse))
+        return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st =
+        check_beam_stream(options.maxT, slots, beam, max_hyp_len, 1, joint_size, alphabet_size, joint_dtype, workspace, options, true);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, slots,
+                                     options.maxT, beam, max_hyp_len, options.blank_label, joint_dtype, true, workspace,
+                                     (hipStream_t)options.stream));
+}
+
+rnntStatus_t compute_rnnt_beam_stream_timed_results(int *hyps, int *hyp_lengths, float *scores, int *stable_lengths, int *hyp_frames,
+                                                    float *hyp_logp, int *timed_stable_lengths, int joint_size, int alphabet_size,
+                                                    int slots, int beam, int max_hyp_len, int joint_dtype, void *workspace,
+                                                    rnntOptions options) {
+    if (!hyps || !hyp_lengths || !scores || !hyp_frames || !hyp_logp) return RNNT_STATUS_INVALID_VALUE;
+    if (!aligned4(hyps) || !aligned4(hyp_lengths) || !aligned4(scores) || !aligned4(stable_lengths) || !aligned4(hyp_frames) ||
+        !aligned4(hyp_logp) || !aligned4(timed_stable_lengths))
+        return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st =
+        check_beam_stream(options.maxT, slots, beam, max_hyp_len, 1, joint_size, alphabet_size, joint_dtype, workspace, options, true);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_results(hyps, hyp_lengths, scores, stable_lengths, hyp_frames, hyp_logp, timed_stable_lengths,
+                                        joint_size, alphabet_size, slots, options.maxT, beam, max_hyp_len, joint_dtype, workspace,
+                                        (hipStream_t)options.stream));
 }
 
 // The LSTM layer for training (include/rnnt.h).  Everything is checked before anything is enqueued.

@@ -19,6 +19,7 @@ for all hypotheses at once, the joint + argmax + state update in one library cal
 per step."""
 from __future__ import annotations
 
+import math
 from typing import List, Optional
 
 import torch
@@ -161,7 +162,8 @@ def _pred_step(pred_net, tokens: torch.Tensor, states):
 
 @torch.no_grad()
 def greedy_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, max_length=None,
-                        max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY, prediction: str = "torch"):
+                        max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY, prediction: str = "torch",
+                        token_times: bool = False):
     """Greedy search over encoder outputs enc [B, T', H] with frame_lengths [B] (the model in eval mode).  See greedy_decode_batch."""
     global LAST_STEPS
     _check_prediction(prediction)
@@ -175,7 +177,9 @@ def greedy_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, m
     else:
         maxsym = torch.full((B,), int(max_length), dtype=torch.int32, device=dev)
         N = max(1, int(max_length))
-    jg = GreedyJoint(model.joint)  # (the current weights: a model may be trained between two decodes)
+    # (the current weights: a model may be trained between two decodes)
+    jg = GreedyJoint(model.joint, token_times=True) if token_times else GreedyJoint(model.joint)
+    done = lambda: (jg.hyps, jg.lengths, jg.scores, jg.frames, jg.logp) if token_times else (jg.hyps, jg.lengths, jg.scores)  # noqa: E731
     key = (dev, torch.cuda.current_stream(dev).cuda_stream) if enc.is_cuda else None
     jg._ws = _WORKSPACES.get(key)  # the workspace of the last decode on this stream, when it is large enough
     jg.begin(enc, frame_lengths, maxsym, int(max_symbols_per_frame or 0), N)
@@ -195,7 +199,7 @@ def greedy_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, m
                     jg.grow_hyps()
             pp = ps.step(emitted)
         LAST_STEPS = steps
-        return jg.hyps, jg.lengths, jg.scores
+        return done()
     pred_net = model.prediction
     g, states = _pred_step(pred_net, torch.zeros(B, dtype=torch.int32, device=dev), [None] * len(pred_net.blocks))
     steps = 0
@@ -215,13 +219,13 @@ def greedy_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, m
         states = [(torch.where(mask[None, :, None], h2, h), torch.where(mask[None, :, None], c2, c))
                   for (h2, c2), (h, c) in zip(states2, states)]
     LAST_STEPS = steps
-    return jg.hyps, jg.lengths, jg.scores
+    return done()
 
 
 @torch.no_grad()
 def greedy_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[torch.Tensor] = None, max_length=None,
                         max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY, prediction: str = "torch",
-                        encoder: str = "torch"):
+                        encoder: str = "torch", token_times: bool = False):
     """Greedy decoding of EVERY utterance of a batch at once -> (ids int32 [B, N] zero-padded, lengths int32 [B], scores [B]).
 
     Per utterance the semantics of greedy_decode (utils/decoding.py:21-108): the hypothesis starts from token 0, symbols are
@@ -237,7 +241,12 @@ def greedy_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[t
     `check_every` steps (read_flag).  prediction="engine" steps the prediction network in the library too (PredictionStep:
     compute_rnnt_prednet_step, through W1 into the joint step), so that the loop body is library calls alone; "torch" (the
     default) steps it with the model's own modules.  encoder="engine" runs the encoder in the library (EncoderStream:
-    compute_rnnt_encoder_run, every row in one call); "torch" (the default) runs model.encoder."""
+    compute_rnnt_encoder_run, every row in one call); "torch" (the default) runs model.encoder.
+
+    token_times=True returns (ids, lengths, scores, frames int32 [B, N], logp [B, N]): per token the 0-based encoder frame whose
+    joint evaluation emitted it (-1 past the hypothesis) and the log-softmax of that decision (0 past it) -- the convention of
+    alignment.rnnt_align's token_frames / token_logp, so alignment.token_times and word_times apply.  ids, lengths and scores
+    are bitwise those of token_times=False."""
     _check_prediction(prediction)
     _check_encoder(encoder)
     was_training = model.training
@@ -249,6 +258,8 @@ def greedy_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[t
             frames = torch.full((B,), T, dtype=torch.int32, device=enc.device)
         else:
             frames = reduced_lengths(spec_lengths.to(enc.device), model.hp.time_reduction_factor)
+        if token_times:
+            return greedy_search_batch(model, enc, frames, max_length, max_symbols_per_frame, check_every, prediction, True)
         return greedy_search_batch(model, enc, frames, max_length, max_symbols_per_frame, check_every, prediction)
     finally:
         model.train(was_training)
@@ -271,7 +282,8 @@ _BEAM_WORKSPACES = {}  # (device, stream) -> the beam workspace of the last deco
 
 
 @torch.no_grad()
-def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, beam: int = 4, prediction: str = "torch"):
+def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, beam: int = 4, prediction: str = "torch",
+                      token_times: bool = False):
     """Modified beam search (one symbol per frame) over encoder outputs enc [B, T', H] with frame_lengths [B] (the model in eval
     mode) -> (ids int32 [B, beam, T'] zero-padded, lengths int32 [B, beam], scores [B, beam]): every utterance's n-best, sorted
     by score (empty slots: length 0, score -inf).  See include/rnnt.h for the algorithm; beam = 1 is greedy_search_batch with
@@ -279,13 +291,20 @@ def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, bea
 
     Runs enc.shape[1] steps without reading the host.  Per step the prediction network runs on all B beam rows; its output and
     LSTM state are gathered by `parents`, and the rows that emitted a symbol advance.  prediction="engine": that step is the
-    library's (PredictionStep), as in greedy_search_batch."""
+    library's (PredictionStep), as in greedy_search_batch.
+
+    token_times=True returns two more: frames int32 [B, beam, T'] (-1 padded) and logp [B, beam, T'] (0 padded), per token the
+    frame that emitted it and the log-softmax of that decision.  Where identical sequences were merged, the hypothesis keeps
+    the frames and log-probabilities of its first-ranked member; its score still sums the members."""
     _check_prediction(prediction)
     B, T = enc.shape[0], enc.shape[1]
     K = int(beam)
     dev = enc.device
-    jb = BeamJoint(model.joint, K)  # (the current weights: a model may be trained between two decodes)
+    # (the current weights: a model may be trained between two decodes)
+    jb = BeamJoint(model.joint, K, token_times=True) if token_times else BeamJoint(model.joint, K)
     key = (dev, torch.cuda.current_stream(dev).cuda_stream) if enc.is_cuda else None
+    if token_times and key is not None:
+        key = key + ("timed",)  # (a timed decode keeps a workspace of its own)
     jb._ws = _BEAM_WORKSPACES.get(key)
     jb.begin(enc, frame_lengths)
     if jb._ws is not None:
@@ -317,10 +336,11 @@ def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, bea
 
 @torch.no_grad()
 def beam_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[torch.Tensor] = None, beam: int = 4,
-                      prediction: str = "torch", encoder: str = "torch"):
+                      prediction: str = "torch", encoder: str = "torch", token_times: bool = False):
     """Beam search of EVERY utterance of a batch -> the best hypothesis of each: (ids int32 [B, T'] zero-padded, lengths int32
     [B], scores [B]).  spec_lengths are spectrogram frames, reduced as greedy_decode_batch reduces them; None: every frame.
-    encoder= as in greedy_decode_batch."""
+    encoder= as in greedy_decode_batch.  token_times=True: (ids, lengths, scores, frames int32 [B, T'], logp [B, T']) of the
+    best hypothesis, as beam_search_batch defines them."""
     _check_prediction(prediction)
     _check_encoder(encoder)
     was_training = model.training
@@ -332,6 +352,8 @@ def beam_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[tor
             frames = torch.full((B,), T, dtype=torch.int32, device=enc.device)
         else:
             frames = reduced_lengths(spec_lengths.to(enc.device), model.hp.time_reduction_factor)
+        if token_times:
+            return tuple(x[:, 0] for x in beam_search_batch(model, enc, frames, beam, prediction, True))
         ids, lengths, scores = beam_search_batch(model, enc, frames, beam, prediction)
         return ids[:, 0], lengths[:, 0], scores[:, 0]
     finally:
@@ -453,6 +475,7 @@ class StreamingGreedyDecoder(_StreamingSlots):
     emits nothing more until the next start.
 
     hypotheses() -> (ids [slots, N] zero-padded, lengths [slots], scores [slots]) of each slot's stream since its start.
+    token_times=True adds timed_hypotheses() -> (ids, frames, logp), and the equivalence below covers them.
 
     A stream delivered through any chunking that follows the rule above, in any slot, beside any other traffic, ends with the
     ids, length and score of the same stream fed in one call to a 1-slot decoder: bitwise on an MI355X (every kernel on the path
@@ -464,13 +487,14 @@ class StreamingGreedyDecoder(_StreamingSlots):
     the fallback rules of those three classes."""
 
     def __init__(self, model, slots: int, max_chunk_frames: int, max_length: Optional[int] = None,
-                 max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY):
+                 max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY, token_times: bool = False):
         self._init_slots(model, slots, max_chunk_frames)
         S = self.S
         self.check_every = max(1, int(check_every))
         self.max_length = None if max_length is None else int(max_length)
+        self.token_times = bool(token_times)
         with self._eval():
-            self.gj = GreedyStreamJoint(model.joint)
+            self.gj = GreedyStreamJoint(model.joint, token_times=True) if token_times else GreedyStreamJoint(model.joint)
             dev = next(model.parameters()).device
             N = max(1, self.max_length) if self.max_length is not None else self.Te + 16
             self.gj.begin(S, self.Te, int(max_symbols_per_frame or 0), N, device=dev)
@@ -533,6 +557,17 @@ class StreamingGreedyDecoder(_StreamingSlots):
         ids = torch.where(torch.arange(h.shape[1], device=h.device)[None, :] < n[:, None], h, 0)
         return ids, n.clone(), self.gj.scores.clone()
 
+    def timed_hypotheses(self):
+        """(ids int32 [slots, N] zero-padded, frames int32 [slots, N] -1 padded, logp [slots, N] 0 padded) of each slot's stream
+        since its start: per token the encoder frame that emitted it, counted from the slot's start across all its chunks, and
+        the log-softmax of that decision.  Greedy never rewrites a token: everything reported is final.  Needs token_times=True."""
+        if not self.token_times:
+            raise RuntimeError("timed_hypotheses() needs a decoder built with token_times=True")
+        h, n = self.gj.hyps, self.gj.lengths
+        live = torch.arange(h.shape[1], device=h.device)[None, :] < n[:, None]
+        return (torch.where(live, h, 0), torch.where(live, self.gj.frames, -1),
+                torch.where(live, self.gj.logp, torch.zeros_like(self.gj.logp)))
+
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # Streaming beam search
@@ -573,8 +608,10 @@ class StreamingBeamDecoder(_StreamingSlots):
 
     DEFAULT_MAX_LENGTH = 512
 
-    def __init__(self, model, slots: int, max_chunk_frames: int, beam: int = 4, max_length: Optional[int] = None):
+    def __init__(self, model, slots: int, max_chunk_frames: int, beam: int = 4, max_length: Optional[int] = None,
+                 token_times: bool = False):
         K = int(beam)
+        self.token_times = bool(token_times)
         if not 1 <= K <= 16:
             raise ValueError(f"beam must be in 1 ... 16, got {beam}")
         if int(slots) * K > BeamStreamJoint.MAX_ROWS:
@@ -586,7 +623,7 @@ class StreamingBeamDecoder(_StreamingSlots):
         S = self.S
         self.K, self.max_length = K, N
         with self._eval():
-            self.bj = BeamStreamJoint(model.joint, K)
+            self.bj = BeamStreamJoint(model.joint, K, token_times=True) if token_times else BeamStreamJoint(model.joint, K)
             dev = next(model.parameters()).device
             self.bj.begin(S, self.Te, N, device=dev)
             W1 = self.bj.W1 if self.bj.engine else model.joint.W1
@@ -620,19 +657,42 @@ class StreamingBeamDecoder(_StreamingSlots):
                 pp = self.ps.step(emitted, parents)  # (after the last frame too: the next feed goes on from it)
             self.pp = pp
             LAST_STEPS = steps
-            ids, lengths, _, stable = self.bj.results()
+            ids, lengths, _, stable = self.bj.results()[:4]
         return ids[:, 0], lengths[:, 0], stable
 
     def hypotheses(self):
         """The best hypothesis of each slot's stream since its start: (ids int32 [slots, N] zero-padded, lengths int32 [slots],
         scores [slots])."""
-        ids, lengths, scores, _ = self.bj.results()
+        ids, lengths, scores = self.bj.results()[:3]
         return ids[:, 0], lengths[:, 0], scores[:, 0]
 
     def nbest(self):
         """(ids int32 [slots, beam, N] zero-padded, lengths int32 [slots, beam], scores [slots, beam]), best first."""
-        ids, lengths, scores, _ = self.bj.results()
+        ids, lengths, scores = self.bj.results()[:3]
         return ids, lengths, scores
+
+    def _timed(self):
+        if not self.token_times:
+            raise RuntimeError("timed results need a decoder built with token_times=True")
+        return self.bj.results()
+
+    def timed_hypotheses(self):
+        """The best hypothesis of each slot with its times: (ids int32 [slots, N] zero-padded, frames int32 [slots, N] -1 padded,
+        logp [slots, N] 0 padded); frames count encoder frames from the slot's start across all its chunks.  A hypothesis that
+        absorbed merged candidates carries the times of its first-ranked member.  Needs token_times=True."""
+        r = self._timed()
+        return r[0][:, 0], r[4][:, 0], r[5][:, 0]
+
+    def timed_nbest(self):
+        """(ids [slots, beam, N], lengths [slots, beam], scores [slots, beam], frames [slots, beam, N], logp [slots, beam, N]),
+        best first.  Needs token_times=True."""
+        r = self._timed()
+        return r[0], r[1], r[2], r[4], r[5]
+
+    def timed_stable_lengths(self):
+        """int32 [slots]: the leading tokens of a slot on which every hypothesis of its beam agrees in token AND emission frame:
+        their ids and times are final.  Never more than feed()'s `stable`.  Needs token_times=True."""
+        return self._timed()[6]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -655,6 +715,7 @@ class StreamingTranscriber:
         from .features import StreamingFrontEnd
 
         dev = next(model.parameters()).device
+        self.hp, self.sample_rate = hp, sample_rate
         self.front = StreamingFrontEnd(hp, sample_rate, slots, max_chunk_samples, int(model.encoder.reduce.factor), norm, device=dev)
         if beam is None:
             self.decoder = StreamingGreedyDecoder(model, slots, self.front.max_rows, **decoder_kwargs)
@@ -676,3 +737,50 @@ class StreamingTranscriber:
         if not hasattr(self.decoder, "nbest"):
             raise RuntimeError("nbest() needs beam search: build the StreamingTranscriber with beam=")
         return self.decoder.nbest()
+
+    def words(self, slot: int, encoder=None):
+        """The words of slot's current (best) hypothesis with times and confidences -> (words, final): words is a list of (word,
+        start_seconds, end_seconds, confidence) and the first `final` of them can no longer change.  `encoder` is the character
+        vocabulary the model was trained with (a features.CharEncoder; None: the reference's default vocabulary, CharEncoder()).
+        Needs token_times=True (a decoder keyword).
+
+        A word starts at the start of the frame that emitted its first token and ends at the end of the frame that emitted its
+        last one (alignment.word_times x alignment.frame_seconds).  Its confidence is exp(min log-probability of its tokens):
+        the weakest decision inside the word -- a product would punish long words, a mean would hide one bad letter.  final:
+        for beam search the words that lie wholly inside the timed stable prefix (every hypothesis of the beam agrees on their
+        tokens and frames); greedy never rewrites, so all words are final.  "Final" is about what was reported: a stream that
+        goes on may still append letters to the last word until a space follows it."""
+        from .alignment import frame_seconds
+        from .features import CharEncoder
+
+        dec = self.decoder
+        if hasattr(dec, "timed_stable_lengths"):  # beam: one results call gives the best hypothesis and the timed stable length
+            r = dec._timed()
+            ids, frames, logp, stable = r[0][slot, 0].cpu(), r[4][slot, 0].cpu(), r[5][slot, 0].cpu(), int(r[6][slot])
+        else:  # greedy never rewrites: every token reported is final
+            ids, frames, logp = (x[slot].cpu() for x in dec.timed_hypotheses())
+            stable = None
+        n = int((frames >= 0).sum())
+        return timed_words(ids[:n], frames[:n], logp[:n], encoder if encoder is not None else CharEncoder(),
+                           frame_seconds(self.hp, self.sample_rate), stable)
+
+
+def timed_words(ids, frames, logp, encoder, seconds_per_frame: float, stable_tokens: Optional[int] = None):
+    """One hypothesis (ids, emission frames, log-probabilities per token) -> (words, final) as StreamingTranscriber.words
+    describes them.  stable_tokens: the leading tokens that are final (None: all)."""
+    from .alignment import word_times
+
+    n = len(ids)
+    by_frame = word_times(ids, frames, encoder)
+    by_index = word_times(ids, list(range(n)), encoder)  # (the same split: first and last token index of every word)
+    lp = [float(v) for v in torch.as_tensor(logp).flatten().tolist()]
+    idl = [int(v) for v in torch.as_tensor(ids).flatten().tolist()]
+    space = encoder.index.get(" ")
+    stable = n if stable_tokens is None else int(stable_tokens)
+    words, final = [], 0
+    for (w, f0, f1), (_, i0, i1) in zip(by_frame, by_index):
+        conf = math.exp(min(lp[i] for i in range(i0, i1 + 1) if idl[i] != space))
+        words.append((w, f0 * seconds_per_frame, (f1 + 1) * seconds_per_frame, conf))
+        if i1 < stable and final == len(words) - 1:
+            final += 1
+    return words, final

@@ -415,10 +415,17 @@ class GreedyJoint:
     begin(enc [B, T, H], frame_lengths [B], max_symbols [B] or None, max_per_frame, max_hyp_len) allocates the outputs
     (`hyps` [B, max_hyp_len] zero-filled, `lengths`, `scores`, `emitted`, `all_done`); step(pred [B, H]) advances every hypothesis
     by one decision and returns `emitted` (the symbol per row, or -1).  all_done[0]: 0 running, 1 finished, 2 paused on a full
-    `hyps` buffer (grow_hyps() resumes them)."""
+    `hyps` buffer (grow_hyps() resumes them).
 
-    def __init__(self, joint: "JointLoss", joint_dtype: str = "auto"):
+    token_times=True (compute_rnnt_greedy_step_timed): begin also allocates `frames` int32 [B, max_hyp_len] (-1 where no token is)
+    and `logp` [B, max_hyp_len] (0 there): per token the encoder frame whose joint evaluation emitted it and the log-softmax of
+    that decision (float32 on the engine; the dtype of `scores` on the torch route).  ids, lengths and scores are bitwise those
+    of the untimed step."""
+
+    def __init__(self, joint: "JointLoss", joint_dtype: str = "auto", token_times: bool = False):
         self.joint = joint
+        self.token_times = bool(token_times)
+        self._frame_base = None  # (the stream: frames of a slot's earlier chunks)
         self.blank = int(joint.blank_label)
         W1, b1, W2, b2 = (x.detach() for x in (joint.W1, joint.b1, joint.W2, joint.b2))
         J, V = W2.shape
@@ -451,9 +458,11 @@ class GreedyJoint:
         frames = frame_lengths.to(device=dev, dtype=torch.int32)
         maxsym = None if max_symbols is None else max_symbols.to(device=dev, dtype=torch.int32)
         if not self.engine:
-            return self._torch_begin(enc, frames, maxsym, max_per_frame)
+            self._torch_begin(enc, frames, maxsym, max_per_frame)
+            return self._new_times(B, max_hyp_len, dev)
         lib = _lib.load()
         self.scores = torch.zeros(B, dtype=torch.float32, device=dev)
+        self._new_times(B, max_hyp_len, dev)
         ep = (torch.matmul(enc.float(), self.W1) + self.b1).contiguous()
         frames = frames.contiguous()
         self._keep = (frames, maxsym.contiguous() if maxsym is not None else None)
@@ -470,12 +479,26 @@ class GreedyJoint:
                                                self.dtype, self._ws.data_ptr(), self._opts)
         _lib.check(st, "compute_rnnt_greedy_begin")
 
+    def _new_times(self, B, max_hyp_len, dev):
+        if self.token_times:
+            self.frames = torch.full((B, max_hyp_len), -1, dtype=torch.int32, device=dev)
+            self.logp = torch.zeros(B, max_hyp_len, dtype=self.scores.dtype, device=dev)
+
     def step(self, pred=None, logit_stats=None, *, pred_proj=None):
         """pred [B, H]: the prediction network's output of every row -> emitted [B] (int32, -1 where nothing was emitted).
         pred_proj [B, Jp] instead of pred: that output already through W1 (PredictionStep); the step skips its matmul."""
         if not self.engine:
             return self._torch_step(pred, pred_proj)
         pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _projected_operand(pred_proj, self.Jp)
+        if self.token_times:
+            fb = self._frame_base
+            st = _lib.load().compute_rnnt_greedy_step_timed(
+                pp.data_ptr(), self.hyps.data_ptr(), self.frames.data_ptr(), self.logp.data_ptr(), self.hyps.shape[1],
+                self.lengths.data_ptr(), self.scores.data_ptr(), self.emitted.data_ptr(), self.all_done.data_ptr(),
+                None if logit_stats is None else logit_stats.data_ptr(), None if fb is None else fb.data_ptr(), self.Jp, self.V,
+                self.B, self.dtype, self._ws.data_ptr(), self._opts)
+            _lib.check(st, "compute_rnnt_greedy_step_timed")
+            return self.emitted
         st = _lib.load().compute_rnnt_greedy_step(pp.data_ptr(), self.hyps.data_ptr(), self.hyps.shape[1], self.lengths.data_ptr(),
                                                   self.scores.data_ptr(), self.emitted.data_ptr(), self.all_done.data_ptr(),
                                                   None if logit_stats is None else logit_stats.data_ptr(), self.Jp, self.V, self.B,
@@ -484,10 +507,15 @@ class GreedyJoint:
         return self.emitted
 
     def grow_hyps(self):
-        """Double the hyps buffer (contents kept): paused hypotheses resume at the next step."""
+        """Double the hyps buffer (contents kept; `frames` and `logp` with it): paused hypotheses resume at the next step."""
         h = self.hyps
         self.hyps = torch.zeros(h.shape[0], 2 * h.shape[1], dtype=h.dtype, device=h.device)
         self.hyps[:, : h.shape[1]] = h
+        if self.token_times:
+            f, l = self.frames, self.logp
+            self.frames = torch.full((h.shape[0], 2 * h.shape[1]), -1, dtype=f.dtype, device=f.device)
+            self.logp = torch.zeros(h.shape[0], 2 * h.shape[1], dtype=l.dtype, device=l.device)
+            self.frames[:, : h.shape[1]], self.logp[:, : h.shape[1]] = f, l
 
     # ---- torch composition: the same state machine (greedy_update_kernel) on JointLoss.logits
     def _torch_begin(self, enc, frames, maxsym, max_per_frame):
@@ -516,6 +544,10 @@ class GreedyJoint:
         emit = live & (k != self.blank)
         pos = self._n.clamp(max=N - 1)[:, None]
         self.hyps.scatter_(1, pos, torch.where(emit, k.to(torch.int32), self.hyps.gather(1, pos)[:, 0])[:, None])
+        if self.token_times:  # (the frame of this decision: before the cursor moves on)
+            fr = self._t if self._frame_base is None else self._t + self._frame_base
+            self.frames.scatter_(1, pos, torch.where(emit, fr.to(torch.int32), self.frames.gather(1, pos)[:, 0])[:, None])
+            self.logp.scatter_(1, pos, torch.where(emit, (M - lse).to(self.logp.dtype), self.logp.gather(1, pos)[:, 0])[:, None])
         self._n = self._n + emit.long()
         self._nf = torch.where(emit, self._nf + 1, self._nf)
         adv = live & ~emit  # blank: next frame
@@ -555,13 +587,17 @@ class GreedyStreamJoint(GreedyJoint):
         self._cap = int(max_per_frame)
         if not self.engine:
             self.scores = torch.zeros(S, dtype=torch.promote_types(self.joint.W2.dtype, torch.float32), device=dev)
+            self._new_times(S, max_hyp_len, dev)
             z = torch.zeros(S, dtype=torch.long, device=dev)
+            self._frame_base = z.clone() if self.token_times else None
             self._t, self._n, self._nf, self._Tb, self._maxsym = z.clone(), z.clone(), z.clone(), z.clone(), z.clone()
             self._done = torch.ones(S, dtype=torch.bool, device=dev)
             self._fin = torch.ones(S, dtype=torch.bool, device=dev)
             return
         self.H = int(self.W1.shape[0])
         self.scores = torch.zeros(S, dtype=torch.float32, device=dev)
+        self._new_times(S, max_hyp_len, dev)
+        self._frame_base = torch.zeros(S, dtype=torch.int32, device=dev) if self.token_times else None
         with torch.cuda.device(dev):
             nbytes = _lib.greedy_stream_workspace_bytes(T, S, self.H, self.Jp, self.V, self.dtype)
             if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
@@ -592,6 +628,12 @@ class GreedyStreamJoint(GreedyJoint):
         fr, rs, fi, ms = cv(frames), cv(reset), cv(final), cv(max_symbols)
         self._feed_args = (enc, fr, rs, fi, ms)  # (alive until the launches have read them)
         ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        if self.token_times:
+            st = _lib.load().compute_rnnt_greedy_stream_feed_timed(
+                ptr(enc) if Te > 0 else None, Te, fr.data_ptr(), ptr(rs), ptr(fi), ptr(ms), self._cap, self.lengths.data_ptr(),
+                self.scores.data_ptr(), self.all_done.data_ptr(), self._frame_base.data_ptr(), self.H, self.Jp, self.V, S, self.dtype,
+                self._ws.data_ptr(), self._opts)
+            return _lib.check(st, "compute_rnnt_greedy_stream_feed_timed")
         st = _lib.load().compute_rnnt_greedy_stream_feed(ptr(enc) if Te > 0 else None, Te, fr.data_ptr(), ptr(rs), ptr(fi), ptr(ms),
                                                          self._cap, self.lengths.data_ptr(), self.scores.data_ptr(),
                                                          self.all_done.data_ptr(), self.H, self.Jp, self.V, S, self.dtype,
@@ -604,6 +646,8 @@ class GreedyStreamJoint(GreedyJoint):
         vec = lambda x, d: torch.full((S,), d, dtype=torch.long, device=dev) if x is None else torch.as_tensor(x).to(dev).reshape(S).long()  # noqa: E731
         rs, fi = vec(reset, 0) != 0, vec(final, 0) != 0
         ms = vec(max_symbols, 2**31 - 1).clamp(min=0)
+        if self.token_times:  # (the frames of the chunk the slot leaves; a reset: frame 0 again)
+            self._frame_base = torch.where(rs, 0, self._frame_base + self._Tb)
         self._n = torch.where(rs, 0, self._n)
         self.scores = torch.where(rs, torch.zeros_like(self.scores), self.scores)
         self._maxsym = torch.where(rs, ms, self._maxsym)
@@ -630,12 +674,17 @@ class BeamJoint:
     (in the model's dtype; per-utterance bookkeeping on the host).
 
     begin(enc [B, T, H], frame_lengths [B]); step(pred [B beam, H]) -> (parents, emitted) [B beam] int32; results() ->
-    (hyps [B, beam, T] int32 zero-padded, lengths [B, beam] int32, scores [B, beam]), best first."""
+    (hyps [B, beam, T] int32 zero-padded, lengths [B, beam] int32, scores [B, beam]), best first.
 
-    def __init__(self, joint: "JointLoss", beam: int = 4, joint_dtype: str = "auto"):
+    token_times=True (compute_rnnt_beam_timed_*): results() returns two more, frames int32 [B, beam, T] (-1 padded) and logp
+    [B, beam, T] (0 padded): per token the frame that emitted it and the log-softmax of that decision.  A hypothesis that
+    absorbed merged candidates keeps the rows of its first-ranked member; its score is still the sum over the members."""
+
+    def __init__(self, joint: "JointLoss", beam: int = 4, joint_dtype: str = "auto", token_times: bool = False):
         if not 1 <= int(beam) <= 16:
             raise ValueError("BeamJoint: beam must be in 1 ... 16")
         self.K = int(beam)
+        self.token_times = bool(token_times)
         g = GreedyJoint(joint, joint_dtype)  # (the same engine / torch decision and padding)
         self.joint, self.blank, self.V, self.engine = joint, g.blank, g.V, g.engine
         if self.engine:
@@ -655,15 +704,18 @@ class BeamJoint:
         ep = (torch.matmul(enc.float(), self.W1) + self.b1).contiguous()
         self._keep = frames
         with torch.cuda.device(dev):
-            nbytes = _lib.beam_workspace_bytes(T, B, self.K, self.Jp, self.V, self.dtype)
+            size = _lib.beam_timed_workspace_bytes if self.token_times else _lib.beam_workspace_bytes
+            nbytes = size(T, B, self.K, self.Jp, self.V, self.dtype)
             if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
                 self._ws = _new_workspace(nbytes, dev)
             elif _WORKSPACE_FILL is not None:
                 self._ws.fill_(int(_WORKSPACE_FILL))
             self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
-            st = _lib.load().compute_rnnt_beam_begin(ep.data_ptr(), frames.data_ptr(), self.W2.data_ptr(), self.b2.data_ptr(),
-                                                     self.Jp, self.V, B, self.K, self.dtype, self._ws.data_ptr(), self._opts)
-        _lib.check(st, "compute_rnnt_beam_begin")
+            lib = _lib.load()
+            fn = lib.compute_rnnt_beam_timed_begin if self.token_times else lib.compute_rnnt_beam_begin
+            st = fn(ep.data_ptr(), frames.data_ptr(), self.W2.data_ptr(), self.b2.data_ptr(), self.Jp, self.V, B, self.K, self.dtype,
+                    self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_beam_timed_begin" if self.token_times else "compute_rnnt_beam_begin")
 
     def step(self, pred=None, topk_logits=None, topk_symbols=None, lse=None, *, pred_proj=None):
         """pred [B beam, H]: the prediction network's output of every slot -> (parents, emitted), int32 [B beam].
@@ -672,10 +724,11 @@ class BeamJoint:
             return self._torch_step(pred, pred_proj)
         pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _projected_operand(pred_proj, self.Jp)
         ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
-        st = _lib.load().compute_rnnt_beam_step(pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(), ptr(topk_logits),
-                                                ptr(topk_symbols), ptr(lse), self.Jp, self.V, self.B, self.K, self.dtype,
-                                                self._ws.data_ptr(), self._opts)
-        _lib.check(st, "compute_rnnt_beam_step")
+        lib = _lib.load()
+        fn = lib.compute_rnnt_beam_timed_step if self.token_times else lib.compute_rnnt_beam_step
+        st = fn(pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(), ptr(topk_logits), ptr(topk_symbols), ptr(lse),
+                self.Jp, self.V, self.B, self.K, self.dtype, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_beam_timed_step" if self.token_times else "compute_rnnt_beam_step")
         return self.parents, self.emitted
 
     def results(self):
@@ -686,6 +739,14 @@ class BeamJoint:
         hyps = torch.empty(B, K, T, dtype=torch.int32, device=dev)
         lengths = torch.empty(B, K, dtype=torch.int32, device=dev)
         scores = torch.empty(B, K, dtype=torch.float32, device=dev)
+        if self.token_times:
+            frames = torch.empty(B, K, T, dtype=torch.int32, device=dev)
+            logp = torch.empty(B, K, T, dtype=torch.float32, device=dev)
+            st = _lib.load().compute_rnnt_beam_timed_results(hyps.data_ptr(), lengths.data_ptr(), scores.data_ptr(), frames.data_ptr(),
+                                                             logp.data_ptr(), self.Jp, self.V, B, K, self.dtype, self._ws.data_ptr(),
+                                                             self._opts)
+            _lib.check(st, "compute_rnnt_beam_timed_results")
+            return hyps, lengths, scores, frames, logp
         st = _lib.load().compute_rnnt_beam_results(hyps.data_ptr(), lengths.data_ptr(), scores.data_ptr(), self.Jp, self.V, B, K,
                                                    self.dtype, self._ws.data_ptr(), self._opts)
         _lib.check(st, "compute_rnnt_beam_results")
@@ -697,6 +758,7 @@ class BeamJoint:
         self._Tb = [int(x) for x in frames.clamp(0, enc.shape[1]).tolist()]
         self._t = 0
         self._beams = [[((), 0.0)] for _ in range(self.B)]  # (tokens, float64 score), best first
+        self._times = [[()] for _ in range(self.B)]  # token_times: per hypothesis its (frame, log-probability) pairs
         self._sdtype = torch.promote_types(enc.dtype, torch.float32)
 
     def _torch_step(self, pred, pred_proj=None):
@@ -712,15 +774,16 @@ class BeamJoint:
         top_l, top_v, lse = top_l[:, :K].tolist(), top_v[:, :K].tolist(), lse.tolist()
         for b in range(B):
             if t < self._Tb[b]:
-                self._torch_rank(b, top_l, top_v, lse, parents, emitted)
+                self._torch_rank(b, top_l, top_v, lse, parents, emitted, frame=t)
         dev = self.parents.device
         self.parents = torch.tensor(parents, dtype=torch.int32, device=dev)
         self.emitted = torch.tensor(emitted, dtype=torch.int32, device=dev)
         return self.parents, self.emitted
 
-    def _torch_rank(self, b, top_l, top_v, lse, parents, emitted, blank_l=None, cap=None):
+    def _torch_rank(self, b, top_l, top_v, lse, parents, emitted, blank_l=None, cap=None, frame=0):
         """One frame of beam b (rules 2 - 5 of include/rnnt.h) from every row's top-K lists and logsumexp; parents / emitted of
-        its rows are filled in.  cap (the stream): a hypothesis of cap tokens offers its blank candidate (logit blank_l[r]) alone."""
+        its rows are filled in.  cap (the stream): a hypothesis of cap tokens offers its blank candidate (logit blank_l[r]) alone.
+        frame: this frame's number for the (frame, log-probability) pairs; a merged hypothesis keeps its first member's."""
         K, blank = self.K, self.blank
         beam = self._beams[b]
         cands = []
@@ -730,22 +793,24 @@ class BeamJoint:
             for l, v in offers:
                 sc = s + (float(l) - lse[r])
                 if sc == sc and sc > -math.inf:
-                    cands.append((sc, i, v))
+                    cands.append((sc, i, v, float(l) - lse[r]))
         cands.sort(key=lambda c: (-c[0], c[1], c[2]))
         taken = cands[:K]
         if not taken:
             return  # the beam is carried over
-        merged = []  # [tokens, score, parent, emitted]
-        for sc, i, v in taken:
+        times = self._times[b]
+        merged = []  # [tokens, score, parent, emitted, (frame, log-probability) pairs]
+        for sc, i, v, lp in taken:
             y = beam[i][0] if v == blank else beam[i][0] + (v,)
             hit = next((m for m in merged if m[0] == y), None)
             if hit is None:
-                merged.append([y, sc, i, -1 if v == blank else v])
+                merged.append([y, sc, i, -1 if v == blank else v, times[i] if v == blank else times[i] + ((frame, lp),)])
             else:
                 hi, lo = max(hit[1], sc), min(hit[1], sc)
                 hit[1] = hi + math.log1p(math.exp(lo - hi))
         merged.sort(key=lambda m: -m[1])  # (stable)
         self._beams[b] = [(m[0], m[1]) for m in merged]
+        self._times[b] = [m[4] for m in merged]
         for k in range(len(merged)):
             parents[b * K + k], emitted[b * K + k] = b * K + merged[k][2], merged[k][3]
 
@@ -759,7 +824,20 @@ class BeamJoint:
                 hyps[b, k, : len(y)] = torch.tensor(y, dtype=torch.int32)
                 lengths[b, k], scores[b, k] = len(y), s
         dev = self.parents.device
-        return hyps.to(dev), lengths.to(dev), scores.to(device=dev, dtype=self._sdtype)
+        out = hyps.to(dev), lengths.to(dev), scores.to(device=dev, dtype=self._sdtype)
+        return out + self._torch_times(T) if self.token_times else out
+
+    def _torch_times(self, N):
+        """(frames int32 [B, K, N] -1 padded, logp [B, K, N] 0 padded) of the mirror's beams."""
+        frames = torch.full((self.B, self.K, N), -1, dtype=torch.int32)
+        logp = torch.zeros(self.B, self.K, N, dtype=torch.float64)
+        for b, rows in enumerate(self._times):
+            for k, row in enumerate(rows):
+                if row:
+                    frames[b, k, : len(row)] = torch.tensor([f for f, _ in row], dtype=torch.int32)
+                    logp[b, k, : len(row)] = torch.tensor([l for _, l in row], dtype=torch.float64)
+        dev = self.parents.device
+        return frames.to(dev), logp.to(device=dev, dtype=self._sdtype)
 
 
 class BeamStreamJoint(BeamJoint):
@@ -777,7 +855,11 @@ class BeamStreamJoint(BeamJoint):
     vectors, or None); then step(pred_proj=...) once per encoder frame of the longest chunk (host data: nothing is polled), each
     followed by a prediction-network step -- after the last frame too.  results() -> (hyps [slots, beam, max_hyp_len] zero-padded,
     lengths [slots, beam], scores [slots, beam], stable [slots]) at any time: stable = the common prefix of a slot's hypotheses,
-    the tokens no later frame can change."""
+    the tokens no later frame can change.
+
+    token_times=True (compute_rnnt_beam_stream_timed_*): results() returns three more: frames int32 [slots, beam, max_hyp_len]
+    (-1 padded; counted from the slot's reset across its chunks), logp [slots, beam, max_hyp_len] (0 padded) and timed_stable
+    [slots] = the prefix on which the slot's hypotheses agree in token and emission frame (<= stable): tokens AND times final."""
 
     MAX_ROWS = 1024  # slots * beam: the prediction network's rows
 
@@ -791,28 +873,32 @@ class BeamStreamJoint(BeamJoint):
         self.B, self.T, self.Tc, self.N = S, T, T, N
         self.parents = torch.arange(S * K, dtype=torch.int32, device=dev)
         self.emitted = torch.full((S * K,), -1, dtype=torch.int32, device=dev)
+        lib = _lib.load() if self.engine else None
         if self.engine:  # (the library's own answer: a size it refuses is a shape the stream kernels do not take)
             n = ctypes.c_size_t(0)
-            self.engine = _lib.load().get_rnnt_beam_stream_workspace_size(T, S, K, N, int(self.W1.shape[0]), self.Jp, self.V,
-                                                                          self.dtype, ctypes.byref(n)) == _lib.STATUS_SUCCESS
+            size = lib.get_rnnt_beam_stream_timed_workspace_size if self.token_times else lib.get_rnnt_beam_stream_workspace_size
+            self.engine = size(T, S, K, N, int(self.W1.shape[0]), self.Jp, self.V, self.dtype, ctypes.byref(n)) == _lib.STATUS_SUCCESS
         if not self.engine:
             self._beams = [[] for _ in range(S)]
+            self._times = [[] for _ in range(S)]
+            self._nsteps = [0] * S  # frames since the slot's reset
             self._fin, self._Tb, self._tc = [True] * S, [0] * S, [0] * S
             self._enc = None
             self._sdtype = torch.promote_types(self.joint.W2.dtype, torch.float32)
             return
         self.H = int(self.W1.shape[0])
         with torch.cuda.device(dev):
-            nbytes = _lib.beam_stream_workspace_bytes(T, S, K, N, self.H, self.Jp, self.V, self.dtype)
+            size = _lib.beam_stream_timed_workspace_bytes if self.token_times else _lib.beam_stream_workspace_bytes
+            nbytes = size(T, S, K, N, self.H, self.Jp, self.V, self.dtype)
             if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
                 self._ws = _new_workspace(nbytes, dev)
             elif _WORKSPACE_FILL is not None:
                 self._ws.fill_(int(_WORKSPACE_FILL))
             self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
-            st = _lib.load().compute_rnnt_beam_stream_begin(self.W1.data_ptr(), self.b1.data_ptr(), self.W2.data_ptr(),
-                                                            self.b2.data_ptr(), self.H, self.Jp, self.V, S, K, N, self.dtype,
-                                                            self._ws.data_ptr(), self._opts)
-        _lib.check(st, "compute_rnnt_beam_stream_begin")
+            fn = lib.compute_rnnt_beam_stream_timed_begin if self.token_times else lib.compute_rnnt_beam_stream_begin
+            st = fn(self.W1.data_ptr(), self.b1.data_ptr(), self.W2.data_ptr(), self.b2.data_ptr(), self.H, self.Jp, self.V, S, K, N,
+                    self.dtype, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_beam_stream_timed_begin" if self.token_times else "compute_rnnt_beam_stream_begin")
 
     def feed(self, enc, frames, reset=None, final=None):
         """enc [slots, Te, H] (None or Te = 0: no frames), frames [slots] encoder frames per slot, reset / final [slots] or None."""
@@ -831,10 +917,11 @@ class BeamStreamJoint(BeamJoint):
         fr, rs, fi = cv(frames), cv(reset), cv(final)
         self._feed_args = (enc, fr, rs, fi)  # (alive until the launches have read them)
         ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
-        st = _lib.load().compute_rnnt_beam_stream_feed(ptr(enc) if Te > 0 else None, Te, fr.data_ptr(), ptr(rs), ptr(fi), self.H,
-                                                       self.Jp, self.V, S, self.K, self.N, self.dtype, self._ws.data_ptr(),
-                                                       self._opts)
-        _lib.check(st, "compute_rnnt_beam_stream_feed")
+        lib = _lib.load()
+        fn = lib.compute_rnnt_beam_stream_timed_feed if self.token_times else lib.compute_rnnt_beam_stream_feed
+        st = fn(ptr(enc) if Te > 0 else None, Te, fr.data_ptr(), ptr(rs), ptr(fi), self.H, self.Jp, self.V, S, self.K, self.N,
+                self.dtype, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_beam_stream_timed_feed" if self.token_times else "compute_rnnt_beam_stream_feed")
 
     def step(self, pred=None, topk_logits=None, topk_symbols=None, lse=None, *, pred_proj=None):
         """One frame of every slot that has one left -> (parents, emitted), int32 [slots beam]; as BeamJoint.step."""
@@ -842,10 +929,11 @@ class BeamStreamJoint(BeamJoint):
             return self._torch_step(pred, pred_proj)
         pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _projected_operand(pred_proj, self.Jp)
         ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
-        st = _lib.load().compute_rnnt_beam_stream_step(pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(),
-                                                       ptr(topk_logits), ptr(topk_symbols), ptr(lse), self.Jp, self.V, self.B, self.K,
-                                                       self.N, self.dtype, self._ws.data_ptr(), self._opts)
-        _lib.check(st, "compute_rnnt_beam_stream_step")
+        lib = _lib.load()
+        fn = lib.compute_rnnt_beam_stream_timed_step if self.token_times else lib.compute_rnnt_beam_stream_step
+        st = fn(pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(), ptr(topk_logits), ptr(topk_symbols), ptr(lse),
+                self.Jp, self.V, self.B, self.K, self.N, self.dtype, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_beam_stream_timed_step" if self.token_times else "compute_rnnt_beam_stream_step")
         return self.parents, self.emitted
 
     def results(self):
@@ -857,6 +945,15 @@ class BeamStreamJoint(BeamJoint):
         lengths = torch.empty(S, K, dtype=torch.int32, device=dev)
         scores = torch.empty(S, K, dtype=torch.float32, device=dev)
         stable = torch.empty(S, dtype=torch.int32, device=dev)
+        if self.token_times:
+            frames = torch.empty(S, K, N, dtype=torch.int32, device=dev)
+            logp = torch.empty(S, K, N, dtype=torch.float32, device=dev)
+            tstable = torch.empty(S, dtype=torch.int32, device=dev)
+            st = _lib.load().compute_rnnt_beam_stream_timed_results(
+                hyps.data_ptr(), lengths.data_ptr(), scores.data_ptr(), stable.data_ptr(), frames.data_ptr(), logp.data_ptr(),
+                tstable.data_ptr(), self.Jp, self.V, S, K, N, self.dtype, self._ws.data_ptr(), self._opts)
+            _lib.check(st, "compute_rnnt_beam_stream_timed_results")
+            return hyps, lengths, scores, stable, frames, logp, tstable
         st = _lib.load().compute_rnnt_beam_stream_results(hyps.data_ptr(), lengths.data_ptr(), scores.data_ptr(), stable.data_ptr(),
                                                           self.Jp, self.V, S, K, N, self.dtype, self._ws.data_ptr(), self._opts)
         _lib.check(st, "compute_rnnt_beam_stream_results")
@@ -870,6 +967,7 @@ class BeamStreamJoint(BeamJoint):
         for s in range(S):
             if rs[s]:
                 self._beams[s], self._fin[s] = [((), 0.0)], False
+                self._times[s], self._nsteps[s] = [()], 0
             self._tc[s] = 0
             if self._fin[s]:
                 self._Tb[s] = 0
@@ -892,8 +990,9 @@ class BeamStreamJoint(BeamJoint):
             top_l, top_v = torch.sort(logits, dim=-1, descending=True, stable=True)  # (logit descending, symbol ascending)
             top_l, top_v, blank_l = top_l[:, :K].tolist(), top_v[:, :K].tolist(), logits[:, self.blank].tolist()
             for s in live:
-                self._torch_rank(s, top_l, top_v, lse, parents, emitted, blank_l, self.N)
+                self._torch_rank(s, top_l, top_v, lse, parents, emitted, blank_l, self.N, frame=self._nsteps[s])
                 self._tc[s] += 1
+                self._nsteps[s] += 1
         self.parents = torch.tensor(parents, dtype=torch.int32, device=dev)
         self.emitted = torch.tensor(emitted, dtype=torch.int32, device=dev)
         return self.parents, self.emitted
@@ -914,7 +1013,16 @@ class BeamStreamJoint(BeamJoint):
                     n += 1
                 stable[s] = n
         dev = self.parents.device
-        return hyps.to(dev), lengths.to(dev), scores.to(device=dev, dtype=self._sdtype), stable.to(dev)
+        out = hyps.to(dev), lengths.to(dev), scores.to(device=dev, dtype=self._sdtype), stable.to(dev)
+        if not self.token_times:
+            return out
+        tstable = torch.zeros(S, dtype=torch.int32)
+        for s, (beam, rows) in enumerate(zip(self._beams, self._times)):
+            n = 0  # the prefix that agrees in token and frame
+            while n < int(stable[s]) and all(r[n][0] == rows[0][n][0] for r in rows):
+                n += 1
+            tstable[s] = n
+        return out + self._torch_times(N) + (tstable.to(dev),)
 
 
 def _aligned16(x: torch.Tensor) -> torch.Tensor:
