@@ -189,6 +189,31 @@ RNNT_API rnntStatus_t compute_rnnt_loss_flags(const float *acts, float *grads, c
                                      const float *cost_scale, int alphabet_size, int minibatch,
                                      float *costs, void *workspace, rnntOptions options, unsigned int flags);
 
+/* Build-only extension (no upstream counterpart): FastEmit regularisation of the GRADIENTS (Yu et al. 2021, "FastEmit: Low-latency
+ * Streaming ASR with Sequence-level Emission Regularization"): the gradient that flows through the lattice's label edges is scaled
+ * by 1 + fastemit_lambda, which trains a streaming model to emit its tokens sooner.  With, per valid cell,
+ *   e_b = alpha(t,u) p(blank) beta(t+1,u) / L  (the terminal cell: alpha p(blank) / L),  e_l = alpha(t,u) p(y_u) beta(t,u+1) / L,
+ *   occ = e_b + e_l = alpha beta / L,
+ *   grads[t,u,v] = cost_scale[b] ( (occ + lambda e_l) softmax(x[t,u,:])[v] - [v == blank] e_b - [v == y_u] (1 + lambda) e_l )
+ * -- the chain rule through the fused log-softmax with d cost / d lp[blank] unchanged and d cost / d lp[y_u] times 1 + lambda, so
+ * every cell's gradients still sum to zero over v.  The costs stay the plain -ln P; lambda = 0 is compute_rnnt_loss_flags, launched
+ * through the same kernels, bit for bit; padded cells stay exact zeros.
+ * fastemit_lambda must be finite and in [0, 1] (typical: 1e-3 ... 1e-2); anything else returns RNNT_STATUS_INVALID_VALUE before
+ * anything is enqueued.  The upper limit keeps the bounds above as they are written: every gradient of a cell is bounded by
+ * (1 + lambda) |cost_scale| x its occupancy (the softmax term by (occ + lambda e_l) p_v, the corrections by e_b <= occ and
+ * (1 + lambda) e_l, and a difference of two non-negative terms by the larger), i.e. by 2 |cost_scale| x occupancy for lambda <= 1:
+ * the occupancy floors of the op (2^-50) and of the fused joints (2^-40) skip only what they skipped before, and the f32-grade
+ * joint's power-of-two dlogits scale keeps |S dl| <= 2^14.  The f16 joint, whose scale is sized to S |cost_scale| <= 2^14 exactly,
+ * halves it when lambda > 0 (S |cost_scale| <= 2^13), so that S |dl| <= 2^14 x occupancy holds for it too.
+ *   compute_rnnt_loss_fastemit = compute_rnnt_loss_flags (same NULL conventions: costs == NULL runs the gradient pass alone,
+ *   grads == NULL the forward alone) with the trailing fastemit_lambda.  The fused joints: compute_rnnt_joint_loss_bwd_fastemit /
+ *   compute_rnnt_joint_net_loss_bwd_fastemit below. */
+RNNT_API rnntStatus_t compute_rnnt_loss_fastemit(const float *acts, float *grads, const int *flat_labels,
+                                        const int *label_lengths, const int *input_lengths,
+                                        const float *cost_scale, int alphabet_size, int minibatch,
+                                        float *costs, void *workspace, rnntOptions options, unsigned int flags,
+                                        float fastemit_lambda);
+
 /* ------------------------------------------------------------------------------------------
  * Build-only extension (no upstream counterpart): the joint network fused with the loss, so the
  * [B,T,U,J] and [B,T,U,V] tensors of model.py:158-166 are never materialised.
@@ -276,6 +301,18 @@ RNNT_API rnntStatus_t compute_rnnt_joint_loss_bwd(const float *enc_proj, const f
                                          float *dW2, float *db2, int joint_dtype, void *workspace,
                                          rnntOptions options);
 
+/* compute_rnnt_joint_loss_bwd with FastEmit (compute_rnnt_loss_fastemit above): the four gradients back-propagated from
+ * FastEmit's dlogits.  The forward entry points serve unchanged -- lambda touches only the backward pass -- and the call may follow
+ * any _fwd call any number of times, with a different fastemit_lambda each time (joint_dtype 1: the first call consumes the parked
+ * values, later ones recompute the logits, as for compute_rnnt_joint_loss_bwd).  fastemit_lambda = 0 is compute_rnnt_joint_loss_bwd. */
+RNNT_API rnntStatus_t compute_rnnt_joint_loss_bwd_fastemit(const float *enc_proj, const float *pred_proj,
+                                         const float *W2, const float *b2, const int *flat_labels,
+                                         const int *label_lengths, const int *input_lengths,
+                                         const float *cost_scale, int joint_size, int alphabet_size,
+                                         int minibatch, float *d_enc_proj, float *d_pred_proj,
+                                         float *dW2, float *db2, int joint_dtype, void *workspace,
+                                         rnntOptions options, float fastemit_lambda);
+
 /* Build-only extension: the WHOLE joint network of model.py:158-166 fused with the loss -- the first Dense layer
  * (model.py:162-163) and its backward run inside the library too, on the matrix cores, f32-grade:
  *   enc   device f32 [B, maxT, H]  encoder output        pred  device f32 [B, maxU, H]  prediction-network output
@@ -316,6 +353,16 @@ RNNT_API rnntStatus_t compute_rnnt_joint_net_loss_bwd(const float *enc, const fl
                                                       int minibatch, float *d_enc, float *d_pred, float *dW1,
                                                       float *db1, float *dW2, float *db2, int joint_dtype,
                                                       void *workspace, rnntOptions options);
+
+/* compute_rnnt_joint_net_loss_bwd with FastEmit (compute_rnnt_loss_fastemit above): all six gradients from FastEmit's dlogits. */
+RNNT_API rnntStatus_t compute_rnnt_joint_net_loss_bwd_fastemit(const float *enc, const float *pred, const float *W1,
+                                                      const float *b1, const float *W2, const float *b2,
+                                                      const int *flat_labels, const int *label_lengths,
+                                                      const int *input_lengths, const float *cost_scale,
+                                                      int hidden_size, int joint_size, int alphabet_size,
+                                                      int minibatch, float *d_enc, float *d_pred, float *dW1,
+                                                      float *db1, float *dW2, float *db2, int joint_dtype,
+                                                      void *workspace, rnntOptions options, float fastemit_lambda);
 
 /* Build-only extension: the joint network alone, for decoding.  Replaces `joint(model, f, g)` of the reference's greedy
  * decoder (utils/decoding.py:6-18: dense_1 (tanh) and dense_2 on f + g for one lattice cell per step; called at :63-69):

@@ -24,10 +24,12 @@ SYMBOLS = [
     "compute_rnnt_loss_bwd",
     "compute_rnnt_loss_ex",
     "compute_rnnt_loss_flags",
+    "compute_rnnt_loss_fastemit",
     "get_joint_workspace_size",
     "compute_rnnt_joint_loss",
     "compute_rnnt_joint_loss_fwd",
     "compute_rnnt_joint_loss_bwd",
+    "compute_rnnt_joint_loss_bwd_fastemit",
     "compute_rnnt_joint_logits",
     "compute_rnnt_joint_net_logits",
     "get_rnnt_joint_backward_rows",
@@ -35,6 +37,7 @@ SYMBOLS = [
     "compute_rnnt_joint_net_loss",
     "compute_rnnt_joint_net_loss_fwd",
     "compute_rnnt_joint_net_loss_bwd",
+    "compute_rnnt_joint_net_loss_bwd_fastemit",
     "get_rnnt_greedy_workspace_size",
     "compute_rnnt_greedy_begin",
     "compute_rnnt_greedy_step",
@@ -155,6 +158,14 @@ def load():
     if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "compute_rnnt_loss_flags"):
         lib.compute_rnnt_loss_flags.restype = ci
         lib.compute_rnnt_loss_flags.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, rnntOptions, ctypes.c_uint]
+    if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "compute_rnnt_loss_fastemit"):
+        cf = ctypes.c_float
+        lib.compute_rnnt_loss_fastemit.restype = ci
+        lib.compute_rnnt_loss_fastemit.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, rnntOptions, ctypes.c_uint, cf]
+        lib.compute_rnnt_joint_loss_bwd_fastemit.restype = ci
+        lib.compute_rnnt_joint_loss_bwd_fastemit.argtypes = [vp] * 8 + [ci, ci, ci] + [vp] * 4 + [ci, vp, rnntOptions, cf]
+        lib.compute_rnnt_joint_net_loss_bwd_fastemit.restype = ci
+        lib.compute_rnnt_joint_net_loss_bwd_fastemit.argtypes = [vp] * 10 + [ci] * 4 + [vp] * 6 + [ci, vp, rnntOptions, cf]
     lib.get_joint_workspace_size.restype = ci
     lib.get_joint_workspace_size.argtypes = [ci, ci, ci, ci, ci, ctypes.POINTER(ctypes.c_size_t)]
     lib.compute_rnnt_joint_loss.restype = ci

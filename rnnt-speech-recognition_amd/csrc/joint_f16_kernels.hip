@@ -121,6 +121,7 @@ struct JhParams {
     int b2_lds_off;  // K1/K2: byte offset of the bias table in LDS, -1 = read it from global memory (does not fit)
     float *logits_out;  // MODE 3 of K1 (compute_rnnt_joint_logits, decoding): f32 logits [cells][V]
     int logits_only;    // every lattice cell is wanted: the prep kernel writes full lengths + zero labels into the workspace
+    float fe_lambda;    // FastEmit weight of the backward (include/rnnt.h): jh_prep_kernel's scale, the FE instantiations of K2 / K3
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -168,7 +169,9 @@ __global__ __launch_bounds__(256) void jh_prep_kernel(const JhParams jp) {
             float fr = frexpf(m, &e);  // m = fr * 2^e, fr in [0.5, 1)
             if (fr == 0.5f) --e;       // exact power of two: ceil(log2 m) = e - 1
         }
-        const float S = ldexpf(1.0f, kDlScaleLog2 - e);
+        // FastEmit: |dlogits| <= (1 + lambda) |cost_scale| x occupancy, lambda <= 1 -- one more bit of headroom, so that S |dlogits|
+        // stays within 2^kDlScaleLog2 and the row floor's argument (jh_rowbits_kernel) holds as written
+        const float S = ldexpf(1.0f, kDlScaleLog2 - e - (jp.fe_lambda != 0.f ? 1 : 0));
         jp.scal[0] = S;
         jp.scal[1] = 1.0f / S;
     }
@@ -181,11 +184,12 @@ __global__ __launch_bounds__(256) void jh_prep_kernel(const JhParams jp) {
 // ---------------------------------------------------------------------------------------------
 // MODE 0: forward (lse, edge weights, edge logits).  MODE 1: forward + PARK: the softmax numerators of every chunk are also
 // written to dl as binary16, relative to the chunk's own integer reference, so that the backward pass is a streaming kernel
-// (the loader of jh_dhx_kernel) instead of this product a second time.  MODE 2: the product again with the dlogits epilogue (the
+// (the loader of jh_dhx_kernel) instead of this product a second time.  MODE 4 = MODE 2 with FastEmit.  MODE 2: the product again with the dlogits epilogue (the
 // route a backward call takes when the parked values are not there any more: a second backward over one forward).
 template <int KS, int MODE, bool B2LDS>
 __global__ __launch_bounds__(512) void jh_logits_kernel(const JhParams jp) {
-    constexpr bool BWD = MODE == 2, PARK = MODE == 1, STAGE = MODE == 1 || MODE == 2, LOGITS = MODE == 3;
+    // MODE 4: MODE 2 with FastEmit (DESIGN.md "FastEmit"): the softmax term times 1 + lambda e_label / occupancy, the label column's correction times 1 + lambda
+    constexpr bool BWD = MODE == 2 || MODE == 4, FE = MODE == 4, PARK = MODE == 1, STAGE = MODE == 1 || BWD, LOGITS = MODE == 3;
     if (BWD && jp.state[0] == 1) return;  // the streaming kernel has the parked values: nothing to recompute
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const LossParams &p = jp.lp;
@@ -282,7 +286,7 @@ __global__ __launch_bounds__(512) void jh_logits_kernel(const JhParams jp) {
     if (has_label) lab = clamp_label(p.labels[(size_t)b * (p.U - 1) + u], V);
     float mref = -1.0e30f, ssum = 0.f;  // FWD: online log2-sum-exp2 state of this lane's share of the vocabulary
     CellGrad g;                         // BWD
-    float scaleS = 0.f, c0 = -1.0e30f;
+    float scaleS = 0.f, c0 = -1.0e30f, lfac = 1.0f;
     f16 *my_stage = (f16 *)(smem + 2 * chunk_bytes) + wave * (32 * kStageStride);
     // FWD: the blank / label logits are picked out of the MFMA tiles (log2-scaled: y = x * log2 e).  Column v sits in
     // chunk v >> 5, in the half-lane ((v & 31) >> 2) & 1, register (v & 3) + 4 * ((v & 31) >> 3).
@@ -296,6 +300,11 @@ __global__ __launch_bounds__(512) void jh_logits_kernel(const JhParams jp) {
             scaleS = g.scale * jp.scal[0];
             c0 = g.c0;
             xb = jp.xbl[2 * (size_t)c], xl = jp.xbl[2 * (size_t)c + 1];  // log2-scaled
+            if (FE && g.has_label) {  // e_label / occupancy <= 1 (rnnt_cell.h fastemit_log)
+                const float r = hex2(fminf((xl + g.nl + g.cl) - (g.c0 - g.nl), 0.f));
+                c0 += __builtin_amdgcn_logf(fmaf(jp.fe_lambda, r, 1.0f));
+                lfac = 1.0f + jp.fe_lambda;
+            }
         }
     }
 
@@ -431,7 +440,7 @@ __global__ __launch_bounds__(512) void jh_logits_kernel(const JhParams jp) {
                 const bool pb = (unsigned)(p.blank - vbase) < 32u, pl = g.has_label && !same && (unsigned)(g.lab - vbase) < 32u;
                 if (pb || pl) {
                     const float cb = g.has_blank_corr ? hex2(xb + g.nl + g.cb) : 0.f;
-                    const float clb = g.has_label ? hex2(xl + g.nl + g.cl) : 0.f;
+                    const float clb = g.has_label ? (FE ? lfac : 1.0f) * hex2(xl + g.nl + g.cl) : 0.f;
                     if (pb) my_stage[n * kStageStride + p.blank - vbase] = (f16)(scaleS * (hex2(xb + c0) - cb - (same ? clb : 0.f)));
                     if (pl) my_stage[n * kStageStride + g.lab - vbase] = (f16)(scaleS * (hex2(xl + c0) - clb));
                 }
@@ -736,7 +745,7 @@ __global__ __launch_bounds__(1024) void jh_order_kernel(const JhParams jp, const
 // LDS: 3 stages x (A 128 rows x 64 B + B J rows x 64 B), 16-byte chunks XOR-swizzled by (row >> 2) & 3 (conflict-free b128 reads),
 //      + [4][J] floats for the d enc_proj hand-over = 157,696 bytes at J = 640.
 // ---------------------------------------------------------------------------------------------
-template <int NT>
+template <int NT, bool FE = false>  // FE: FastEmit in the per-cell factors (cell_finish)
 __global__ __launch_bounds__(512) void jh_dhx_kernel(const JhParams jp) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const LossParams &p = jp.lp;
@@ -847,7 +856,7 @@ __global__ __launch_bounds__(512) void jh_dhx_kernel(const JhParams jp) {
         const int ct = t_it + g.crow;
         const double da = (double)r.a + ((double)r.oa - ll2);
         const float nl = -r.lse * kLog2e;
-        const float c0 = (float)(da + ((double)r.bt + (double)r.obt)) + nl;
+        float c0 = (float)(da + ((double)r.bt + (double)r.obt)) + nl;
         float cb = 0.f;
         bool has_bc = true;
         if (ct < Tb - 1) cb = (float)(da + ((double)r.b_t1 + (double)r.ob_t1));
@@ -855,7 +864,12 @@ __global__ __launch_bounds__(512) void jh_dhx_kernel(const JhParams jp) {
         else has_bc = false;
         const float cl = has_label ? (float)(da + ((double)r.b_u1 + (double)r.ob_u1)) : 0.f;
         const float cbv = has_bc ? hex2(r.x.x + nl + cb) : 0.f;
-        const float clb = has_label ? hex2(r.x.y + nl + cl) : 0.f;
+        float clb = has_label ? hex2(r.x.y + nl + cl) : 0.f;
+        if (FE && has_label) {  // e_label / occupancy <= 1 (rnnt_cell.h fastemit_log)
+            const float rr = hex2(fminf((r.x.y + nl + cl) - (c0 - nl), 0.f));
+            c0 += __builtin_amdgcn_logf(fmaf(jp.fe_lambda, rr, 1.0f));
+            clb = fmaf(jp.fe_lambda, clb, clb);
+        }
         c.c0 = c0;
         c.eb = cscale * (hex2(r.x.x + c0) - cbv - (same ? clb : 0.f));
         c.el = cscale * (hex2(r.x.y + c0) - clb);
@@ -1548,7 +1562,7 @@ template <int KS, int MODE>
 static hipError_t launch_logits_mode(const JhParams &jp, unsigned grid, hipStream_t s) {
     // W2^T double buffer (+ staging tile when the epilogue writes [cells][V] rows), overlaid during the prologue by the
     // enc_proj / pred_proj images; bias table last
-    size_t shm = 2 * (size_t)64 * (KS * 16) + ((MODE == 1 || MODE == 2) ? (size_t)8 * 32 * kStageStride * sizeof(f16) : 0);
+    size_t shm = 2 * (size_t)64 * (KS * 16) + ((MODE == 1 || MODE == 2 || MODE == 4) ? (size_t)8 * 32 * kStageStride * sizeof(f16) : 0);
     const size_t images = (size_t)KS * 4 * 32 * 16 + (size_t)8 * KS * 64;
     if (shm < images) shm = images;
     JhParams jq = jp;
@@ -1587,6 +1601,7 @@ static hipError_t launch_logits(const JhParams &jp, int mode, unsigned grid, hip
         case 0: return launch_logits_mode<KS, 0>(jp, grid, s);
         case 1: return launch_logits_mode<KS, 1>(jp, grid, s);
         case 3: return launch_logits_mode<KS, 3>(jp, grid, s);
+        case 4: return launch_logits_mode<KS, 4>(jp, grid, s);
         default: return launch_logits_mode<KS, 2>(jp, grid, s);
     }
 }
@@ -1627,7 +1642,7 @@ static hipError_t jh_fill_params(JhParams &jp, const JhLayout &L, const float *e
     jp.order = (int *)(ws + L.order), jp.uorder = (int *)(ws + L.uorder);
     jp.J = J, jp.n_ut = L.n_ut, jp.n_tt = L.n_tt, jp.n_ts = L.n_ts, jp.TS = L.TS, jp.n_tq = L.n_tq;
     jp.n_units = L.n_units, jp.n_ranges = L.n_ranges;
-    jp.logits_out = nullptr, jp.logits_only = 0;
+    jp.logits_out = nullptr, jp.logits_only = 0, jp.fe_lambda = 0.f;
     jp.b2_lds_off = -1;
     return hipSuccess;
 }
@@ -1657,7 +1672,7 @@ hipError_t launch_joint_loss_f16(const float *enc_proj, const float *pred_proj, 
                                  const int *labels, const int *label_lengths, const int *input_lengths,
                                  const float *cost_scale, int J, int V, int B, int T, int U, int blank, float *costs,
                                  float *d_enc_proj, float *d_pred_proj, float *dW2, float *db2, int phases,
-                                 void *workspace, hipStream_t s, const JointHooks *hooks) {
+                                 void *workspace, hipStream_t s, const JointHooks *hooks, float fe_lambda) {
     if (!joint_f16_supported(J, V)) return hipErrorInvalidValue;
     if (((uintptr_t)enc_proj & 15) || ((uintptr_t)pred_proj & 15) || ((uintptr_t)b2 & 15)) return hipErrorInvalidValue;
     if ((unsigned long long)B * T * J >= (1ull << 32) || (unsigned long long)B * U * J >= (1ull << 32)) return hipErrorInvalidValue;  // 32-bit indices in the reductions
@@ -1666,6 +1681,7 @@ hipError_t launch_joint_loss_f16(const float *enc_proj, const float *pred_proj, 
     hipError_t e = jh_fill_params(jp, L, enc_proj, pred_proj, W2, b2, labels, label_lengths, input_lengths, cost_scale, J, V, B, T, U,
                                   blank, costs, workspace);
     if (e != hipSuccess) return e;
+    jp.fe_lambda = (phases & 2) && d_enc_proj ? fe_lambda : 0.f;  // the backward's alone: a forward-only call keeps the plain scale
 
     const unsigned tiles = (unsigned)B * L.n_tt * L.n_ut;
     auto logits = [&](int mode) -> hipError_t { return jh_launch_logits_for_J(jp, J, mode, tiles, s); };
@@ -1696,7 +1712,7 @@ hipError_t launch_joint_loss_f16(const float *enc_proj, const float *pred_proj, 
     // (Cutting the batch into utterance ranges and converting range q + 1 on a second stream beside the dh kernel of range q
     // was measured at config 5: the two kernels do overlap, and slow each other down by as much as the overlap hides.)
     // (a call that parked in its own forward phase knows the answer: the recompute kernel would read the state word and return)
-    if (!((phases & 1) && park) && (e = logits(2)) != hipSuccess) return e;
+    if (!((phases & 1) && park) && (e = logits(jp.fe_lambda != 0.f ? 4 : 2)) != hipSuccess) return e;
     // dC partials + the zero row + the row counters (the dA partials need no zero-fill: reduce_f16_backward_kernel reads only the rows K3 writes)
     if (launch_fill(jp.dCpart, 0, L.live8 - L.dCpart, s) != hipSuccess) return hipErrorUnknown;
     // which lattice rows (x 32-column tiles) the backward visits: K3, K4 and the d enc_proj reduction follow these bits
@@ -1714,12 +1730,22 @@ hipError_t launch_joint_loss_f16(const float *enc_proj, const float *pred_proj, 
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), shm, s, jp);
             return hipGetLastError();
         };
-        switch (J / 128) {
-            case 1: e = go(jh_dhx_kernel<1>); break;
-            case 2: e = go(jh_dhx_kernel<2>); break;
-            case 3: e = go(jh_dhx_kernel<3>); break;
-            case 4: e = go(jh_dhx_kernel<4>); break;
-            default: e = go(jh_dhx_kernel<5>); break;
+        if (jp.fe_lambda != 0.f) {
+            switch (J / 128) {
+                case 1: e = go(jh_dhx_kernel<1, true>); break;
+                case 2: e = go(jh_dhx_kernel<2, true>); break;
+                case 3: e = go(jh_dhx_kernel<3, true>); break;
+                case 4: e = go(jh_dhx_kernel<4, true>); break;
+                default: e = go(jh_dhx_kernel<5, true>); break;
+            }
+        } else {
+            switch (J / 128) {
+                case 1: e = go(jh_dhx_kernel<1>); break;
+                case 2: e = go(jh_dhx_kernel<2>); break;
+                case 3: e = go(jh_dhx_kernel<3>); break;
+                case 4: e = go(jh_dhx_kernel<4>); break;
+                default: e = go(jh_dhx_kernel<5>); break;
+            }
         }
         if (e != hipSuccess) return e;
     }

@@ -82,6 +82,7 @@ struct JointParams {
     int logits_only;  // compute_rnnt_joint_logits: full lengths written by the prep kernel, only the parked logits are kept
     int nblk;         // workgroups per J group of joint_bwd_kernel (sizes what the reduction reads of the partial buffers)
     int need_state;   // backward-only whole-network call: the reductions return NaN unless tflag[3] says the state is there
+    float fe_lambda;  // FastEmit weight of the backward (include/rnnt.h); read by the FE instantiations of the per-cell record kernels only
 };
 
 constexpr int kMaxVT = 4;  // vocabulary tiles of 32 symbols the f32-grade joint takes (V <= 128)
@@ -773,6 +774,7 @@ __global__ __launch_bounds__(kFwdWaves * 64) void joint_fwd_kernel(const JointPa
 // ---------------------------------------------------------------------------------------------
 constexpr int kDlChunks = 8;  // 256-cell chunks per workgroup (fewer, fatter db2 partials)
 
+template <bool FE = false>  // FE: FastEmit (rnnt_cell.h fastemit_log; lambda = jp.fe_lambda)
 __global__ __launch_bounds__(256) void joint_dl_kernel(const JointParams jp) {
     __shared__ float red[256][33];
     const LossParams &p = jp.lp;
@@ -806,15 +808,16 @@ __global__ __launch_bounds__(256) void joint_dl_kernel(const JointParams jp) {
 #pragma unroll
         for (int v = 0; v < 32; ++v) x[v] = red[tid][v];
         if (cl.valid) {
-            const CellGrad g = cell_grad_setup(p, cl, c);
+            CellGrad g = cell_grad_setup(p, cl, c);
             float xb = 0.f, xl = 0.f;
 #pragma unroll
             for (int v = 0; v < 32; ++v) {
                 xb = (v == p.blank) ? x[v] : xb;
                 xl = (g.has_label && v == g.lab) ? x[v] : xl;
             }
-            const float cb = g.has_blank_corr ? g.scale * jex2(fmaf(xb, kLog2e, g.nl) + g.cb) : 0.f;
-            const float clb = g.has_label ? g.scale * jex2(fmaf(xl, kLog2e, g.nl) + g.cl) : 0.f;
+            if (FE) fastemit_log(g, xl, jp.fe_lambda);
+            const float cb = g.has_blank_corr ? (FE ? g.bscale : g.scale) * jex2(fmaf(xb, kLog2e, g.nl) + g.cb) : 0.f;
+            const float clb = g.has_label ? (FE ? g.lscale : g.scale) * jex2(fmaf(xl, kLog2e, g.nl) + g.cl) : 0.f;
 #pragma unroll
             for (int v = 0; v < 32; ++v) {
                 float gv = (v < V) ? g.scale * jex2(fmaf(x[v], kLog2e, g.c0)) : 0.f;
@@ -1357,20 +1360,31 @@ __device__ void bwd_consumer(const JointParams &jp, char *ring, const uint32_t s
 // Workgroup = a patch of 8 lattice rows x 32 columns.  The lattice state is diagonal-major (row n = t + u of the skewed
 // arrays): the patch touches 40 diagonals and, on each, a window of at most 10 consecutive columns -- staged through LDS with
 // window-contiguous loads (a lane-per-cell gather touches a different 64-byte sector for every lane: 4 x 64 sectors per wave).
+// FE (FastEmit): the record alone carries it -- rec.w = (1 + lambda) x the label correction and rec.x = log2(occupancy +
+// lambda e_label) - lse log2e, with e_label / occupancy <= 1 as in fastemit_log (rnnt_cell.h) -- so the producers of joint_bwd_kernel
+// form FastEmit's dlogits from it unchanged.  Every dlogits value of a cell stays within (1 + lambda) |cost_scale| x occupancy
+// <= 2 |cost_scale| x occupancy (lambda <= 1): bwd_scale and the occupancy floor hold as they are.
+template <bool FE = false>
 __device__ __forceinline__ void rec_from_log(const JointParams &jp, const CellGrad &g, const float2 xx, const float S, float4 &rec,
                                              int &lab) {
     const float sS = g.scale * S;
     rec.x = g.c0, rec.y = sS;
     if (g.has_blank_corr) rec.z = sS * jex2(fmaf(xx.x, kLog2e, g.nl) + g.cb);
     if (g.has_label) lab = g.lab, rec.w = sS * jex2(fmaf(xx.y, kLog2e, g.nl) + g.cl);
+    if (FE && g.has_label) {
+        const float r = jex2(fminf((fmaf(xx.y, kLog2e, g.nl) + g.cl) - (g.c0 - g.nl), 0.f));
+        rec.x += jlg2(fmaf(jp.fe_lambda, r, 1.0f));
+        rec.w = fmaf(jp.fe_lambda, rec.w, rec.w);
+    }
 }
 // The same record from the linear lattice: ma = alpha^(t,u), mb = beta^(t,u), m_t1 = beta^(t+1,u), m_u1 = beta^(t,u+1) as
 // mantissas relative to the frame tables (the last two are only looked at where that neighbour exists).  Returns false when
 // the cell fails the range certificate (rnnt_lin.h lin_grad_setup: what a flush can have cost x the other side's mass, over the
 // likelihood, must stay below 2^kCertBits).
+template <bool FE = false>
 __device__ __forceinline__ bool rec_from_lin(const LossParams &p, const Cell &cl, const uint32_t c, const float ma, const float mb,
                                              const float m_t1, const float m_u1, const float2 xx, const float S, float4 &rec,
-                                             int &lab) {
+                                             int &lab, const float lambda = 0.f) {
     const int n = cl.t + cl.u;
     const int sh = p.lshift[cl.b];  // the block length the sweeps chose for this utterance
     const int kc = n >> sh, kc1 = (n + 1) >> sh;
@@ -1398,7 +1412,15 @@ __device__ __forceinline__ bool rec_from_lin(const LossParams &p, const Cell &cl
     if (cl.u < cl.Ub - 1) {
         lab = clamp_label(p.labels[(size_t)cl.b * (p.U - 1) + cl.u], p.V);
         const float occ = ldexp_f(qa * frexp_m(m_u1), base + p.EB[tb + (size_t)kc1 * 64 + l1] + frexp_e(m_u1));
-        rec.w = sS * occ * jex2(fmaf(xx.y, kLog2e, nl));
+        const float el = occ * jex2(fmaf(xx.y, kLog2e, nl));  // e_label: the label edge's share of the occupancy
+        rec.w = sS * el;
+        if (FE) {
+            // e_label / occupancy from the two mantissa products (a cell without mass: no ratio, and rec.x is -inf already)
+            const float tot = ldexp_f(qa * frexp_m(mb), base + eb + xb);
+            const float r = tot > 0.f ? fminf(el * __builtin_amdgcn_rcpf(tot), 1.0f) : 0.f;
+            rec.x += jlg2(fmaf(lambda, r, 1.0f));
+            rec.w = fmaf(lambda, rec.w, rec.w);
+        }
     }
     int worst = ea + eb - 252 - EL;
     if (mb != 0.f) worst = max(worst, ea - 126 + eb + xb - EL);
@@ -1407,6 +1429,7 @@ __device__ __forceinline__ bool rec_from_lin(const LossParams &p, const Cell &cl
 }
 
 constexpr int kRecRows = 8, kRecDiags = kRecRows + 32, kRecWin = 10;
+template <bool FE = false>
 __global__ __launch_bounds__(256) void joint_cellrec_kernel(const JointParams jp) {
     __shared__ float As[kRecDiags][kRecWin], Bs[kRecDiags][kRecWin];
     const LossParams &p = jp.lp;
@@ -1452,13 +1475,14 @@ __global__ __launch_bounds__(256) void joint_cellrec_kernel(const JointParams jp
         // sectors of every cell's 128-byte row: the whole 369 MB at C2 for 23 MB of payload)
         const float2 xx = jp.xbl[c];
         if (lin) {
-            if (!rec_from_lin(p, cl, c, As[n][cu - w0], Bs[n][cu - w0], Bs[n1][cu - w1], Bs[n1][cu + 1 - w1], xx, S, rec, lab))
+            if (!rec_from_lin<FE>(p, cl, c, As[n][cu - w0], Bs[n][cu - w0], Bs[n1][cu - w1], Bs[n1][cu + 1 - w1], xx, S, rec, lab, FE ? jp.fe_lambda : 0.f))
                 atomicOr(p.flags + 4 * b + kFlagG, 1);  // (rare) the utterance is redone in the log domain
         } else {
             const CellGrad g = cell_grad_from(p, cl, c, As[n][cu - w0], Bs[n][cu - w0], Bs[n1][cu - w1], Bs[n1][cu + 1 - w1]);
-            rec_from_log(jp, g, xx, S, rec, lab);
+            rec_from_log<FE>(jp, g, xx, S, rec, lab);
         }
-        // rec.x = log2(occupancy) - lse log2 e: the occupancy alone decides whether the backward visits the cell's row (NaN: yes)
+        // rec.x = log2(occupancy) - lse log2 e: the occupancy alone decides whether the backward visits the cell's row (NaN: yes).
+        // (FastEmit: occupancy + lambda e_label, which bounds |dlogits| / |cost_scale| of the cell by itself)
         occupied = jp.visit_all || !(fmaf(p.lse[c], kLog2e, rec.x) <= (float)-kOccFloor);
     }
     const unsigned long long occ = __ballot(occupied);
@@ -1483,7 +1507,7 @@ __global__ __launch_bounds__(256) void joint_cellrec_kernel(const JointParams jp
 // the loss parameters with acts = the [cells][32] tile (pad symbols at -1e30: probability zero) -- and, when the backward
 // wants them, its per-cell records are rewritten from the log-domain lattice.  Its state word then says "log-domain lattice".
 // ---------------------------------------------------------------------------------------------
-template <int K, int G, int NB>
+template <int K, int G, int NB, bool FE = false>
 __global__ __launch_bounds__(kRedoThreads) void joint_redo_kernel(const JointParams jp, const LossParams q, const int want_rec,
                                                                   const int team) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1513,7 +1537,7 @@ __global__ __launch_bounds__(kRedoThreads) void joint_redo_kernel(const JointPar
         int lab = -1;
         if (cl.valid) {
             const CellGrad g = cell_grad_setup<true>(p, cl, c);
-            rec_from_log(jp, g, jp.xbl[c], S, rec, lab);
+            rec_from_log<FE>(jp, g, jp.xbl[c], S, rec, lab);
             if (!tm.ok) rec.x = NAN;
         }
         jp.rec[c] = rec;
@@ -2142,7 +2166,7 @@ hipError_t launch_joint_loss_f16(const float *enc_proj, const float *pred_proj, 
                                  const int *labels, const int *label_lengths, const int *input_lengths,
                                  const float *cost_scale, int J, int V, int B, int T, int U, int blank, float *costs,
                                  float *d_enc_proj, float *d_pred_proj, float *dW2, float *db2, int phases,
-                                 void *workspace, hipStream_t s, const JointHooks *hooks);
+                                 void *workspace, hipStream_t s, const JointHooks *hooks, float fe_lambda);
 
 // The four reductions behind the f16 joint's backward in ONE launch (round 6; four launches before, 23 us + a launch gap apiece at
 // the small end): blocks [0, kHookBlocks) d enc_proj from its u-tile partial rows, [kHookBlocks, 2 kHookBlocks) d pred_proj from its
@@ -2316,13 +2340,13 @@ hipError_t launch_joint_logits(const float *enc_proj, const float *pred_proj, co
 }
 
 // the hand-back launch of the fused joint (joint_redo_kernel) with the chunk geometry of the utterance's sweeps
-template <int K, int G>
+template <int K, int G, bool FE = false>
 static hipError_t launch_joint_redo_k(const JointParams &jp, const LossParams &q, const bool want_rec, hipStream_t s) {
     using R = SweepRing<K, G>;
-    hipError_t e = set_lds(joint_redo_kernel<K, G, R::NB>, R::kBytes);
+    hipError_t e = set_lds(joint_redo_kernel<K, G, R::NB, FE>, R::kBytes);
     if (e != hipSuccess) return e;
     const int team = redo_team_size(jp.lp.nb, jp.lp.T, jp.lp.U, device_cu_count());
-    hipLaunchKernelGGL((joint_redo_kernel<K, G, R::NB>), dim3(jp.lp.nb * team), dim3(kRedoThreads), R::kBytes, s, jp, q, want_rec ? 1 : 0, team);
+    hipLaunchKernelGGL((joint_redo_kernel<K, G, R::NB, FE>), dim3(jp.lp.nb * team), dim3(kRedoThreads), R::kBytes, s, jp, q, want_rec ? 1 : 0, team);
     return hipGetLastError();
 }
 static hipError_t launch_joint_redo(const JointParams &jp, const bool want_rec, hipStream_t s) {
@@ -2330,6 +2354,8 @@ static hipError_t launch_joint_redo(const JointParams &jp, const bool want_rec, 
     LossParams q = jp.lp;
     q.acts = jp.dl, q.grads = nullptr, q.V = 32 * jp.VT;
     q.divV = make_fastdiv((uint32_t)q.V);
+    if (want_rec && jp.fe_lambda != 0.f)  // FastEmit: the rewritten records carry it (rec_from_log)
+        return sweep_dispatch(jp.lp.U, [&](auto K, auto G) { return launch_joint_redo_k<K, G, true>(jp, q, want_rec, s); });
     return sweep_dispatch(jp.lp.U, [&](auto K, auto G) { return launch_joint_redo_k<K, G>(jp, q, want_rec, s); });
 }
 
@@ -2337,13 +2363,14 @@ hipError_t launch_joint_loss(const float *enc_proj, const float *pred_proj, cons
                              const int *labels, const int *label_lengths, const int *input_lengths,
                              const float *cost_scale, int J, int V, int B, int T, int U, int blank, float *costs,
                              float *d_enc_proj, float *d_pred_proj, float *dW2, float *db2, int joint_dtype,
-                             int phases, void *workspace, hipStream_t s, const JointHooks *hooks) {
+                             int phases, void *workspace, hipStream_t s, const JointHooks *hooks, float fe_lambda) {
+    // fe_lambda: FastEmit's weight of the backward (0: the plain gradient kernels; range checked by the entry points)
     // phases: bit 0 = forward (costs + lattice state in the workspace), bit 1 = backward (needs that state),
     // bit 2 = a backward-only call will follow this forward-only one (the f16 joint parks its softmax numerators for it),
     // bit 3 = RNNT_VISIT_ALL: the backward visits every lattice row (no occupancy floor)
     if (joint_dtype == 1)
         return launch_joint_loss_f16(enc_proj, pred_proj, W2, b2, labels, label_lengths, input_lengths, cost_scale, J, V,
-                                     B, T, U, blank, costs, d_enc_proj, d_pred_proj, dW2, db2, phases, workspace, s, hooks);
+                                     B, T, U, blank, costs, d_enc_proj, d_pred_proj, dW2, db2, phases, workspace, s, hooks, fe_lambda);
     if (!joint_supported(J, V) || joint_dtype != 0 || sweep_K(U) == 0) return hipErrorInvalidValue;
     if (((uintptr_t)enc_proj & 15) || ((uintptr_t)pred_proj & 15)) return hipErrorInvalidValue;
     // the reductions over the [B][T][J] / [B][U][J] arrays index with 32 bits (B*T*U < 2^31 alone does not bound B*T*J)
@@ -2360,6 +2387,7 @@ hipError_t launch_joint_loss(const float *enc_proj, const float *pred_proj, cons
     jp.d_enc_proj = d_enc_proj, jp.d_pred_proj = d_pred_proj, jp.dW2 = dW2, jp.db2 = db2;
     jp.logits_only = 0;
     jp.visit_all = (phases & 8) ? 1 : 0;
+    jp.fe_lambda = fe_lambda;
     const int prep_mode = hooks ? hooks->prep_mode : 0;
     jp.tables_ready = prep_mode == 1;
     jp.need_state = prep_mode == 2;
@@ -2404,7 +2432,10 @@ hipError_t launch_joint_loss(const float *enc_proj, const float *pred_proj, cons
         if (nblk > kBwdMaxBlocks) nblk = kBwdMaxBlocks;
         if (nblk < 1) nblk = 1;
         jp.nblk = nblk;
-        hipLaunchKernelGGL(joint_cellrec_kernel, dim3((unsigned)B * L.n_ut * ((T + kRecRows - 1) / kRecRows)), dim3(256), 0, s, jp);
+        if (jp.fe_lambda != 0.f)
+            hipLaunchKernelGGL(joint_cellrec_kernel<true>, dim3((unsigned)B * L.n_ut * ((T + kRecRows - 1) / kRecRows)), dim3(256), 0, s, jp);
+        else
+            hipLaunchKernelGGL(joint_cellrec_kernel<false>, dim3((unsigned)B * L.n_ut * ((T + kRecRows - 1) / kRecRows)), dim3(256), 0, s, jp);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if ((e = launch_joint_redo(jp, true, s)) != hipSuccess) return e;
         hipLaunchKernelGGL(joint_rowplan_kernel, dim3(1), dim3(kPlanThreads), 0, s, jp);  // (after the hand-back: it turns whole utterances on)
@@ -2419,7 +2450,10 @@ hipError_t launch_joint_loss(const float *enc_proj, const float *pred_proj, cons
         // workgroups that path does not write must read as zero; the d enc_proj partials need none)
         if (launch_fill(jp.dCpart, 0, (L.dbpart - L.dCpart) + (size_t)L.nDb * 32 * sizeof(float), s) != hipSuccess) return hipErrorUnknown;
         const unsigned gdl = (jp.lp.cells + 256u * kDlChunks - 1u) / (256u * kDlChunks);
-        hipLaunchKernelGGL(joint_dl_kernel, dim3(gdl), dim3(256), 0, s, jp);
+        if (jp.fe_lambda != 0.f)
+            hipLaunchKernelGGL(joint_dl_kernel<true>, dim3(gdl), dim3(256), 0, s, jp);
+        else
+            hipLaunchKernelGGL(joint_dl_kernel<false>, dim3(gdl), dim3(256), 0, s, jp);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         const unsigned g2 = (unsigned)B * L.n_ut * (J / 64) * L.n_ts;
         const size_t shm2s = ((size_t)64 * 36 + 4 * 32 * 36 + 4 * 32 * kStagePad) * sizeof(float) + 8192;

@@ -64,6 +64,7 @@ struct CellGrad {
     bool has_blank_corr, has_label;
     int lab;
     float scale;
+    float bscale, lscale;  // FastEmit only (fastemit_log): the scales of the blank correction (the plain one) and of the label correction
 };
 
 // The set-up from the cell's lattice values: a = alpha~(t,u), bt = beta~(t,u), b_t1 = beta~(t+1,u), b_u1 = beta~(t,u+1) (the
@@ -100,6 +101,20 @@ __device__ __forceinline__ CellGrad cell_grad_from(const LossParams &p, const Ce
         g.cl = (float)(da + ((double)b_u1 + (double)ld_f32<SC1>(p.offB + ob + (size_t)kc1 * p.NG + g1)));
     }
     return g;
+}
+
+// FastEmit on a log-domain set-up (DESIGN.md "FastEmit"), xl = the cell's label logit: the softmax term's multiplier becomes
+// cost_scale (occupancy + lambda e_label) = scale (1 + lambda r), r = e_label / occupancy = 2^(xl log2e + nl + cl - (c0 - nl)) <= 1
+// (the label edge carries part of the cell's mass: the clamp only takes rounding noise off a ratio of exactly one and keeps a
+// "log zero" difference from overflowing); the label correction's becomes scale (1 + lambda) (lscale) and the blank's stays what it was (bscale).
+// A NaN lattice still reaches every gradient through c0.
+__device__ __forceinline__ void fastemit_log(CellGrad &g, const float xl, const float lambda) {
+    g.bscale = g.lscale = g.scale;
+    if (g.has_label) {
+        const float r = __builtin_amdgcn_exp2f(fminf((fmaf(xl, kLog2e, g.nl) + g.cl) - (g.c0 - g.nl), 0.f));
+        g.lscale = fmaf(lambda, g.scale, g.scale);
+        g.scale = fmaf(lambda * r, g.scale, g.scale);
+    }
 }
 
 template <bool SC1 = false>

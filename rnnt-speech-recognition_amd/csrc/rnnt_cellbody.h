@@ -14,7 +14,9 @@ namespace rnnt {
 // LIN: the linear-domain lattice (rnnt_lin.h): edge probabilities instead of log2 weights and no lse store in the lsm pass;
 // in the gradient pass the softmax numerators are recomputed and scaled by occupancies formed from mantissas + frames: `lg`, the
 // cell's lin_grad_setup, which the caller forms (and certifies) before it stages the logits.
-template <int VP, bool V4, bool GRAD, bool LIN = false, bool SC1 = false>
+// FE: FastEmit (DESIGN.md "FastEmit"): the label edge's gradient times 1 + lambda through the fused log-softmax -- the softmax term
+// takes occupancy + lambda e_label, the label correction (1 + lambda) e_label; lambda = p.fe_lambda.  FE = false is the plain gradient.
+template <int VP, bool V4, bool GRAD, bool LIN = false, bool SC1 = false, bool FE = false>
 __device__ __forceinline__ float cell_body(const LossParams &p, const Cell &cl, const uint32_t c, const float *xs, float *out,
                                            const LinGrad *lg = nullptr) {
     float stat = 0.f;  // LIN lsm: the cell's decay statistic (rnnt_lin.h), else unused
@@ -49,8 +51,9 @@ __device__ __forceinline__ float cell_body(const LossParams &p, const Cell &cl, 
             for (int i = 0; i < VP; ++i) x[i] = ex2(fmaf(x[i], kLog2e, nml)), s += x[i];
             const float inv = __builtin_amdgcn_rcpf(s);
             const float cb = g.has_blank_corr ? g.hb * inv * ex2(fmaf(xs[p.blank], kLog2e, nml)) : 0.f;
-            const float cl2 = g.has_label ? g.hl * inv * ex2(fmaf(xs[g.lab], kLog2e, nml)) : 0.f;
-            const float h0 = g.h0 * inv;
+            float cl2 = g.has_label ? g.hl * inv * ex2(fmaf(xs[g.lab], kLog2e, nml)) : 0.f;
+            float h0 = g.h0 * inv;
+            if (FE) h0 = fmaf(p.fe_lambda, cl2, g.h0) * inv, cl2 = fmaf(p.fe_lambda, cl2, cl2);
             if (V4) {
 #pragma unroll
                 for (int i = 0; i < VP / 4; ++i)
@@ -89,9 +92,10 @@ __device__ __forceinline__ float cell_body(const LossParams &p, const Cell &cl, 
                 ((float2 *)p.W)[wi] = make_float2(ob, ol);
             }
         } else {
-            const CellGrad g = cell_grad_setup<SC1>(p, cl, c);
+            CellGrad g = cell_grad_setup<SC1>(p, cl, c);
             const float xb = xs[p.blank];
             const float xl = g.has_label ? xs[g.lab] : 0.f;
+            if (FE) fastemit_log(g, xl, p.fe_lambda);
             if (V4) {
 #pragma unroll
                 for (int i = 0; i < VP / 4; ++i)
@@ -108,8 +112,8 @@ __device__ __forceinline__ float cell_body(const LossParams &p, const Cell &cl, 
                 for (int i = 0; i < VP; ++i)
                     if (i < V) out[i] = g.scale * ex2(fmaf(x[i], kLog2e, g.c0));
             }
-            if (g.has_blank_corr) out[p.blank] -= g.scale * ex2(fmaf(xb, kLog2e, g.nl) + g.cb);
-            if (g.has_label) out[g.lab] -= g.scale * ex2(fmaf(xl, kLog2e, g.nl) + g.cl);
+            if (g.has_blank_corr) out[p.blank] -= (FE ? g.bscale : g.scale) * ex2(fmaf(xb, kLog2e, g.nl) + g.cb);
+            if (g.has_label) out[g.lab] -= (FE ? g.lscale : g.scale) * ex2(fmaf(xl, kLog2e, g.nl) + g.cl);
         }
     } else if (GRAD) {
         if (V4) {

@@ -85,6 +85,7 @@ struct LossParams {
     uint32_t cells;  // B*T*U
     FastDiv divU, divT, divV, divOG;  // divOG: lattice column -> offset group
     TileGeom tile;
+    float fe_lambda;  // FastEmit weight of the gradient pass (include/rnnt.h compute_rnnt_loss_fastemit); read by the FE instantiations only
 };
 
 struct WsLayout {

@@ -20,7 +20,7 @@ hipError_t launch_joint_loss(const float *enc_proj, const float *pred_proj, cons
                              const int *labels, const int *label_lengths, const int *input_lengths,
                              const float *cost_scale, int J, int V, int B, int T, int U, int blank, float *costs,
                              float *d_enc_proj, float *d_pred_proj, float *dW2, float *db2, int joint_dtype,
-                             int phases, void *workspace, hipStream_t s, const JointHooks *hooks);
+                             int phases, void *workspace, hipStream_t s, const JointHooks *hooks, float fe_lambda);
 hipError_t joint_aux_pointers(void *workspace, int T, int U, int B, int J, int V, float **expE, float **expP, float **tflag);
 hipError_t launch_joint_prefill(void *workspace, int T, int U, int B, int J, int V, hipStream_t s);
 bool joint_dtype_supported(int joint_dtype, int J, int V);
@@ -149,6 +149,7 @@ static bool fill_params(LossParams &p, const float *acts, float *grads, const in
     p.b0 = 0, p.nb = B;
     p.precise = 0;
     p.visit_all = 0;
+    p.fe_lambda = 0.f;
     p.tile = make_tile(o.maxT, o.maxU, V);
     p.N = w.N, p.Nr = w.Nr, p.Up = w.Up, p.NC = w.NC, p.NG = w.NG;
     p.cells = (uint32_t)cells;
@@ -270,10 +271,13 @@ rnntStatus_t compute_rnnt_loss_bwd(const float *acts, float *grads, const int *f
 
 // compute_rnnt_loss with the upstream gradient folded in (cost_scale NULL = 1) and the build-only flags (include/rnnt.h):
 // costs == NULL = the gradient pass alone (compute_rnnt_loss_bwd), grads == NULL = the forward alone.
-rnntStatus_t compute_rnnt_loss_flags(const float *acts, float *grads, const int *flat_labels,
-                                     const int *label_lengths, const int *input_lengths, const float *cost_scale,
-                                     int alphabet_size, int minibatch, float *costs, void *workspace,
-                                     rnntOptions options, unsigned int flags) {
+// FastEmit's weight (include/rnnt.h): finite and in [0, 1] (a NaN fails both comparisons)
+static bool fastemit_ok(float lambda) { return lambda >= 0.f && lambda <= 1.f; }
+
+static rnntStatus_t loss_flags_call(const float *acts, float *grads, const int *flat_labels,
+                                    const int *label_lengths, const int *input_lengths, const float *cost_scale,
+                                    int alphabet_size, int minibatch, float *costs, void *workspace,
+                                    const rnntOptions &options, unsigned int flags, float fastemit_lambda) {
     if (flags & ~(unsigned)RNNT_VISIT_ALL) return RNNT_STATUS_INVALID_VALUE;
     if (!grads)
         return compute_rnnt_loss_fwd(acts, flat_labels, label_lengths, input_lengths, alphabet_size, minibatch,
@@ -286,6 +290,7 @@ rnntStatus_t compute_rnnt_loss_flags(const float *acts, float *grads, const int 
                      minibatch, costs, workspace, options))
         return RNNT_STATUS_INVALID_VALUE;
     p.visit_all = (flags & RNNT_VISIT_ALL) ? 1 : 0;
+    p.fe_lambda = fastemit_lambda;  // (0: the plain gradient kernels)
     hipStream_t s = (hipStream_t)options.stream;
     if (costs) {
         const WsLayout w = make_layout(options.maxT, options.maxU, minibatch);
@@ -293,6 +298,24 @@ rnntStatus_t compute_rnnt_loss_flags(const float *acts, float *grads, const int 
         if (st != RNNT_STATUS_SUCCESS) return st;
     }
     return run_backward(p, s);
+}
+
+rnntStatus_t compute_rnnt_loss_flags(const float *acts, float *grads, const int *flat_labels,
+                                     const int *label_lengths, const int *input_lengths, const float *cost_scale,
+                                     int alphabet_size, int minibatch, float *costs, void *workspace,
+                                     rnntOptions options, unsigned int flags) {
+    return loss_flags_call(acts, grads, flat_labels, label_lengths, input_lengths, cost_scale, alphabet_size, minibatch, costs,
+                           workspace, options, flags, 0.f);
+}
+
+// compute_rnnt_loss_flags with FastEmit regularisation of the gradients (include/rnnt.h); the costs do not depend on lambda
+rnntStatus_t compute_rnnt_loss_fastemit(const float *acts, float *grads, const int *flat_labels,
+                                        const int *label_lengths, const int *input_lengths, const float *cost_scale,
+                                        int alphabet_size, int minibatch, float *costs, void *workspace,
+                                        rnntOptions options, unsigned int flags, float fastemit_lambda) {
+    if (!fastemit_ok(fastemit_lambda)) return RNNT_STATUS_INVALID_VALUE;
+    return loss_flags_call(acts, grads, flat_labels, label_lengths, input_lengths, cost_scale, alphabet_size, minibatch, costs,
+                           workspace, options, flags, fastemit_lambda);
 }
 
 rnntStatus_t compute_rnnt_loss_ex(const float *acts, float *grads, const int *flat_labels,
@@ -322,7 +345,7 @@ static rnntStatus_t joint_call(const float *enc_proj, const float *pred_proj, co
                                const int *flat_labels, const int *label_lengths, const int *input_lengths,
                                const float *cost_scale, int joint_size, int alphabet_size, int minibatch, float *costs,
                                float *d_enc_proj, float *d_pred_proj, float *dW2, float *db2, int joint_dtype,
-                               int phases, void *workspace, const rnntOptions &options) {
+                               int phases, void *workspace, const rnntOptions &options, float fastemit_lambda = 0.f) {
     if (!enc_proj || !pred_proj || !W2 || !b2 || !flat_labels || !label_lengths || !input_lengths || !workspace)
         return RNNT_STATUS_INVALID_VALUE;
     if ((phases & 1) && !costs) return RNNT_STATUS_INVALID_VALUE;
@@ -341,7 +364,7 @@ static rnntStatus_t joint_call(const float *enc_proj, const float *pred_proj, co
     return from_hip(launch_joint_loss(enc_proj, pred_proj, W2, b2, flat_labels, label_lengths, input_lengths,
                                       cost_scale, joint_size, alphabet_size, minibatch, options.maxT, options.maxU,
                                       options.blank_label, costs, d_enc_proj, d_pred_proj, dW2, db2, joint_dtype,
-                                      phases, workspace, (hipStream_t)options.stream, nullptr));
+                                      phases, workspace, (hipStream_t)options.stream, nullptr, fastemit_lambda));
 }
 
 rnntStatus_t compute_rnnt_joint_loss(const float *enc_proj, const float *pred_proj, const float *W2,
@@ -376,6 +399,19 @@ rnntStatus_t compute_rnnt_joint_loss_bwd(const float *enc_proj, const float *pre
                       options);
 }
 
+// compute_rnnt_joint_loss_bwd with FastEmit regularisation (include/rnnt.h): the same backward from FastEmit's dlogits
+rnntStatus_t compute_rnnt_joint_loss_bwd_fastemit(const float *enc_proj, const float *pred_proj, const float *W2,
+                                                  const float *b2, const int *flat_labels, const int *label_lengths,
+                                                  const int *input_lengths, const float *cost_scale, int joint_size,
+                                                  int alphabet_size, int minibatch, float *d_enc_proj, float *d_pred_proj,
+                                                  float *dW2, float *db2, int joint_dtype, void *workspace,
+                                                  rnntOptions options, float fastemit_lambda) {
+    if (!d_enc_proj || !fastemit_ok(fastemit_lambda)) return RNNT_STATUS_INVALID_VALUE;
+    return joint_call(enc_proj, pred_proj, W2, b2, flat_labels, label_lengths, input_lengths, cost_scale, joint_size,
+                      alphabet_size, minibatch, nullptr, d_enc_proj, d_pred_proj, dW2, db2, joint_dtype, 2, workspace,
+                      options, fastemit_lambda);
+}
+
 // ---- the whole joint network (first Dense layer included) fused with the loss ----
 rnntStatus_t get_joint_net_workspace_size(int maxT, int maxU, int minibatch, int hidden_size, int joint_size, int alphabet_size,
                                           size_t *size_bytes) {
@@ -391,7 +427,8 @@ static rnntStatus_t joint_net_call(const float *enc, const float *pred, const fl
                                    const float *b2, const int *flat_labels, const int *label_lengths, const int *input_lengths,
                                    const float *cost_scale, int hidden_size, int joint_size, int alphabet_size, int minibatch,
                                    float *costs, float *d_enc, float *d_pred, float *dW1, float *db1, float *dW2, float *db2,
-                                   int joint_dtype, int phases, void *workspace, const rnntOptions &options) {
+                                   int joint_dtype, int phases, void *workspace, const rnntOptions &options,
+                                   float fastemit_lambda = 0.f) {
     if (!enc || !pred || !W1 || !b1 || !W2 || !b2 || !flat_labels || !label_lengths || !input_lengths || !workspace)
         return RNNT_STATUS_INVALID_VALUE;
     if ((phases & 1) && !costs) return RNNT_STATUS_INVALID_VALUE;
@@ -440,7 +477,7 @@ static rnntStatus_t joint_net_call(const float *enc, const float *pred, const fl
     const bool bwd = (phases & 2) && any_grad;
     e = launch_joint_loss(ep, pp, W2, b2, flat_labels, label_lengths, input_lengths, cost_scale, joint_size, alphabet_size, B, T, U,
                           options.blank_label, costs, bwd ? dep : nullptr, bwd ? dpp : nullptr, bwd ? dW2 : nullptr,
-                          bwd ? db2 : nullptr, joint_dtype, phases, workspace, s, &hooks);
+                          bwd ? db2 : nullptr, joint_dtype, phases, workspace, s, &hooks, fastemit_lambda);
     if (e != hipSuccess || !bwd) return from_hip(e);
     return from_hip(launch_dense_bwd(B, T, U, hidden_size, joint_size, d_enc, d_pred, dW1, db1, workspace, base, s));
 }
@@ -471,6 +508,19 @@ rnntStatus_t compute_rnnt_joint_net_loss_bwd(const float *enc, const float *pred
     if (!d_enc) return RNNT_STATUS_INVALID_VALUE;
     return joint_net_call(enc, pred, W1, b1, W2, b2, flat_labels, label_lengths, input_lengths, cost_scale, hidden_size, joint_size,
                           alphabet_size, minibatch, nullptr, d_enc, d_pred, dW1, db1, dW2, db2, joint_dtype, 2, workspace, options);
+}
+
+rnntStatus_t compute_rnnt_joint_net_loss_bwd_fastemit(const float *enc, const float *pred, const float *W1, const float *b1,
+                                                      const float *W2, const float *b2, const int *flat_labels,
+                                                      const int *label_lengths, const int *input_lengths,
+                                                      const float *cost_scale, int hidden_size, int joint_size,
+                                                      int alphabet_size, int minibatch, float *d_enc, float *d_pred, float *dW1,
+                                                      float *db1, float *dW2, float *db2, int joint_dtype, void *workspace,
+                                                      rnntOptions options, float fastemit_lambda) {
+    if (!d_enc || !fastemit_ok(fastemit_lambda)) return RNNT_STATUS_INVALID_VALUE;
+    return joint_net_call(enc, pred, W1, b1, W2, b2, flat_labels, label_lengths, input_lengths, cost_scale, hidden_size, joint_size,
+                          alphabet_size, minibatch, nullptr, d_enc, d_pred, dW1, db1, dW2, db2, joint_dtype, 2, workspace, options,
+                          fastemit_lambda);
 }
 
 // The joint alone, for decoding (utils/decoding.py:6-18 evaluates dense_1 / dense_2 on one lattice cell per step).

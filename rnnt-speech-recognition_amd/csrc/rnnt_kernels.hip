@@ -53,7 +53,7 @@ __device__ __forceinline__ void grad_store16(gs_v4f *dst, const gs_v4f v) { __bu
 // (then no aligned span reaches past the tensor).
 constexpr int kFillRows = 16;  // W diagonals per fill workgroup of the lsm launch
 
-template <int VP, bool GRAD, bool AL = true, bool LIN = false>
+template <int VP, bool GRAD, bool AL = true, bool LIN = false, bool FE = false>
 __global__ __launch_bounds__(256) void cell_tile_kernel(const LossParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
@@ -233,10 +233,10 @@ __global__ __launch_bounds__(256) void cell_tile_kernel(const LossParams p) {
 
     float stat = 0.f;
     if (AL) {
-        if ((GRAD && tid < tg.TT * tg.UU) || cl.valid) stat = cell_body<VP, true, GRAD, LIN>(p, cl, c, lds + tid * V, lds + tid * V, &lg);  // (lanes beyond the patch own no LDS)
+        if ((GRAD && tid < tg.TT * tg.UU) || cl.valid) stat = cell_body<VP, true, GRAD, LIN, false, FE>(p, cl, c, lds + tid * V, lds + tid * V, &lg);  // (lanes beyond the patch own no LDS)
     } else if ((int)r < tg.TT) {
         const int a = (int)((patch0 + r * row_f) & 3);
-        if (GRAD || cl.valid) stat = cell_body<VP, false, GRAD, LIN>(p, cl, c, lds + r * row_lds + a + cu * V, lds + r * row_lds + a + cu * V, &lg);
+        if (GRAD || cl.valid) stat = cell_body<VP, false, GRAD, LIN, false, FE>(p, cl, c, lds + r * row_lds + a + cu * V, lds + r * row_lds + a + cu * V, &lg);
     }
     if (!GRAD && LIN) {  // wave sums by butterfly (no LDS: the patch image is still being read by other waves)
         float cnt = cl.valid ? 1.f : 0.f;
@@ -286,13 +286,13 @@ __global__ __launch_bounds__(256) void cell_tile_kernel(const LossParams p) {
 // ---------------------------------------------------------------------------------------------
 // General path (any V, any alignment): one lattice cell per WAVE, lanes stride over V (rnnt_cellwave.h).
 // ---------------------------------------------------------------------------------------------
-template <bool V4, bool GRAD>
+template <bool V4, bool GRAD, bool FE = false>
 __global__ __launch_bounds__(256) void cell_wave_kernel(const LossParams p) {
     // No grid stride: a workgroup owns ONE contiguous span of cells (about 16 KB of logits: 4 waves x wave_cells(V) cells), as the
     // streaming kernels that reach 6 TB/s on this part do (scripts/probes/probe_hbm.hip; grid-stride loops: 4.7-5.0 TB/s).
     const uint32_t cpw = (uint32_t)wave_cells(p.V);
     const uint32_t c_lo = (blockIdx.x * 4u + (threadIdx.x >> 6)) * cpw;
-    cell_wave_range<V4, GRAD>(p, c_lo, min(c_lo + cpw, p.cells), threadIdx.x & 63);
+    cell_wave_range<V4, GRAD, false, FE>(p, c_lo, min(c_lo + cpw, p.cells), threadIdx.x & 63);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -368,7 +368,8 @@ bool tile_path_ok(const LossParams &p, bool grad) {
 }
 
 // Patch kernels (one lattice cell per lane) for V <= 60 and 16-byte-aligned tensors; otherwise one cell per wave.
-template <bool GRAD, bool LIN = false>
+// FE: the FastEmit instantiations of the gradient kernels (p.fe_lambda != 0); every other call launches the plain ones.
+template <bool GRAD, bool LIN = false, bool FE = false>
 static hipError_t launch_cell(const LossParams &p, hipStream_t s) {
     if (LIN && !tile_path_ok(p, GRAD)) return hipErrorInvalidValue;
     if (tile_path_ok(p, GRAD)) {
@@ -386,29 +387,29 @@ static hipError_t launch_cell(const LossParams &p, hipStream_t s) {
             size_t shmu = (size_t)p.tile.TT * pitch * sizeof(float);
             if (shmu < shm) shmu = shm;
             if (p.V <= 32)
-                hipLaunchKernelGGL((cell_tile_kernel<32, GRAD, false, LIN>), dim3(blocks), dim3(256), shmu, s, p);
+                hipLaunchKernelGGL((cell_tile_kernel<32, GRAD, false, LIN, FE>), dim3(blocks), dim3(256), shmu, s, p);
             else
-                hipLaunchKernelGGL((cell_tile_kernel<64, GRAD, false, LIN>), dim3(blocks), dim3(256), shmu, s, p);
+                hipLaunchKernelGGL((cell_tile_kernel<64, GRAD, false, LIN, FE>), dim3(blocks), dim3(256), shmu, s, p);
         } else if (p.V <= 32)
-            hipLaunchKernelGGL((cell_tile_kernel<32, GRAD, true, LIN>), dim3(blocks), dim3(256), shm, s, p);
+            hipLaunchKernelGGL((cell_tile_kernel<32, GRAD, true, LIN, FE>), dim3(blocks), dim3(256), shm, s, p);
         else
-            hipLaunchKernelGGL((cell_tile_kernel<64, GRAD, true, LIN>), dim3(blocks), dim3(256), shm, s, p);
+            hipLaunchKernelGGL((cell_tile_kernel<64, GRAD, true, LIN, FE>), dim3(blocks), dim3(256), shm, s, p);
     } else {
         const bool v4 = (p.V % 4) == 0 && ((uintptr_t)p.acts & 15) == 0 && (!GRAD || ((uintptr_t)p.grads & 15) == 0);
         const unsigned per_wg = 4u * (unsigned)wave_cells(p.V);
         const unsigned blocks = (p.cells + per_wg - 1u) / per_wg;
         if (v4)
-            hipLaunchKernelGGL((cell_wave_kernel<true, GRAD>), dim3(blocks), dim3(256), 0, s, p);
+            hipLaunchKernelGGL((cell_wave_kernel<true, GRAD, FE>), dim3(blocks), dim3(256), 0, s, p);
         else
-            hipLaunchKernelGGL((cell_wave_kernel<false, GRAD>), dim3(blocks), dim3(256), 0, s, p);
+            hipLaunchKernelGGL((cell_wave_kernel<false, GRAD, FE>), dim3(blocks), dim3(256), 0, s, p);
     }
     return hipGetLastError();
 }
 
 hipError_t launch_lsm(const LossParams &p, hipStream_t s) { return launch_cell<false>(p, s); }
-hipError_t launch_grad(const LossParams &p, hipStream_t s) { return launch_cell<true>(p, s); }
+hipError_t launch_grad(const LossParams &p, hipStream_t s) { return p.fe_lambda != 0.f ? launch_cell<true, false, true>(p, s) : launch_cell<true>(p, s); }
 hipError_t launch_lsm_lin(const LossParams &p, hipStream_t s) { return launch_cell<false, true>(p, s); }
-hipError_t launch_grad_lin(const LossParams &p, hipStream_t s) { return launch_cell<true, true>(p, s); }
+hipError_t launch_grad_lin(const LossParams &p, hipStream_t s) { return p.fe_lambda != 0.f ? launch_cell<true, true, true>(p, s) : launch_cell<true, true>(p, s); }
 
 
 template <int K, int G, int NB>

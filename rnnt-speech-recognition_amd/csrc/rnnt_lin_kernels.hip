@@ -462,7 +462,7 @@ __global__ __launch_bounds__(64 * (1 + kLinLoaders)) void lin_sweep_kernel(const
 // state word says that its lattice is in the log format, so that a later backward-only call goes straight to the gradient
 // stage here.
 // ---------------------------------------------------------------------------------------------
-template <int K, int G, int NB>
+template <int K, int G, int NB, bool FE = false>
 __global__ __launch_bounds__(kRedoThreads) void lin_redo_kernel(const LossParams p, const int force, const int team) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int chunkf = G * 2 * 64 * K;
@@ -490,7 +490,7 @@ __global__ __launch_bounds__(kRedoThreads) void lin_redo_kernel(const LossParams
     if (redo) redo_lattice<K, G, NB>(p, b, tm, lds, tid);
     uint32_t lo, hi;
     redo_cell_range(p, b, tm, lo, hi);
-    if (p.grads) redo_cells<true>(p, lo, hi, tid, lds, NB * chunkf);
+    if (p.grads) redo_cells<true, FE>(p, lo, hi, tid, lds, NB * chunkf);
     if (!tm.ok) {  // a team member never arrived (bounded spin): the utterance's results must not look valid
         if (p.costs && tm.k == 0 && tid == 0) st_f32_wt(p.costs + b, NAN);
         if (p.grads)
@@ -516,13 +516,13 @@ static hipError_t launch_lin_sweep(const LossParams &p, hipStream_t s) {
     hipLaunchKernelGGL((lin_sweep_kernel<K, G, R::NB>), dim3(2 * p.nb), dim3(64 * (1 + kLinLoaders)), R::kBytes, s, p);
     return hipGetLastError();
 }
-template <int K, int G>
+template <int K, int G, bool FE = false>
 static hipError_t launch_lin_redo(const LossParams &p, const bool force, hipStream_t s) {
     using R = SweepRing<K, G>;
-    hipError_t e = set_lds(lin_redo_kernel<K, G, R::NB>, R::kBytes);
+    hipError_t e = set_lds(lin_redo_kernel<K, G, R::NB, FE>, R::kBytes);
     if (e != hipSuccess) return e;
     const int team = redo_team_size(p.nb, p.T, p.U, device_cu_count());
-    hipLaunchKernelGGL((lin_redo_kernel<K, G, R::NB>), dim3(p.nb * team), dim3(kRedoThreads), R::kBytes, s, p, force ? 1 : 0, team);
+    hipLaunchKernelGGL((lin_redo_kernel<K, G, R::NB, FE>), dim3(p.nb * team), dim3(kRedoThreads), R::kBytes, s, p, force ? 1 : 0, team);
     return hipGetLastError();
 }
 
@@ -530,6 +530,8 @@ hipError_t launch_sweeps_lin(const LossParams &p, hipStream_t s) {
     return sweep_dispatch(p.U, [&](auto K, auto G) { return launch_lin_sweep<K, G>(p, s); });
 }
 hipError_t launch_redo_lin(const LossParams &p, const bool force, hipStream_t s) {
+    if (p.grads && p.fe_lambda != 0.f)  // FastEmit: the hand-back's gradient stage with the label edge weighted (rnnt_cellbody.h)
+        return sweep_dispatch(p.U, [&](auto K, auto G) { return launch_lin_redo<K, G, true>(p, force, s); });
     return sweep_dispatch(p.U, [&](auto K, auto G) { return launch_lin_redo<K, G>(p, force, s); });
 }
 

@@ -111,7 +111,7 @@ __device__ __forceinline__ void cell_lsm_loop(const LossParams &p, const Cell &c
 // workgroup-wide "load a chunk, barrier, compute, barrier, store, barrier" of round 4 left the CU waiting on every step: a batch
 // in which every utterance is handed back took 1.0 ms in this kernel).  Otherwise (V % 4 != 0 or unaligned tensors): straight
 // from / to global memory.
-template <bool GRAD>
+template <bool GRAD, bool FE = false>
 __device__ __forceinline__ void redo_cells(const LossParams &p, const uint32_t c0, const uint32_t c1, const int tid, float *lds,
                                            const int lds_floats) {
     const bool v4 = (p.V % 4) == 0 && (((uintptr_t)p.acts | (uintptr_t)p.grads) & 15) == 0;
@@ -142,9 +142,9 @@ __device__ __forceinline__ void redo_cells(const LossParams &p, const uint32_t c
                 float *xs = my + (size_t)lane * V;
                 if (GRAD || cl.valid) {
                     if (V <= 32)
-                        cell_body<32, true, GRAD, false, true>(p, cl, c, xs, xs);
+                        cell_body<32, true, GRAD, false, true, FE>(p, cl, c, xs, xs);
                     else if (V <= 64)
-                        cell_body<64, true, GRAD, false, true>(p, cl, c, xs, xs);
+                        cell_body<64, true, GRAD, false, true, FE>(p, cl, c, xs, xs);
                     else if (!GRAD)
                         cell_lsm_loop(p, cl, c, xs);  // (the fused joint's parked logits at 65 ... 128 symbols: edge weights only)
                     else  // no gradient body beyond 64 symbols (the loss op's linear path stops at 60, the joint passes no grads):
@@ -172,9 +172,9 @@ __device__ __forceinline__ void redo_cells(const LossParams &p, const uint32_t c
         float *out = GRAD ? p.grads + (size_t)c * p.V : nullptr;
         if (!GRAD && !cl.valid) continue;
         if (p.V <= 32)
-            cell_body<32, false, GRAD, false, true>(p, cl, c, xs, out);
+            cell_body<32, false, GRAD, false, true, FE>(p, cl, c, xs, out);
         else if (p.V <= 64)
-            cell_body<64, false, GRAD, false, true>(p, cl, c, xs, out);
+            cell_body<64, false, GRAD, false, true, FE>(p, cl, c, xs, out);
         else if (!GRAD)
             cell_lsm_loop(p, cl, c, xs);
         else  // (unreachable today, see above: loud, not wrong)

@@ -21,7 +21,7 @@ from . import _lib
 
 class _JointLossFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, enc_proj, pred_proj, W2, b2, labels, input_lengths, label_lengths, blank_label, joint_dtype):
+    def forward(ctx, enc_proj, pred_proj, W2, b2, labels, input_lengths, label_lengths, blank_label, joint_dtype, fastemit_lambda=0.0):
         lib = _lib.load()
         for name, x in (("enc_proj", enc_proj), ("pred_proj", pred_proj), ("W2", W2), ("b2", b2)):
             if not x.is_cuda:
@@ -62,6 +62,7 @@ class _JointLossFunction(torch.autograd.Function):
         ctx.save_for_backward(ep, pp, w2, bb, labels, il, ll, ws)
         ctx.blank = int(blank_label)
         ctx.joint_dtype = int(joint_dtype)
+        ctx.fastemit_lambda = float(fastemit_lambda)
         return costs
 
     @staticmethod
@@ -75,13 +76,17 @@ class _JointLossFunction(torch.autograd.Function):
         with torch.cuda.device(dev):
             d_ep, d_pp, d_w2, d_b2 = (torch.empty_like(x) for x in (ep, pp, w2, bb))
             opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, ctx.blank, T, U)
-            st = lib.compute_rnnt_joint_loss_bwd(ep.data_ptr(), pp.data_ptr(), w2.data_ptr(), bb.data_ptr(),
-                                                 labels.data_ptr(), ll.data_ptr(), il.data_ptr(), scale.data_ptr(),
-                                                 J, V, B, d_ep.data_ptr(), d_pp.data_ptr(), d_w2.data_ptr(),
-                                                 d_b2.data_ptr(), ctx.joint_dtype, ws.data_ptr(), opts)
+            args = (ep.data_ptr(), pp.data_ptr(), w2.data_ptr(), bb.data_ptr(),
+                    labels.data_ptr(), ll.data_ptr(), il.data_ptr(), scale.data_ptr(),
+                    J, V, B, d_ep.data_ptr(), d_pp.data_ptr(), d_w2.data_ptr(),
+                    d_b2.data_ptr(), ctx.joint_dtype, ws.data_ptr(), opts)
+            if ctx.fastemit_lambda != 0.0:
+                st = lib.compute_rnnt_joint_loss_bwd_fastemit(*args, ctx.fastemit_lambda)
+            else:
+                st = lib.compute_rnnt_joint_loss_bwd(*args)
             _lib.check(st, "compute_rnnt_joint_loss_bwd")
             _note_backward_rows(ws, T, U, B, J, V, ctx.blank)
-        return d_ep, d_pp, d_w2, d_b2, None, None, None, None, None
+        return d_ep, d_pp, d_w2, d_b2, None, None, None, None, None, None
 
 
 class _JointNetLossFunction(torch.autograd.Function):
@@ -89,7 +94,7 @@ class _JointNetLossFunction(torch.autograd.Function):
     backward run in the library too (csrc/dense_kernels.hip), not in torch."""
 
     @staticmethod
-    def forward(ctx, enc, pred, W1, b1, W2, b2, labels, input_lengths, label_lengths, blank_label, joint_dtype):
+    def forward(ctx, enc, pred, W1, b1, W2, b2, labels, input_lengths, label_lengths, blank_label, joint_dtype, fastemit_lambda=0.0):
         lib = _lib.load()
         for name, x in (("enc", enc), ("pred", pred), ("W1", W1), ("b1", b1), ("W2", W2), ("b2", b2)):
             if not x.is_cuda:
@@ -132,6 +137,7 @@ class _JointNetLossFunction(torch.autograd.Function):
         ctx.save_for_backward(e, p, w1, bb1, w2, bb2, labels, il, ll, ws)
         ctx.blank = int(blank_label)
         ctx.joint_dtype = int(joint_dtype)
+        ctx.fastemit_lambda = float(fastemit_lambda)
         return costs
 
     @staticmethod
@@ -146,13 +152,17 @@ class _JointNetLossFunction(torch.autograd.Function):
         with torch.cuda.device(dev):
             grads = [torch.empty_like(x) for x in (e, p, w1, bb1, w2, bb2)]
             opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, ctx.blank, T, U)
-            st = lib.compute_rnnt_joint_net_loss_bwd(e.data_ptr(), p.data_ptr(), w1.data_ptr(), bb1.data_ptr(), w2.data_ptr(),
-                                                     bb2.data_ptr(), labels.data_ptr(), ll.data_ptr(), il.data_ptr(),
-                                                     scale.data_ptr(), H, J, V, B, *(g.data_ptr() for g in grads),
-                                                     ctx.joint_dtype, ws.data_ptr(), opts)
+            args = (e.data_ptr(), p.data_ptr(), w1.data_ptr(), bb1.data_ptr(), w2.data_ptr(),
+                    bb2.data_ptr(), labels.data_ptr(), ll.data_ptr(), il.data_ptr(),
+                    scale.data_ptr(), H, J, V, B, *(g.data_ptr() for g in grads),
+                    ctx.joint_dtype, ws.data_ptr(), opts)
+            if ctx.fastemit_lambda != 0.0:
+                st = lib.compute_rnnt_joint_net_loss_bwd_fastemit(*args, ctx.fastemit_lambda)
+            else:
+                st = lib.compute_rnnt_joint_net_loss_bwd(*args)
             _lib.check(st, "compute_rnnt_joint_net_loss_bwd")
             _note_backward_rows(ws, T, U, B, J, V, ctx.blank)
-        return (*grads, None, None, None, None, None)
+        return (*grads, None, None, None, None, None, None)
 
 
 JOINT_DTYPES = {"f32": 0, "f16": 1}
@@ -195,7 +205,8 @@ def _new_workspace(nbytes: int, dev) -> torch.Tensor:
 
 
 def rnnt_joint_loss(enc, pred, W1, b1, W2, b2, labels, input_lengths, label_lengths, blank_label: int = 0,
-                    joint_dtype: str = "auto", first_layer: str = "auto", visit_all: bool = False):
+                    joint_dtype: str = "auto", first_layer: str = "auto", visit_all: bool = False,
+                    fastemit_lambda: float = 0.0):
     """costs[b] = transducer NLL of  logits = tanh((enc[:,:,None]+pred[:,None]) @ W1 + b1) @ W2 + b2.
 
     enc [B,T,H] (encoder output), pred [B,U,H] (prediction-network output), W1 [H,J], b1 [J],
@@ -213,7 +224,13 @@ def rnnt_joint_loss(enc, pred, W1, b1, W2, b2, labels, input_lengths, label_leng
 
     visit_all: RNNT_VISIT_ALL of include/rnnt.h -- the backward visits every lattice row instead of skipping the rows (x 32-column
     tiles) whose cells all have an occupancy below 2^-40 (their binary16 dlogits parts are exact zeros already: same results up to the
-    order of a few f32 sums; timing then does not depend on the data)."""
+    order of a few f32 sums; timing then does not depend on the data).
+
+    fastemit_lambda in [0, 1]: FastEmit regularisation (include/rnnt.h compute_rnnt_loss_fastemit) -- the backward starts from the
+    dlogits with the label edges' gradient scaled by 1 + fastemit_lambda; the costs do not change."""
+    from .loss import check_fastemit_lambda
+
+    fastemit_lambda = check_fastemit_lambda(fastemit_lambda)
     dtype_word = lambda name: JOINT_DTYPES[name] | (_lib.RNNT_VISIT_ALL if visit_all else 0)  # noqa: E731
     if joint_dtype == "auto":
         joint_dtype = _auto_joint_dtype(W2.shape[0], W2.shape[1])
@@ -238,7 +255,7 @@ def rnnt_joint_loss(enc, pred, W1, b1, W2, b2, labels, input_lengths, label_leng
     if first_layer == "engine":
         # the whole joint network behind the C ABI: W1 GEMMs, their backward, tanh, W2, the lattice (include/rnnt.h)
         return _JointNetLossFunction.apply(enc, pred, W1, b1, W2, b2, labels, input_lengths, label_lengths, blank_label,
-                                           dtype_word(joint_dtype))
+                                           dtype_word(joint_dtype), fastemit_lambda)
     if first_layer != "torch":
         raise ValueError("rnnt_joint_loss: first_layer must be 'auto', 'engine' or 'torch'")
     # hidden sizes the library's dense kernels do not take (not a multiple of 32): the first layer through torch.matmul
@@ -246,7 +263,7 @@ def rnnt_joint_loss(enc, pred, W1, b1, W2, b2, labels, input_lengths, label_leng
     enc_proj = torch.matmul(enc, W1) + b1
     pred_proj = torch.matmul(pred, W1)
     return _JointLossFunction.apply(enc_proj, pred_proj, W2, b2, labels, input_lengths, label_lengths, blank_label,
-                                    dtype_word(joint_dtype))
+                                    dtype_word(joint_dtype), fastemit_lambda)
 
 
 _LOGITS_CACHE = {}  # (device, entry, shape) -> (workspace, output): a greedy decoder asks for one cell per emitted symbol
@@ -349,9 +366,13 @@ class JointLoss(torch.nn.Module):
     """The reference's joint network (model.py:158-166) + loss as one module.  Parameters follow Keras'
     Dense defaults: glorot-uniform kernels, zero biases."""
 
-    def __init__(self, hidden: int, joint_size: int, vocab_size: int, blank_label: int = 0, visit_all: bool = False):
+    def __init__(self, hidden: int, joint_size: int, vocab_size: int, blank_label: int = 0, visit_all: bool = False,
+                 fastemit_lambda: float = 0.0):
         super().__init__()
+        from .loss import check_fastemit_lambda
+
         self.blank_label = blank_label
+        self.fastemit_lambda = check_fastemit_lambda(fastemit_lambda)  # FastEmit's weight on the label edges' gradient (rnnt_joint_loss)
         self.visit_all = visit_all  # RNNT_VISIT_ALL: no occupancy floor in the backward (rnnt_joint_loss)
         self.W1 = torch.nn.Parameter(torch.empty(hidden, joint_size))
         self.b1 = torch.nn.Parameter(torch.zeros(joint_size))
@@ -363,7 +384,8 @@ class JointLoss(torch.nn.Module):
 
     def forward(self, enc, pred, labels, input_lengths, label_lengths):
         return rnnt_joint_loss(enc, pred, self.W1, self.b1, self.W2, self.b2, labels, input_lengths,
-                               label_lengths, self.blank_label, visit_all=self.visit_all)
+                               label_lengths, self.blank_label, visit_all=self.visit_all,
+                               fastemit_lambda=self.fastemit_lambda)
 
     def logits(self, enc, pred):
         """Unfused reference form (materialises [B,T,U,J] and [B,T,U,V] in torch); for tests and host-logic checks on CPU."""

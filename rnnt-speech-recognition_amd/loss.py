@@ -26,9 +26,17 @@ def _as_i32(x: torch.Tensor, device) -> torch.Tensor:
     return x.to(device=device, dtype=torch.int32).contiguous()
 
 
+def check_fastemit_lambda(fastemit_lambda) -> float:
+    """FastEmit's weight as a float; ValueError unless it is finite and in [0, 1] (include/rnnt.h compute_rnnt_loss_fastemit)."""
+    lam = float(fastemit_lambda)
+    if not (0.0 <= lam <= 1.0):  # (NaN fails both comparisons)
+        raise ValueError(f"fastemit_lambda must be finite and in [0, 1], got {fastemit_lambda!r}")
+    return lam
+
+
 class _RNNTLossFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, acts, labels, input_lengths, label_lengths, blank_label):
+    def forward(ctx, acts, labels, input_lengths, label_lengths, blank_label, fastemit_lambda=0.0):
         lib = _lib.load()
         if not acts.is_cuda:
             raise RuntimeError(
@@ -60,6 +68,7 @@ class _RNNTLossFunction(torch.autograd.Function):
         _lib.check(st, "compute_rnnt_loss_fwd")
         ctx.save_for_backward(acts_c, labels, input_lengths, label_lengths, ws)
         ctx.blank = int(blank_label)
+        ctx.fastemit_lambda = float(fastemit_lambda)
         return costs
 
     @staticmethod
@@ -72,28 +81,39 @@ class _RNNTLossFunction(torch.autograd.Function):
         with torch.cuda.device(dev):
             grads = torch.empty_like(acts)
             opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, ctx.blank, T, U)
-            st = lib.compute_rnnt_loss_bwd(
-                acts.data_ptr(), grads.data_ptr(), labels.data_ptr(), label_lengths.data_ptr(),
-                input_lengths.data_ptr(), scale.data_ptr(), V, B, ws.data_ptr(), opts)
+            if ctx.fastemit_lambda != 0.0:  # costs == NULL: the gradient pass alone, with FastEmit's weight on the label edges
+                st = lib.compute_rnnt_loss_fastemit(
+                    acts.data_ptr(), grads.data_ptr(), labels.data_ptr(), label_lengths.data_ptr(),
+                    input_lengths.data_ptr(), scale.data_ptr(), V, B, None, ws.data_ptr(), opts, 0, ctx.fastemit_lambda)
+            else:
+                st = lib.compute_rnnt_loss_bwd(
+                    acts.data_ptr(), grads.data_ptr(), labels.data_ptr(), label_lengths.data_ptr(),
+                    input_lengths.data_ptr(), scale.data_ptr(), V, B, ws.data_ptr(), opts)
         _lib.check(st, "compute_rnnt_loss_bwd")
-        return grads, None, None, None, None
+        return grads, None, None, None, None, None
 
 
-def rnnt_loss(acts, labels, input_lengths, label_lengths, blank_label: int = 0):
+def rnnt_loss(acts, labels, input_lengths, label_lengths, blank_label: int = 0, fastemit_lambda: float = 0.0):
     """Per-utterance transducer negative log-likelihood, differentiable in `acts`.
+
+    fastemit_lambda in [0, 1]: FastEmit regularisation -- the gradient through the lattice's label edges is scaled by
+    1 + fastemit_lambda (typical 1e-3 ... 1e-2); the returned costs do not depend on it.
 
     Same contract as warprnnt_tensorflow.rnnt_loss on a CUDA build (utils/loss.py:34-35):
     acts are RAW LOGITS [B, T, U, V] (the log-softmax is fused), labels [B, U-1] int,
     input_lengths / label_lengths [B] int; returns costs [B] float32."""
-    return _RNNTLossFunction.apply(acts, labels, input_lengths, label_lengths, blank_label)
+    return _RNNTLossFunction.apply(acts, labels, input_lengths, label_lengths, blank_label, check_fastemit_lambda(fastemit_lambda))
 
 
-def rnnt_loss_and_grad(acts, labels, input_lengths, label_lengths, blank_label: int = 0, visit_all: bool = False):
+def rnnt_loss_and_grad(acts, labels, input_lengths, label_lengths, blank_label: int = 0, visit_all: bool = False,
+                       fastemit_lambda: float = 0.0):
     """The upstream C entry point as one call: compute_rnnt_loss(acts, grads, ...) ->
     (costs [B], grads [B,T,U,V]) with grads = d cost_b / d acts (unscaled), like the two outputs of
     the reference's WarpRNNT op.  No autograd graph is built.
     visit_all: compute_rnnt_loss_flags(..., RNNT_VISIT_ALL) -- no occupancy floor (vocabularies above 60 symbols otherwise
-    write zeros for cells whose occupancy is below 2^-50 without reading their logits)."""
+    write zeros for cells whose occupancy is below 2^-50 without reading their logits).
+    fastemit_lambda in [0, 1]: compute_rnnt_loss_fastemit -- FastEmit's gradients (the costs do not change)."""
+    lam = check_fastemit_lambda(fastemit_lambda)
     lib = _lib.load()
     if not acts.is_cuda:
         raise RuntimeError("rnnt_loss_and_grad: acts must live on an MI355X (cuda/HIP) device")
@@ -112,7 +132,12 @@ def rnnt_loss_and_grad(acts, labels, input_lengths, label_lengths, blank_label: 
         costs = torch.empty(B, dtype=torch.float32, device=dev)
         grads = torch.empty_like(acts_c)
         opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, int(blank_label), T, U)
-        if visit_all:
+        if lam != 0.0:
+            st = lib.compute_rnnt_loss_fastemit(
+                acts_c.data_ptr(), grads.data_ptr(), labels.data_ptr(), label_lengths.data_ptr(),
+                input_lengths.data_ptr(), None, V, B, costs.data_ptr(), ws.data_ptr(), opts,
+                _lib.RNNT_VISIT_ALL if visit_all else 0, lam)
+        elif visit_all:
             st = lib.compute_rnnt_loss_flags(
                 acts_c.data_ptr(), grads.data_ptr(), labels.data_ptr(), label_lengths.data_ptr(),
                 input_lengths.data_ptr(), None, V, B, costs.data_ptr(), ws.data_ptr(), opts, _lib.RNNT_VISIT_ALL)
@@ -127,15 +152,16 @@ def rnnt_loss_and_grad(acts, labels, input_lengths, label_lengths, blank_label: 
 class RNNTLoss(torch.nn.Module):
     """nn.Module wrapper; reduction 'none' returns the reference's per-utterance costs."""
 
-    def __init__(self, blank_label: int = 0, reduction: str = "none"):
+    def __init__(self, blank_label: int = 0, reduction: str = "none", fastemit_lambda: float = 0.0):
         super().__init__()
+        self.fastemit_lambda = check_fastemit_lambda(fastemit_lambda)
         if reduction not in ("none", "sum", "mean"):
             raise ValueError(reduction)
         self.blank_label = blank_label
         self.reduction = reduction
 
     def forward(self, acts, labels, input_lengths, label_lengths):
-        costs = rnnt_loss(acts, labels, input_lengths, label_lengths, self.blank_label)
+        costs = rnnt_loss(acts, labels, input_lengths, label_lengths, self.blank_label, self.fastemit_lambda)
         if self.reduction == "sum":
             return costs.sum()
         if self.reduction == "mean":

@@ -221,9 +221,11 @@ class PredictionNetwork(nn.Module):
 class Transducer(nn.Module):
     """build_keras_model (model.py:119-169) with the joint fused into the loss.  `lstm="engine"` runs every LSTM layer of
     `forward` (training included) through the library's step kernels instead of nn.LSTM; parameters, state_dict() and
-    checkpoints are the same on both routes, and the decoders' `encoder=` / `prediction=` options are independent of it."""
+    checkpoints are the same on both routes, and the decoders' `encoder=` / `prediction=` options are independent of it.
+    `fastemit_lambda` (0 ... 1) is handed to the JointLoss: FastEmit regularisation of the loss's gradients, so that TrainStep trains
+    a streaming model to emit sooner without any change of its own."""
 
-    def __init__(self, hp: HParams, blank_label: int = 0, lstm: str = "torch"):
+    def __init__(self, hp: HParams, blank_label: int = 0, lstm: str = "torch", fastemit_lambda: float = 0.0):
         super().__init__()
         self.hp = hp
         self.lstm_route = _check_lstm_route(lstm)
@@ -234,7 +236,8 @@ class Transducer(nn.Module):
                 f"encoder output width {self.encoder.out_width} != prediction-network width "
                 f"{self.prediction.out_width}: the broadcast add of model.py:158-160 needs equal widths (put "
                 "time_reduction_index before the last encoder layer)")
-        self.joint = JointLoss(self.encoder.out_width, hp.joint_net_size, hp.vocab_size, blank_label)
+        self.joint = JointLoss(self.encoder.out_width, hp.joint_net_size, hp.vocab_size, blank_label,
+                               fastemit_lambda=fastemit_lambda)
 
     def forward(self, mel_specs, pred_inp):
         """-> (enc [B, T', H], pred [B, U, H]); U = L_max + 1 because pred_inp = [0] ++ labels
