@@ -6,10 +6,15 @@ from __future__ import annotations
 import ctypes
 import os
 
+from .build import BIAS_LIB_PATH as _DEFAULT_BIAS_LIB_PATH
 from .build import LIB_PATH as _DEFAULT_LIB_PATH
 
 # dev knob: load an experimental build of the library instead (scripts/build_variant.sh)
 LIB_PATH = os.environ.get("RNNT_LIBWARPRNNT", _DEFAULT_LIB_PATH)
+# the extension library goes with the base library: a variant base library is paired with the libwarprnnt_bias.so beside it, never
+# with the stock one (the two step each other's workspaces)
+BIAS_LIB_PATH = (_DEFAULT_BIAS_LIB_PATH if LIB_PATH == _DEFAULT_LIB_PATH
+                 else os.path.join(os.path.dirname(LIB_PATH), "libwarprnnt_bias.so"))
 
 RNNT_CPU, RNNT_GPU = 0, 1
 STATUS_SUCCESS = 0
@@ -117,7 +122,27 @@ class rnntPrednetBlock(ctypes.Structure):
     ]
 
 
+class rnntBiasGraph(ctypes.Structure):
+    """The context graph of the biased beam steps (include/rnnt_bias.h): a host struct of device pointers."""
+    _fields_ = [
+        ("num_states", ctypes.c_int),
+        ("num_arcs", ctypes.c_int),
+        ("arc_offsets", ctypes.c_void_p),
+        ("arc_tokens", ctypes.c_void_p),
+        ("arc_next", ctypes.c_void_p),
+        ("arc_bias", ctypes.c_void_p),
+        ("fail_bias", ctypes.c_void_p),
+    ]
+
+
 _lib = None
+_bias_lib = None
+BIAS_SYMBOLS = [  # include/rnnt_bias.h, exported by libwarprnnt_bias.so
+    "compute_rnnt_beam_step_biased",
+    "compute_rnnt_beam_timed_step_biased",
+    "compute_rnnt_beam_stream_step_biased",
+    "compute_rnnt_beam_stream_timed_step_biased",
+]
 
 
 class RNNTLibraryError(RuntimeError):
@@ -125,6 +150,28 @@ class RNNTLibraryError(RuntimeError):
 
 
 RNNT_VISIT_ALL = 0x100  # include/rnnt.h: no occupancy floor -- the gradient kernels visit every lattice cell / row
+
+
+def load_bias():
+    """Load libwarprnnt_bias.so (once): the biased beam steps of include/rnnt_bias.h.  They work on the workspaces that the
+    entry points of load() set up.  Raises RNNTLibraryError loudly when the library is absent."""
+    global _bias_lib
+    if _bias_lib is not None:
+        return _bias_lib
+    if not os.path.exists(BIAS_LIB_PATH):
+        raise RNNTLibraryError(f"{BIAS_LIB_PATH} not found: the HIP extension has not been built (__graft_entry__.build()). "
+                               "There is no eager fallback for the biased beam steps.")
+    try:
+        lib = ctypes.CDLL(BIAS_LIB_PATH)
+    except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
+        raise RNNTLibraryError(f"failed to load {BIAS_LIB_PATH}: {e}") from e
+    vp, ci, gp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(rnntBiasGraph)
+    for name, ints in zip(BIAS_SYMBOLS, (5, 5, 6, 6)):
+        fn = getattr(lib, name)
+        fn.restype = ci
+        fn.argtypes = [vp] * 6 + [ci] * ints + [vp, rnntOptions, gp, vp]
+    _bias_lib = lib
+    return lib
 
 
 def load():

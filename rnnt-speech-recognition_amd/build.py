@@ -13,6 +13,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libwarprnnt.so")
+# the extension library of include/rnnt_bias.h: the kernel objects of SOURCES (the host side of the beam search rests on them),
+# the biased kernels and rnnt_bias_entrypoint.hip in place of rnnt_entrypoint.hip; rnnt_bias.map: it exports the four biased
+# steps alone.  libwarprnnt.so is built from SOURCES as it always was and holds nothing of the extension.
+BIAS_LIB_PATH = os.path.join(LIB_DIR, "libwarprnnt_bias.so")
+BIAS_SOURCES = ["beam_bias_kernels.hip", "rnnt_bias_entrypoint.hip"]
+BIAS_MAP = os.path.join(CSRC, "rnnt_bias.map")
 SOURCES = ["rnnt_kernels.hip", "rnnt_lin_kernels.hip", "joint_kernels.hip", "joint_f16_kernels.hip", "dense_kernels.hip", "greedy_kernels.hip",
            "beam_kernels.hip", "prednet_kernels.hip", "encoder_kernels.hip", "lstm_train_kernels.hip", "frontend_kernels.hip",
            "align_kernels.hip", "rnnt_entrypoint.hip"]
@@ -24,20 +30,21 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 # HBM-bound cell kernels of rnnt_kernels.hip keep the vectoriser (the op at config 5's shape: 16.4 against 17.0 ms).
 _NO_SLP = ["-fno-slp-vectorize"]
 EXTRA_FLAGS = {"rnnt_lin_kernels.hip": _NO_SLP, "joint_kernels.hip": _NO_SLP, "joint_f16_kernels.hip": _NO_SLP, "dense_kernels.hip": _NO_SLP,
-               "greedy_kernels.hip": _NO_SLP, "beam_kernels.hip": _NO_SLP,
+               "greedy_kernels.hip": _NO_SLP, "beam_kernels.hip": _NO_SLP, "beam_bias_kernels.hip": _NO_SLP,
                "prednet_kernels.hip": _NO_SLP, "encoder_kernels.hip": _NO_SLP, "lstm_train_kernels.hip": _NO_SLP}
 
 
 def _deps():
-    files = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
+    files = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".map"))]
     files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt.h"))
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_bias.h"))
     return files
 
 
 def needs_build() -> bool:
-    if not os.path.exists(LIB_PATH):
+    if not os.path.exists(LIB_PATH) or not os.path.exists(BIAS_LIB_PATH):
         return True
-    t = os.path.getmtime(LIB_PATH)
+    t = min(os.path.getmtime(LIB_PATH), os.path.getmtime(BIAS_LIB_PATH))
     return any(os.path.getmtime(f) > t for f in _deps())
 
 
@@ -51,7 +58,8 @@ def _compile_one(args):
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    """Compile every HIP source (one hipcc per source, in parallel) and link lib/libwarprnnt.so; returns the path."""
+    """Compile every HIP source (one hipcc per source, in parallel) and link lib/libwarprnnt.so and, from the same kernel
+    objects, lib/libwarprnnt_bias.so; returns the path of the former."""
     if not force and not needs_build():
         return LIB_PATH
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -59,19 +67,22 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("hipcc not found: cannot build libwarprnnt.so (ROCm toolchain required)")
     os.makedirs(LIB_DIR, exist_ok=True)
     tag = f".tmp{os.getpid()}"  # several ranks may arrive here at once
-    jobs = [(hipcc, os.path.join(CSRC, s), os.path.join(LIB_DIR, s[:-4] + tag + ".o"), verbose) for s in SOURCES]
+    jobs = [(hipcc, os.path.join(CSRC, s), os.path.join(LIB_DIR, s[:-4] + tag + ".o"), verbose) for s in SOURCES + BIAS_SOURCES]
     objs = []
     try:
         from concurrent.futures import ThreadPoolExecutor
 
         with ThreadPoolExecutor(max_workers=len(jobs)) as ex:
             objs = list(ex.map(_compile_one, jobs))
-        tmp = LIB_PATH + tag
-        cmd = [hipcc] + HIPCC_FLAGS + objs + ["-o", tmp]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.run(cmd, check=True)
-        os.replace(tmp, LIB_PATH)
+        n = len(SOURCES)  # (SOURCES ends with rnnt_entrypoint.hip)
+        links = ((BIAS_LIB_PATH, objs[: n - 1] + objs[n:], ["-Wl,--version-script=" + BIAS_MAP]), (LIB_PATH, objs[:n], []))
+        for path, members, extra in links:
+            tmp = path + tag
+            cmd = [hipcc] + HIPCC_FLAGS + extra + members + ["-o", tmp]
+            if verbose:
+                print(" ".join(cmd))
+            subprocess.run(cmd, check=True)
+            os.replace(tmp, path)
     finally:
         for _, _, obj, _ in jobs:
             if os.path.exists(obj):

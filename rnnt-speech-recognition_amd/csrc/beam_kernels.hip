@@ -26,42 +26,16 @@
 // keeps the first-ranked survivor's row.  The workspace is the untimed one with the pair rows appended.
 #include "rnnt_decode.h"
 
-#include <limits.h>
-#include <math.h>
+namespace rnnt {
+constexpr int kBeamMax = 16;
+constexpr unsigned long long kHashMul = 0x9E3779B97F4A7C15ull;  // rolling hash of a prefix: h' = h kHashMul + (v + 1)
+}  // namespace rnnt
+
+#include "beam_common.h"
 
 namespace rnnt {
 
-constexpr int kBeamMax = 16;
-constexpr unsigned long long kHashMul = 0x9E3779B97F4A7C15ull;  // rolling hash of a prefix: h' = h kHashMul + (v + 1)
 
-struct BeamSlot {
-    double score;             // -inf: empty slot
-    unsigned long long hash;  // rolling hash of the token sequence
-    int len;                  // tokens
-    int pad;
-};
-
-struct BeamArgs {
-    GreedyArgs g;  // the joint's tables and image; g.st: per-utterance frame counter (t) and frames (Tb)
-    BeamSlot *slot;  // [B K]
-    int *nslot;      // [B] occupied slots (the first nslot[b] of the beam)
-    float *pl;       // [NS][B K][K] slice top-K logits
-    int *pv;         // [NS][B K][K] their symbols (-1: none)
-    float *bl;       // [B K] the blank's logit (what a hypothesis with a full token row offers)
-    int *tok;        // [2][B][K][N] token rows
-    int2 *tt;        // timed: [2][B][K][N] {emission frame, f32 bits of the log-probability} of every token
-    int *hyp_frames, *tstable;  // timed results: [B][K][N] (-1 padded), [B] (NULL: not written)
-    float *hyp_logp;            // timed results: [B][K][N] (0 padded)
-    int *parents, *emitted;
-    float *topl, *lse;  // diagnostics (NULL: not written)
-    int *tops;
-    int *hyps, *hyp_lengths, *stable;
-    float *scores;
-    int K, R;
-    int N;  // token row stride = tokens a hypothesis may hold (offline: maxT)
-};
-
-__device__ __forceinline__ bool bm_better(float l, int v, float bl, int bv) { return l > bl || (l == bl && v < bv); }
 
 // ---------------------------------------------------------------------------------------------
 // prepare: every beam = [((), 0)]
@@ -80,121 +54,19 @@ __global__ __launch_bounds__(256) void beam_begin_kernel(const BeamArgs a) {
 // step: grid (NS vocabulary slices, ceil(B K / 32) row tiles), 4 waves; the same LDS image as greedy_step_kernel plus the
 // tile's logits of the slice, [32 rows][128 symbols] (+1 padding column)
 // ---------------------------------------------------------------------------------------------
-template <int DT>
-__global__ __launch_bounds__(kGrWaves * 64) void beam_step_kernel(const BeamArgs ba) {
-    const GreedyArgs &a = ba.g;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ int s_t[32], s_live[32], s_slow[32];
-    __shared__ float r_m[kGrWaves * 64], r_s[kGrWaves * 64];
-    __shared__ float stage[DT == 2 ? 32 * 33 : 1];
-    __shared__ float lg[32 * (32 * kGrWaves + 1)];
-    constexpr int LW = 32 * kGrWaves + 1;
-    const int J = a.J, K = ba.K;
-    const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, n31 = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int slice = blockIdx.x, r0 = blockIdx.y * 32;
-
-    bool live = false;
-    if (tid < 32) {
-        const int r = r0 + tid, b = r / K;
-        int t = 0, slow = 0;
-        if (r < ba.R) {
-            const GreedyState s = a.st[b];
-            live = s.t < s.Tb && r - b * K < ba.nslot[b];
-            t = min(max(s.t, 0), a.T - 1);
-            if (live) slow = a.rowflag[(size_t)b * a.T + t];
-        }
-        s_live[tid] = live ? 1 : 0, s_t[tid] = t, s_slow[tid] = slow;
-    }
-    if (!__syncthreads_or(live)) return;  // a tile without live hypotheses reads and writes nothing
-    dec_pred_route(a, J, r0, s_live, s_slow, tid);
-    __syncthreads();
-    gf16 *hA = (gf16 *)smem, *hL = hA + (size_t)J * 32;
-    const bool hform = DT == 0 && a.tflag[1] != 0.f;
-    dec_build_h<DT>(a, J, r0, s_live, s_slow, [&](int n) { return (size_t)((r0 + n) / K) * a.T + s_t[n]; }, hform, hA, hL, tid);
-    __syncthreads();
-
-    // ---- this wave's chunk of 32 symbols: greedy's (max, sum) per lane, and the logits into lg (NaN: takes no part)
-    const int vc = slice * kGrWaves + wave;
-    float bm = -INFINITY, bs = 0.f;
-    if (vc < a.NC) {
-        const gf32x16 acc = dec_chunk_acc<DT>(a, vc, hA, hL, stage, lane);
-        float m2inv, w2inv;
-        dec_logit_scales<DT>(a, hform, m2inv, w2inv);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int vv = gr_cdrow(r, half), v = 32 * vc + vv;
-            const float l = dec_logit<DT>(a, acc[r], vc, vv, v, m2inv, w2inv);
-            if (v < a.V) {  // padding columns take no part
-                if (l > bm) {
-                    bs = fmaf(bs, __builtin_amdgcn_exp2f((bm - l) * kLog2e), 1.0f);
-                    bm = l;
-                } else {
-                    bs += __builtin_amdgcn_exp2f((l - bm) * kLog2e);
-                }
-            }
-            lg[n31 * LW + 32 * wave + vv] = v < a.V ? l : __builtin_nanf("");
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) lg[n31 * LW + 32 * wave + gr_cdrow(r, half)] = __builtin_nanf("");
-    }
-    r_m[tid] = bm, r_s[tid] = bs;
-    __syncthreads();
-    if (tid < 32 && s_live[tid] && slice == a.blank / (32 * kGrWaves)) ba.bl[r0 + tid] = lg[tid * LW + a.blank % (32 * kGrWaves)];
-    if (tid < 32 && s_live[tid]) {  // the 2 kGrWaves partials of row tid, in greedy_step_kernel's order
-        float M = -INFINITY;
-        for (int q = 0; q < 2 * kGrWaves; ++q) {
-            const int src = (q >> 1) * 64 + tid + 32 * (q & 1);
-            if (r_m[src] > M) M = r_m[src];
-        }
-        float S = 0.f;
-        for (int q = 0; q < 2 * kGrWaves; ++q) {
-            const int src = (q >> 1) * 64 + tid + 32 * (q & 1);
-            if (r_s[src] > 0.f) S += r_s[src] * __builtin_amdgcn_exp2f((r_m[src] - M) * kLog2e);
-        }
-        const size_t o = (size_t)slice * ba.R + r0 + tid;
-        a.part_m[o] = M, a.part_s[o] = S;
-    }
-    // ---- the slice's top-K per row: 8 threads per row, 16 consecutive symbols each; K rounds of a best-untaken reduction
-    const int n = tid >> 3, q = tid & 7;
-    float val[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) val[i] = lg[n * LW + 16 * q + i];
-    const int sym0 = slice * 32 * kGrWaves + 16 * q;
-    const size_t lo = ((size_t)slice * ba.R + r0 + n) * K;
-    unsigned taken = 0;
-    for (int k = 0; k < K; ++k) {  // (uniform trip count: every lane takes part in the shuffles)
-        float bl = -INFINITY;
-        int bj = -1;
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            if (!((taken >> i) & 1) && val[i] > bl) bl = val[i], bj = i;  // ascending symbols: the lowest wins a tie
-        int bv = bj >= 0 ? sym0 + bj : INT_MAX;
-        const int mine = bv;
-#pragma unroll
-        for (int off = 1; off < 8; off <<= 1) {
-            const float ol = __shfl_xor(bl, off, 8);
-            const int ov = __shfl_xor(bv, off, 8);
-            if (bm_better(ol, ov, bl, bv)) bl = ol, bv = ov;
-        }
-        if (bv != INT_MAX && bv == mine) taken |= 1u << bj;
-        if (q == 0 && s_live[n]) {
-            ba.pl[lo + k] = bv != INT_MAX ? bl : -INFINITY;
-            ba.pv[lo + k] = bv != INT_MAX ? bv : -1;
-        }
-    }
-}
+#define BEAM_STEP_KERNEL beam_step_kernel
+#define BEAM_STEP_BIAS 0
+#include "beam_step_body.h"
+#undef BEAM_STEP_KERNEL
+#undef BEAM_STEP_BIAS
 
 // ---------------------------------------------------------------------------------------------
 // select: one workgroup (256 threads) per utterance
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int bm_token(const int *row, int len, int v, int p) {
-    return p < len ? row[p] : v;  // token p of y_i + (v,): row = y_i's token row, len = |y_i|
-}
 
 #define BEAM_SELECT_KERNEL beam_select_kernel
 #define BEAM_SELECT_TIMED 0
+#define BEAM_SELECT_BIAS 0
 #include "beam_select_body.h"
 #undef BEAM_SELECT_KERNEL
 #undef BEAM_SELECT_TIMED
@@ -203,6 +75,7 @@ __device__ __forceinline__ int bm_token(const int *row, int len, int v, int p) {
 #include "beam_select_body.h"
 #undef BEAM_SELECT_KERNEL
 #undef BEAM_SELECT_TIMED
+#undef BEAM_SELECT_BIAS
 
 // ---------------------------------------------------------------------------------------------
 // results: one workgroup per utterance; the current beams, zero-padded; stable (NULL: not written): the length of the longest
@@ -265,66 +138,6 @@ __global__ __launch_bounds__(256) void beam_results_timed_kernel(const BeamArgs 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-size_t joint_w2_image_bytes(int J, int V);
-
-struct BeamLayout {
-    size_t st, slot, nslot, pm, ps, pl, pv, bl, tok, rowflag, expE, encraw, img, btab, tflag, tt, total;
-    int NC, NS, DT;
-};
-
-// N: the token row stride (offline: T).  timed: the {frame, log-probability} rows follow the untimed layout, which stays as it
-// is; the token and pair rows together are 6 B K N words, and that count must stay below 2^31
-static bool make_beam_layout(int T, int B, int K, int N, int J, int V, int joint_dtype, bool timed, BeamLayout &L) {
-    L.DT = greedy_dt(joint_dtype, J, V);
-    if (L.DT < 0 || T <= 0 || B <= 0 || K < 1 || K > kBeamMax || N < 1) return false;
-    if ((unsigned long long)B * T * J >= (1ull << 31) || (timed ? 6ull : 2ull) * B * K * N >= (1ull << 31)) return false;
-    L.NC = (V + 31) / 32;
-    L.NS = (L.NC + kGrWaves - 1) / kGrWaves;
-    const size_t R = (size_t)B * K;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
-    L.st = take((size_t)B * sizeof(GreedyState));
-    L.slot = take(R * sizeof(BeamSlot));
-    L.nslot = take((size_t)B * sizeof(int));
-    L.pm = take((size_t)L.NS * R * sizeof(float));
-    L.ps = take((size_t)L.NS * R * sizeof(float));
-    L.pl = take((size_t)L.NS * R * K * sizeof(float));
-    L.pv = take((size_t)L.NS * R * K * sizeof(int));
-    L.tok = take(2 * R * (size_t)N * sizeof(int));
-    L.rowflag = take((size_t)B * T * sizeof(int));
-    L.expE = take((size_t)B * T * J * sizeof(float));
-    L.encraw = take((size_t)B * T * J * sizeof(float));
-    L.img = take(L.DT == 1 ? (size_t)L.NC * 32 * J * sizeof(gf16) : joint_w2_image_bytes(J, V));
-    L.btab = take((size_t)L.NC * 32 * sizeof(float));
-    L.tflag = take(256 + 1024);  // joint_prep_kernel's flag words + b2s (as greedy's layout)
-    L.bl = take(R * sizeof(float));
-    L.tt = timed ? take(2 * R * (size_t)N * sizeof(int2)) : off;
-    L.total = off;
-    return true;
-}
-
-static bool beam_bind(BeamArgs &a, int T, int B, int K, int N, int J, int V, int joint_dtype, bool timed, void *workspace,
-                      BeamLayout &L) {
-    if (!make_beam_layout(T, B, K, N, J, V, joint_dtype, timed, L)) return false;
-    char *ws = (char *)workspace;
-    GreedyArgs &g = a.g;
-    g.st = (GreedyState *)(ws + L.st);
-    g.part_m = (float *)(ws + L.pm), g.part_s = (float *)(ws + L.ps);
-    g.rowflag = (int *)(ws + L.rowflag);
-    g.expE = (float *)(ws + L.expE), g.encraw = (float *)(ws + L.encraw);
-    g.img = (gf16 *)(ws + L.img), g.btab = (float *)(ws + L.btab), g.tflag = (const float *)(ws + L.tflag);
-    g.NC = L.NC, g.NS = L.NS;
-    g.B = B, g.T = T, g.J = J, g.V = V;
-    a.slot = (BeamSlot *)(ws + L.slot), a.nslot = (int *)(ws + L.nslot);
-    a.pl = (float *)(ws + L.pl), a.pv = (int *)(ws + L.pv), a.bl = (float *)(ws + L.bl), a.tok = (int *)(ws + L.tok);
-    a.tt = timed ? (int2 *)(ws + L.tt) : nullptr;
-    a.K = K, a.R = B * K, a.N = N;
-    return true;
-}
 
 hipError_t beam_workspace_bytes(int T, int B, int K, int J, int V, int joint_dtype, bool timed, size_t *bytes) {
     BeamLayout L;

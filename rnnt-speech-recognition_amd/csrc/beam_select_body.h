@@ -1,8 +1,18 @@
 // beam_select_body.h -- the select kernel of beam_kernels.hip, included there once per instantiation: BEAM_SELECT_KERNEL is the
 // kernel's name and BEAM_SELECT_TIMED 0 / 1 whether it keeps the {frame, log-probability} rows (beam_select_kernel and
-// beam_select_timed_kernel).  One source, two kernels with names of their own: both are compiled as kernels, so the untimed one
+// beam_select_timed_kernel).  One source, kernels with names of their own: all are compiled as kernels, so the untimed one
 // comes out of the compiler as it did before the timed one existed.  No include guard on purpose.
+// BEAM_SELECT_BIAS 1 (beam_select_bias_kernel, beam_select_timed_bias_kernel): the context graph bg.  The slice lists hold raw
+// logits in key order; beta and the next state of every listed entry are re-derived by bisection (s_pb / s_pn, the entries
+// spread over the wave's lanes), the lists are merged on the key logit + beta, beta goes into the candidate's score in float64
+// and the next state travels with the candidate into BeamSlot::pad.  Everything of it is compiled out at 0.
+#if BEAM_SELECT_BIAS
+__global__ __launch_bounds__(256) void BEAM_SELECT_KERNEL(const BeamArgs a, const BiasArgs bg) {
+    __shared__ float s_pb[kGrWaves][64 * kBeamMax], s_tb[kBeamMax * kBeamMax];
+    __shared__ int s_pn[kGrWaves][64 * kBeamMax], s_tn[kBeamMax * kBeamMax], s_q[kBeamMax], s_nx[kBeamMax];
+#else
 __global__ __launch_bounds__(256) void BEAM_SELECT_KERNEL(const BeamArgs a) {
+#endif
     constexpr bool TIMED = BEAM_SELECT_TIMED;
     __shared__ float s_tl[kBeamMax * kBeamMax];  // per-hypothesis top-K
     __shared__ int s_tv[kBeamMax * kBeamMax];
@@ -18,6 +28,9 @@ __global__ __launch_bounds__(256) void BEAM_SELECT_KERNEL(const BeamArgs a) {
     const int rb = b * K;
     if (st.t >= st.Tb) {  // frozen: nothing changes
         if (tid < K) a.parents[rb + tid] = rb + tid, a.emitted[rb + tid] = -1;
+#if BEAM_SELECT_BIAS
+        if (tid < K && bg.states) bg.states[rb + tid] = a.slot[rb + tid].pad;
+#endif
         return;
     }
     const int nb = a.nslot[b], T = a.N, cur = st.n & 1;
@@ -43,14 +56,33 @@ __global__ __launch_bounds__(256) void BEAM_SELECT_KERNEL(const BeamArgs a) {
             s_lse[i] = (double)M + log(S);
             if (a.lse) a.lse[r] = (float)s_lse[i];
         }
+#if BEAM_SELECT_BIAS
+        const int qi = bg_state(bg, a.slot[r].pad);
+        if (lane == 0) s_q[i] = qi;
+        for (int e = lane; e < g.NS * K; e += 64) {  // entry e % K of slice e / K
+            const int v = a.pv[((size_t)(e / K) * a.R + r) * K + e % K];
+            int nx = qi;
+            const float be = v >= 0 ? bg_delta(bg, qi, v, blank, nx) : 0.f;
+            s_pb[wave][e] = be, s_pn[wave][e] = nx;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#endif
         int h = 0;
         for (int k = 0; k < K; ++k) {
             float l = -INFINITY;
             int v = INT_MAX;
+#if BEAM_SELECT_BIAS
+            float raw = -INFINITY;
+            if (lane < g.NS && h < K) {
+                const size_t o = ((size_t)lane * a.R + r) * K + h;
+                if (a.pv[o] >= 0) raw = a.pl[o], v = a.pv[o], l = raw + s_pb[wave][lane * K + h];  // (the step's key)
+            }
+#else
             if (lane < g.NS && h < K) {
                 const size_t o = ((size_t)lane * a.R + r) * K + h;
                 if (a.pv[o] >= 0) l = a.pl[o], v = a.pv[o];
             }
+#endif
             const int mine = v;
             float bl = l;
             int bv = v;
@@ -60,6 +92,17 @@ __global__ __launch_bounds__(256) void BEAM_SELECT_KERNEL(const BeamArgs a) {
                 const int ov = __shfl_xor(bv, off);
                 if (bm_better(ol, ov, bl, bv)) bl = ol, bv = ov;
             }
+#if BEAM_SELECT_BIAS
+            if (bv != INT_MAX ? bv == mine : lane == 0) {  // the winning lane: the raw logit, beta and the next state
+                s_tl[i * K + k] = bv != INT_MAX ? raw : -INFINITY;
+                s_tv[i * K + k] = bv != INT_MAX ? bv : -1;
+                s_tb[i * K + k] = bv != INT_MAX ? s_pb[wave][lane * K + h] : 0.f;
+                s_tn[i * K + k] = bv != INT_MAX ? s_pn[wave][lane * K + h] : qi;
+                if (a.topl) a.topl[(size_t)r * K + k] = bv != INT_MAX ? raw : -INFINITY;
+                if (a.tops) a.tops[(size_t)r * K + k] = bv != INT_MAX ? bv : -1;
+            }
+            if (bv != INT_MAX && bv == mine) ++h;
+#else
             if (bv != INT_MAX && bv == mine) ++h;
             if (lane == 0) {
                 s_tl[i * K + k] = bv != INT_MAX ? bl : -INFINITY;
@@ -67,6 +110,7 @@ __global__ __launch_bounds__(256) void BEAM_SELECT_KERNEL(const BeamArgs a) {
                 if (a.topl) a.topl[(size_t)r * K + k] = bv != INT_MAX ? bl : -INFINITY;
                 if (a.tops) a.tops[(size_t)r * K + k] = bv != INT_MAX ? bv : -1;
             }
+#endif
         }
     }
     __syncthreads();
@@ -74,6 +118,9 @@ __global__ __launch_bounds__(256) void BEAM_SELECT_KERNEL(const BeamArgs a) {
     if (tid < nb && a.slot[rb + tid].len >= a.N) {
         for (int k = 0; k < K; ++k) s_tv[tid * K + k] = -1;
         s_tv[tid * K] = blank, s_tl[tid * K] = a.bl[rb + tid];
+#if BEAM_SELECT_BIAS
+        s_tb[tid * K] = 0.f, s_tn[tid * K] = s_q[tid];
+#endif
     }
     __syncthreads();
 
@@ -81,7 +128,11 @@ __global__ __launch_bounds__(256) void BEAM_SELECT_KERNEL(const BeamArgs a) {
     const int nc = nb * K;
     if (tid < nc) {
         const int i = tid / K;
+#if BEAM_SELECT_BIAS
+        const double sc = a.slot[rb + i].score + ((double)s_tl[tid] - s_lse[i]) + (double)s_tb[tid];
+#else
         const double sc = a.slot[rb + i].score + ((double)s_tl[tid] - s_lse[i]);
+#endif
         s_cs[tid] = (s_tv[tid] >= 0 && sc > -INFINITY) ? sc : __builtin_nan("");
     }
     if (tid == 0) s_m = 0;
@@ -110,8 +161,14 @@ __global__ __launch_bounds__(256) void BEAM_SELECT_KERNEL(const BeamArgs a) {
         s_len[tid] = p.len + (emit ? 1 : 0);
         s_hash[tid] = emit ? p.hash * kHashMul + (unsigned long long)(v + 1) : p.hash;
         s_sc[tid] = s_cs[c];
+#if BEAM_SELECT_BIAS
+        s_nx[tid] = s_tn[c];
+#endif
     } else if (m == 0 && tid < nb) {  // nothing can be taken: the beam is carried over unchanged
         const BeamSlot p = a.slot[rb + tid];
+#if BEAM_SELECT_BIAS
+        s_nx[tid] = p.pad;
+#endif
         s_par[tid] = tid, s_v[tid] = -1, s_len[tid] = p.len, s_hash[tid] = p.hash, s_sc[tid] = p.score;
     }
     __syncthreads();
@@ -161,12 +218,18 @@ __global__ __launch_bounds__(256) void BEAM_SELECT_KERNEL(const BeamArgs a) {
         if (tid < nn) {
             const int x = s_ord[tid];
             s.score = s_sc[x], s.hash = s_hash[x], s.len = s_len[x];
+#if BEAM_SELECT_BIAS
+            s.pad = s_nx[x];  // (identical sequences have identical states: a merge keeps the survivor's)
+#endif
             a.parents[r] = rb + s_par[x], a.emitted[r] = s_v[x];
         } else {
             s.score = -INFINITY, s.hash = 0, s.len = 0;
             a.parents[r] = r, a.emitted[r] = -1;
         }
         a.slot[r] = s;
+#if BEAM_SELECT_BIAS
+        if (bg.states) bg.states[r] = s.pad;
+#endif
     }
     for (int k = 0; k < nn; ++k) {
         const int x = s_ord[k], i = s_par[x], n = s_len[x];

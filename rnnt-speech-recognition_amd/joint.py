@@ -700,13 +700,22 @@ class BeamJoint:
 
     token_times=True (compute_rnnt_beam_timed_*): results() returns two more, frames int32 [B, beam, T] (-1 padded) and logp
     [B, beam, T] (0 padded): per token the frame that emitted it and the log-softmax of that decision.  A hypothesis that
-    absorbed merged candidates keeps the rows of its first-ranked member; its score is still the sum over the members."""
+    absorbed merged candidates keeps the rows of its first-ranked member; its score is still the sum over the members.
 
-    def __init__(self, joint: "JointLoss", beam: int = 4, joint_dtype: str = "auto", token_times: bool = False):
+    context=biasing.ContextGraph (compute_rnnt_beam_*_step_biased): every step ranks on logit + beta and carries the automaton
+    state of every hypothesis; bias_states() -> int32 [B beam] after the last step.  results() of the OFFLINE search are
+    finalised (score + fail_bias[state]: what a hypothesis left mid-phrase has not earned is taken back) and stably re-sorted
+    by that score; the per-token log-probabilities stay the model's."""
+
+    def __init__(self, joint: "JointLoss", beam: int = 4, joint_dtype: str = "auto", token_times: bool = False, context=None):
         if not 1 <= int(beam) <= 16:
             raise ValueError("BeamJoint: beam must be in 1 ... 16")
         self.K = int(beam)
         self.token_times = bool(token_times)
+        self.context = context
+        if context is not None and (context.blank != joint.blank_label or context.vocab_size != joint.W2.shape[1]):
+            raise ValueError(f"context graph built for blank {context.blank} / {context.vocab_size} symbols, the joint has blank "
+                             f"{joint.blank_label} / {joint.W2.shape[1]} symbols")
         g = GreedyJoint(joint, joint_dtype)  # (the same engine / torch decision and padding)
         self.joint, self.blank, self.V, self.engine = joint, g.blank, g.V, g.engine
         if self.engine:
@@ -720,6 +729,7 @@ class BeamJoint:
         R = B * self.K
         self.parents = torch.arange(R, dtype=torch.int32, device=dev)
         self.emitted = torch.full((R,), -1, dtype=torch.int32, device=dev)
+        self._bias_states = torch.zeros(R, dtype=torch.int32, device=dev)
         frames = frame_lengths.to(device=dev, dtype=torch.int32).contiguous()
         if not self.engine:
             return self._torch_begin(enc, frames)
@@ -747,16 +757,38 @@ class BeamJoint:
         pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _projected_operand(pred_proj, self.Jp)
         ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         lib = _lib.load()
+        if self.context is not None:
+            lib = _lib.load_bias()  # (include/rnnt_bias.h)
+            fn = lib.compute_rnnt_beam_timed_step_biased if self.token_times else lib.compute_rnnt_beam_step_biased
+            st = fn(pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(), ptr(topk_logits), ptr(topk_symbols), ptr(lse),
+                    self.Jp, self.V, self.B, self.K, self.dtype, self._ws.data_ptr(), self._opts, self.context.byref(pp.device),
+                    self._bias_states.data_ptr())
+            _lib.check(st, "compute_rnnt_beam_timed_step_biased" if self.token_times else "compute_rnnt_beam_step_biased")
+            return self.parents, self.emitted
         fn = lib.compute_rnnt_beam_timed_step if self.token_times else lib.compute_rnnt_beam_step
         st = fn(pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(), ptr(topk_logits), ptr(topk_symbols), ptr(lse),
                 self.Jp, self.V, self.B, self.K, self.dtype, self._ws.data_ptr(), self._opts)
         _lib.check(st, "compute_rnnt_beam_timed_step" if self.token_times else "compute_rnnt_beam_step")
         return self.parents, self.emitted
 
+    def bias_states(self):
+        """int32 [B beam]: the context graph's state of every slot after the last step (zeros without a context)."""
+        return self._bias_states
+
+    def _finalised(self, out):
+        """The offline results with a context: score + fail_bias[state], every beam stably re-sorted by it."""
+        if self.context is None:
+            return out
+        B, K = self.B, self.K
+        scores = self.context.finalize(out[2], self._bias_states.reshape(B, K))
+        scores, order = torch.sort(scores, dim=1, descending=True, stable=True)
+        pick = lambda x: torch.gather(x, 1, order.reshape(B, K, *([1] * (x.dim() - 2))).expand_as(x))  # noqa: E731
+        return (pick(out[0]), pick(out[1]), scores) + tuple(pick(x) for x in out[3:])
+
     def results(self):
         B, K, T = self.B, self.K, self.T
         if not self.engine:
-            return self._torch_results()
+            return self._finalised(self._torch_results())
         dev = self.parents.device
         hyps = torch.empty(B, K, T, dtype=torch.int32, device=dev)
         lengths = torch.empty(B, K, dtype=torch.int32, device=dev)
@@ -768,11 +800,11 @@ class BeamJoint:
                                                              logp.data_ptr(), self.Jp, self.V, B, K, self.dtype, self._ws.data_ptr(),
                                                              self._opts)
             _lib.check(st, "compute_rnnt_beam_timed_results")
-            return hyps, lengths, scores, frames, logp
+            return self._finalised((hyps, lengths, scores, frames, logp))
         st = _lib.load().compute_rnnt_beam_results(hyps.data_ptr(), lengths.data_ptr(), scores.data_ptr(), self.Jp, self.V, B, K,
                                                    self.dtype, self._ws.data_ptr(), self._opts)
         _lib.check(st, "compute_rnnt_beam_results")
-        return hyps, lengths, scores
+        return self._finalised((hyps, lengths, scores))
 
     # ---- torch composition: the same state machine (beam_select_kernel) on JointLoss.logits
     def _torch_begin(self, enc, frames):
@@ -781,6 +813,7 @@ class BeamJoint:
         self._t = 0
         self._beams = [[((), 0.0)] for _ in range(self.B)]  # (tokens, float64 score), best first
         self._times = [[()] for _ in range(self.B)]  # token_times: per hypothesis its (frame, log-probability) pairs
+        self._states = [[0] for _ in range(self.B)]  # context: per hypothesis its state in the graph
         self._sdtype = torch.promote_types(enc.dtype, torch.float32)
 
     def _torch_step(self, pred, pred_proj=None):
@@ -792,47 +825,84 @@ class BeamJoint:
         e = self._enc[:, min(t, self.T - 1)]  # [B, H]
         logits = _torch_cell_logits(self.joint, e.repeat_interleave(K, 0), pred, pred_proj)  # [B K, V]
         lse = torch.logsumexp(logits, dim=-1)
-        top_l, top_v = torch.sort(logits, dim=-1, descending=True, stable=True)  # (logit descending, symbol ascending)
-        top_l, top_v, lse = top_l[:, :K].tolist(), top_v[:, :K].tolist(), lse.tolist()
+        top_l, top_v, bias = self._torch_top(logits)
+        lse = lse.tolist()
         for b in range(B):
             if t < self._Tb[b]:
-                self._torch_rank(b, top_l, top_v, lse, parents, emitted, frame=t)
+                self._torch_rank(b, top_l, top_v, lse, parents, emitted, frame=t, bias=bias)
         dev = self.parents.device
         self.parents = torch.tensor(parents, dtype=torch.int32, device=dev)
         self.emitted = torch.tensor(emitted, dtype=torch.int32, device=dev)
+        self._torch_bias_states()
         return self.parents, self.emitted
 
-    def _torch_rank(self, b, top_l, top_v, lse, parents, emitted, blank_l=None, cap=None, frame=0):
+    def _torch_top(self, logits):
+        """Every row's top-K (logit, symbol) lists.  With a context: by the f32 key logit + beta (rule 2'), the logits raw, and
+        bias = (beta, next state) of every listed symbol."""
+        K = self.K
+        if self.context is None:
+            top_l, top_v = torch.sort(logits, dim=-1, descending=True, stable=True)  # (logit descending, symbol ascending)
+            return top_l[:, :K].tolist(), top_v[:, :K].tolist(), None
+        import numpy as np
+
+        R = logits.shape[0]
+        q = [0] * R
+        for b, states in enumerate(self._states):
+            q[b * K: b * K + len(states)] = states
+        rows = [self.context.row(s) for s in q]
+        beta = torch.from_numpy(np.stack([r[0] for r in rows])).to(logits.device)
+        nxt = torch.from_numpy(np.stack([r[1] for r in rows])).to(logits.device)
+        key = logits.float() + beta
+        key = torch.where(torch.isnan(key), torch.full_like(key, -math.inf), key)  # (takes no part; the raw NaN drops it below)
+        _, top_v = torch.sort(key, dim=-1, descending=True, stable=True)
+        top_v = top_v[:, :K]
+        return (torch.gather(logits, 1, top_v).tolist(), top_v.tolist(),
+                (torch.gather(beta, 1, top_v).tolist(), torch.gather(nxt, 1, top_v).tolist()))
+
+    def _torch_bias_states(self):
+        if self.context is None:
+            return
+        q = [0] * (self.B * self.K)
+        for b, states in enumerate(self._states):
+            q[b * self.K: b * self.K + len(states)] = states
+        self._bias_states = torch.tensor(q, dtype=torch.int32, device=self.parents.device)
+
+    def _torch_rank(self, b, top_l, top_v, lse, parents, emitted, blank_l=None, cap=None, frame=0, bias=None):
         """One frame of beam b (rules 2 - 5 of include/rnnt.h) from every row's top-K lists and logsumexp; parents / emitted of
         its rows are filled in.  cap (the stream): a hypothesis of cap tokens offers its blank candidate (logit blank_l[r]) alone.
-        frame: this frame's number for the (frame, log-probability) pairs; a merged hypothesis keeps its first member's."""
+        frame: this frame's number for the (frame, log-probability) pairs; a merged hypothesis keeps its first member's.
+        bias (a context): (beta, next state) beside every listed symbol -- beta joins the score, the state the hypothesis."""
         K, blank = self.K, self.blank
         beam = self._beams[b]
+        states = self._states[b]
         cands = []
         for i, (y, s) in enumerate(beam):
             r = b * K + i
-            offers = zip(top_l[r], top_v[r]) if cap is None or len(y) < cap else [(blank_l[r], blank)]
-            for l, v in offers:
-                sc = s + (float(l) - lse[r])
+            full = cap is not None and len(y) >= cap
+            offers = [(blank_l[r], blank)] if full else zip(top_l[r], top_v[r])
+            extra = [(0.0, states[i])] * K if bias is None or full else zip(bias[0][r], bias[1][r])
+            for (l, v), (be, nx) in zip(offers, extra):
+                sc = s + (float(l) - lse[r]) + float(be) if bias is not None else s + (float(l) - lse[r])
                 if sc == sc and sc > -math.inf:
-                    cands.append((sc, i, v, float(l) - lse[r]))
+                    cands.append((sc, i, v, float(l) - lse[r], nx))
         cands.sort(key=lambda c: (-c[0], c[1], c[2]))
         taken = cands[:K]
         if not taken:
             return  # the beam is carried over
         times = self._times[b]
-        merged = []  # [tokens, score, parent, emitted, (frame, log-probability) pairs]
-        for sc, i, v, lp in taken:
+        merged = []  # [tokens, score, parent, emitted, (frame, log-probability) pairs, state]
+        for sc, i, v, lp, nx in taken:
             y = beam[i][0] if v == blank else beam[i][0] + (v,)
             hit = next((m for m in merged if m[0] == y), None)
             if hit is None:
-                merged.append([y, sc, i, -1 if v == blank else v, times[i] if v == blank else times[i] + ((frame, lp),)])
+                merged.append([y, sc, i, -1 if v == blank else v, times[i] if v == blank else times[i] + ((frame, lp),), nx])
             else:
                 hi, lo = max(hit[1], sc), min(hit[1], sc)
                 hit[1] = hi + math.log1p(math.exp(lo - hi))
         merged.sort(key=lambda m: -m[1])  # (stable)
         self._beams[b] = [(m[0], m[1]) for m in merged]
         self._times[b] = [m[4] for m in merged]
+        self._states[b] = [m[5] for m in merged]
         for k in range(len(merged)):
             parents[b * K + k], emitted[b * K + k] = b * K + merged[k][2], merged[k][3]
 
@@ -881,7 +951,11 @@ class BeamStreamJoint(BeamJoint):
 
     token_times=True (compute_rnnt_beam_stream_timed_*): results() returns three more: frames int32 [slots, beam, max_hyp_len]
     (-1 padded; counted from the slot's reset across its chunks), logp [slots, beam, max_hyp_len] (0 padded) and timed_stable
-    [slots] = the prefix on which the slot's hypotheses agree in token and emission frame (<= stable): tokens AND times final."""
+    [slots] = the prefix on which the slot's hypotheses agree in token and emission frame (<= stable): tokens AND times final.
+
+    context=biasing.ContextGraph: the biased steps; a reset returns a slot's states to the root and a finished slot keeps its
+    states.  results() report the beam's own scores and order (a stream is never finalised: `stable` keeps its meaning);
+    bias_states() -> int32 [slots beam], for a caller that wants context.finalize(scores, states) at a stream's end."""
 
     MAX_ROWS = 1024  # slots * beam: the prediction network's rows
 
@@ -895,6 +969,7 @@ class BeamStreamJoint(BeamJoint):
         self.B, self.T, self.Tc, self.N = S, T, T, N
         self.parents = torch.arange(S * K, dtype=torch.int32, device=dev)
         self.emitted = torch.full((S * K,), -1, dtype=torch.int32, device=dev)
+        self._bias_states = torch.zeros(S * K, dtype=torch.int32, device=dev)
         lib = _lib.load() if self.engine else None
         if self.engine:  # (the library's own answer: a size it refuses is a shape the stream kernels do not take)
             n = ctypes.c_size_t(0)
@@ -903,6 +978,7 @@ class BeamStreamJoint(BeamJoint):
         if not self.engine:
             self._beams = [[] for _ in range(S)]
             self._times = [[] for _ in range(S)]
+            self._states = [[] for _ in range(S)]
             self._nsteps = [0] * S  # frames since the slot's reset
             self._fin, self._Tb, self._tc = [True] * S, [0] * S, [0] * S
             self._enc = None
@@ -952,6 +1028,14 @@ class BeamStreamJoint(BeamJoint):
         pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _projected_operand(pred_proj, self.Jp)
         ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         lib = _lib.load()
+        if self.context is not None:
+            lib = _lib.load_bias()  # (include/rnnt_bias.h)
+            fn = lib.compute_rnnt_beam_stream_timed_step_biased if self.token_times else lib.compute_rnnt_beam_stream_step_biased
+            st = fn(pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(), ptr(topk_logits), ptr(topk_symbols), ptr(lse),
+                    self.Jp, self.V, self.B, self.K, self.N, self.dtype, self._ws.data_ptr(), self._opts,
+                    self.context.byref(pp.device), self._bias_states.data_ptr())
+            _lib.check(st, "compute_rnnt_beam_stream_timed_step_biased" if self.token_times else "compute_rnnt_beam_stream_step_biased")
+            return self.parents, self.emitted
         fn = lib.compute_rnnt_beam_stream_timed_step if self.token_times else lib.compute_rnnt_beam_stream_step
         st = fn(pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(), ptr(topk_logits), ptr(topk_symbols), ptr(lse),
                 self.Jp, self.V, self.B, self.K, self.N, self.dtype, self._ws.data_ptr(), self._opts)
@@ -990,6 +1074,7 @@ class BeamStreamJoint(BeamJoint):
             if rs[s]:
                 self._beams[s], self._fin[s] = [((), 0.0)], False
                 self._times[s], self._nsteps[s] = [()], 0
+                self._states[s] = [0]
             self._tc[s] = 0
             if self._fin[s]:
                 self._Tb[s] = 0
@@ -1009,14 +1094,15 @@ class BeamStreamJoint(BeamJoint):
             e = self._enc[torch.arange(S, device=self._enc.device), cur]  # [S, H]
             logits = _torch_cell_logits(self.joint, e.repeat_interleave(K, 0), pred, pred_proj)  # [S K, V]
             lse = torch.logsumexp(logits, dim=-1).tolist()
-            top_l, top_v = torch.sort(logits, dim=-1, descending=True, stable=True)  # (logit descending, symbol ascending)
-            top_l, top_v, blank_l = top_l[:, :K].tolist(), top_v[:, :K].tolist(), logits[:, self.blank].tolist()
+            top_l, top_v, bias = self._torch_top(logits)
+            blank_l = logits[:, self.blank].tolist()
             for s in live:
-                self._torch_rank(s, top_l, top_v, lse, parents, emitted, blank_l, self.N, frame=self._nsteps[s])
+                self._torch_rank(s, top_l, top_v, lse, parents, emitted, blank_l, self.N, frame=self._nsteps[s], bias=bias)
                 self._tc[s] += 1
                 self._nsteps[s] += 1
         self.parents = torch.tensor(parents, dtype=torch.int32, device=dev)
         self.emitted = torch.tensor(emitted, dtype=torch.int32, device=dev)
+        self._torch_bias_states()
         return self.parents, self.emitted
 
     def _torch_results(self):
