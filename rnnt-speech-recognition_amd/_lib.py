@@ -8,6 +8,7 @@ import os
 
 from .build import BIAS_LIB_PATH as _DEFAULT_BIAS_LIB_PATH
 from .build import LIB_PATH as _DEFAULT_LIB_PATH
+from .build import MOD_LIB_PATH as _DEFAULT_MOD_LIB_PATH
 
 # dev knob: load an experimental build of the library instead (scripts/build_variant.sh)
 LIB_PATH = os.environ.get("RNNT_LIBWARPRNNT", _DEFAULT_LIB_PATH)
@@ -15,6 +16,8 @@ LIB_PATH = os.environ.get("RNNT_LIBWARPRNNT", _DEFAULT_LIB_PATH)
 # with the stock one (the two step each other's workspaces)
 BIAS_LIB_PATH = (_DEFAULT_BIAS_LIB_PATH if LIB_PATH == _DEFAULT_LIB_PATH
                  else os.path.join(os.path.dirname(LIB_PATH), "libwarprnnt_bias.so"))
+# the modified-topology library shares nothing with the base library (its own kernels and workspace): always this tree's build
+MOD_LIB_PATH = _DEFAULT_MOD_LIB_PATH
 
 RNNT_CPU, RNNT_GPU = 0, 1
 STATUS_SUCCESS = 0
@@ -143,6 +146,11 @@ BIAS_SYMBOLS = [  # include/rnnt_bias.h, exported by libwarprnnt_bias.so
     "compute_rnnt_beam_stream_step_biased",
     "compute_rnnt_beam_stream_timed_step_biased",
 ]
+_mod_lib = None
+MOD_SYMBOLS = [  # include/rnnt_modified.h, exported by libwarprnnt_mod.so
+    "get_rnnt_modified_workspace_size",
+    "compute_rnnt_loss_modified",
+]
 
 
 class RNNTLibraryError(RuntimeError):
@@ -171,6 +179,28 @@ def load_bias():
         fn.restype = ci
         fn.argtypes = [vp] * 6 + [ci] * ints + [vp, rnntOptions, gp, vp]
     _bias_lib = lib
+    return lib
+
+
+def load_mod():
+    """Load libwarprnnt_mod.so (once): the loss op on the modified (one symbol per frame) lattice, include/rnnt_modified.h.  Raises
+    RNNTLibraryError loudly when the library is absent."""
+    global _mod_lib
+    if _mod_lib is not None:
+        return _mod_lib
+    if not os.path.exists(MOD_LIB_PATH):
+        raise RNNTLibraryError(f"{MOD_LIB_PATH} not found: the HIP extension has not been built (__graft_entry__.build()). "
+                               "There is no eager fallback for the modified topology of the loss.")
+    try:
+        lib = ctypes.CDLL(MOD_LIB_PATH)
+    except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
+        raise RNNTLibraryError(f"failed to load {MOD_LIB_PATH}: {e}") from e
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    lib.get_rnnt_modified_workspace_size.restype = ci
+    lib.get_rnnt_modified_workspace_size.argtypes = [ci, ci, ci, ctypes.POINTER(ctypes.c_size_t)]
+    lib.compute_rnnt_loss_modified.restype = ci
+    lib.compute_rnnt_loss_modified.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, rnntOptions, ctypes.c_float]
+    _mod_lib = lib
     return lib
 
 
@@ -453,6 +483,12 @@ def frontend_workspace_bytes(max_chunk_samples: int, slots: int, frame_len: int,
 def align_workspace_bytes(maxT: int, maxU: int, minibatch: int) -> int:
     n = ctypes.c_size_t(0)
     check(load().get_rnnt_align_workspace_size(maxT, maxU, minibatch, ctypes.byref(n)), "get_rnnt_align_workspace_size")
+    return int(n.value)
+
+
+def modified_workspace_bytes(maxT: int, maxU: int, minibatch: int) -> int:
+    n = ctypes.c_size_t(0)
+    check(load_mod().get_rnnt_modified_workspace_size(maxT, maxU, minibatch, ctypes.byref(n)), "get_rnnt_modified_workspace_size")
     return int(n.value)
 
 

@@ -19,6 +19,11 @@ LIB_PATH = os.path.join(LIB_DIR, "libwarprnnt.so")
 BIAS_LIB_PATH = os.path.join(LIB_DIR, "libwarprnnt_bias.so")
 BIAS_SOURCES = ["beam_bias_kernels.hip", "rnnt_bias_entrypoint.hip"]
 BIAS_MAP = os.path.join(CSRC, "rnnt_bias.map")
+# the extension library of include/rnnt_modified.h: the loss op on the modified (one symbol per frame) lattice.  It is self-contained
+# (its own kernels, entry points and workspace); rnnt_mod.map: it exports its two entry points alone.
+MOD_LIB_PATH = os.path.join(LIB_DIR, "libwarprnnt_mod.so")
+MOD_SOURCES = ["rnnt_mod_kernels.hip", "rnnt_mod_entrypoint.hip"]
+MOD_MAP = os.path.join(CSRC, "rnnt_mod.map")
 SOURCES = ["rnnt_kernels.hip", "rnnt_lin_kernels.hip", "joint_kernels.hip", "joint_f16_kernels.hip", "dense_kernels.hip", "greedy_kernels.hip",
            "beam_kernels.hip", "prednet_kernels.hip", "encoder_kernels.hip", "lstm_train_kernels.hip", "frontend_kernels.hip",
            "align_kernels.hip", "rnnt_entrypoint.hip"]
@@ -38,13 +43,15 @@ def _deps():
     files = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".map"))]
     files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_bias.h"))
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_modified.h"))
     return files
 
 
 def needs_build() -> bool:
-    if not os.path.exists(LIB_PATH) or not os.path.exists(BIAS_LIB_PATH):
+    libs = (LIB_PATH, BIAS_LIB_PATH, MOD_LIB_PATH)
+    if not all(os.path.exists(p) for p in libs):
         return True
-    t = min(os.path.getmtime(LIB_PATH), os.path.getmtime(BIAS_LIB_PATH))
+    t = min(os.path.getmtime(p) for p in libs)
     return any(os.path.getmtime(f) > t for f in _deps())
 
 
@@ -59,7 +66,7 @@ def _compile_one(args):
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile every HIP source (one hipcc per source, in parallel) and link lib/libwarprnnt.so and, from the same kernel
-    objects, lib/libwarprnnt_bias.so; returns the path of the former."""
+    objects, lib/libwarprnnt_bias.so, and lib/libwarprnnt_mod.so from MOD_SOURCES; returns the path of the first."""
     if not force and not needs_build():
         return LIB_PATH
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -67,7 +74,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("hipcc not found: cannot build libwarprnnt.so (ROCm toolchain required)")
     os.makedirs(LIB_DIR, exist_ok=True)
     tag = f".tmp{os.getpid()}"  # several ranks may arrive here at once
-    jobs = [(hipcc, os.path.join(CSRC, s), os.path.join(LIB_DIR, s[:-4] + tag + ".o"), verbose) for s in SOURCES + BIAS_SOURCES]
+    jobs = [(hipcc, os.path.join(CSRC, s), os.path.join(LIB_DIR, s[:-4] + tag + ".o"), verbose) for s in SOURCES + BIAS_SOURCES + MOD_SOURCES]
     objs = []
     try:
         from concurrent.futures import ThreadPoolExecutor
@@ -75,7 +82,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         with ThreadPoolExecutor(max_workers=len(jobs)) as ex:
             objs = list(ex.map(_compile_one, jobs))
         n = len(SOURCES)  # (SOURCES ends with rnnt_entrypoint.hip)
-        links = ((BIAS_LIB_PATH, objs[: n - 1] + objs[n:], ["-Wl,--version-script=" + BIAS_MAP]), (LIB_PATH, objs[:n], []))
+        m = n + len(BIAS_SOURCES)
+        links = ((BIAS_LIB_PATH, objs[: n - 1] + objs[n:m], ["-Wl,--version-script=" + BIAS_MAP]),
+                 (MOD_LIB_PATH, objs[m:], ["-Wl,--version-script=" + MOD_MAP]), (LIB_PATH, objs[:n], []))
         for path, members, extra in links:
             tmp = path + tag
             cmd = [hipcc] + HIPCC_FLAGS + extra + members + ["-o", tmp]

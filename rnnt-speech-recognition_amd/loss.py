@@ -93,7 +93,81 @@ class _RNNTLossFunction(torch.autograd.Function):
         return grads, None, None, None, None, None
 
 
-def rnnt_loss(acts, labels, input_lengths, label_lengths, blank_label: int = 0, fastemit_lambda: float = 0.0):
+TOPOLOGIES = ("standard", "modified")
+
+
+def check_topology(topology) -> str:
+    """'standard' (the Graves lattice: a label edge stays on its frame) or 'modified' (one symbol per frame: the paths the beam
+    searches of decoding.py produce; include/rnnt_modified.h compute_rnnt_loss_modified); ValueError otherwise."""
+    if topology not in TOPOLOGIES:
+        raise ValueError(f"topology must be one of {TOPOLOGIES}, got {topology!r}")
+    return topology
+
+
+def _modified_inputs(what, acts, labels, input_lengths, label_lengths):
+    """The checks and conversions of the standard route, for the modified op: (acts_c, labels, input_lengths, label_lengths)."""
+    _lib.load()
+    if not acts.is_cuda:
+        raise RuntimeError(f"{what}: acts must live on an MI355X (cuda/HIP) device; this engine has no CPU path")
+    if acts.dim() != 4:
+        raise ValueError(f"{what}: acts must be [B, T, U, V]")
+    if acts.dtype != torch.float32:
+        raise TypeError(f"{what}: acts must be float32 (the reference op is float32-only)")
+    B, T, U, V = acts.shape
+    dev = acts.device
+    labels = _as_i32(labels, dev)
+    input_lengths = _as_i32(input_lengths, dev)
+    label_lengths = _as_i32(label_lengths, dev)
+    if U > 1 and tuple(labels.shape) != (B, U - 1):
+        raise ValueError(f"{what}: labels must be [B, U-1] = [{B}, {U - 1}], got {tuple(labels.shape)}")
+    if input_lengths.numel() != B or label_lengths.numel() != B:
+        raise ValueError(f"{what}: input_lengths and label_lengths must be [B]")
+    if labels.numel() == 0:
+        labels = torch.zeros((B, 1), dtype=torch.int32, device=dev)
+    return acts.detach().contiguous(), labels, input_lengths, label_lengths
+
+
+def _modified_call(acts, grads, labels, input_lengths, label_lengths, scale, costs, ws, blank, lam):
+    """compute_rnnt_loss_modified on the current stream (grads / scale / costs: tensors or None)."""
+    B, T, U, V = acts.shape
+    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+    with torch.cuda.device(acts.device):
+        opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, int(blank), T, U)
+        st = _lib.load_mod().compute_rnnt_loss_modified(
+            acts.data_ptr(), ptr(grads), labels.data_ptr(), label_lengths.data_ptr(), input_lengths.data_ptr(), ptr(scale),
+            V, B, ptr(costs), ws.data_ptr(), opts, lam)
+    _lib.check(st, "compute_rnnt_loss_modified")
+
+
+class _RNNTModifiedLossFunction(torch.autograd.Function):
+    """The modified topology: a forward-only call in forward, a gradient-only call in backward with the upstream gradient as
+    cost_scale and FastEmit's weight passed through."""
+
+    @staticmethod
+    def forward(ctx, acts, labels, input_lengths, label_lengths, blank_label, fastemit_lambda=0.0):
+        acts_c, labels, input_lengths, label_lengths = _modified_inputs("rnnt_loss", acts, labels, input_lengths, label_lengths)
+        B, T, U, V = acts_c.shape
+        with torch.cuda.device(acts_c.device):
+            ws = torch.empty(_lib.modified_workspace_bytes(T, U, B), dtype=torch.uint8, device=acts_c.device)
+            costs = torch.empty(B, dtype=torch.float32, device=acts_c.device)
+        _modified_call(acts_c, None, labels, input_lengths, label_lengths, None, costs, ws, blank_label, float(fastemit_lambda))
+        ctx.save_for_backward(acts_c, labels, input_lengths, label_lengths, ws)
+        ctx.blank = int(blank_label)
+        ctx.fastemit_lambda = float(fastemit_lambda)
+        return costs
+
+    @staticmethod
+    def backward(ctx, grad_costs):
+        acts, labels, input_lengths, label_lengths, ws = ctx.saved_tensors
+        scale = grad_costs.to(device=acts.device, dtype=torch.float32).contiguous()
+        with torch.cuda.device(acts.device):
+            grads = torch.empty_like(acts)
+        _modified_call(acts, grads, labels, input_lengths, label_lengths, scale, None, ws, ctx.blank, ctx.fastemit_lambda)
+        return grads, None, None, None, None, None
+
+
+def rnnt_loss(acts, labels, input_lengths, label_lengths, blank_label: int = 0, fastemit_lambda: float = 0.0,
+              topology: str = "standard"):
     """Per-utterance transducer negative log-likelihood, differentiable in `acts`.
 
     fastemit_lambda in [0, 1]: FastEmit regularisation -- the gradient through the lattice's label edges is scaled by
@@ -101,19 +175,39 @@ def rnnt_loss(acts, labels, input_lengths, label_lengths, blank_label: int = 0, 
 
     Same contract as warprnnt_tensorflow.rnnt_loss on a CUDA build (utils/loss.py:34-35):
     acts are RAW LOGITS [B, T, U, V] (the log-softmax is fused), labels [B, U-1] int,
-    input_lengths / label_lengths [B] int; returns costs [B] float32."""
+    input_lengths / label_lengths [B] int; returns costs [B] float32.
+
+    topology: "standard" (the contract above) or "modified" -- every frame emits exactly one of {blank, next label}, the lattice
+    of the paths the beam searches produce (include/rnnt_modified.h compute_rnnt_loss_modified); an utterance with more labels than frames
+    then costs +inf and has zero gradients."""
+    if check_topology(topology) == "modified":
+        return _RNNTModifiedLossFunction.apply(acts, labels, input_lengths, label_lengths, blank_label,
+                                               check_fastemit_lambda(fastemit_lambda))
     return _RNNTLossFunction.apply(acts, labels, input_lengths, label_lengths, blank_label, check_fastemit_lambda(fastemit_lambda))
 
 
 def rnnt_loss_and_grad(acts, labels, input_lengths, label_lengths, blank_label: int = 0, visit_all: bool = False,
-                       fastemit_lambda: float = 0.0):
+                       fastemit_lambda: float = 0.0, topology: str = "standard"):
     """The upstream C entry point as one call: compute_rnnt_loss(acts, grads, ...) ->
     (costs [B], grads [B,T,U,V]) with grads = d cost_b / d acts (unscaled), like the two outputs of
     the reference's WarpRNNT op.  No autograd graph is built.
     visit_all: compute_rnnt_loss_flags(..., RNNT_VISIT_ALL) -- no occupancy floor (vocabularies above 60 symbols otherwise
     write zeros for cells whose occupancy is below 2^-50 without reading their logits).
-    fastemit_lambda in [0, 1]: compute_rnnt_loss_fastemit -- FastEmit's gradients (the costs do not change)."""
+    fastemit_lambda in [0, 1]: compute_rnnt_loss_fastemit -- FastEmit's gradients (the costs do not change).
+    topology "modified": compute_rnnt_loss_modified in one call; it has no occupancy floor, so visit_all with it is a ValueError."""
     lam = check_fastemit_lambda(fastemit_lambda)
+    if check_topology(topology) == "modified":
+        if visit_all:
+            raise ValueError("rnnt_loss_and_grad: visit_all does not apply to topology='modified' (the modified op has no occupancy floor)")
+        acts_c, labels, input_lengths, label_lengths = _modified_inputs("rnnt_loss_and_grad", acts, labels, input_lengths,
+                                                                        label_lengths)
+        B, T, U, V = acts_c.shape
+        with torch.cuda.device(acts_c.device):
+            ws = torch.empty(_lib.modified_workspace_bytes(T, U, B), dtype=torch.uint8, device=acts_c.device)
+            costs = torch.empty(B, dtype=torch.float32, device=acts_c.device)
+            grads = torch.empty_like(acts_c)
+        _modified_call(acts_c, grads, labels, input_lengths, label_lengths, None, costs, ws, blank_label, lam)
+        return costs, grads
     lib = _lib.load()
     if not acts.is_cuda:
         raise RuntimeError("rnnt_loss_and_grad: acts must live on an MI355X (cuda/HIP) device")
@@ -152,16 +246,17 @@ def rnnt_loss_and_grad(acts, labels, input_lengths, label_lengths, blank_label: 
 class RNNTLoss(torch.nn.Module):
     """nn.Module wrapper; reduction 'none' returns the reference's per-utterance costs."""
 
-    def __init__(self, blank_label: int = 0, reduction: str = "none", fastemit_lambda: float = 0.0):
+    def __init__(self, blank_label: int = 0, reduction: str = "none", fastemit_lambda: float = 0.0, topology: str = "standard"):
         super().__init__()
         self.fastemit_lambda = check_fastemit_lambda(fastemit_lambda)
+        self.topology = check_topology(topology)
         if reduction not in ("none", "sum", "mean"):
             raise ValueError(reduction)
         self.blank_label = blank_label
         self.reduction = reduction
 
     def forward(self, acts, labels, input_lengths, label_lengths):
-        costs = rnnt_loss(acts, labels, input_lengths, label_lengths, self.blank_label, self.fastemit_lambda)
+        costs = rnnt_loss(acts, labels, input_lengths, label_lengths, self.blank_label, self.fastemit_lambda, self.topology)
         if self.reduction == "sum":
             return costs.sum()
         if self.reduction == "mean":
@@ -174,8 +269,9 @@ def reduced_lengths(spec_lengths: torch.Tensor, reduction_factor) -> torch.Tenso
     return torch.ceil(spec_lengths.to(torch.float64) / float(reduction_factor)).to(torch.int32)
 
 
-def get_loss_fn(reduction_factor):
+def get_loss_fn(reduction_factor, topology: str = "standard"):
     """Mirror of utils/loss.py:12-38.  Returns fn(y_true, y_pred, spec_lengths, label_lengths) -> costs [B].
+    topology: rnnt_loss's ("standard", the reference's lattice, or "modified").
 
     y_true: labels [B, U-1]; y_pred: joint logits [B, T', U, V]; spec_lengths: encoder input
     lengths BEFORE time reduction; label_lengths [B].  The reference log-softmaxes first only on
@@ -183,11 +279,12 @@ def get_loss_fn(reduction_factor):
     CPU tensor raises instead of silently training on garbage."""
     if reduction_factor is None or float(reduction_factor) <= 0 or math.isnan(float(reduction_factor)):
         raise ValueError("reduction_factor must be positive")
+    check_topology(topology)
     _lib.load()  # fail at construction time (run_rnnt.py:493-494), not at the first step
 
     def _loss_fn(y_true, y_pred, spec_lengths, label_lengths):
         y_true = y_true.to(torch.int32)
         spec_lengths = reduced_lengths(spec_lengths, reduction_factor)
-        return rnnt_loss(y_pred, y_true, spec_lengths, label_lengths)
+        return rnnt_loss(y_pred, y_true, spec_lengths, label_lengths, topology=topology)
 
     return _loss_fn

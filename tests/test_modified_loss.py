@@ -1,0 +1,181 @@
+"""CPU tests of the modified (one symbol per frame) topology: they pin the float64 restatement of tests/modified_cases.py against
+the path sum and finite differences, and check what needs no device -- the ABI, the argument validation of
+compute_rnnt_loss_modified and the Python surface's `topology` option."""
+import ctypes
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+import rnnt_speech_recognition_amd as pkg
+from rnnt_speech_recognition_amd import _lib
+from tests import modified_cases as mc
+
+INVALID = 2  # RNNT_STATUS_INVALID_VALUE
+
+
+@pytest.fixture(scope="module")
+def lib():
+    pkg.build()
+    return _lib.load_mod()
+
+
+def _one(T, L, V, seed, blank=0):
+    acts, labels, _, _ = mc.full_case(1, T, L, V, seed, blank=blank)
+    return acts[0].astype(np.float64), labels[0]
+
+
+# ---- the restatement ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("T,L", [(4, 2), (5, 0), (3, 3), (6, 1)])
+def test_cost_is_the_sum_over_all_paths(T, L):
+    x, y = _one(T, L, 4, seed=T * 10 + L)
+    assert math.comb(T, L) >= 1
+    cost, _ = mc.utterance(x, y)
+    assert abs(cost - mc.brute_force_cost(x, y)) <= 1e-12
+
+
+def test_gradients_match_finite_differences():
+    x, y = _one(5, 3, 4, seed=1)
+    _, g = mc.utterance(x, y, lam=0.0)
+    h = 1e-5
+    num = np.zeros_like(x)
+    for idx in np.ndindex(*x.shape):
+        xp, xm = x.copy(), x.copy()
+        xp[idx] += h
+        xm[idx] -= h
+        num[idx] = (mc.utterance(xp, y)[0] - mc.utterance(xm, y)[0]) / (2 * h)
+    assert np.abs(num - g).max() <= 1e-7
+    assert not g[~mc.band(5, 3)].any()  # the cost does not depend on cells no path passes through
+
+
+@pytest.mark.parametrize("lam", [0.0, 0.01, 1.0])
+def test_every_cell_sums_to_zero(lam):
+    x, y = _one(7, 4, 6, seed=2)
+    _, g = mc.utterance(x, y, lam=lam)
+    assert np.abs(g.sum(-1)).max() <= 1e-14
+    c0, g0 = mc.utterance(x, y, lam=0.0)
+    assert mc.utterance(x, y, lam=lam)[0] == c0  # the cost does not depend on lambda
+    assert lam == 0.0 or np.abs(g - g0).max() > 1e-4 * lam
+
+
+def test_no_labels_is_the_blank_path():
+    x, y = _one(6, 0, 5, seed=3, blank=2)
+    cost, g = mc.utterance(x, y, blank=2)
+    assert abs(cost + mc.log_softmax(x)[:, 0, 2].sum()) <= 1e-12
+    assert g.shape == (6, 1, 5)
+
+
+def test_as_many_labels_as_frames_is_the_single_path():
+    T = 5
+    x, y = _one(T, T, 4, seed=4)
+    cost, g = mc.utterance(x, y)
+    lp = mc.log_softmax(x)
+    assert abs(cost + sum(lp[t, t, y[t]] for t in range(T))) <= 1e-12
+    on_path = np.zeros((T, T + 1), bool)
+    on_path[np.arange(T), np.arange(T)] = True
+    assert np.array_equal(mc.band(T, T), on_path) and not g[~on_path].any()
+
+
+def test_more_labels_than_frames_is_infeasible():
+    x, y = _one(3, 5, 4, seed=5)
+    cost, g = mc.utterance(x, y, lam=0.5)
+    assert cost == np.inf and g.shape == x.shape and not g.any()
+    acts, labels, il, ll = mc.ragged_case()
+    costs, grads = mc.loss_and_grad(acts, labels, il, ll, 0.01, np.linspace(-1, 1, 6))
+    assert costs[5] == np.inf and not grads[5].any() and np.isfinite(costs[:5]).all() and np.isfinite(grads).all()
+    assert not grads[~mc.band_mask(acts.shape[:3], il, ll)].any()
+
+
+# ---- the ABI ------------------------------------------------------------------------------------------------------------
+def test_symbols_exist(lib):
+    """include/rnnt_modified.h declares the two entry points, _lib.MOD_SYMBOLS binds them and libwarprnnt_mod.so defines them."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(root, "include", "rnnt_modified.h")).read(), flags=re.S)
+    declared = sorted(set(re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\([^;{]*\)\s*;", text)))
+    assert declared == sorted(_lib.MOD_SYMBOLS) == ["compute_rnnt_loss_modified", "get_rnnt_modified_workspace_size"]
+    for name in declared:
+        assert ctypes.cast(getattr(lib, name), ctypes.c_void_p).value
+
+
+def test_extension_library_exports_its_two_entry_points_alone():
+    """libwarprnnt_mod.so (csrc/rnnt_mod.map): besides the two entry points only what the HIP toolchain emits for device code."""
+    import shutil
+    import subprocess
+
+    from rnnt_speech_recognition_amd.build import MOD_LIB_PATH
+
+    nm = shutil.which("nm")
+    if nm is None:
+        pytest.skip("binutils nm not available")
+    pkg.build()
+    out = subprocess.run([nm, "-D", "--defined-only", MOD_LIB_PATH], check=True, capture_output=True, text=True).stdout
+    names = [ln.split()[-1] for ln in out.splitlines() if ln.strip()]
+    plain = sorted(n for n in names if not n.startswith("_Z") and not n.startswith("__hip_cuid_"))
+    assert plain == sorted(_lib.MOD_SYMBOLS)
+    for n in names:
+        if n.startswith("_Z"):
+            assert n.startswith("_ZN4rnnt") and "kernel" in n, n
+
+
+def test_workspace_size(lib):
+    n = _lib.modified_workspace_bytes(600, 150, 32)
+    assert n % 256 == 0
+    assert n >= 32 * 600 * 150 * (8 + 4 + 8 + 8)  # {lpb, lpl}, lse, alpha and beta in float64 per cell
+    assert _lib.modified_workspace_bytes(600, 150, 64) > n
+    assert _lib.modified_workspace_bytes(10, 1100, 2) > _lib.modified_workspace_bytes(10, 1024, 2)
+    out = ctypes.c_size_t(0)
+    assert lib.get_rnnt_modified_workspace_size(0, 150, 32, ctypes.byref(out)) == INVALID
+    assert lib.get_rnnt_modified_workspace_size(600, 0, 32, ctypes.byref(out)) == INVALID
+    assert lib.get_rnnt_modified_workspace_size(600, 150, 0, ctypes.byref(out)) == INVALID
+    assert lib.get_rnnt_modified_workspace_size(600, 150, 32, None) == INVALID
+    assert lib.get_rnnt_modified_workspace_size(10, 8193, 2, ctypes.byref(out)) == INVALID       # maxU > 8192
+    assert lib.get_rnnt_modified_workspace_size(1 << 16, 1 << 10, 32, ctypes.byref(out)) == INVALID  # B maxT maxU >= 2^31
+
+
+def test_argument_validation_needs_no_device(lib):
+    fake = ctypes.c_void_p(256)  # never dereferenced: rejected before any launch
+    o = _lib.make_options(0, 0, 10, 5)
+
+    def call(acts=fake, grads=fake, labels=fake, ll=fake, il=fake, scale=None, V=28, B=4, costs=fake, ws=fake, opts=o, lam=0.0):
+        return lib.compute_rnnt_loss_modified(acts, grads, labels, ll, il, scale, V, B, costs, ws, opts, lam)
+
+    for name in ("acts", "labels", "ll", "il", "ws"):  # a NULL required pointer
+        assert call(**{name: None}) == INVALID, name
+    assert call(grads=None, costs=None) == INVALID       # nothing to compute
+    assert call(V=1) == INVALID and call(V=0) == INVALID  # alphabet_size < 2
+    assert call(B=0) == INVALID
+    assert call(opts=_lib.make_options(0, 28, 10, 5)) == INVALID   # blank outside [0, V)
+    assert call(opts=_lib.make_options(0, -1, 10, 5)) == INVALID
+    assert call(opts=_lib.make_options(0, 0, 10, 8193)) == INVALID  # maxU > 8192
+    assert call(opts=_lib.make_options(0, 0, 1 << 16, 1 << 10), B=32) == INVALID  # B maxT maxU >= 2^31
+    assert call(opts=_lib.make_options(0, 0, 10, 5, loc=_lib.RNNT_CPU)) == INVALID  # no CPU fallback
+    assert call(ws=ctypes.c_void_p(260)) == INVALID      # misaligned workspace
+    for lam in (-0.1, 1.5, float("nan"), float("inf"), -float("inf")):
+        assert call(lam=lam) == INVALID, lam
+
+
+# ---- the Python surface -------------------------------------------------------------------------------------------------
+def test_topology_is_checked_before_anything_else(lib):
+    import torch
+
+    acts = torch.zeros(1, 2, 2, 4)
+    args = (acts, torch.ones(1, 1, dtype=torch.int32), torch.tensor([2]), torch.tensor([1]))
+    with pytest.raises(ValueError, match="topology"):
+        pkg.rnnt_loss(*args, topology="bogus")
+    with pytest.raises(ValueError, match="topology"):
+        pkg.rnnt_loss_and_grad(*args, topology="bogus")
+    with pytest.raises(ValueError, match="topology"):
+        pkg.RNNTLoss(topology="bogus")
+    with pytest.raises(ValueError, match="topology"):
+        pkg.get_loss_fn(2, topology="bogus")
+    with pytest.raises(ValueError, match="visit_all"):
+        pkg.rnnt_loss_and_grad(*args, visit_all=True, topology="modified")
+    # the modified route has no CPU path either
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        pkg.rnnt_loss(*args, topology="modified")
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        pkg.RNNTLoss(topology="modified")(*args)
+    assert pkg.RNNTLoss(topology="modified").topology == "modified" and pkg.RNNTLoss().topology == "standard"
+    pkg.get_loss_fn(2, topology="modified")
