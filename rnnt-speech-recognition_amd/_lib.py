@@ -9,6 +9,7 @@ import os
 from .build import BIAS_LIB_PATH as _DEFAULT_BIAS_LIB_PATH
 from .build import LIB_PATH as _DEFAULT_LIB_PATH
 from .build import MOD_LIB_PATH as _DEFAULT_MOD_LIB_PATH
+from .build import MODALIGN_LIB_PATH as _DEFAULT_MODALIGN_LIB_PATH
 
 # dev knob: load an experimental build of the library instead (scripts/build_variant.sh)
 LIB_PATH = os.environ.get("RNNT_LIBWARPRNNT", _DEFAULT_LIB_PATH)
@@ -18,6 +19,8 @@ BIAS_LIB_PATH = (_DEFAULT_BIAS_LIB_PATH if LIB_PATH == _DEFAULT_LIB_PATH
                  else os.path.join(os.path.dirname(LIB_PATH), "libwarprnnt_bias.so"))
 # the modified-topology library shares nothing with the base library (its own kernels and workspace): always this tree's build
 MOD_LIB_PATH = _DEFAULT_MOD_LIB_PATH
+# and so does the modified-lattice aligner
+MODALIGN_LIB_PATH = _DEFAULT_MODALIGN_LIB_PATH
 
 RNNT_CPU, RNNT_GPU = 0, 1
 STATUS_SUCCESS = 0
@@ -151,6 +154,13 @@ MOD_SYMBOLS = [  # include/rnnt_modified.h, exported by libwarprnnt_mod.so
     "get_rnnt_modified_workspace_size",
     "compute_rnnt_loss_modified",
 ]
+_modalign_lib = None
+MODALIGN_SYMBOLS = [  # include/rnnt_modified_align.h, exported by libwarprnnt_modalign.so
+    "get_rnnt_modified_align_workspace_size",
+    "compute_rnnt_modified_align_cells",
+    "compute_rnnt_modified_align_path",
+    "compute_rnnt_modified_align",
+]
 
 
 class RNNTLibraryError(RuntimeError):
@@ -201,6 +211,32 @@ def load_mod():
     lib.compute_rnnt_loss_modified.restype = ci
     lib.compute_rnnt_loss_modified.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, rnntOptions, ctypes.c_float]
     _mod_lib = lib
+    return lib
+
+
+def load_modalign():
+    """Load libwarprnnt_modalign.so (once): forced alignment on the modified (one symbol per frame) lattice,
+    include/rnnt_modified_align.h.  Raises RNNTLibraryError loudly when the library is absent."""
+    global _modalign_lib
+    if _modalign_lib is not None:
+        return _modalign_lib
+    if not os.path.exists(MODALIGN_LIB_PATH):
+        raise RNNTLibraryError(f"{MODALIGN_LIB_PATH} not found: the HIP extension has not been built (__graft_entry__.build()). "
+                               "There is no eager fallback for the modified-lattice aligner on a device.")
+    try:
+        lib = ctypes.CDLL(MODALIGN_LIB_PATH)
+    except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
+        raise RNNTLibraryError(f"failed to load {MODALIGN_LIB_PATH}: {e}") from e
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    lib.get_rnnt_modified_align_workspace_size.restype = ci
+    lib.get_rnnt_modified_align_workspace_size.argtypes = [ci, ci, ci, ctypes.POINTER(ctypes.c_size_t)]
+    lib.compute_rnnt_modified_align_cells.restype = ci
+    lib.compute_rnnt_modified_align_cells.argtypes = [vp, ci, ci, vp, vp, vp, ci, ci, vp, rnntOptions]
+    lib.compute_rnnt_modified_align_path.restype = ci
+    lib.compute_rnnt_modified_align_path.argtypes = [vp, vp, vp, vp, vp, ci, vp, rnntOptions]
+    lib.compute_rnnt_modified_align.restype = ci
+    lib.compute_rnnt_modified_align.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, rnntOptions]
+    _modalign_lib = lib
     return lib
 
 
@@ -489,6 +525,13 @@ def align_workspace_bytes(maxT: int, maxU: int, minibatch: int) -> int:
 def modified_workspace_bytes(maxT: int, maxU: int, minibatch: int) -> int:
     n = ctypes.c_size_t(0)
     check(load_mod().get_rnnt_modified_workspace_size(maxT, maxU, minibatch, ctypes.byref(n)), "get_rnnt_modified_workspace_size")
+    return int(n.value)
+
+
+def modified_align_workspace_bytes(maxT: int, maxU: int, minibatch: int) -> int:
+    n = ctypes.c_size_t(0)
+    check(load_modalign().get_rnnt_modified_align_workspace_size(maxT, maxU, minibatch, ctypes.byref(n)),
+          "get_rnnt_modified_align_workspace_size")
     return int(n.value)
 
 

@@ -1,14 +1,20 @@
 """Forced alignment: the maximum-probability monotone path through the transducer lattice and the frame at which every label
 is emitted (include/rnnt.h "Forced alignment"; csrc/align_kernels.hip).
 
-  rnnt_align(acts, labels, input_lengths, label_lengths, blank_label=0) -> (token_frames, token_logp, scores)
-  align_joint(joint, enc, pred, labels, input_lengths, label_lengths, slab_frames=None)   the same from enc / pred, in slabs
+  rnnt_align(acts, labels, input_lengths, label_lengths, blank_label=0, topology="standard") -> (token_frames, token_logp, scores)
+  align_joint(joint, enc, pred, labels, input_lengths, label_lengths, slab_frames=None, topology="standard")
+                                                 the same from enc / pred, in slabs
   token_times(token_frames, hp, sample_rate)     lattice frames -> seconds
   word_times(ids, token_frames, encoder)         character tokens -> (word, first_frame, last_frame)
 
 Device tensors go through libwarprnnt.so.  CPU tensors run the SAME equations in torch (float32 log-softmax, float64 sweep, the
 strict-greater tie rule): the mirror every module here has, so the host logic and its tests run without a GPU.  The two routes
-agree wherever the best path's decisions are not within rounding of a tie (the normalisers differ in their last bits)."""
+agree wherever the best path's decisions are not within rounding of a tie (the normalisers differ in their last bits).
+
+topology="standard" is the lattice of compute_rnnt_loss (a label edge stays on its frame; several labels may share a frame).
+topology="modified" is the lattice of rnnt_loss(..., topology="modified") and of every decoder here: each frame emits exactly one
+of {blank, next label}, token_frames is strictly increasing, scores <= -cost of the modified loss
+(include/rnnt_modified_align.h; csrc/rnnt_modalign_kernels.hip in libwarprnnt_modalign.so)."""
 from __future__ import annotations
 
 from typing import List, Optional, Tuple
@@ -19,6 +25,12 @@ from . import _lib
 
 # align_joint: the logits of one slab of frames, [B, slab, U, V] float32, stay under this many bytes unless the caller says otherwise
 SLAB_BYTES = 256 << 20
+TOPOLOGIES = ("standard", "modified")
+
+
+def _check_topology(topology, what):
+    if topology not in TOPOLOGIES:
+        raise ValueError(f"{what}: topology must be one of {TOPOLOGIES}, got {topology!r}")
 
 
 def _as_i32(x, device) -> torch.Tensor:
@@ -100,19 +112,72 @@ def _torch_path(lpb, lpl, input_lengths, label_lengths):
     return frames.to(dev), logp.to(dev), scores
 
 
+def _torch_path_modified(lpb, lpl, input_lengths, label_lengths):
+    """The recurrence and the back-trace of include/rnnt_modified_align.h on [B, T, U] cell log-probabilities: float64 values, row
+    by row (every edge advances the frame), label arrival only if strictly greater, nodes outside the band u <= t,
+    L - u <= T - t at -inf."""
+    B, T, U = lpb.shape
+    dev = lpb.device
+    il, ll = input_lengths.long(), label_lengths.long()
+    bad = (il < 1) | (il > T) | (ll < 0) | (ll > U - 1)
+    Tb, Ub = il.clamp(1, T)[:, None], ll.clamp(0, U - 1)[:, None]
+    lpb64, lpl64 = lpb.double(), lpl.double()
+    u = torch.arange(U, device=dev)[None, :]
+    neg = torch.full((B, U), float("-inf"), dtype=torch.float64, device=dev)
+    v = neg.clone()
+    v[:, 0] = 0.0
+    took_label = torch.zeros(B, T + 1, U, dtype=torch.bool, device=dev)
+    final = neg[:, 0].clone()
+
+    def in_band(t):
+        return (u <= t) & (u <= Ub) & (Ub - u <= Tb - t)
+
+    for t in range(T):
+        src_ok = in_band(t)
+        stay = torch.where(src_ok, v + lpb64[:, t], neg)
+        move = torch.where(src_ok & (u < Ub), v + lpl64[:, t], neg)
+        frm = torch.cat([neg[:, :1], move[:, :-1]], dim=1)
+        dst_ok = in_band(t + 1)
+        lab = frm > stay
+        v = torch.where(dst_ok, torch.where(lab, frm, stay), neg)
+        took_label[:, t + 1] = lab & dst_ok
+        final = torch.where(Tb[:, 0] == t + 1, v.gather(1, Ub)[:, 0], final)
+    frames = torch.full((B, max(U - 1, 0)), -1, dtype=torch.int32)
+    logp = torch.zeros(B, max(U - 1, 0), dtype=torch.float32)
+    tl = took_label.cpu().numpy()
+    lpl_c = lpl.cpu()
+    for b in range(B):
+        uu, t = int(Ub[b]), int(Tb[b])
+        if bool(bad[b]) or uu > t:  # out-of-range lengths, or more labels than frames: no path
+            continue
+        while t >= 1:
+            if tl[b, t, uu]:
+                frames[b, uu - 1] = t - 1
+                logp[b, uu - 1] = lpl_c[b, t - 1, uu - 1]
+                uu -= 1
+            t -= 1
+    scores = torch.where(bad, torch.full_like(final, float("nan")), final).float()
+    return frames.to(dev), logp.to(dev), scores
+
+
 # ---- the engine ---------------------------------------------------------------------------------------------------
 class _Aligner:
     """One alignment in flight on the engine: the workspace, the outputs and the slab feed."""
 
-    def __init__(self, B, T, U, V, labels, input_lengths, label_lengths, blank, dev):
-        self.lib = _lib.load()
+    def __init__(self, B, T, U, V, labels, input_lengths, label_lengths, blank, dev, topology="standard"):
+        if topology == "modified":  # libwarprnnt_modalign.so: the same three calls on a workspace of its own
+            self.lib, ws_bytes = _lib.load_modalign(), _lib.modified_align_workspace_bytes
+            self.names = ("compute_rnnt_modified_align_cells", "compute_rnnt_modified_align_path", "compute_rnnt_modified_align")
+        else:
+            self.lib, ws_bytes = _lib.load(), _lib.align_workspace_bytes
+            self.names = ("compute_rnnt_align_cells", "compute_rnnt_align_path", "compute_rnnt_align")
         self.B, self.T, self.U, self.V, self.blank, self.dev = B, T, U, V, int(blank), dev
         self.labels = _as_i32(labels, dev)
         if self.labels.numel() == 0:
             self.labels = torch.zeros((B, 1), dtype=torch.int32, device=dev)
         self.il, self.ll = _as_i32(input_lengths, dev), _as_i32(label_lengths, dev)
         with torch.cuda.device(dev):
-            self.ws = torch.empty(_lib.align_workspace_bytes(T, U, B), dtype=torch.uint8, device=dev)
+            self.ws = torch.empty(ws_bytes(T, U, B), dtype=torch.uint8, device=dev)
 
     def _opts(self):
         return _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, self.T, self.U)
@@ -122,10 +187,10 @@ class _Aligner:
             raise ValueError(f"align: a slab must be float32 [{self.B}, frames, {self.U}, {self.V}], got {tuple(slab.shape)}")
         slab = slab.contiguous()
         with torch.cuda.device(self.dev):
-            st = self.lib.compute_rnnt_align_cells(slab.data_ptr(), slab.shape[1], int(frame_offset), self.labels.data_ptr(),
-                                                   self.ll.data_ptr(), self.il.data_ptr(), self.V, self.B, self.ws.data_ptr(),
-                                                   self._opts())
-        _lib.check(st, "compute_rnnt_align_cells")
+            st = getattr(self.lib, self.names[0])(slab.data_ptr(), slab.shape[1], int(frame_offset), self.labels.data_ptr(),
+                                                  self.ll.data_ptr(), self.il.data_ptr(), self.V, self.B, self.ws.data_ptr(),
+                                                  self._opts())
+        _lib.check(st, self.names[0])
 
     def path(self):
         n = max(self.U - 1, 1)
@@ -133,19 +198,21 @@ class _Aligner:
             frames = torch.empty(self.B, n, dtype=torch.int32, device=self.dev)
             logp = torch.empty(self.B, n, dtype=torch.float32, device=self.dev)
             scores = torch.empty(self.B, dtype=torch.float32, device=self.dev)
-            st = self.lib.compute_rnnt_align_path(frames.data_ptr(), logp.data_ptr(), scores.data_ptr(), self.ll.data_ptr(),
+            st = getattr(self.lib, self.names[1])(frames.data_ptr(), logp.data_ptr(), scores.data_ptr(), self.ll.data_ptr(),
                                                   self.il.data_ptr(), self.B, self.ws.data_ptr(), self._opts())
-        _lib.check(st, "compute_rnnt_align_path")
+        _lib.check(st, self.names[1])
         return frames[:, : self.U - 1], logp[:, : self.U - 1], scores
 
 
 @torch.no_grad()
-def rnnt_align(acts, labels, input_lengths, label_lengths, blank_label: int = 0):
+def rnnt_align(acts, labels, input_lengths, label_lengths, blank_label: int = 0, topology: str = "standard"):
     """Best path through the lattice of `acts` (RAW LOGITS [B, T, U, V] float32, the loss op's convention).
 
     Returns (token_frames i32 [B, U-1], token_logp f32 [B, U-1], scores f32 [B]): the frame at which label u is emitted (-1 past
     the utterance's labels), its log-probability there (0 past them) and the path's log-probability.  An utterance whose lengths
-    are out of range comes back with a NaN score and -1 frames."""
+    are out of range comes back with a NaN score and -1 frames.  topology="modified": the one-symbol-per-frame lattice (strictly
+    increasing frames; an utterance with more labels than frames has no path: score -inf, -1 frames)."""
+    _check_topology(topology, "rnnt_align")
     if acts.dim() != 4:
         raise ValueError("rnnt_align: acts must be [B, T, U, V]")
     if acts.dtype != torch.float32:
@@ -159,17 +226,18 @@ def rnnt_align(acts, labels, input_lengths, label_lengths, blank_label: int = 0)
         raise ValueError("rnnt_align: blank_label outside the vocabulary")
     if not acts.is_cuda:
         lpb, lpl = _torch_cells(acts.detach(), labels, int(blank_label))
-        return _torch_path(lpb, lpl, input_lengths, label_lengths)
-    al = _Aligner(B, T, U, V, labels, input_lengths, label_lengths, blank_label, dev)
+        path = _torch_path_modified if topology == "modified" else _torch_path
+        return path(lpb, lpl, input_lengths, label_lengths)
+    al = _Aligner(B, T, U, V, labels, input_lengths, label_lengths, blank_label, dev, topology)
     acts_c = acts.detach().contiguous()
     with torch.cuda.device(dev):
         n = max(U - 1, 1)
         frames = torch.empty(B, n, dtype=torch.int32, device=dev)
         logp = torch.empty(B, n, dtype=torch.float32, device=dev)
         scores = torch.empty(B, dtype=torch.float32, device=dev)
-        st = al.lib.compute_rnnt_align(acts_c.data_ptr(), al.labels.data_ptr(), al.ll.data_ptr(), al.il.data_ptr(), V, B,
-                                       frames.data_ptr(), logp.data_ptr(), scores.data_ptr(), al.ws.data_ptr(), al._opts())
-    _lib.check(st, "compute_rnnt_align")
+        st = getattr(al.lib, al.names[2])(acts_c.data_ptr(), al.labels.data_ptr(), al.ll.data_ptr(), al.il.data_ptr(), V, B,
+                                          frames.data_ptr(), logp.data_ptr(), scores.data_ptr(), al.ws.data_ptr(), al._opts())
+    _lib.check(st, al.names[2])
     return frames[:, : U - 1], logp[:, : U - 1], scores
 
 
@@ -180,11 +248,13 @@ def slab_frames_for(B: int, T: int, U: int, V: int, slab_bytes: int = SLAB_BYTES
 
 @torch.no_grad()
 def align_joint(joint, enc, pred, labels, input_lengths, label_lengths, slab_frames: Optional[int] = None,
-                slab_bytes: int = SLAB_BYTES):
+                slab_bytes: int = SLAB_BYTES, topology: str = "standard"):
     """rnnt_align on the logits of `joint` (a JointLoss) for enc [B, T, H] / pred [B, U, H] without holding [B, T, U, V]: the
     logits come from joint.cell_logits one slab of frames at a time, each slab is reduced to two floats per lattice cell
     (compute_rnnt_align_cells), and the sweep runs once.  slab_frames=None picks the largest slab whose logits stay under
-    `slab_bytes` (default SLAB_BYTES = 256 MiB).  The outputs are bitwise those of rnnt_align on joint.cell_logits(enc, pred)."""
+    `slab_bytes` (default SLAB_BYTES = 256 MiB).  The outputs are bitwise those of rnnt_align on joint.cell_logits(enc, pred), with
+    the same `topology`."""
+    _check_topology(topology, "align_joint")
     B, T, _ = enc.shape
     U = pred.shape[1]
     V = joint.W2.shape[1]
@@ -198,8 +268,9 @@ def align_joint(joint, enc, pred, labels, input_lengths, label_lengths, slab_fra
     if not enc.is_cuda:
         parts = [_torch_cells(joint.cell_logits(enc[:, t0:t0 + S], pred).float(), labels, joint.blank_label) for t0 in range(0, T, S)]
         lpb, lpl = torch.cat([p[0] for p in parts], dim=1), torch.cat([p[1] for p in parts], dim=1)
-        return _torch_path(lpb, lpl, input_lengths, label_lengths)
-    al = _Aligner(B, T, U, V, labels, input_lengths, label_lengths, joint.blank_label, dev)
+        path = _torch_path_modified if topology == "modified" else _torch_path
+        return path(lpb, lpl, input_lengths, label_lengths)
+    al = _Aligner(B, T, U, V, labels, input_lengths, label_lengths, joint.blank_label, dev, topology)
     for t0 in range(0, T, S):
         slab = joint.cell_logits(enc[:, t0:t0 + S].contiguous(), pred)
         al.cells(slab, t0)

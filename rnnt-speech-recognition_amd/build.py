@@ -24,6 +24,11 @@ BIAS_MAP = os.path.join(CSRC, "rnnt_bias.map")
 MOD_LIB_PATH = os.path.join(LIB_DIR, "libwarprnnt_mod.so")
 MOD_SOURCES = ["rnnt_mod_kernels.hip", "rnnt_mod_entrypoint.hip"]
 MOD_MAP = os.path.join(CSRC, "rnnt_mod.map")
+# the extension library of include/rnnt_modified_align.h: forced alignment on the modified lattice.  Self-contained as well;
+# rnnt_modalign.map: it exports its four entry points alone.
+MODALIGN_LIB_PATH = os.path.join(LIB_DIR, "libwarprnnt_modalign.so")
+MODALIGN_SOURCES = ["rnnt_modalign_kernels.hip", "rnnt_modalign_entrypoint.hip"]
+MODALIGN_MAP = os.path.join(CSRC, "rnnt_modalign.map")
 SOURCES = ["rnnt_kernels.hip", "rnnt_lin_kernels.hip", "joint_kernels.hip", "joint_f16_kernels.hip", "dense_kernels.hip", "greedy_kernels.hip",
            "beam_kernels.hip", "prednet_kernels.hip", "encoder_kernels.hip", "lstm_train_kernels.hip", "frontend_kernels.hip",
            "align_kernels.hip", "rnnt_entrypoint.hip"]
@@ -44,11 +49,12 @@ def _deps():
     files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_bias.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_modified.h"))
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_modified_align.h"))
     return files
 
 
 def needs_build() -> bool:
-    libs = (LIB_PATH, BIAS_LIB_PATH, MOD_LIB_PATH)
+    libs = (LIB_PATH, BIAS_LIB_PATH, MOD_LIB_PATH, MODALIGN_LIB_PATH)
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
@@ -66,7 +72,8 @@ def _compile_one(args):
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile every HIP source (one hipcc per source, in parallel) and link lib/libwarprnnt.so and, from the same kernel
-    objects, lib/libwarprnnt_bias.so, and lib/libwarprnnt_mod.so from MOD_SOURCES; returns the path of the first."""
+    objects, lib/libwarprnnt_bias.so, lib/libwarprnnt_mod.so from MOD_SOURCES and lib/libwarprnnt_modalign.so from MODALIGN_SOURCES;
+    returns the path of the first."""
     if not force and not needs_build():
         return LIB_PATH
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -74,7 +81,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("hipcc not found: cannot build libwarprnnt.so (ROCm toolchain required)")
     os.makedirs(LIB_DIR, exist_ok=True)
     tag = f".tmp{os.getpid()}"  # several ranks may arrive here at once
-    jobs = [(hipcc, os.path.join(CSRC, s), os.path.join(LIB_DIR, s[:-4] + tag + ".o"), verbose) for s in SOURCES + BIAS_SOURCES + MOD_SOURCES]
+    jobs = [(hipcc, os.path.join(CSRC, s), os.path.join(LIB_DIR, s[:-4] + tag + ".o"), verbose) for s in SOURCES + BIAS_SOURCES + MOD_SOURCES + MODALIGN_SOURCES]
     objs = []
     try:
         from concurrent.futures import ThreadPoolExecutor
@@ -83,8 +90,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
             objs = list(ex.map(_compile_one, jobs))
         n = len(SOURCES)  # (SOURCES ends with rnnt_entrypoint.hip)
         m = n + len(BIAS_SOURCES)
+        k = m + len(MOD_SOURCES)
         links = ((BIAS_LIB_PATH, objs[: n - 1] + objs[n:m], ["-Wl,--version-script=" + BIAS_MAP]),
-                 (MOD_LIB_PATH, objs[m:], ["-Wl,--version-script=" + MOD_MAP]), (LIB_PATH, objs[:n], []))
+                 (MOD_LIB_PATH, objs[m:k], ["-Wl,--version-script=" + MOD_MAP]),
+                 (MODALIGN_LIB_PATH, objs[k:], ["-Wl,--version-script=" + MODALIGN_MAP]), (LIB_PATH, objs[:n], []))
         for path, members, extra in links:
             tmp = path + tag
             cmd = [hipcc] + HIPCC_FLAGS + extra + members + ["-o", tmp]

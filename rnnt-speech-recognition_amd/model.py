@@ -255,14 +255,15 @@ class Transducer(nn.Module):
         return self.joint.logits(enc, pred)
 
     @torch.no_grad()
-    def align(self, mel_specs, pred_inp, spec_lengths, label_lengths, labels, slab_frames=None):
+    def align(self, mel_specs, pred_inp, spec_lengths, label_lengths, labels, slab_frames=None, topology="standard"):
         """Forced alignment of `labels` with the loss's argument set: (token_frames, token_logp, scores) of alignment.align_joint,
-        frames counted after the encoder's time reduction (alignment.token_times turns them into seconds)."""
+        frames counted after the encoder's time reduction (alignment.token_times turns them into seconds).  topology="modified":
+        the one-symbol-per-frame lattice of rnnt_loss(..., topology="modified") and of the decoders."""
         from .alignment import align_joint
 
         enc, pred = self(mel_specs, pred_inp)
         t_len = reduced_lengths(spec_lengths, self.hp.time_reduction_factor)
-        return align_joint(self.joint, enc, pred, labels, t_len, label_lengths, slab_frames=slab_frames)
+        return align_joint(self.joint, enc, pred, labels, t_len, label_lengths, slab_frames=slab_frames, topology=topology)
 
 
 def save_weights(model: nn.Module, path: str) -> None:
