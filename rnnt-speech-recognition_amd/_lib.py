@@ -10,6 +10,7 @@ from .build import BIAS_LIB_PATH as _DEFAULT_BIAS_LIB_PATH
 from .build import LIB_PATH as _DEFAULT_LIB_PATH
 from .build import MOD_LIB_PATH as _DEFAULT_MOD_LIB_PATH
 from .build import MODALIGN_LIB_PATH as _DEFAULT_MODALIGN_LIB_PATH
+from .build import PRUNED_LIB_PATH as _DEFAULT_PRUNED_LIB_PATH
 
 # dev knob: load an experimental build of the library instead (scripts/build_variant.sh)
 LIB_PATH = os.environ.get("RNNT_LIBWARPRNNT", _DEFAULT_LIB_PATH)
@@ -21,6 +22,8 @@ BIAS_LIB_PATH = (_DEFAULT_BIAS_LIB_PATH if LIB_PATH == _DEFAULT_LIB_PATH
 MOD_LIB_PATH = _DEFAULT_MOD_LIB_PATH
 # and so does the modified-lattice aligner
 MODALIGN_LIB_PATH = _DEFAULT_MODALIGN_LIB_PATH
+# and the pruned loss
+PRUNED_LIB_PATH = _DEFAULT_PRUNED_LIB_PATH
 
 RNNT_CPU, RNNT_GPU = 0, 1
 STATUS_SUCCESS = 0
@@ -161,6 +164,12 @@ MODALIGN_SYMBOLS = [  # include/rnnt_modified_align.h, exported by libwarprnnt_m
     "compute_rnnt_modified_align_path",
     "compute_rnnt_modified_align",
 ]
+_pruned_lib = None
+PRUNED_SYMBOLS = [  # include/rnnt_pruned.h, exported by libwarprnnt_pruned.so
+    "get_rnnt_pruned_workspace_size",
+    "compute_rnnt_loss_pruned",
+]
+RNNT_PRUNED_STANDARD, RNNT_PRUNED_MODIFIED = 0, 1
 
 
 class RNNTLibraryError(RuntimeError):
@@ -237,6 +246,28 @@ def load_modalign():
     lib.compute_rnnt_modified_align.restype = ci
     lib.compute_rnnt_modified_align.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, rnntOptions]
     _modalign_lib = lib
+    return lib
+
+
+def load_pruned():
+    """Load libwarprnnt_pruned.so (once): the loss op on a band of S symbols per frame, include/rnnt_pruned.h.  Raises
+    RNNTLibraryError loudly when the library is absent."""
+    global _pruned_lib
+    if _pruned_lib is not None:
+        return _pruned_lib
+    if not os.path.exists(PRUNED_LIB_PATH):
+        raise RNNTLibraryError(f"{PRUNED_LIB_PATH} not found: the HIP extension has not been built (__graft_entry__.build()). "
+                               "There is no eager fallback for the pruned loss on a device.")
+    try:
+        lib = ctypes.CDLL(PRUNED_LIB_PATH)
+    except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
+        raise RNNTLibraryError(f"failed to load {PRUNED_LIB_PATH}: {e}") from e
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    lib.get_rnnt_pruned_workspace_size.restype = ci
+    lib.get_rnnt_pruned_workspace_size.argtypes = [ci, ci, ci, ctypes.POINTER(ctypes.c_size_t)]
+    lib.compute_rnnt_loss_pruned.restype = ci
+    lib.compute_rnnt_loss_pruned.argtypes = [vp] * 7 + [ci] * 4 + [vp, vp, rnntOptions, ctypes.c_float]
+    _pruned_lib = lib
     return lib
 
 
@@ -532,6 +563,12 @@ def modified_align_workspace_bytes(maxT: int, maxU: int, minibatch: int) -> int:
     n = ctypes.c_size_t(0)
     check(load_modalign().get_rnnt_modified_align_workspace_size(maxT, maxU, minibatch, ctypes.byref(n)),
           "get_rnnt_modified_align_workspace_size")
+    return int(n.value)
+
+
+def pruned_workspace_bytes(maxT: int, s_range: int, minibatch: int) -> int:
+    n = ctypes.c_size_t(0)
+    check(load_pruned().get_rnnt_pruned_workspace_size(maxT, s_range, minibatch, ctypes.byref(n)), "get_rnnt_pruned_workspace_size")
     return int(n.value)
 
 
