@@ -11,6 +11,7 @@ from .build import LIB_PATH as _DEFAULT_LIB_PATH
 from .build import MOD_LIB_PATH as _DEFAULT_MOD_LIB_PATH
 from .build import MODALIGN_LIB_PATH as _DEFAULT_MODALIGN_LIB_PATH
 from .build import PRUNED_LIB_PATH as _DEFAULT_PRUNED_LIB_PATH
+from .build import SIMPLE_LIB_PATH as _DEFAULT_SIMPLE_LIB_PATH
 
 # dev knob: load an experimental build of the library instead (scripts/build_variant.sh)
 LIB_PATH = os.environ.get("RNNT_LIBWARPRNNT", _DEFAULT_LIB_PATH)
@@ -24,6 +25,8 @@ MOD_LIB_PATH = _DEFAULT_MOD_LIB_PATH
 MODALIGN_LIB_PATH = _DEFAULT_MODALIGN_LIB_PATH
 # and the pruned loss
 PRUNED_LIB_PATH = _DEFAULT_PRUNED_LIB_PATH
+# and the simple (additive joiner) loss, its first pass
+SIMPLE_LIB_PATH = _DEFAULT_SIMPLE_LIB_PATH
 
 RNNT_CPU, RNNT_GPU = 0, 1
 STATUS_SUCCESS = 0
@@ -170,6 +173,12 @@ PRUNED_SYMBOLS = [  # include/rnnt_pruned.h, exported by libwarprnnt_pruned.so
     "compute_rnnt_loss_pruned",
 ]
 RNNT_PRUNED_STANDARD, RNNT_PRUNED_MODIFIED = 0, 1
+_simple_lib = None
+SIMPLE_SYMBOLS = [  # include/rnnt_simple.h, exported by libwarprnnt_simple.so
+    "get_rnnt_simple_workspace_size",
+    "compute_rnnt_loss_simple",
+]
+RNNT_SIMPLE_STANDARD, RNNT_SIMPLE_MODIFIED = 0, 1
 
 
 class RNNTLibraryError(RuntimeError):
@@ -268,6 +277,28 @@ def load_pruned():
     lib.compute_rnnt_loss_pruned.restype = ci
     lib.compute_rnnt_loss_pruned.argtypes = [vp] * 7 + [ci] * 4 + [vp, vp, rnntOptions, ctypes.c_float]
     _pruned_lib = lib
+    return lib
+
+
+def load_simple():
+    """Load libwarprnnt_simple.so (once): the loss op of an additive joiner, include/rnnt_simple.h.  Raises RNNTLibraryError if
+    it is missing: there is no fallback on a device."""
+    global _simple_lib
+    if _simple_lib is not None:
+        return _simple_lib
+    if not os.path.exists(SIMPLE_LIB_PATH):
+        raise RNNTLibraryError(f"{SIMPLE_LIB_PATH} not found: the HIP extension has not been built (__graft_entry__.build()). "
+                               "There is no eager fallback for the simple loss on a device.")
+    try:
+        lib = ctypes.CDLL(SIMPLE_LIB_PATH)
+    except OSError as e:
+        raise RNNTLibraryError(f"failed to load {SIMPLE_LIB_PATH}: {e}") from e
+    ci, vp = ctypes.c_int, ctypes.c_void_p
+    lib.get_rnnt_simple_workspace_size.restype = ci
+    lib.get_rnnt_simple_workspace_size.argtypes = [ci, ci, ci, ctypes.POINTER(ctypes.c_size_t)]
+    lib.compute_rnnt_loss_simple.restype = ci
+    lib.compute_rnnt_loss_simple.argtypes = [vp] * 9 + [ci] * 3 + [ctypes.c_float] * 2 + [vp, vp, rnntOptions]
+    _simple_lib = lib
     return lib
 
 
@@ -569,6 +600,12 @@ def modified_align_workspace_bytes(maxT: int, maxU: int, minibatch: int) -> int:
 def pruned_workspace_bytes(maxT: int, s_range: int, minibatch: int) -> int:
     n = ctypes.c_size_t(0)
     check(load_pruned().get_rnnt_pruned_workspace_size(maxT, s_range, minibatch, ctypes.byref(n)), "get_rnnt_pruned_workspace_size")
+    return int(n.value)
+
+
+def simple_workspace_bytes(maxT: int, maxU: int, minibatch: int) -> int:
+    n = ctypes.c_size_t(0)
+    check(load_simple().get_rnnt_simple_workspace_size(maxT, maxU, minibatch, ctypes.byref(n)), "get_rnnt_simple_workspace_size")
     return int(n.value)
 
 

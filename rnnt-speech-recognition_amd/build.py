@@ -34,6 +34,11 @@ MODALIGN_MAP = os.path.join(CSRC, "rnnt_modalign.map")
 PRUNED_LIB_PATH = os.path.join(LIB_DIR, "libwarprnnt_pruned.so")
 PRUNED_SOURCES = ["rnnt_pruned_kernels.hip", "rnnt_pruned_entrypoint.hip"]
 PRUNED_MAP = os.path.join(CSRC, "rnnt_pruned.map")
+# the extension library of include/rnnt_simple.h: the loss op of an additive joiner (am + lm), the first pass of the pruned loss.
+# Self-contained as well; rnnt_simple.map: it exports its two entry points alone.
+SIMPLE_LIB_PATH = os.path.join(LIB_DIR, "libwarprnnt_simple.so")
+SIMPLE_SOURCES = ["rnnt_simple_kernels.hip", "rnnt_simple_entrypoint.hip"]
+SIMPLE_MAP = os.path.join(CSRC, "rnnt_simple.map")
 SOURCES = ["rnnt_kernels.hip", "rnnt_lin_kernels.hip", "joint_kernels.hip", "joint_f16_kernels.hip", "dense_kernels.hip", "greedy_kernels.hip",
            "beam_kernels.hip", "prednet_kernels.hip", "encoder_kernels.hip", "lstm_train_kernels.hip", "frontend_kernels.hip",
            "align_kernels.hip", "rnnt_entrypoint.hip"]
@@ -56,11 +61,12 @@ def _deps():
     files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_modified.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_modified_align.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_pruned.h"))
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_simple.h"))
     return files
 
 
 def needs_build() -> bool:
-    libs = (LIB_PATH, BIAS_LIB_PATH, MOD_LIB_PATH, MODALIGN_LIB_PATH, PRUNED_LIB_PATH)
+    libs = (LIB_PATH, BIAS_LIB_PATH, MOD_LIB_PATH, MODALIGN_LIB_PATH, PRUNED_LIB_PATH, SIMPLE_LIB_PATH)
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
@@ -78,8 +84,8 @@ def _compile_one(args):
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile every HIP source (one hipcc per source, in parallel) and link lib/libwarprnnt.so and, from the same kernel
-    objects, lib/libwarprnnt_bias.so, lib/libwarprnnt_mod.so from MOD_SOURCES, lib/libwarprnnt_modalign.so from MODALIGN_SOURCES
-    and lib/libwarprnnt_pruned.so from PRUNED_SOURCES; returns the path of the first."""
+    objects, lib/libwarprnnt_bias.so, lib/libwarprnnt_mod.so from MOD_SOURCES, lib/libwarprnnt_modalign.so from MODALIGN_SOURCES,
+    lib/libwarprnnt_pruned.so from PRUNED_SOURCES and lib/libwarprnnt_simple.so from SIMPLE_SOURCES; returns the path of the first."""
     if not force and not needs_build():
         return LIB_PATH
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -87,7 +93,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("hipcc not found: cannot build libwarprnnt.so (ROCm toolchain required)")
     os.makedirs(LIB_DIR, exist_ok=True)
     tag = f".tmp{os.getpid()}"  # several ranks may arrive here at once
-    jobs = [(hipcc, os.path.join(CSRC, s), os.path.join(LIB_DIR, s[:-4] + tag + ".o"), verbose) for s in SOURCES + BIAS_SOURCES + MOD_SOURCES + MODALIGN_SOURCES + PRUNED_SOURCES]
+    jobs = [(hipcc, os.path.join(CSRC, s), os.path.join(LIB_DIR, s[:-4] + tag + ".o"), verbose) for s in SOURCES + BIAS_SOURCES + MOD_SOURCES + MODALIGN_SOURCES + PRUNED_SOURCES + SIMPLE_SOURCES]
     objs = []
     try:
         from concurrent.futures import ThreadPoolExecutor
@@ -98,10 +104,12 @@ def build(force: bool = False, verbose: bool = False) -> str:
         m = n + len(BIAS_SOURCES)
         k = m + len(MOD_SOURCES)
         q = k + len(MODALIGN_SOURCES)
+        r = q + len(PRUNED_SOURCES)
         links = ((BIAS_LIB_PATH, objs[: n - 1] + objs[n:m], ["-Wl,--version-script=" + BIAS_MAP]),
                  (MOD_LIB_PATH, objs[m:k], ["-Wl,--version-script=" + MOD_MAP]),
                  (MODALIGN_LIB_PATH, objs[k:q], ["-Wl,--version-script=" + MODALIGN_MAP]),
-                 (PRUNED_LIB_PATH, objs[q:], ["-Wl,--version-script=" + PRUNED_MAP]), (LIB_PATH, objs[:n], []))
+                 (PRUNED_LIB_PATH, objs[q:r], ["-Wl,--version-script=" + PRUNED_MAP]),
+                 (SIMPLE_LIB_PATH, objs[r:], ["-Wl,--version-script=" + SIMPLE_MAP]), (LIB_PATH, objs[:n], []))
         for path, members, extra in links:
             tmp = path + tag
             cmd = [hipcc] + HIPCC_FLAGS + extra + members + ["-o", tmp]

@@ -10,6 +10,9 @@ symbol per frame) lattice, with FastEmit's gradients.
     a, p = prune_joint_inputs(enc_proj, pred_proj, sb, s_range)
     costs = rnnt_loss_pruned(torch.tanh(a + p) @ W2 + b2, sb, labels, input_lengths, label_lengths)
 
+simple.py has the first pass that produces the occupancies (rnnt_loss_simple, an additive joiner) and the whole pipeline as one
+function (rnnt_loss_two_pass).
+
 acts[b, t, s, :] are the logits of lattice cell (t, u), u = s_begin[b, t] + s; the cell is PRESENT iff t < T_b and 0 <= u <= L_b,
 everything else is absent: no edges, exact-zero gradients, logits never read.  Any int32 is a legal s_begin value; a band that does
 not connect (0, 0) to the end costs +inf and has zero gradients.
