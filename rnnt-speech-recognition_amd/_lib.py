@@ -12,6 +12,7 @@ from .build import MOD_LIB_PATH as _DEFAULT_MOD_LIB_PATH
 from .build import MODALIGN_LIB_PATH as _DEFAULT_MODALIGN_LIB_PATH
 from .build import PRUNED_LIB_PATH as _DEFAULT_PRUNED_LIB_PATH
 from .build import SIMPLE_LIB_PATH as _DEFAULT_SIMPLE_LIB_PATH
+from .build import PRUNEDJOINT_LIB_PATH as _DEFAULT_PRUNEDJOINT_LIB_PATH
 
 # dev knob: load an experimental build of the library instead (scripts/build_variant.sh)
 LIB_PATH = os.environ.get("RNNT_LIBWARPRNNT", _DEFAULT_LIB_PATH)
@@ -27,6 +28,8 @@ MODALIGN_LIB_PATH = _DEFAULT_MODALIGN_LIB_PATH
 PRUNED_LIB_PATH = _DEFAULT_PRUNED_LIB_PATH
 # and the simple (additive joiner) loss, its first pass
 SIMPLE_LIB_PATH = _DEFAULT_SIMPLE_LIB_PATH
+# and the fused joint on the pruned band
+PRUNEDJOINT_LIB_PATH = _DEFAULT_PRUNEDJOINT_LIB_PATH
 
 RNNT_CPU, RNNT_GPU = 0, 1
 STATUS_SUCCESS = 0
@@ -179,6 +182,11 @@ SIMPLE_SYMBOLS = [  # include/rnnt_simple.h, exported by libwarprnnt_simple.so
     "compute_rnnt_loss_simple",
 ]
 RNNT_SIMPLE_STANDARD, RNNT_SIMPLE_MODIFIED = 0, 1
+_prunedjoint_lib = None
+PRUNEDJOINT_SYMBOLS = [  # include/rnnt_pruned_joint.h, exported by libwarprnnt_prunedjoint.so
+    "get_rnnt_pruned_joint_workspace_size",
+    "compute_rnnt_joint_loss_pruned",
+]
 
 
 class RNNTLibraryError(RuntimeError):
@@ -277,6 +285,28 @@ def load_pruned():
     lib.compute_rnnt_loss_pruned.restype = ci
     lib.compute_rnnt_loss_pruned.argtypes = [vp] * 7 + [ci] * 4 + [vp, vp, rnntOptions, ctypes.c_float]
     _pruned_lib = lib
+    return lib
+
+
+def load_prunedjoint():
+    """Load libwarprnnt_prunedjoint.so (once): the fused joint on the pruned band, include/rnnt_pruned_joint.h.  Raises
+    RNNTLibraryError if the library is missing or does not load."""
+    global _prunedjoint_lib
+    if _prunedjoint_lib is not None:
+        return _prunedjoint_lib
+    if not os.path.exists(PRUNEDJOINT_LIB_PATH):
+        raise RNNTLibraryError(f"{PRUNEDJOINT_LIB_PATH} not found: the HIP extension has not been built (__graft_entry__.build()). "
+                               "There is no eager fallback for the fused pruned joint on a device.")
+    try:
+        lib = ctypes.CDLL(PRUNEDJOINT_LIB_PATH)
+    except OSError as e:
+        raise RNNTLibraryError(f"failed to load {PRUNEDJOINT_LIB_PATH}: {e}") from e
+    ci, vp = ctypes.c_int, ctypes.c_void_p
+    lib.get_rnnt_pruned_joint_workspace_size.restype = ci
+    lib.get_rnnt_pruned_joint_workspace_size.argtypes = [ci, ci, ci, ci, ctypes.POINTER(ctypes.c_size_t)]
+    lib.compute_rnnt_joint_loss_pruned.restype = ci
+    lib.compute_rnnt_joint_loss_pruned.argtypes = [vp] * 9 + [ci] * 5 + [vp] * 6 + [rnntOptions, ctypes.c_float]
+    _prunedjoint_lib = lib
     return lib
 
 
@@ -601,6 +631,13 @@ def pruned_workspace_bytes(maxT: int, s_range: int, minibatch: int) -> int:
     n = ctypes.c_size_t(0)
     check(load_pruned().get_rnnt_pruned_workspace_size(maxT, s_range, minibatch, ctypes.byref(n)), "get_rnnt_pruned_workspace_size")
     return int(n.value)
+
+
+def pruned_joint_workspace_bytes(maxT: int, s_range: int, minibatch: int, joint_size: int) -> int:
+    n = ctypes.c_size_t(0)
+    check(load_prunedjoint().get_rnnt_pruned_joint_workspace_size(maxT, s_range, minibatch, joint_size, ctypes.byref(n)),
+          "get_rnnt_pruned_joint_workspace_size")
+    return n.value
 
 
 def simple_workspace_bytes(maxT: int, maxU: int, minibatch: int) -> int:
