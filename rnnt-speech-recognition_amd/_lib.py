@@ -13,6 +13,7 @@ from .build import MODALIGN_LIB_PATH as _DEFAULT_MODALIGN_LIB_PATH
 from .build import PRUNED_LIB_PATH as _DEFAULT_PRUNED_LIB_PATH
 from .build import SIMPLE_LIB_PATH as _DEFAULT_SIMPLE_LIB_PATH
 from .build import PRUNEDJOINT_LIB_PATH as _DEFAULT_PRUNEDJOINT_LIB_PATH
+from .build import PRUNERANGES_LIB_PATH as _DEFAULT_PRUNERANGES_LIB_PATH
 
 # dev knob: load an experimental build of the library instead (scripts/build_variant.sh)
 LIB_PATH = os.environ.get("RNNT_LIBWARPRNNT", _DEFAULT_LIB_PATH)
@@ -30,6 +31,8 @@ PRUNED_LIB_PATH = _DEFAULT_PRUNED_LIB_PATH
 SIMPLE_LIB_PATH = _DEFAULT_SIMPLE_LIB_PATH
 # and the fused joint on the pruned band
 PRUNEDJOINT_LIB_PATH = _DEFAULT_PRUNEDJOINT_LIB_PATH
+# and the band positions between the two passes
+PRUNERANGES_LIB_PATH = _DEFAULT_PRUNERANGES_LIB_PATH
 
 RNNT_CPU, RNNT_GPU = 0, 1
 STATUS_SUCCESS = 0
@@ -187,6 +190,10 @@ PRUNEDJOINT_SYMBOLS = [  # include/rnnt_pruned_joint.h, exported by libwarprnnt_
     "get_rnnt_pruned_joint_workspace_size",
     "compute_rnnt_joint_loss_pruned",
 ]
+_pruneranges_lib = None
+PRUNERANGES_SYMBOLS = [  # include/rnnt_prune_ranges.h, exported by libwarprnnt_pruneranges.so
+    "compute_rnnt_prune_ranges",
+]
 
 
 class RNNTLibraryError(RuntimeError):
@@ -307,6 +314,26 @@ def load_prunedjoint():
     lib.compute_rnnt_joint_loss_pruned.restype = ci
     lib.compute_rnnt_joint_loss_pruned.argtypes = [vp] * 9 + [ci] * 5 + [vp] * 6 + [rnntOptions, ctypes.c_float]
     _prunedjoint_lib = lib
+    return lib
+
+
+def load_pruneranges():
+    """Load libwarprnnt_pruneranges.so (once): the band positions of the pruned loss with a defined order of additions,
+    include/rnnt_prune_ranges.h.  Raises RNNTLibraryError if it is missing: there is no fallback on a device."""
+    global _pruneranges_lib
+    if _pruneranges_lib is not None:
+        return _pruneranges_lib
+    if not os.path.exists(PRUNERANGES_LIB_PATH):
+        raise RNNTLibraryError(f"{PRUNERANGES_LIB_PATH} not found: the HIP extension has not been built (__graft_entry__.build()). "
+                               "There is no eager fallback for the ordered band positions on a device.")
+    try:
+        lib = ctypes.CDLL(PRUNERANGES_LIB_PATH)
+    except OSError as e:
+        raise RNNTLibraryError(f"failed to load {PRUNERANGES_LIB_PATH}: {e}") from e
+    ci, vp = ctypes.c_int, ctypes.c_void_p
+    lib.compute_rnnt_prune_ranges.restype = ci
+    lib.compute_rnnt_prune_ranges.argtypes = [vp, vp, vp, ci, ci, vp, rnntOptions]
+    _pruneranges_lib = lib
     return lib
 
 

@@ -44,6 +44,11 @@ SIMPLE_MAP = os.path.join(CSRC, "rnnt_simple.map")
 PRUNEDJOINT_LIB_PATH = os.path.join(LIB_DIR, "libwarprnnt_prunedjoint.so")
 PRUNEDJOINT_SOURCES = ["rnnt_pruned_joint_kernels.hip", "rnnt_pruned_joint_entrypoint.hip"]
 PRUNEDJOINT_MAP = os.path.join(CSRC, "rnnt_pruned_joint.map")
+# the extension library of include/rnnt_prune_ranges.h: the band positions between the two passes of the pruned loss, with a defined
+# order of additions.  Self-contained as well (no workspace); rnnt_prune_ranges.map: it exports its one entry point alone.
+PRUNERANGES_LIB_PATH = os.path.join(LIB_DIR, "libwarprnnt_pruneranges.so")
+PRUNERANGES_SOURCES = ["rnnt_prune_ranges_kernels.hip", "rnnt_prune_ranges_entrypoint.hip"]
+PRUNERANGES_MAP = os.path.join(CSRC, "rnnt_prune_ranges.map")
 SOURCES = ["rnnt_kernels.hip", "rnnt_lin_kernels.hip", "joint_kernels.hip", "joint_f16_kernels.hip", "dense_kernels.hip", "greedy_kernels.hip",
            "beam_kernels.hip", "prednet_kernels.hip", "encoder_kernels.hip", "lstm_train_kernels.hip", "frontend_kernels.hip",
            "align_kernels.hip", "rnnt_entrypoint.hip"]
@@ -69,11 +74,13 @@ def _deps():
     files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_pruned.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_simple.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_pruned_joint.h"))
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_prune_ranges.h"))
     return files
 
 
 def needs_build() -> bool:
-    libs = (LIB_PATH, BIAS_LIB_PATH, MOD_LIB_PATH, MODALIGN_LIB_PATH, PRUNED_LIB_PATH, SIMPLE_LIB_PATH, PRUNEDJOINT_LIB_PATH)
+    libs = (LIB_PATH, BIAS_LIB_PATH, MOD_LIB_PATH, MODALIGN_LIB_PATH, PRUNED_LIB_PATH, SIMPLE_LIB_PATH, PRUNEDJOINT_LIB_PATH,
+            PRUNERANGES_LIB_PATH)
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
@@ -92,8 +99,9 @@ def _compile_one(args):
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile every HIP source (one hipcc per source, in parallel) and link lib/libwarprnnt.so and, from the same kernel
     objects, lib/libwarprnnt_bias.so, lib/libwarprnnt_mod.so from MOD_SOURCES, lib/libwarprnnt_modalign.so from MODALIGN_SOURCES,
-    lib/libwarprnnt_pruned.so from PRUNED_SOURCES, lib/libwarprnnt_simple.so from SIMPLE_SOURCES and lib/libwarprnnt_prunedjoint.so
-    from PRUNEDJOINT_SOURCES and the kernel object of PRUNED_SOURCES; returns the path of the first."""
+    lib/libwarprnnt_pruned.so from PRUNED_SOURCES, lib/libwarprnnt_simple.so from SIMPLE_SOURCES, lib/libwarprnnt_prunedjoint.so
+    from PRUNEDJOINT_SOURCES and the kernel object of PRUNED_SOURCES and lib/libwarprnnt_pruneranges.so from PRUNERANGES_SOURCES;
+    returns the path of the first."""
     if not force and not needs_build():
         return LIB_PATH
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -101,7 +109,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("hipcc not found: cannot build libwarprnnt.so (ROCm toolchain required)")
     os.makedirs(LIB_DIR, exist_ok=True)
     tag = f".tmp{os.getpid()}"  # several ranks may arrive here at once
-    jobs = [(hipcc, os.path.join(CSRC, s), os.path.join(LIB_DIR, s[:-4] + tag + ".o"), verbose) for s in SOURCES + BIAS_SOURCES + MOD_SOURCES + MODALIGN_SOURCES + PRUNED_SOURCES + SIMPLE_SOURCES + PRUNEDJOINT_SOURCES]
+    jobs = [(hipcc, os.path.join(CSRC, s), os.path.join(LIB_DIR, s[:-4] + tag + ".o"), verbose) for s in SOURCES + BIAS_SOURCES + MOD_SOURCES + MODALIGN_SOURCES + PRUNED_SOURCES + SIMPLE_SOURCES + PRUNEDJOINT_SOURCES + PRUNERANGES_SOURCES]
     objs = []
     try:
         from concurrent.futures import ThreadPoolExecutor
@@ -114,12 +122,14 @@ def build(force: bool = False, verbose: bool = False) -> str:
         q = k + len(MODALIGN_SOURCES)
         r = q + len(PRUNED_SOURCES)
         v = r + len(SIMPLE_SOURCES)
+        x = v + len(PRUNEDJOINT_SOURCES)
         links = ((BIAS_LIB_PATH, objs[: n - 1] + objs[n:m], ["-Wl,--version-script=" + BIAS_MAP]),
                  (MOD_LIB_PATH, objs[m:k], ["-Wl,--version-script=" + MOD_MAP]),
                  (MODALIGN_LIB_PATH, objs[k:q], ["-Wl,--version-script=" + MODALIGN_MAP]),
                  (PRUNED_LIB_PATH, objs[q:r], ["-Wl,--version-script=" + PRUNED_MAP]),
                  (SIMPLE_LIB_PATH, objs[r:v], ["-Wl,--version-script=" + SIMPLE_MAP]),
-                 (PRUNEDJOINT_LIB_PATH, objs[q:q + 1] + objs[v:], ["-Wl,--version-script=" + PRUNEDJOINT_MAP]), (LIB_PATH, objs[:n], []))
+                 (PRUNEDJOINT_LIB_PATH, objs[q:q + 1] + objs[v:x], ["-Wl,--version-script=" + PRUNEDJOINT_MAP]),
+                 (PRUNERANGES_LIB_PATH, objs[x:], ["-Wl,--version-script=" + PRUNERANGES_MAP]), (LIB_PATH, objs[:n], []))
         for path, members, extra in links:
             tmp = path + tag
             cmd = [hipcc] + HIPCC_FLAGS + extra + members + ["-o", tmp]

@@ -35,6 +35,7 @@ from .loss import reduced_lengths
 from .lstm import lstm_layer
 
 LSTM_ROUTES = ("torch", "engine")
+LOSS_MODES = ("full", "pruned")
 
 
 def _check_lstm_route(lstm: str) -> str:
@@ -223,10 +224,21 @@ class Transducer(nn.Module):
     `forward` (training included) through the library's step kernels instead of nn.LSTM; parameters, state_dict() and
     checkpoints are the same on both routes, and the decoders' `encoder=` / `prediction=` options are independent of it.
     `fastemit_lambda` (0 ... 1) is handed to the JointLoss: FastEmit regularisation of the loss's gradients, so that TrainStep trains
-    a streaming model to emit sooner without any change of its own."""
+    a streaming model to emit sooner without any change of its own.
 
-    def __init__(self, hp: HParams, blank_label: int = 0, lstm: str = "torch", fastemit_lambda: float = 0.0):
+    `loss` picks the TRAINING objective.  "full" (the default) is the full-lattice fused joint, and nothing else is constructed.
+    "pruned" adds `self.pruned`, a pruned_training.PrunedJointLoss with the two heads of the first pass (`s_range`,
+    `simple_loss_scale`, `lm_only_scale`, `am_only_scale` are its settings): while `self.training`, `loss()` returns the two-pass
+    pruned objective, simple_loss_scale * simple + pruned.  In eval mode it returns the full-lattice cost through `self.joint`,
+    exactly as a "full" model does, and that is deliberate: the decoders use the full joint, and the evaluation figure stays the
+    model's negative log-likelihood, comparable between the two training modes."""
+
+    def __init__(self, hp: HParams, blank_label: int = 0, lstm: str = "torch", fastemit_lambda: float = 0.0, loss: str = "full",
+                 s_range: int = 5, simple_loss_scale: float = 0.5, lm_only_scale: float = 0.25, am_only_scale: float = 0.0):
         super().__init__()
+        if loss not in LOSS_MODES:
+            raise ValueError(f"loss must be one of {LOSS_MODES}, got {loss!r}")
+        self.loss_mode = loss
         self.hp = hp
         self.lstm_route = _check_lstm_route(lstm)
         self.encoder = Encoder(hp, lstm)
@@ -238,6 +250,12 @@ class Transducer(nn.Module):
                 "time_reduction_index before the last encoder layer)")
         self.joint = JointLoss(self.encoder.out_width, hp.joint_net_size, hp.vocab_size, blank_label,
                                fastemit_lambda=fastemit_lambda)
+        if loss == "pruned":
+            from .pruned_training import PrunedJointLoss
+
+            self.pruned = PrunedJointLoss(self.encoder.out_width, hp.joint_net_size, hp.vocab_size, s_range=s_range,
+                                          simple_loss_scale=simple_loss_scale, lm_only_scale=lm_only_scale,
+                                          am_only_scale=am_only_scale)
 
     def forward(self, mel_specs, pred_inp):
         """-> (enc [B, T', H], pred [B, U, H]); U = L_max + 1 because pred_inp = [0] ++ labels
@@ -245,9 +263,12 @@ class Transducer(nn.Module):
         return self.encoder(mel_specs), self.prediction(pred_inp)
 
     def loss(self, mel_specs, pred_inp, spec_lengths, label_lengths, labels):
-        """Per-utterance costs with the reference's argument set (run_rnnt.py:262-273)."""
+        """Per-utterance costs with the reference's argument set (run_rnnt.py:262-273).  A loss="pruned" model in train mode
+        returns the two-pass pruned objective instead (the class docstring)."""
         enc, pred = self(mel_specs, pred_inp)
         t_len = reduced_lengths(spec_lengths, self.hp.time_reduction_factor)  # utils/loss.py:31-33
+        if self.loss_mode == "pruned" and self.training:
+            return self.pruned(self.joint, enc, pred, labels, t_len, label_lengths)
         return self.joint(enc, pred, labels, t_len, label_lengths)
 
     def logits(self, mel_specs, pred_inp):
@@ -271,5 +292,7 @@ def save_weights(model: nn.Module, path: str) -> None:
     torch.save(model.state_dict(), path)
 
 
-def load_weights(model: nn.Module, path: str, map_location: Optional[str] = None) -> None:
-    model.load_state_dict(torch.load(path, map_location=map_location))
+def load_weights(model: nn.Module, path: str, map_location: Optional[str] = None, strict: bool = True) -> None:
+    """strict=False lets a checkpoint of a loss="full" model initialise a loss="pruned" one: the two heads of the first pass stay
+    at their initialisation."""
+    model.load_state_dict(torch.load(path, map_location=map_location), strict=strict)

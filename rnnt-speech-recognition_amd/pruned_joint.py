@@ -217,17 +217,18 @@ def rnnt_joint_loss_pruned_and_grad(enc_proj, pred_proj, W2, b2, s_begin, labels
 
 def rnnt_loss_two_pass_fused(am, lm, enc_proj, pred_proj, W2, b2, labels, input_lengths, label_lengths, s_range: int,
                              blank_label: int = 0, lm_only_scale: float = 0.0, am_only_scale: float = 0.0,
-                             fastemit_lambda: float = 0.0, topology: str = "standard"):
+                             fastemit_lambda: float = 0.0, topology: str = "standard", ordered_ranges: bool = False):
     """simple.rnnt_loss_two_pass with the fused second pass: (simple_costs [B], pruned_costs [B], s_begin [B, T] int32).
 
     1. rnnt_loss_simple(am, lm, ...) -> simple_costs (differentiable in am and lm) and the occupancies;
-    2. prune_ranges(occupancy, ..., s_range) -> s_begin;
+    2. prune_ranges(occupancy, ..., s_range, ordered=ordered_ranges) -> s_begin (ordered: the rule with a defined order of
+       additions, the same band on every route; on a device two launches of libwarprnnt_pruneranges.so);
     3. rnnt_joint_loss_pruned(enc_proj, pred_proj, W2, b2, s_begin, ...) -> pruned_costs, differentiable in the four: the joint
        tanh(enc_proj[b, t] + pred_proj[b, u]) @ W2 + b2 is evaluated inside the library, on the band alone."""
     lam = check_fastemit_lambda(fastemit_lambda)
     simple_costs, occ = rnnt_loss_simple(am, lm, labels, input_lengths, label_lengths, blank_label, lm_only_scale, am_only_scale,
                                          topology)
-    s_begin = prune_ranges(occ, input_lengths, label_lengths, s_range)
+    s_begin = prune_ranges(occ, input_lengths, label_lengths, s_range, ordered=ordered_ranges)
     pruned_costs = rnnt_joint_loss_pruned(enc_proj, pred_proj, W2, b2, s_begin, labels, input_lengths, label_lengths, blank_label,
                                           lam, topology, s_range=s_range)
     return simple_costs, pruned_costs, s_begin

@@ -268,9 +268,27 @@ def rnnt_loss_pruned_and_grad(acts, s_begin, labels, input_lengths, label_length
     return costs, grads
 
 
-def prune_ranges(occupancy, input_lengths, label_lengths, s_range: int):
+def _ordered_ranges_call(occupancy, input_lengths, label_lengths, S):
+    """compute_rnnt_prune_ranges (include/rnnt_prune_ranges.h, libwarprnnt_pruneranges.so) on the current stream: s_begin [B, T] int32."""
+    if occupancy.dtype != torch.float32:
+        raise TypeError("prune_ranges: ordered=True takes float32 occupancies on a device")
+    B, T, U = occupancy.shape
+    if B < 1 or T < 1 or not 1 <= U <= 8192:
+        raise ValueError(f"prune_ranges: occupancy must be [B >= 1, T >= 1, 1 <= U <= 8192], got {tuple(occupancy.shape)}")
+    dev = occupancy.device
+    occ = occupancy.detach().contiguous()
+    il, ll = _as_i32(input_lengths, dev).reshape(B), _as_i32(label_lengths, dev).reshape(B)
+    with torch.cuda.device(dev):
+        sb = torch.empty((B, T), dtype=torch.int32, device=dev)
+        opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, 0, T, U)
+        st = _lib.load_pruneranges().compute_rnnt_prune_ranges(occ.data_ptr(), il.data_ptr(), ll.data_ptr(), B, S, sb.data_ptr(), opts)
+    _lib.check(st, "compute_rnnt_prune_ranges")
+    return sb
+
+
+def prune_ranges(occupancy, input_lengths, label_lengths, s_range: int, ordered: bool = False):
     """Where each frame's band of `s_range` symbols begins: int32 [B, T] from per-cell occupancies [B, T, U] (non-negative:
-    e_b + e_l per lattice cell, from whatever first pass the caller has).  Torch only.
+    e_b + e_l per lattice cell, from whatever first pass the caller has).  Torch only, unless `ordered` is set.
 
     Per utterance (T_b frames, L_b labels, hi = max(0, L_b + 1 - s_range)), for the frames t < T_b:
       1. sb[t] is the LOWEST s0 in [0, hi] that maximises sum(occupancy[b, t, s0 : s0 + s_range]);
@@ -278,7 +296,15 @@ def prune_ranges(occupancy, input_lengths, label_lengths, s_range: int):
       3. a running maximum forwards: the result is non-decreasing;
       4. backwards over t = T_b - 2 ... 1: sb[t] = max(sb[t], sb[t + 1] - (s_range - 1)), so consecutive bands overlap;
       5. the frames t >= T_b repeat sb[T_b - 1].
-    This is the same idea as k2's get_rnnt_prune_ranges but NOT bit-compatible with it: the rule above is the definition."""
+    This is the same idea as k2's get_rnnt_prune_ranges but NOT bit-compatible with it: the rule above is the definition.
+
+    The window sum of step 1 is a float64 torch `sum`, whose order of additions torch chooses: on peaked occupancies (one entry
+    near 1, its neighbours at 1e-11 ... 1e-20) two windows that both hold the peak differ by less than an ulp, and which of them
+    wins depends on that order.  ordered=True fixes it (include/rnnt_prune_ranges.h): w(s0) = ((occ[s0] + occ[s0 + 1]) + ...) +
+    occ[s0 + S - 1], the terms widened to float64 and added in increasing s; the lowest s0 wins by a strict > from -inf, so a NaN
+    sum never wins.  Steps 2 - 5 are the same.  A device tensor (float32) then runs the HIP library (two launches, no temporaries;
+    no eager fallback: a missing library is an error), a CPU tensor a torch mirror of the same rule: the same occupancies give
+    the same band on every route.  ordered=False is the rule above as it always was."""
     if occupancy.dim() != 3:
         raise ValueError("prune_ranges: occupancy must be [B, T, U]")
     S = int(s_range)
@@ -288,13 +314,22 @@ def prune_ranges(occupancy, input_lengths, label_lengths, s_range: int):
     dev = occupancy.device
     if input_lengths.numel() != B or label_lengths.numel() != B:
         raise ValueError("prune_ranges: input_lengths and label_lengths must be [B]")
+    if ordered and occupancy.is_cuda:
+        return _ordered_ranges_call(occupancy, input_lengths, label_lengths, S)
     Tb = input_lengths.to(device=dev, dtype=torch.int64).reshape(B).clamp(1, T)
     Lb = label_lengths.to(device=dev, dtype=torch.int64).reshape(B).clamp(0, U - 1)
     hi = (Lb + 1 - S).clamp(min=0)
     occ = torch.nn.functional.pad(occupancy.detach().to(torch.float64), (0, S - 1))
-    win = occ.unfold(-1, S, 1).sum(-1)  # [B, T, U]: the window that starts at s0 (cut off at U)
     s0 = torch.arange(U, device=dev)
-    win = torch.where(s0[None, None, :] <= hi[:, None, None], win, torch.full_like(win, -1.0))
+    if ordered:  # the mirror of the ordered rule: the same left-to-right additions, vectorised over s0
+        win = occ[..., 0:U]
+        for s in range(1, S):
+            win = win + occ[..., s:s + U]
+        # a window beyond hi and a NaN sum never win; where nothing beats -inf the answer is 0 (the lowest s0 of the maximum)
+        win = torch.where((s0[None, None, :] <= hi[:, None, None]) & ~torch.isnan(win), win, torch.full_like(win, _NEG_INF))
+    else:
+        win = occ.unfold(-1, S, 1).sum(-1)  # [B, T, U]: the window that starts at s0 (cut off at U)
+        win = torch.where(s0[None, None, :] <= hi[:, None, None], win, torch.full_like(win, -1.0))
     best = win.max(dim=-1, keepdim=True).values
     sb = torch.where(win == best, s0[None, None, :], torch.full((1, 1, 1), U, device=dev, dtype=torch.int64)).min(dim=-1).values
     t = torch.arange(T, device=dev)[None, :]

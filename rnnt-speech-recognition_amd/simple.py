@@ -260,11 +260,11 @@ def rnnt_loss_simple_and_grad(am, lm, labels, input_lengths, label_lengths, blan
 
 def rnnt_loss_two_pass(am, lm, enc_proj, pred_proj, joint, labels, input_lengths, label_lengths, s_range: int,
                        blank_label: int = 0, lm_only_scale: float = 0.0, am_only_scale: float = 0.0,
-                       fastemit_lambda: float = 0.0, topology: str = "standard"):
+                       fastemit_lambda: float = 0.0, topology: str = "standard", ordered_ranges: bool = False):
     """The two-pass pruned loss on one topology: (simple_costs [B], pruned_costs [B], s_begin [B, T] int32).
 
     1. rnnt_loss_simple(am, lm, ...) -> simple_costs (differentiable in am and lm) and the occupancies;
-    2. prune_ranges(occupancy, ..., s_range) -> s_begin, where each frame's band of s_range symbols begins;
+    2. prune_ranges(occupancy, ..., s_range, ordered=ordered_ranges) -> s_begin, where each frame's band of s_range symbols begins;
     3. prune_joint_inputs(enc_proj [B, T, J], pred_proj [B, U, J], s_begin, s_range) -> (a [B, T, 1, J], p [B, T, S, J]);
     4. joint(a, p) -> the band's logits [B, T, S, V] float32 (the caller's joint, e.g. lambda a, p: torch.tanh(a + p) @ W2 + b2);
     5. rnnt_loss_pruned(logits, s_begin, ..., fastemit_lambda) -> pruned_costs (differentiable in enc_proj, pred_proj and
@@ -273,7 +273,7 @@ def rnnt_loss_two_pass(am, lm, enc_proj, pred_proj, joint, labels, input_lengths
     lam = check_fastemit_lambda(fastemit_lambda)
     simple_costs, occ = rnnt_loss_simple(am, lm, labels, input_lengths, label_lengths, blank_label, lm_only_scale,
                                          am_only_scale, topology)
-    s_begin = prune_ranges(occ, input_lengths, label_lengths, s_range)
+    s_begin = prune_ranges(occ, input_lengths, label_lengths, s_range, ordered=ordered_ranges)
     a, p = prune_joint_inputs(enc_proj, pred_proj, s_begin, s_range)
     pruned_costs = rnnt_loss_pruned(joint(a, p), s_begin, labels, input_lengths, label_lengths, blank_label, lam, topology)
     return simple_costs, pruned_costs, s_begin

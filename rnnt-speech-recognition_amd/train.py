@@ -39,7 +39,8 @@ class TrainStep:
 
     def __call__(self, mel_specs, pred_inp, spec_lengths, label_lengths, labels) -> Dict[str, float]:
         """`inputs` are THIS rank's shard of the global batch (parallel.shard_batch).  Returns the log fields of
-        run_rnnt.py:360-364 (loss, step time)."""
+        run_rnnt.py:360-364 (loss, step time); with a loss="pruned" model also `simple_loss` and `pruned_loss`, the means of the
+        two passes' detached per-utterance costs."""
         t0 = time.time()
         self.model.train()
         logged = parallel.dp_loss_step(
@@ -47,7 +48,12 @@ class TrainStep:
             self.params, self.global_batch, self.group)
         self.optimizer.step()
         self.step_count += 1
-        return {"loss": float(logged), "step_time": time.time() - t0, "step": self.step_count}
+        out = {"loss": float(logged), "step_time": time.time() - t0, "step": self.step_count}
+        pruned = getattr(self.model, "pruned", None)
+        if pruned is not None:  # a loss="pruned" model: the two parts of the objective, means over this rank's shard
+            out["simple_loss"] = float(pruned.last_simple_costs.mean())
+            out["pruned_loss"] = float(pruned.last_pruned_costs.mean())
+        return out
 
     @torch.no_grad()
     def evaluate(self, mel_specs, pred_inp, spec_lengths, label_lengths, labels,

@@ -1,0 +1,178 @@
+"""CPU tests of the ordered band-position rule (include/rnnt_prune_ranges.h): the torch mirror of prune_ranges(..., ordered=True)
+against the loop restatement of tests/prune_ranges_cases.py, bit for bit; the rule against prune_ranges(..., ordered=False) where
+every order of additions gives the same sum; and what needs no device: the export table of libwarprnnt_pruneranges.so, the entry
+point's argument checks and the Python surface's errors."""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import rnnt_speech_recognition_amd as pkg
+from rnnt_speech_recognition_amd import _lib
+from tests import prune_ranges_cases as pc
+
+INVALID = 2  # RNNT_STATUS_INVALID_VALUE
+SHAPES = [(3, 7, 6, 1), (4, 9, 6, 2), (7, 12, 13, 5), (5, 6, 9, 9), (4, 5, 4, 7), (2, 1, 1, 1), (6, 20, 40, 33), (3, 4, 70, 64)]  # B, T, U, S
+
+
+@pytest.fixture(scope="module")
+def lib():
+    pkg.build()
+    return _lib.load_pruneranges()
+
+
+def _mirror(occ, il, ll, S, ordered=True):
+    sb = pkg.prune_ranges(torch.as_tensor(occ), torch.as_tensor(il), torch.as_tensor(ll), S, ordered=ordered)
+    assert sb.dtype == torch.int32 and tuple(sb.shape) == occ.shape[:2]
+    return sb.numpy()
+
+
+# ---- the mirror is the restatement ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("maker", [pc.random_case, pc.exact_case, pc.peaked_case])
+def test_mirror_is_the_restatement(maker):
+    for seed, (B, T, U, S) in enumerate(SHAPES):
+        occ, il, ll = maker(B, T, U, S, seed)
+        ref = pc.ranges(occ, il, ll, S)
+        pc.check_invariants(ref, il, ll, S, U)
+        assert np.array_equal(_mirror(occ, il, ll, S), ref), (maker.__name__, B, T, U, S)
+        assert np.array_equal(_mirror(occ.astype(np.float64), il, ll, S), ref)  # float64 occupancies: the same terms
+
+
+def test_ordered_is_the_torch_rule_where_sums_are_exact():
+    """Multiples of 1/4: every order of additions gives the same float64 sum, ties are everywhere, and the lowest s0 wins in
+    both rules.  30 random batches."""
+    rng = np.random.default_rng(100)
+    for seed in range(30):
+        B, T, U = (int(x) for x in rng.integers(1, 8, size=3))
+        U, S = U + int(rng.integers(0, 12)), int(rng.integers(1, 9))
+        occ, il, ll = pc.exact_case(B, T, U, S, 200 + seed)
+        ref = pc.ranges(occ, il, ll, S)
+        assert np.array_equal(_mirror(occ, il, ll, S, ordered=True), ref)
+        assert np.array_equal(_mirror(occ, il, ll, S, ordered=False), ref), (B, T, U, S)
+
+
+@pytest.mark.parametrize("topology", ["standard", "modified"])
+def test_on_the_occupancies_of_the_simple_loss(topology):
+    """B2 T30 U13 S5 on 3 N(0,1) inputs: peaked occupancies, on which the torch rule's answer depends on torch's order of
+    additions (profiles/prune_ranges_notes.md) -- equality with ordered=False is deliberately NOT asserted."""
+    B, T, U, V, S = 2, 30, 13, 6, 5
+    for seed in (0, 1, 2):
+        am, lm, labels, il, ll = pc.simple_inputs(B, T, U, V, seed)
+        t = [torch.as_tensor(x) for x in (am, lm, labels, il, ll)]
+        _, occ, _, _ = pkg.rnnt_loss_simple_and_grad(*t, topology=topology)
+        ref = pc.ranges(occ.numpy(), il, ll, S)
+        sb = pkg.prune_ranges(occ, t[3], t[4], S, ordered=True)
+        assert np.array_equal(sb.numpy(), ref)
+        pc.check_invariants(sb.numpy(), il, ll, S, U)
+        acts = torch.as_tensor(np.random.default_rng(seed).normal(size=(B, T, S, V)).astype(np.float32))
+        costs = pkg.rnnt_loss_pruned(acts, sb, t[2], t[3], t[4], topology=topology)
+        assert torch.isfinite(costs).all()
+
+
+def test_nan_beyond_the_lengths_and_nan_rows():
+    occ, il, ll = pc.random_case(5, 9, 11, 4, seed=7)
+    ref = pc.ranges(occ, il, ll, 4)
+    poisoned = occ.copy()
+    for b in range(5):
+        poisoned[b, il[b]:] = np.nan
+        poisoned[b, :, ll[b] + 1:] = np.nan
+    assert np.array_equal(_mirror(poisoned, il, ll, 4), ref) and np.array_equal(pc.ranges(poisoned, il, ll, 4), ref)
+    bad = occ.copy()
+    bad[0] = np.nan  # an utterance of NaN occupancies: no sum wins, raw = 0 everywhere, and the rule's ends still hold
+    got = _mirror(bad, il, ll, 4)
+    assert np.array_equal(got, pc.ranges(bad, il, ll, 4))
+    pc.check_invariants(got, il, ll, 4, 11)
+    keep = [1, 2, 3, 4]
+    assert np.array_equal(got[keep], ref[keep])
+
+
+@pytest.mark.parametrize("what,value", [("T", 0), ("T", 10), ("L", -1), ("L", 11)])
+def test_out_of_range_lengths_clamp(what, value):
+    occ, il, ll = pc.random_case(3, 9, 11, 3, seed=8)
+    il_c, ll_c = il.copy(), ll.copy()
+    (il if what == "T" else ll)[1] = value
+    (il_c if what == "T" else ll_c)[1] = np.clip(value, 1, 9) if what == "T" else np.clip(value, 0, 10)
+    assert np.array_equal(_mirror(occ, il, ll, 3), pc.ranges(occ, il_c, ll_c, 3))
+
+
+def test_two_pass_hands_the_option_through():
+    B, T, U, J, V, S = 2, 8, 6, 64, 5, 3
+    am, lm, labels, il, ll = pc.simple_inputs(B, T, U, V, seed=3)
+    g = torch.Generator().manual_seed(0)
+    enc, pred = torch.randn(B, T, J, generator=g), torch.randn(B, U, J, generator=g)
+    W2, b2 = 0.1 * torch.randn(J, V, generator=g), torch.zeros(V)
+    t = [torch.as_tensor(x) for x in (am, lm)]
+    rest = [torch.as_tensor(x) for x in (labels, il, ll)]
+    _, occ = pkg.rnnt_loss_simple(*t, *rest)
+    ref = pc.ranges(occ.numpy(), il, ll, S)
+    _, _, sb = pkg.rnnt_loss_two_pass_fused(*t, enc, pred, W2, b2, *rest, S, ordered_ranges=True)
+    assert np.array_equal(sb.numpy(), ref)
+    _, _, sb = pkg.rnnt_loss_two_pass(*t, enc, pred, lambda a, p: torch.tanh(a + p) @ W2 + b2, *rest, S, ordered_ranges=True)
+    assert np.array_equal(sb.numpy(), ref)
+
+
+# ---- the Python surface ---------------------------------------------------------------------------------------------------
+def test_python_argument_errors():
+    occ, il, ll = torch.zeros(2, 4, 5), torch.tensor([4, 4]), torch.tensor([2, 2])
+    for ordered in (False, True):
+        with pytest.raises(ValueError, match="occupancy must be"):
+            pkg.prune_ranges(occ[0], il, ll, 2, ordered=ordered)
+        for S in (0, 65):
+            with pytest.raises(ValueError, match="s_range"):
+                pkg.prune_ranges(occ, il, ll, S, ordered=ordered)
+        with pytest.raises(ValueError, match=r"must be \[B\]"):
+            pkg.prune_ranges(occ, il[:1], ll, 2, ordered=ordered)
+
+
+def test_a_missing_library_is_an_error(monkeypatch, tmp_path):
+    monkeypatch.setattr(_lib, "_pruneranges_lib", None)
+    monkeypatch.setattr(_lib, "PRUNERANGES_LIB_PATH", str(tmp_path / "libwarprnnt_pruneranges.so"))
+    with pytest.raises(_lib.RNNTLibraryError, match="no eager fallback"):
+        _lib.load_pruneranges()
+
+
+# ---- the ABI --------------------------------------------------------------------------------------------------------------
+def test_symbols_exist(lib):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(root, "include", "rnnt_prune_ranges.h")).read(), flags=re.S)
+    declared = sorted(set(re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\([^;{]*\)\s*;", text)))
+    assert declared == _lib.PRUNERANGES_SYMBOLS == ["compute_rnnt_prune_ranges"]
+    assert ctypes.cast(lib.compute_rnnt_prune_ranges, ctypes.c_void_p).value
+
+
+def test_extension_library_exports_its_entry_point_alone():
+    from rnnt_speech_recognition_amd.build import PRUNERANGES_LIB_PATH
+
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/llvm/bin/llvm-nm"  # (the ROCm toolchain that built it has one)
+    assert os.path.exists(nm), "neither binutils nm nor llvm-nm found: the export table cannot be checked"
+    pkg.build()
+    out = subprocess.run([nm, "-D", "--defined-only", PRUNERANGES_LIB_PATH], check=True, capture_output=True, text=True).stdout
+    names = [ln.split()[-1] for ln in out.splitlines() if ln.strip()]
+    plain = sorted(n for n in names if not n.startswith("_Z") and not n.startswith("__hip_cuid_"))
+    assert plain == _lib.PRUNERANGES_SYMBOLS
+    for n in names:
+        if n.startswith("_Z"):
+            assert n.startswith("_ZN4rnnt") and "kernel" in n, n
+
+
+def test_argument_validation_needs_no_device(lib):
+    fake = ctypes.c_void_p(256)  # never dereferenced: rejected before any launch
+    o = _lib.make_options(0, 0, 10, 5)
+
+    def call(occ=fake, il=fake, ll=fake, B=4, S=3, sb=fake, opts=o):
+        return lib.compute_rnnt_prune_ranges(occ, il, ll, B, S, sb, opts)
+
+    for name in ("occ", "il", "ll", "sb"):  # a NULL pointer
+        assert call(**{name: None}) == INVALID, name
+    assert call(B=0) == INVALID and call(B=-1) == INVALID
+    assert call(opts=_lib.make_options(0, 0, 0, 5)) == INVALID          # maxT < 1
+    assert call(opts=_lib.make_options(0, 0, 10, 0)) == INVALID         # maxU outside [1, 8192]
+    assert call(opts=_lib.make_options(0, 0, 10, 8193)) == INVALID
+    assert call(S=0) == INVALID and call(S=65) == INVALID and call(S=-3) == INVALID
+    assert call(opts=_lib.make_options(0, 0, 1 << 20, 64), B=32) == INVALID  # B maxT maxU >= 2^31
+    assert call(opts=_lib.make_options(0, 0, 10, 5, loc=_lib.RNNT_CPU)) == INVALID  # no CPU fallback in the library
