@@ -9,6 +9,7 @@ from .decoding import beam_decode_batch, beam_decode_batch_fn, beam_search_batch
 from .decoding import StreamingBeamDecoder, StreamingGreedyDecoder, StreamingTranscriber  # noqa: F401
 from .lstm import LSTMLayerFunction  # noqa: F401
 from .biasing import ContextGraph  # noqa: F401
+from .lm import NgramLM  # noqa: F401
 from . import features, metrics, records  # noqa: F401
 from .alignment import align_joint, rnnt_align, token_times, word_times  # noqa: F401
 from .loss import RNNTLoss, get_loss_fn, reduced_lengths, rnnt_loss, rnnt_loss_and_grad  # noqa: F401

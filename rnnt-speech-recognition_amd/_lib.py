@@ -8,6 +8,7 @@ import os
 
 from .build import BIAS_LIB_PATH as _DEFAULT_BIAS_LIB_PATH
 from .build import LIB_PATH as _DEFAULT_LIB_PATH
+from .build import LM_LIB_PATH as _DEFAULT_LM_LIB_PATH
 from .build import MOD_LIB_PATH as _DEFAULT_MOD_LIB_PATH
 from .build import MODALIGN_LIB_PATH as _DEFAULT_MODALIGN_LIB_PATH
 from .build import PRUNED_LIB_PATH as _DEFAULT_PRUNED_LIB_PATH
@@ -21,6 +22,9 @@ LIB_PATH = os.environ.get("RNNT_LIBWARPRNNT", _DEFAULT_LIB_PATH)
 # with the stock one (the two step each other's workspaces)
 BIAS_LIB_PATH = (_DEFAULT_BIAS_LIB_PATH if LIB_PATH == _DEFAULT_LIB_PATH
                  else os.path.join(os.path.dirname(LIB_PATH), "libwarprnnt_bias.so"))
+# and so is the LM fusion library
+LM_LIB_PATH = (_DEFAULT_LM_LIB_PATH if LIB_PATH == _DEFAULT_LIB_PATH
+               else os.path.join(os.path.dirname(LIB_PATH), "libwarprnnt_lm.so"))
 # the modified-topology library shares nothing with the base library (its own kernels and workspace): always this tree's build
 MOD_LIB_PATH = _DEFAULT_MOD_LIB_PATH
 # and so does the modified-lattice aligner
@@ -153,6 +157,22 @@ class rnntBiasGraph(ctypes.Structure):
     ]
 
 
+class rnntLmGraph(ctypes.Structure):
+    """The n-gram LM of the fused beam steps (include/rnnt_lm.h): a host struct of device pointers."""
+    _fields_ = [
+        ("num_states", ctypes.c_int),
+        ("num_arcs", ctypes.c_int),
+        ("empty_state", ctypes.c_int),
+        ("unk_score", ctypes.c_float),
+        ("arc_offsets", ctypes.c_void_p),
+        ("arc_tokens", ctypes.c_void_p),
+        ("arc_next", ctypes.c_void_p),
+        ("arc_score", ctypes.c_void_p),
+        ("backoff_next", ctypes.c_void_p),
+        ("backoff_score", ctypes.c_void_p),
+    ]
+
+
 _lib = None
 _bias_lib = None
 BIAS_SYMBOLS = [  # include/rnnt_bias.h, exported by libwarprnnt_bias.so
@@ -160,6 +180,13 @@ BIAS_SYMBOLS = [  # include/rnnt_bias.h, exported by libwarprnnt_bias.so
     "compute_rnnt_beam_timed_step_biased",
     "compute_rnnt_beam_stream_step_biased",
     "compute_rnnt_beam_stream_timed_step_biased",
+]
+_lm_lib = None
+LM_SYMBOLS = [  # include/rnnt_lm.h, exported by libwarprnnt_lm.so
+    "compute_rnnt_beam_step_lm",
+    "compute_rnnt_beam_timed_step_lm",
+    "compute_rnnt_beam_stream_step_lm",
+    "compute_rnnt_beam_stream_timed_step_lm",
 ]
 _mod_lib = None
 MOD_SYMBOLS = [  # include/rnnt_modified.h, exported by libwarprnnt_mod.so
@@ -222,6 +249,28 @@ def load_bias():
         fn.restype = ci
         fn.argtypes = [vp] * 6 + [ci] * ints + [vp, rnntOptions, gp, vp]
     _bias_lib = lib
+    return lib
+
+
+def load_lm():
+    """Load libwarprnnt_lm.so (once): the LM beam steps of include/rnnt_lm.h.  They work on the workspaces that the entry points
+    of load() set up.  Raises RNNTLibraryError loudly when the library is absent."""
+    global _lm_lib
+    if _lm_lib is not None:
+        return _lm_lib
+    if not os.path.exists(LM_LIB_PATH):
+        raise RNNTLibraryError(f"{LM_LIB_PATH} not found: the HIP extension has not been built (__graft_entry__.build()). "
+                               "There is no eager fallback for the LM beam steps.")
+    try:
+        lib = ctypes.CDLL(LM_LIB_PATH)
+    except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
+        raise RNNTLibraryError(f"failed to load {LM_LIB_PATH}: {e}") from e
+    vp, ci, gp = ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(rnntLmGraph)
+    for name, ints in zip(LM_SYMBOLS, (5, 5, 6, 6)):
+        fn = getattr(lib, name)
+        fn.restype = ci
+        fn.argtypes = [vp] * 6 + [ci] * ints + [vp, rnntOptions, gp, vp]
+    _lm_lib = lib
     return lib
 
 

@@ -49,6 +49,12 @@ PRUNEDJOINT_MAP = os.path.join(CSRC, "rnnt_pruned_joint.map")
 PRUNERANGES_LIB_PATH = os.path.join(LIB_DIR, "libwarprnnt_pruneranges.so")
 PRUNERANGES_SOURCES = ["rnnt_prune_ranges_kernels.hip", "rnnt_prune_ranges_entrypoint.hip"]
 PRUNERANGES_MAP = os.path.join(CSRC, "rnnt_prune_ranges.map")
+# the extension library of include/rnnt_lm.h: n-gram LM shallow fusion in the beam searches.  Built as libwarprnnt_bias.so is: the
+# kernel objects of SOURCES, the LM kernels and rnnt_lm_entrypoint.hip in place of rnnt_entrypoint.hip; rnnt_lm.map: it exports the
+# four LM steps alone.
+LM_LIB_PATH = os.path.join(LIB_DIR, "libwarprnnt_lm.so")
+LM_SOURCES = ["beam_lm_kernels.hip", "rnnt_lm_entrypoint.hip"]
+LM_MAP = os.path.join(CSRC, "rnnt_lm.map")
 SOURCES = ["rnnt_kernels.hip", "rnnt_lin_kernels.hip", "joint_kernels.hip", "joint_f16_kernels.hip", "dense_kernels.hip", "greedy_kernels.hip",
            "beam_kernels.hip", "prednet_kernels.hip", "encoder_kernels.hip", "lstm_train_kernels.hip", "frontend_kernels.hip",
            "align_kernels.hip", "rnnt_entrypoint.hip"]
@@ -61,6 +67,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 _NO_SLP = ["-fno-slp-vectorize"]
 EXTRA_FLAGS = {"rnnt_lin_kernels.hip": _NO_SLP, "joint_kernels.hip": _NO_SLP, "joint_f16_kernels.hip": _NO_SLP, "dense_kernels.hip": _NO_SLP,
                "greedy_kernels.hip": _NO_SLP, "beam_kernels.hip": _NO_SLP, "beam_bias_kernels.hip": _NO_SLP,
+               "beam_lm_kernels.hip": _NO_SLP,
                "prednet_kernels.hip": _NO_SLP, "encoder_kernels.hip": _NO_SLP, "lstm_train_kernels.hip": _NO_SLP,
                "rnnt_pruned_joint_kernels.hip": _NO_SLP}
 
@@ -75,12 +82,13 @@ def _deps():
     files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_simple.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_pruned_joint.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_prune_ranges.h"))
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "rnnt_lm.h"))
     return files
 
 
 def needs_build() -> bool:
     libs = (LIB_PATH, BIAS_LIB_PATH, MOD_LIB_PATH, MODALIGN_LIB_PATH, PRUNED_LIB_PATH, SIMPLE_LIB_PATH, PRUNEDJOINT_LIB_PATH,
-            PRUNERANGES_LIB_PATH)
+            PRUNERANGES_LIB_PATH, LM_LIB_PATH)
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
@@ -100,8 +108,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     """Compile every HIP source (one hipcc per source, in parallel) and link lib/libwarprnnt.so and, from the same kernel
     objects, lib/libwarprnnt_bias.so, lib/libwarprnnt_mod.so from MOD_SOURCES, lib/libwarprnnt_modalign.so from MODALIGN_SOURCES,
     lib/libwarprnnt_pruned.so from PRUNED_SOURCES, lib/libwarprnnt_simple.so from SIMPLE_SOURCES, lib/libwarprnnt_prunedjoint.so
-    from PRUNEDJOINT_SOURCES and the kernel object of PRUNED_SOURCES and lib/libwarprnnt_pruneranges.so from PRUNERANGES_SOURCES;
-    returns the path of the first."""
+    from PRUNEDJOINT_SOURCES and the kernel object of PRUNED_SOURCES and lib/libwarprnnt_pruneranges.so from PRUNERANGES_SOURCES, and lib/libwarprnnt_lm.so
+    from the kernel objects of SOURCES and LM_SOURCES; returns the path of the first."""
     if not force and not needs_build():
         return LIB_PATH
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -109,7 +117,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("hipcc not found: cannot build libwarprnnt.so (ROCm toolchain required)")
     os.makedirs(LIB_DIR, exist_ok=True)
     tag = f".tmp{os.getpid()}"  # several ranks may arrive here at once
-    jobs = [(hipcc, os.path.join(CSRC, s), os.path.join(LIB_DIR, s[:-4] + tag + ".o"), verbose) for s in SOURCES + BIAS_SOURCES + MOD_SOURCES + MODALIGN_SOURCES + PRUNED_SOURCES + SIMPLE_SOURCES + PRUNEDJOINT_SOURCES + PRUNERANGES_SOURCES]
+    jobs = [(hipcc, os.path.join(CSRC, s), os.path.join(LIB_DIR, s[:-4] + tag + ".o"), verbose) for s in SOURCES + BIAS_SOURCES + MOD_SOURCES + MODALIGN_SOURCES + PRUNED_SOURCES + SIMPLE_SOURCES + PRUNEDJOINT_SOURCES + PRUNERANGES_SOURCES + LM_SOURCES]
     objs = []
     try:
         from concurrent.futures import ThreadPoolExecutor
@@ -123,13 +131,15 @@ def build(force: bool = False, verbose: bool = False) -> str:
         r = q + len(PRUNED_SOURCES)
         v = r + len(SIMPLE_SOURCES)
         x = v + len(PRUNEDJOINT_SOURCES)
+        z = x + len(PRUNERANGES_SOURCES)
         links = ((BIAS_LIB_PATH, objs[: n - 1] + objs[n:m], ["-Wl,--version-script=" + BIAS_MAP]),
                  (MOD_LIB_PATH, objs[m:k], ["-Wl,--version-script=" + MOD_MAP]),
                  (MODALIGN_LIB_PATH, objs[k:q], ["-Wl,--version-script=" + MODALIGN_MAP]),
                  (PRUNED_LIB_PATH, objs[q:r], ["-Wl,--version-script=" + PRUNED_MAP]),
                  (SIMPLE_LIB_PATH, objs[r:v], ["-Wl,--version-script=" + SIMPLE_MAP]),
                  (PRUNEDJOINT_LIB_PATH, objs[q:q + 1] + objs[v:x], ["-Wl,--version-script=" + PRUNEDJOINT_MAP]),
-                 (PRUNERANGES_LIB_PATH, objs[x:], ["-Wl,--version-script=" + PRUNERANGES_MAP]), (LIB_PATH, objs[:n], []))
+                 (PRUNERANGES_LIB_PATH, objs[x:z], ["-Wl,--version-script=" + PRUNERANGES_MAP]),
+                 (LM_LIB_PATH, objs[: n - 1] + objs[z:], ["-Wl,--version-script=" + LM_MAP]), (LIB_PATH, objs[:n], []))
         for path, members, extra in links:
             tmp = path + tag
             cmd = [hipcc] + HIPCC_FLAGS + extra + members + ["-o", tmp]

@@ -6,8 +6,14 @@
 // logits in key order; beta and the next state of every listed entry are re-derived by bisection (s_pb / s_pn, the entries
 // spread over the wave's lanes), the lists are merged on the key logit + beta, beta goes into the candidate's score in float64
 // and the next state travels with the candidate into BeamSlot::pad.  Everything of it is compiled out at 0.
+// BEAM_SELECT_BIAS 2 (beam_select_lm_kernel, beam_select_timed_lm_kernel): bg is the n-gram LM of include/rnnt_lm.h (LmArgs), with
+// bg_state / bg_delta overloads of its own (beam_lm_kernels.hip); the body is the biased one.
 #if BEAM_SELECT_BIAS
+#if BEAM_SELECT_BIAS == 2
+__global__ __launch_bounds__(256) void BEAM_SELECT_KERNEL(const BeamArgs a, const LmArgs bg) {
+#else
 __global__ __launch_bounds__(256) void BEAM_SELECT_KERNEL(const BeamArgs a, const BiasArgs bg) {
+#endif
     __shared__ float s_pb[kGrWaves][64 * kBeamMax], s_tb[kBeamMax * kBeamMax];
     __shared__ int s_pn[kGrWaves][64 * kBeamMax], s_tn[kBeamMax * kBeamMax], s_q[kBeamMax], s_nx[kBeamMax];
 #else

@@ -2,8 +2,12 @@
 // kernel's name and BEAM_STEP_BIAS 0 / 1 whether it ranks on logit + beta(q, v) of the context graph bg and lists the raw logits
 // (beam_step_kernel<DT> and beam_step_bias_kernel<DT>).  One source, two kernel templates with names of their own, so the
 // unbiased one comes out of the compiler as it did before the biased one existed.  No include guard on purpose.
+// BEAM_STEP_BIAS 2 (beam_step_lm_kernel<DT>, beam_lm_kernels.hip): bg is the n-gram LM of include/rnnt_lm.h (LmArgs) and beta its
+// back-off transition; everything else is the biased kernel's.  The preprocessed text at 0 and at 1 is what it was.
 template <int DT>
-#if BEAM_STEP_BIAS
+#if BEAM_STEP_BIAS == 2
+__global__ __launch_bounds__(kGrWaves * 64) void BEAM_STEP_KERNEL(const BeamArgs ba, const LmArgs bg) {
+#elif BEAM_STEP_BIAS
 __global__ __launch_bounds__(kGrWaves * 64) void BEAM_STEP_KERNEL(const BeamArgs ba, const BiasArgs bg) {
 #else
 __global__ __launch_bounds__(kGrWaves * 64) void BEAM_STEP_KERNEL(const BeamArgs ba) {
@@ -87,7 +91,7 @@ __global__ __launch_bounds__(kGrWaves * 64) void BEAM_STEP_KERNEL(const BeamArgs
     }
     // ---- the slice's top-K per row: 8 threads per row, 16 consecutive symbols each; K rounds of a best-untaken reduction
     const int n = tid >> 3, q = tid & 7;
-#if BEAM_STEP_BIAS
+#if BEAM_STEP_BIAS == 1
     {  // beta of row n's 128 symbols, by the row's 8 threads.  Row n of bt is written and read by those 8 threads ALONE, and they
        // sit in one wave (n = tid >> 3), whose LDS operations complete in the order they were issued: the three passes below
        // overwrite each other in program order without a workgroup barrier.  The s_waitcnt asm statements are compiler barriers
@@ -117,6 +121,49 @@ __global__ __launch_bounds__(kGrWaves * 64) void BEAM_STEP_KERNEL(const BeamArgs
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        }
+    }
+#endif
+#if BEAM_STEP_BIAS == 2
+    {  // beta of row n's 128 symbols under the LM, by the row's 8 threads: the back-off chain c_0 = q ... c_d = E of the row's
+       // state is walked once (lm_backoff: the hop the select kernel takes too, so both form the same f32 sums), then the row is
+       // filled with the unknown-token score and the arcs of c_d, c_(d-1), ... c_0 that fall into the slice are scattered over it,
+       // the nearer level overwriting the farther.  As in the biased kernel above: row n of bt is written and read by those 8
+       // threads ALONE, and they sit in one wave (n = tid >> 3), whose LDS operations complete in the order they were issued, so
+       // the fill and EVERY pass of the level loop overwrite each other in program order without a workgroup barrier.  The
+       // s_waitcnt asm statements are compiler barriers (they keep each pass's stores, the next pass's stores and the loads
+       // after the loop in this order), not what makes the hardware ordering hold.  A change of the row-to-thread mapping that
+       // spreads a row over two waves needs __syncthreads() after the fill and after every level instead.
+        const int v0 = slice * 32 * kGrWaves;
+        if (s_live[n]) {
+            int c[RNNT_LM_MAX_HOPS + 1];
+            float ac[RNNT_LM_MAX_HOPS + 1];
+            int cur = bg_state(bg, ba.slot[r0 + n].pad), hop = 0;
+            float acc = 0.f;
+            c[0] = cur, ac[0] = 0.f;
+#pragma unroll
+            for (int h = 1; h <= RNNT_LM_MAX_HOPS; ++h) {  // (static indices: the chain stays in registers)
+                if (cur != bg.E) lm_backoff(bg, cur, acc, hop);
+                c[h] = cur, ac[h] = acc;
+            }
+            const int d = hop;  // c[d] == E
+            const float unk = d == 0 ? bg.unk : acc + bg.unk;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) bt[n * LW + 16 * q + i] = v0 + 16 * q + i == a.blank ? 0.f : unk;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+            for (int j = RNNT_LM_MAX_HOPS; j >= 0; --j) {
+                if (j <= d) {  // (uniform over the row's 8 threads)
+                    int lo, hi;
+                    bg_arcs(bg, c[j], lo, hi);
+                    const int sl = bg_lower(bg, lo, hi, v0), sh = bg_lower(bg, sl, hi, v0 + 32 * kGrWaves);
+                    for (int e = sl + q; e < sh; e += 8) {
+                        const int col = bg.tok[e] - v0;
+                        if ((unsigned)col < 32u * kGrWaves && col + v0 != a.blank) bt[n * LW + col] = j == 0 ? bg.sc[e] : ac[j] + bg.sc[e];
+                    }
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            }
         }
     }
 #endif

@@ -1,0 +1,110 @@
+// rnnt_lm_entrypoint.hip -- the extern "C" boundary of libwarprnnt_lm.so (declared in include/rnnt_lm.h): the LM steps
+// of the four beam searches.  libwarprnnt.so and include/rnnt.h, the base interface, stay as they are.  This translation unit
+// includes rnnt_entrypoint.hip for the base steps' argument checks (they are static there) and for the graph == NULL forward;
+// build.py links it with the kernel objects and beam_lm_kernels.hip, and rnnt_lm.map keeps everything but the four twins
+// local, so the library defines no base entry point a second time.
+#include "rnnt_entrypoint.hip"
+#include "../../include/rnnt_lm.h"
+
+#include <cmath>
+
+namespace rnnt {
+// beam_lm_kernels.hip
+hipError_t launch_beam_step_lm(const float *pred_proj, int *parents, int *emitted, float *topk_logits, int *topk_symbols,
+                                   float *lse, int J, int V, int B, int T, int K, int N, int blank, int joint_dtype, bool timed,
+                                   void *workspace, hipStream_t s, const rnntLmGraph *graph, int *lm_states);
+}  // namespace rnnt
+
+extern "C" {
+
+// The LM beam steps (include/rnnt_lm.h): the checks of the step they are twins of, then the graph's; graph == NULL
+// is the unfused entry.  Begin, feed, results and the workspace are those of the unfused decode.
+static rnntStatus_t check_lm(const rnntLmGraph *g, const int *lm_states) {
+    if (g->num_states < 1 || g->num_arcs < 0 || !aligned4(lm_states)) return RNNT_STATUS_INVALID_VALUE;
+    if (g->empty_state < 0 || g->empty_state >= g->num_states || !std::isfinite(g->unk_score)) return RNNT_STATUS_INVALID_VALUE;
+    if (!g->backoff_next || !g->backoff_score) return RNNT_STATUS_INVALID_VALUE;
+    if (g->num_arcs > 0 && (!g->arc_offsets || !g->arc_tokens || !g->arc_next || !g->arc_score)) return RNNT_STATUS_INVALID_VALUE;
+    if (!aligned4(g->arc_offsets) || !aligned4(g->arc_tokens) || !aligned4(g->arc_next) || !aligned4(g->arc_score) ||
+        !aligned4(g->backoff_next) || !aligned4(g->backoff_score))
+        return RNNT_STATUS_INVALID_VALUE;
+    return RNNT_STATUS_SUCCESS;
+}
+
+static rnntStatus_t beam_step_lm(const float *pred_proj, int *parents, int *emitted, float *topk_logits, int *topk_symbols,
+                                     float *lse, int joint_size, int alphabet_size, int minibatch, int beam, int joint_dtype,
+                                     void *workspace, const rnntOptions &options, bool timed, const rnntLmGraph *graph,
+                                     int *lm_states) {
+    if (!pred_proj || !parents || !emitted) return RNNT_STATUS_INVALID_VALUE;
+    if (!aligned4(pred_proj) || !aligned4(parents) || !aligned4(emitted) || !aligned4(topk_logits) || !aligned4(topk_symbols) ||
+        !aligned4(lse))
+        return RNNT_STATUS_INVALID_VALUE;
+    rnntStatus_t st = check_lm(graph, lm_states);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    st = check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options, timed);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_step_lm(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size,
+                                     minibatch, options.maxT, beam, options.maxT, options.blank_label, joint_dtype, timed, workspace,
+                                     (hipStream_t)options.stream, graph, lm_states));
+}
+
+static rnntStatus_t beam_stream_step_lm(const float *pred_proj, int *parents, int *emitted, float *topk_logits,
+                                            int *topk_symbols, float *lse, int joint_size, int alphabet_size, int slots, int beam,
+                                            int max_hyp_len, int joint_dtype, void *workspace, const rnntOptions &options, bool timed,
+                                            const rnntLmGraph *graph, int *lm_states) {
+    if (!pred_proj || !parents || !emitted) return RNNT_STATUS_INVALID_VALUE;
+    if (!aligned4(pred_proj) || !aligned4(parents) || !aligned4(emitted) || !aligned4(topk_logits) || !aligned4(topk_symbols) ||
+        !aligned4(lse))
+        return RNNT_STATUS_INVALID_VALUE;
+    rnntStatus_t st = check_lm(graph, lm_states);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    st = check_beam_stream(options.maxT, slots, beam, max_hyp_len, 1, joint_size, alphabet_size, joint_dtype, workspace, options, timed);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_step_lm(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, slots,
+                                     options.maxT, beam, max_hyp_len, options.blank_label, joint_dtype, timed, workspace,
+                                     (hipStream_t)options.stream, graph, lm_states));
+}
+
+rnntStatus_t compute_rnnt_beam_step_lm(const float *pred_proj, int *parents, int *emitted, float *topk_logits, int *topk_symbols,
+                                           float *lse, int joint_size, int alphabet_size, int minibatch, int beam, int joint_dtype,
+                                           void *workspace, rnntOptions options, const rnntLmGraph *graph, int *lm_states) {
+    if (!graph)
+        return compute_rnnt_beam_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, minibatch,
+                                      beam, joint_dtype, workspace, options);
+    return beam_step_lm(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, minibatch, beam,
+                            joint_dtype, workspace, options, false, graph, lm_states);
+}
+
+rnntStatus_t compute_rnnt_beam_timed_step_lm(const float *pred_proj, int *parents, int *emitted, float *topk_logits,
+                                                 int *topk_symbols, float *lse, int joint_size, int alphabet_size, int minibatch,
+                                                 int beam, int joint_dtype, void *workspace, rnntOptions options,
+                                                 const rnntLmGraph *graph, int *lm_states) {
+    if (!graph)
+        return compute_rnnt_beam_timed_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size,
+                                            minibatch, beam, joint_dtype, workspace, options);
+    return beam_step_lm(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, minibatch, beam,
+                            joint_dtype, workspace, options, true, graph, lm_states);
+}
+
+rnntStatus_t compute_rnnt_beam_stream_step_lm(const float *pred_proj, int *parents, int *emitted, float *topk_logits,
+                                                  int *topk_symbols, float *lse, int joint_size, int alphabet_size, int slots, int beam,
+                                                  int max_hyp_len, int joint_dtype, void *workspace, rnntOptions options,
+                                                  const rnntLmGraph *graph, int *lm_states) {
+    if (!graph)
+        return compute_rnnt_beam_stream_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size,
+                                             slots, beam, max_hyp_len, joint_dtype, workspace, options);
+    return beam_stream_step_lm(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, slots, beam,
+                                   max_hyp_len, joint_dtype, workspace, options, false, graph, lm_states);
+}
+
+rnntStatus_t compute_rnnt_beam_stream_timed_step_lm(const float *pred_proj, int *parents, int *emitted, float *topk_logits,
+                                                        int *topk_symbols, float *lse, int joint_size, int alphabet_size, int slots,
+                                                        int beam, int max_hyp_len, int joint_dtype, void *workspace,
+                                                        rnntOptions options, const rnntLmGraph *graph, int *lm_states) {
+    if (!graph)
+        return compute_rnnt_beam_stream_timed_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size,
+                                                   alphabet_size, slots, beam, max_hyp_len, joint_dtype, workspace, options);
+    return beam_stream_step_lm(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, slots, beam,
+                                   max_hyp_len, joint_dtype, workspace, options, true, graph, lm_states);
+}
+
+}  // extern "C"

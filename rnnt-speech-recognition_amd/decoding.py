@@ -283,7 +283,7 @@ _BEAM_WORKSPACES = {}  # (device, stream) -> the beam workspace of the last deco
 
 @torch.no_grad()
 def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, beam: int = 4, prediction: str = "torch",
-                      token_times: bool = False, context=None):
+                      token_times: bool = False, context=None, lm=None):
     """Modified beam search (one symbol per frame) over encoder outputs enc [B, T', H] with frame_lengths [B] (the model in eval
     mode) -> (ids int32 [B, beam, T'] zero-padded, lengths int32 [B, beam], scores [B, beam]): every utterance's n-best, sorted
     by score (empty slots: length 0, score -inf).  See include/rnnt.h for the algorithm; beam = 1 is greedy_search_batch with
@@ -299,13 +299,17 @@ def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, bea
 
     context=biasing.ContextGraph: contextual biasing (hotword boosting).  Candidates are ranked with the graph's bonus, the
     scores include it, and the results are finalised -- a hypothesis that ends in the middle of a phrase gives back what it has
-    not earned -- and re-sorted (stably) by the finalised score.  logp stays the model's log-probability."""
+    not earned -- and re-sorted (stably) by the finalised score.  logp stays the model's log-probability.
+
+    lm=lm.NgramLM: shallow fusion of a back-off n-gram LM (in place of a context: both together raise).  Candidates are ranked
+    with the LM's score of the token (already scaled by the LM weight), the scores include it, and the results are finalised with
+    the LM's end-of-sentence score and re-sorted (stably).  logp stays the model's log-probability."""
     _check_prediction(prediction)
     B, T = enc.shape[0], enc.shape[1]
     K = int(beam)
     dev = enc.device
     # (the current weights: a model may be trained between two decodes)
-    jb = BeamJoint(model.joint, K, token_times=bool(token_times), context=context)
+    jb = BeamJoint(model.joint, K, token_times=bool(token_times), context=context, lm=lm)
     key = (dev, torch.cuda.current_stream(dev).cuda_stream) if enc.is_cuda else None
     if token_times and key is not None:
         key = key + ("timed",)  # (a timed decode keeps a workspace of its own)
@@ -340,11 +344,12 @@ def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, bea
 
 @torch.no_grad()
 def beam_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[torch.Tensor] = None, beam: int = 4,
-                      prediction: str = "torch", encoder: str = "torch", token_times: bool = False, context=None):
+                      prediction: str = "torch", encoder: str = "torch", token_times: bool = False, context=None,
+                      lm=None):
     """Beam search of EVERY utterance of a batch -> the best hypothesis of each: (ids int32 [B, T'] zero-padded, lengths int32
     [B], scores [B]).  spec_lengths are spectrogram frames, reduced as greedy_decode_batch reduces them; None: every frame.
     encoder= as in greedy_decode_batch.  token_times=True: (ids, lengths, scores, frames int32 [B, T'], logp [B, T']) of the
-    best hypothesis, as beam_search_batch defines them.  context= as in beam_search_batch."""
+    best hypothesis, as beam_search_batch defines them.  context= and lm= as in beam_search_batch."""
     _check_prediction(prediction)
     _check_encoder(encoder)
     was_training = model.training
@@ -357,8 +362,8 @@ def beam_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[tor
         else:
             frames = reduced_lengths(spec_lengths.to(enc.device), model.hp.time_reduction_factor)
         if token_times:
-            return tuple(x[:, 0] for x in beam_search_batch(model, enc, frames, beam, prediction, True, context=context))
-        ids, lengths, scores = beam_search_batch(model, enc, frames, beam, prediction, context=context)
+            return tuple(x[:, 0] for x in beam_search_batch(model, enc, frames, beam, prediction, True, context=context, lm=lm))
+        ids, lengths, scores = beam_search_batch(model, enc, frames, beam, prediction, context=context, lm=lm)
         return ids[:, 0], lengths[:, 0], scores[:, 0]
     finally:
         model.train(was_training)
@@ -613,7 +618,7 @@ class StreamingBeamDecoder(_StreamingSlots):
     DEFAULT_MAX_LENGTH = 512
 
     def __init__(self, model, slots: int, max_chunk_frames: int, beam: int = 4, max_length: Optional[int] = None,
-                 token_times: bool = False, context=None):
+                 token_times: bool = False, context=None, lm=None):
         K = int(beam)
         self.token_times = bool(token_times)
         if not 1 <= K <= 16:
@@ -627,7 +632,7 @@ class StreamingBeamDecoder(_StreamingSlots):
         S = self.S
         self.K, self.max_length = K, N
         with self._eval():
-            self.bj = BeamStreamJoint(model.joint, K, token_times=bool(token_times), context=context)
+            self.bj = BeamStreamJoint(model.joint, K, token_times=bool(token_times), context=context, lm=lm)
             dev = next(model.parameters()).device
             self.bj.begin(S, self.Te, N, device=dev)
             W1 = self.bj.W1 if self.bj.engine else model.joint.W1
@@ -680,6 +685,11 @@ class StreamingBeamDecoder(_StreamingSlots):
         scores and order; context.finalize(scores, states) is what a stream that ends here would keep."""
         return self.bj.bias_states().reshape(self.S, self.K)
 
+    def lm_states(self):
+        """int32 [slots, beam]: with lm=, the LM's state of every hypothesis.  The stream reports the beam's own scores and
+        order; lm.finalize(scores, states) adds the end-of-sentence score a stream that ends here would get."""
+        return self.bj.lm_states().reshape(self.S, self.K)
+
     def _timed(self):
         if not self.token_times:
             raise RuntimeError("timed results need a decoder built with token_times=True")
@@ -712,7 +722,7 @@ class StreamingTranscriber:
     reduction factor, so that every non-final feed hands the decoder a multiple of it) in front of a StreamingGreedyDecoder, or
     of a StreamingBeamDecoder when `beam` is given.  The decoder is sized by the front end's max_rows; decoder_kwargs go to it
     (max_length, max_symbols_per_frame, check_every for greedy; max_length for beam).  context=biasing.ContextGraph (beam search
-    only): contextual biasing, as StreamingBeamDecoder takes it.
+    only): contextual biasing, as StreamingBeamDecoder takes it; lm=lm.NgramLM (beam search only): LM shallow fusion, likewise.
 
     start(slots) starts a stream in the given slots of both; feed(audio [slots, N], samples [slots], final [slots]) (N <=
     max_chunk_samples; samples and final are host data) returns what the decoder's feed returns for the rows this audio
@@ -721,11 +731,13 @@ class StreamingTranscriber:
     features.running_mean_log_mel for it.  A stream's result is bitwise independent of how its audio was chunked."""
 
     def __init__(self, model, hp, sample_rate, slots: int, max_chunk_samples: int, beam: Optional[int] = None,
-                 norm: str = "running", context=None, **decoder_kwargs):
+                 norm: str = "running", context=None, lm=None, **decoder_kwargs):
         from .features import StreamingFrontEnd
 
         if context is not None and beam is None:
             raise ValueError("context= needs beam search: build the StreamingTranscriber with beam=")
+        if lm is not None and beam is None:
+            raise ValueError("lm= needs beam search: build the StreamingTranscriber with beam=")
 
         dev = next(model.parameters()).device
         self.hp, self.sample_rate = hp, sample_rate
@@ -733,7 +745,7 @@ class StreamingTranscriber:
         if beam is None:
             self.decoder = StreamingGreedyDecoder(model, slots, self.front.max_rows, **decoder_kwargs)
         else:
-            self.decoder = StreamingBeamDecoder(model, slots, self.front.max_rows, beam=beam, context=context, **decoder_kwargs)
+            self.decoder = StreamingBeamDecoder(model, slots, self.front.max_rows, beam=beam, context=context, lm=lm, **decoder_kwargs)
 
     def start(self, slots) -> None:
         self.front.start(slots)

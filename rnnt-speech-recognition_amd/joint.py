@@ -705,16 +705,28 @@ class BeamJoint:
     context=biasing.ContextGraph (compute_rnnt_beam_*_step_biased): every step ranks on logit + beta and carries the automaton
     state of every hypothesis; bias_states() -> int32 [B beam] after the last step.  results() of the OFFLINE search are
     finalised (score + fail_bias[state]: what a hypothesis left mid-phrase has not earned is taken back) and stably re-sorted
-    by that score; the per-token log-probabilities stay the model's."""
+    by that score; the per-token log-probabilities stay the model's.
 
-    def __init__(self, joint: "JointLoss", beam: int = 4, joint_dtype: str = "auto", token_times: bool = False, context=None):
+    lm=lm.NgramLM (compute_rnnt_beam_*_step_lm, include/rnnt_lm.h): shallow fusion of a back-off n-gram LM, in place of a context
+    (one state word per hypothesis: lm together with context raises).  Every step ranks on logit + the LM's score of the token
+    and carries the LM state of every hypothesis, which starts at the sentence start; lm_states() -> int32 [B beam].  results()
+    of the OFFLINE search add the end-of-sentence score (final_score[state]) and are stably re-sorted, as with a context."""
+
+    def __init__(self, joint: "JointLoss", beam: int = 4, joint_dtype: str = "auto", token_times: bool = False, context=None,
+                 lm=None):
         if not 1 <= int(beam) <= 16:
             raise ValueError("BeamJoint: beam must be in 1 ... 16")
         self.K = int(beam)
         self.token_times = bool(token_times)
-        self.context = context
+        if lm is not None and context is not None:
+            raise ValueError("lm= together with context=: a hypothesis carries one automaton state, take one of the two")
+        self.context, self.lm = context, lm
+        self._fsa = context if lm is None else lm  # the automaton of the torch mirror: either has row() and finalize()
         if context is not None and (context.blank != joint.blank_label or context.vocab_size != joint.W2.shape[1]):
             raise ValueError(f"context graph built for blank {context.blank} / {context.vocab_size} symbols, the joint has blank "
+                             f"{joint.blank_label} / {joint.W2.shape[1]} symbols")
+        if lm is not None and (lm.blank != joint.blank_label or lm.vocab_size != joint.W2.shape[1]):
+            raise ValueError(f"LM built for blank {lm.blank} / {lm.vocab_size} symbols, the joint has blank "
                              f"{joint.blank_label} / {joint.W2.shape[1]} symbols")
         g = GreedyJoint(joint, joint_dtype)  # (the same engine / torch decision and padding)
         self.joint, self.blank, self.V, self.engine = joint, g.blank, g.V, g.engine
@@ -765,6 +777,14 @@ class BeamJoint:
                     self._bias_states.data_ptr())
             _lib.check(st, "compute_rnnt_beam_timed_step_biased" if self.token_times else "compute_rnnt_beam_step_biased")
             return self.parents, self.emitted
+        if self.lm is not None:
+            lib = _lib.load_lm()  # (include/rnnt_lm.h)
+            fn = lib.compute_rnnt_beam_timed_step_lm if self.token_times else lib.compute_rnnt_beam_step_lm
+            st = fn(pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(), ptr(topk_logits), ptr(topk_symbols), ptr(lse),
+                    self.Jp, self.V, self.B, self.K, self.dtype, self._ws.data_ptr(), self._opts, self.lm.byref(pp.device),
+                    self._bias_states.data_ptr())
+            _lib.check(st, "compute_rnnt_beam_timed_step_lm" if self.token_times else "compute_rnnt_beam_step_lm")
+            return self.parents, self.emitted
         fn = lib.compute_rnnt_beam_timed_step if self.token_times else lib.compute_rnnt_beam_step
         st = fn(pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(), ptr(topk_logits), ptr(topk_symbols), ptr(lse),
                 self.Jp, self.V, self.B, self.K, self.dtype, self._ws.data_ptr(), self._opts)
@@ -775,12 +795,17 @@ class BeamJoint:
         """int32 [B beam]: the context graph's state of every slot after the last step (zeros without a context)."""
         return self._bias_states
 
+    def lm_states(self):
+        """int32 [B beam]: the LM's state of every slot after the last step (zeros without an LM: the same word as bias_states)."""
+        return self._bias_states
+
     def _finalised(self, out):
-        """The offline results with a context: score + fail_bias[state], every beam stably re-sorted by it."""
-        if self.context is None:
+        """The offline results with a context or an LM: score + fail_bias[state] / final_score[state], every beam stably
+        re-sorted by it."""
+        if self._fsa is None:
             return out
         B, K = self.B, self.K
-        scores = self.context.finalize(out[2], self._bias_states.reshape(B, K))
+        scores = self._fsa.finalize(out[2], self._bias_states.reshape(B, K))
         scores, order = torch.sort(scores, dim=1, descending=True, stable=True)
         pick = lambda x: torch.gather(x, 1, order.reshape(B, K, *([1] * (x.dim() - 2))).expand_as(x))  # noqa: E731
         return (pick(out[0]), pick(out[1]), scores) + tuple(pick(x) for x in out[3:])
@@ -840,7 +865,7 @@ class BeamJoint:
         """Every row's top-K (logit, symbol) lists.  With a context: by the f32 key logit + beta (rule 2'), the logits raw, and
         bias = (beta, next state) of every listed symbol."""
         K = self.K
-        if self.context is None:
+        if self._fsa is None:
             top_l, top_v = torch.sort(logits, dim=-1, descending=True, stable=True)  # (logit descending, symbol ascending)
             return top_l[:, :K].tolist(), top_v[:, :K].tolist(), None
         import numpy as np
@@ -849,7 +874,7 @@ class BeamJoint:
         q = [0] * R
         for b, states in enumerate(self._states):
             q[b * K: b * K + len(states)] = states
-        rows = [self.context.row(s) for s in q]
+        rows = [self._fsa.row(s) for s in q]
         beta = torch.from_numpy(np.stack([r[0] for r in rows])).to(logits.device)
         nxt = torch.from_numpy(np.stack([r[1] for r in rows])).to(logits.device)
         key = logits.float() + beta
@@ -860,7 +885,7 @@ class BeamJoint:
                 (torch.gather(beta, 1, top_v).tolist(), torch.gather(nxt, 1, top_v).tolist()))
 
     def _torch_bias_states(self):
-        if self.context is None:
+        if self._fsa is None:
             return
         q = [0] * (self.B * self.K)
         for b, states in enumerate(self._states):
@@ -955,7 +980,10 @@ class BeamStreamJoint(BeamJoint):
 
     context=biasing.ContextGraph: the biased steps; a reset returns a slot's states to the root and a finished slot keeps its
     states.  results() report the beam's own scores and order (a stream is never finalised: `stable` keeps its meaning);
-    bias_states() -> int32 [slots beam], for a caller that wants context.finalize(scores, states) at a stream's end."""
+    bias_states() -> int32 [slots beam], for a caller that wants context.finalize(scores, states) at a stream's end.
+
+    lm=lm.NgramLM: the LM steps, as BeamJoint takes it; a reset returns a slot's states to state 0 (the sentence start) and a
+    finished slot keeps its states.  lm_states() -> int32 [slots beam], for lm.finalize(scores, states) at a stream's end."""
 
     MAX_ROWS = 1024  # slots * beam: the prediction network's rows
 
@@ -1035,6 +1063,14 @@ class BeamStreamJoint(BeamJoint):
                     self.Jp, self.V, self.B, self.K, self.N, self.dtype, self._ws.data_ptr(), self._opts,
                     self.context.byref(pp.device), self._bias_states.data_ptr())
             _lib.check(st, "compute_rnnt_beam_stream_timed_step_biased" if self.token_times else "compute_rnnt_beam_stream_step_biased")
+            return self.parents, self.emitted
+        if self.lm is not None:
+            lib = _lib.load_lm()  # (include/rnnt_lm.h)
+            fn = lib.compute_rnnt_beam_stream_timed_step_lm if self.token_times else lib.compute_rnnt_beam_stream_step_lm
+            st = fn(pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(), ptr(topk_logits), ptr(topk_symbols), ptr(lse),
+                    self.Jp, self.V, self.B, self.K, self.N, self.dtype, self._ws.data_ptr(), self._opts,
+                    self.lm.byref(pp.device), self._bias_states.data_ptr())
+            _lib.check(st, "compute_rnnt_beam_stream_timed_step_lm" if self.token_times else "compute_rnnt_beam_stream_step_lm")
             return self.parents, self.emitted
         fn = lib.compute_rnnt_beam_stream_timed_step if self.token_times else lib.compute_rnnt_beam_stream_step
         st = fn(pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(), ptr(topk_logits), ptr(topk_symbols), ptr(lse),
