@@ -8,6 +8,7 @@
 #include "rnnt_common.h"
 #include "rnnt_lin.h"
 #include "rnnt_align.h"
+#include "rnnt_host.h"
 
 using namespace rnnt;
 
@@ -169,12 +170,6 @@ bool fill_loss_params(LossParams &p, const float *acts, float *grads, const int 
     return fill_params(p, acts, grads, labels, label_lengths, input_lengths, cost_scale, V, B, costs, workspace, o);
 }
 }  // namespace rnnt
-
-static rnntStatus_t from_hip(hipError_t e) {
-    if (e == hipSuccess) return RNNT_STATUS_SUCCESS;
-    if (e == hipErrorInvalidValue) return RNNT_STATUS_INVALID_VALUE;
-    return RNNT_STATUS_EXECUTION_FAILED;
-}
 
 extern "C" {
 
@@ -713,8 +708,6 @@ rnntStatus_t compute_rnnt_beam_results(int *hyps, int *hyp_lengths, float *score
 
 
 // The prediction-network step (include/rnnt.h).  Everything is checked before anything is enqueued.
-static bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-
 static rnntStatus_t check_prednet(const rnntPrednetBlock *blocks, int num_blocks, int embed_size, int vocab_size, int joint_size,
                                   int rows, const void *workspace, bool weights, const rnntOptions &o) {
     if (!blocks || !workspace) return RNNT_STATUS_INVALID_VALUE;
@@ -904,8 +897,6 @@ rnntStatus_t compute_rnnt_greedy_stream_feed_timed(const float *enc, int enc_fra
 }
 
 // The beam stream (include/rnnt.h).  enc_width 1: step and results do not reach W1 / b1, which follow the beam workspace.
-static bool aligned4(const void *p) { return (((uintptr_t)p) & 3) == 0; }
-
 static rnntStatus_t check_beam_stream(int max_chunk_frames, int slots, int beam, int max_hyp_len, int enc_width, int joint_size,
                                       int alphabet_size, int joint_dtype, const void *workspace, const rnntOptions &o,
                                       bool timed = false) {

@@ -4,14 +4,9 @@
 // before anything is enqueued, nothing is allocated, both launches go to the caller's stream.
 #include "../../include/rnnt_prune_ranges.h"
 #include "rnnt_prune_ranges.h"
+#include "rnnt_host.h"
 
 using namespace rnnt;
-
-static rnntStatus_t from_hip(hipError_t e) {
-    if (e == hipSuccess) return RNNT_STATUS_SUCCESS;
-    if (e == hipErrorInvalidValue) return RNNT_STATUS_INVALID_VALUE;
-    return RNNT_STATUS_EXECUTION_FAILED;
-}
 
 extern "C" {
 

@@ -5,17 +5,9 @@
 // the caller's stream.
 #include "../../include/rnnt_pruned_joint.h"
 #include "rnnt_pruned_joint.h"
+#include "rnnt_host.h"
 
 using namespace rnnt;
-
-static bool aligned4(const void *p) { return (((uintptr_t)p) & 3) == 0; }
-static bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-
-static rnntStatus_t from_hip(hipError_t e) {
-    if (e == hipSuccess) return RNNT_STATUS_SUCCESS;
-    if (e == hipErrorInvalidValue) return RNNT_STATUS_INVALID_VALUE;
-    return RNNT_STATUS_EXECUTION_FAILED;
-}
 
 // 1 <= s_range <= 64, minibatch * maxT * s_range < 2^31, joint_size a multiple of 64 up to 640
 static bool shape_ok(int maxT, int s_range, int minibatch, int joint_size) {

@@ -4,16 +4,9 @@
 // nothing is allocated, everything is enqueued on the caller's stream.
 #include "../../include/rnnt_simple.h"
 #include "rnnt_simple.h"
+#include "rnnt_host.h"
 
 using namespace rnnt;
-
-static bool aligned4(const void *p) { return (((uintptr_t)p) & 3) == 0; }
-
-static rnntStatus_t from_hip(hipError_t e) {
-    if (e == hipSuccess) return RNNT_STATUS_SUCCESS;
-    if (e == hipErrorInvalidValue) return RNNT_STATUS_INVALID_VALUE;
-    return RNNT_STATUS_EXECUTION_FAILED;
-}
 
 // 1 <= maxU <= 8192, minibatch * maxT * maxU < 2^31
 static bool shape_ok(int maxT, int maxU, int minibatch) {

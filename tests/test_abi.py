@@ -1,5 +1,5 @@
-"""CPU tests of the C-ABI boundary: the library builds/loads without a GPU, exports every symbol
-include/rnnt.h declares, and rejects bad arguments before touching the device."""
+"""CPU tests of the C-ABI boundary: every library of build.LIBRARIES builds/loads without a GPU and exports exactly the symbols
+its header declares, and libwarprnnt.so rejects bad arguments before touching the device."""
 import ctypes
 import os
 import re
@@ -8,6 +8,7 @@ import pytest
 
 import rnnt_speech_recognition_amd as pkg
 from rnnt_speech_recognition_amd import _lib
+from rnnt_speech_recognition_amd.build import LIBRARIES, lib_path
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -18,37 +19,85 @@ def lib():
     return _lib.load()
 
 
-def _declared_functions():
-    text = open(os.path.join(ROOT, "include", "rnnt.h")).read()
+# every library of build.LIBRARIES and what it exports: the entry points of its header, spelled out
+EXPORTS = {
+    "base": [
+        "get_warprnnt_version", "rnntGetStatusString", "get_workspace_size", "compute_rnnt_loss", "compute_rnnt_loss_fwd",
+        "compute_rnnt_loss_bwd", "compute_rnnt_loss_ex", "compute_rnnt_loss_flags", "compute_rnnt_loss_fastemit",
+        "get_joint_workspace_size", "compute_rnnt_joint_loss", "compute_rnnt_joint_loss_fwd", "compute_rnnt_joint_loss_bwd",
+        "compute_rnnt_joint_loss_bwd_fastemit", "compute_rnnt_joint_logits", "compute_rnnt_joint_net_logits",
+        "get_rnnt_joint_backward_rows", "get_joint_net_workspace_size", "compute_rnnt_joint_net_loss",
+        "compute_rnnt_joint_net_loss_fwd", "compute_rnnt_joint_net_loss_bwd", "compute_rnnt_joint_net_loss_bwd_fastemit",
+        "get_rnnt_greedy_workspace_size", "compute_rnnt_greedy_begin", "compute_rnnt_greedy_step", "get_rnnt_beam_workspace_size",
+        "compute_rnnt_beam_begin", "compute_rnnt_beam_step", "compute_rnnt_beam_results", "get_rnnt_prednet_workspace_size",
+        "compute_rnnt_prednet_begin", "compute_rnnt_prednet_step", "get_rnnt_encoder_workspace_size", "compute_rnnt_encoder_begin",
+        "compute_rnnt_encoder_run", "compute_rnnt_encoder_run_rows", "compute_rnnt_prednet_reset",
+        "get_rnnt_greedy_stream_workspace_size", "compute_rnnt_greedy_stream_begin", "compute_rnnt_greedy_stream_feed",
+        "get_rnnt_lstm_train_workspace_size", "compute_rnnt_lstm_train_fwd", "compute_rnnt_lstm_train_bwd",
+        "get_rnnt_beam_stream_workspace_size", "compute_rnnt_beam_stream_begin", "compute_rnnt_beam_stream_feed",
+        "compute_rnnt_beam_stream_step", "compute_rnnt_beam_stream_results", "get_rnnt_frontend_workspace_size",
+        "compute_rnnt_frontend_begin", "compute_rnnt_frontend_feed", "get_rnnt_align_workspace_size", "compute_rnnt_align_cells",
+        "compute_rnnt_align_path", "compute_rnnt_align", "compute_rnnt_greedy_step_timed", "compute_rnnt_greedy_stream_feed_timed",
+        "get_rnnt_beam_timed_workspace_size", "compute_rnnt_beam_timed_begin", "compute_rnnt_beam_timed_step",
+        "compute_rnnt_beam_timed_results", "get_rnnt_beam_stream_timed_workspace_size", "compute_rnnt_beam_stream_timed_begin",
+        "compute_rnnt_beam_stream_timed_feed", "compute_rnnt_beam_stream_timed_step", "compute_rnnt_beam_stream_timed_results",
+    ],
+    "bias": ["compute_rnnt_beam_step_biased", "compute_rnnt_beam_timed_step_biased", "compute_rnnt_beam_stream_step_biased",
+             "compute_rnnt_beam_stream_timed_step_biased"],
+    "mod": ["get_rnnt_modified_workspace_size", "compute_rnnt_loss_modified"],
+    "modalign": ["get_rnnt_modified_align_workspace_size", "compute_rnnt_modified_align_cells", "compute_rnnt_modified_align_path",
+                 "compute_rnnt_modified_align"],
+    "pruned": ["get_rnnt_pruned_workspace_size", "compute_rnnt_loss_pruned"],
+    "simple": ["get_rnnt_simple_workspace_size", "compute_rnnt_loss_simple"],
+    "prunedjoint": ["get_rnnt_pruned_joint_workspace_size", "compute_rnnt_joint_loss_pruned"],
+    "pruneranges": ["compute_rnnt_prune_ranges"],
+    "lm": ["compute_rnnt_beam_step_lm", "compute_rnnt_beam_timed_step_lm", "compute_rnnt_beam_stream_step_lm",
+           "compute_rnnt_beam_stream_timed_step_lm"],
+}
+
+
+def _loader(name):
+    """The public entry point of a library: _lib.load() for the base library, _lib.load_<name>() for an extension."""
+    return getattr(_lib, "load" if name == "base" else "load_" + name)
+
+
+def test_every_library_of_the_build_table_is_covered():
+    assert list(EXPORTS) == list(LIBRARIES) == list(_lib.SIGNATURES)
+
+
+@pytest.mark.parametrize("name", list(EXPORTS))
+def test_header_binding_and_library_agree(name):
+    """The functions the library's header declares are the keys of its binding table -- what _lib binds -- and the list above,
+    and the library defines every one of them."""
+    text = open(os.path.join(ROOT, "include", LIBRARIES[name].header)).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\([^;{]*\)\s*;", text)))
+    declared = sorted(set(re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\([^;{]*\)\s*;", text)))
+    assert declared == sorted(_lib.SIGNATURES[name]) == sorted(EXPORTS[name])
+    assert len(set(EXPORTS[name])) == len(EXPORTS[name])
+    pkg.build()
+    lib = _loader(name)()
+    for symbol in declared:
+        assert hasattr(lib, symbol), symbol
+        assert ctypes.cast(getattr(lib, symbol), ctypes.c_void_p).value
 
 
-def test_header_and_binding_agree():
-    assert _declared_functions() == sorted(_lib.SYMBOLS)
-
-
-def test_exports_every_declared_symbol(lib):
-    for name in _declared_functions():
-        assert hasattr(lib, name), name
-        assert ctypes.cast(getattr(lib, name), ctypes.c_void_p).value
-
-
-def test_dynamic_symbol_table_is_the_abi_and_nothing_else(lib):
-    """The library is built with -fvisibility=hidden: its dynamic symbol table holds the entry points of include/rnnt.h and,
-    besides them, only what the HIP toolchain itself emits for device code -- the kernel handles (mangled, inside namespace
-    rnnt) and the __hip_cuid_* translation-unit tags.  No host-side helper (validate, run_forward, rnnt::launch_* ...) is
-    exported, so nothing of this library can be interposed in a TensorFlow / PyTorch process."""
+@pytest.mark.parametrize("name", list(EXPORTS))
+def test_dynamic_symbol_table_is_the_abi_and_nothing_else(name):
+    """Every library is built with -fvisibility=hidden (the extensions with a version script besides): its dynamic symbol table
+    holds the entry points of its header and, besides them, only what the HIP toolchain itself emits for device code -- the
+    kernel handles (mangled, inside namespace rnnt) and the __hip_cuid_* translation-unit tags.  No host-side helper (validate,
+    run_forward, rnnt::launch_* ...) is exported, so nothing of a library can be interposed in a TensorFlow / PyTorch process,
+    and no entry point is defined twice in a process that loads several of them."""
     import shutil
     import subprocess
 
-    nm = shutil.which("nm")
-    if nm is None:
-        pytest.skip("binutils nm not available")
-    out = subprocess.run([nm, "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or "/opt/rocm/llvm/bin/llvm-nm"  # (the ROCm toolchain that built it has one)
+    assert os.path.exists(nm), "neither binutils nm nor llvm-nm found: the export table cannot be checked"
+    pkg.build()
+    out = subprocess.run([nm, "-D", "--defined-only", lib_path(name)], check=True, capture_output=True, text=True).stdout
     names = [ln.split()[-1] for ln in out.splitlines() if ln.strip()]
     plain = sorted(n for n in names if not n.startswith("_Z") and not n.startswith("__hip_cuid_"))
-    assert plain == sorted(_lib.SYMBOLS)
+    assert plain == sorted(EXPORTS[name])
     for n in names:
         if n.startswith("_Z"):
             assert n.startswith("_ZN4rnnt") and "kernel" in n and "launch" not in n and "device_stub" not in n, n
@@ -137,11 +186,12 @@ def test_python_surface_fails_loudly_on_cpu_tensors(lib):
         fn(torch.ones(1, 1), acts, torch.tensor([4]), torch.tensor([1]))
 
 
-def test_missing_library_is_an_error(monkeypatch, tmp_path):
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "libwarprnnt.so"))
-    with pytest.raises(_lib.RNNTLibraryError):
-        _lib.load()
+@pytest.mark.parametrize("name", list(EXPORTS))
+def test_missing_library_is_an_error(name, monkeypatch, tmp_path):
+    monkeypatch.delitem(_lib._libs, name, raising=False)
+    monkeypatch.setitem(_lib._PATHS, name, str(tmp_path / os.path.basename(lib_path(name))))
+    with pytest.raises(_lib.RNNTLibraryError, match="no eager fallback"):
+        _loader(name)()
 
 
 def test_reduced_lengths_matches_reference_ceil():

@@ -3,8 +3,6 @@ tests/modified_align_cases.py against brute force, the torch mirror of alignment
 no device -- the `topology` option, the header, the symbols and the exports of libwarprnnt_modalign.so, and the argument
 validation of its entry points."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -203,42 +201,6 @@ def test_align_joint_modified_equals_alignment_of_the_cell_logits():
 
 
 # ---- the ABI ------------------------------------------------------------------------------------------------------------
-FOUR = ["compute_rnnt_modified_align", "compute_rnnt_modified_align_cells", "compute_rnnt_modified_align_path",
-        "get_rnnt_modified_align_workspace_size"]
-
-
-def test_symbols_exist(lib):
-    """include/rnnt_modified_align.h declares the four entry points, _lib.MODALIGN_SYMBOLS binds them and
-    libwarprnnt_modalign.so defines them."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(root, "include", "rnnt_modified_align.h")).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\([^;{]*\)\s*;", text)))
-    assert declared == sorted(_lib.MODALIGN_SYMBOLS) == FOUR
-    for name in declared:
-        assert ctypes.cast(getattr(lib, name), ctypes.c_void_p).value
-
-
-def test_extension_library_exports_its_four_entry_points_alone():
-    """libwarprnnt_modalign.so (csrc/rnnt_modalign.map): besides the four entry points only what the HIP toolchain emits for
-    device code."""
-    import shutil
-    import subprocess
-
-    from rnnt_speech_recognition_amd.build import MODALIGN_LIB_PATH
-
-    nm = shutil.which("nm")
-    if nm is None:
-        pytest.skip("binutils nm not available")
-    pkg.build()
-    out = subprocess.run([nm, "-D", "--defined-only", MODALIGN_LIB_PATH], check=True, capture_output=True, text=True).stdout
-    names = [ln.split()[-1] for ln in out.splitlines() if ln.strip()]
-    plain = sorted(n for n in names if not n.startswith("_Z") and not n.startswith("__hip_cuid_"))
-    assert plain == sorted(_lib.MODALIGN_SYMBOLS)
-    for n in names:
-        if n.startswith("_Z"):
-            assert n.startswith("_ZN4rnnt") and "kernel" in n, n
-
-
 def test_workspace_size(lib):
     n = _lib.modified_align_workspace_bytes(600, 150, 32)
     assert n % 256 == 0

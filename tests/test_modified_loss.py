@@ -3,8 +3,6 @@ the path sum and finite differences, and check what needs no device -- the ABI, 
 compute_rnnt_loss_modified and the Python surface's `topology` option."""
 import ctypes
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -89,36 +87,6 @@ def test_more_labels_than_frames_is_infeasible():
 
 
 # ---- the ABI ------------------------------------------------------------------------------------------------------------
-def test_symbols_exist(lib):
-    """include/rnnt_modified.h declares the two entry points, _lib.MOD_SYMBOLS binds them and libwarprnnt_mod.so defines them."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(root, "include", "rnnt_modified.h")).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\([^;{]*\)\s*;", text)))
-    assert declared == sorted(_lib.MOD_SYMBOLS) == ["compute_rnnt_loss_modified", "get_rnnt_modified_workspace_size"]
-    for name in declared:
-        assert ctypes.cast(getattr(lib, name), ctypes.c_void_p).value
-
-
-def test_extension_library_exports_its_two_entry_points_alone():
-    """libwarprnnt_mod.so (csrc/rnnt_mod.map): besides the two entry points only what the HIP toolchain emits for device code."""
-    import shutil
-    import subprocess
-
-    from rnnt_speech_recognition_amd.build import MOD_LIB_PATH
-
-    nm = shutil.which("nm")
-    if nm is None:
-        pytest.skip("binutils nm not available")
-    pkg.build()
-    out = subprocess.run([nm, "-D", "--defined-only", MOD_LIB_PATH], check=True, capture_output=True, text=True).stdout
-    names = [ln.split()[-1] for ln in out.splitlines() if ln.strip()]
-    plain = sorted(n for n in names if not n.startswith("_Z") and not n.startswith("__hip_cuid_"))
-    assert plain == sorted(_lib.MOD_SYMBOLS)
-    for n in names:
-        if n.startswith("_Z"):
-            assert n.startswith("_ZN4rnnt") and "kernel" in n, n
-
-
 def test_workspace_size(lib):
     n = _lib.modified_workspace_bytes(600, 150, 32)
     assert n % 256 == 0

@@ -3,8 +3,6 @@ against the path sum, finite differences and the full-lattice oracles, the torch
 rnnt_speech_recognition_amd.pruning against the restatement, and check what needs no device: the ABI and the argument validation."""
 import ctypes
 import itertools
-import os
-import re
 
 import numpy as np
 import pytest
@@ -237,34 +235,6 @@ def test_prune_joint_inputs():
 
 
 # ---- the ABI ------------------------------------------------------------------------------------------------------------
-def test_symbols_exist(lib):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(root, "include", "rnnt_pruned.h")).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\([^;{]*\)\s*;", text)))
-    assert declared == sorted(_lib.PRUNED_SYMBOLS) == ["compute_rnnt_loss_pruned", "get_rnnt_pruned_workspace_size"]
-    for name in declared:
-        assert ctypes.cast(getattr(lib, name), ctypes.c_void_p).value
-
-
-def test_extension_library_exports_its_two_entry_points_alone():
-    import shutil
-    import subprocess
-
-    from rnnt_speech_recognition_amd.build import PRUNED_LIB_PATH
-
-    nm = shutil.which("nm")
-    if nm is None:
-        pytest.skip("binutils nm not available")
-    pkg.build()
-    out = subprocess.run([nm, "-D", "--defined-only", PRUNED_LIB_PATH], check=True, capture_output=True, text=True).stdout
-    names = [ln.split()[-1] for ln in out.splitlines() if ln.strip()]
-    plain = sorted(n for n in names if not n.startswith("_Z") and not n.startswith("__hip_cuid_"))
-    assert plain == sorted(_lib.PRUNED_SYMBOLS)
-    for n in names:
-        if n.startswith("_Z"):
-            assert n.startswith("_ZN4rnnt") and "kernel" in n, n
-
-
 def test_workspace_size(lib):
     n = _lib.pruned_workspace_bytes(600, 5, 32)
     assert n % 256 == 0
