@@ -192,14 +192,23 @@ SIGNATURES = {
     "pruneranges": {"compute_rnnt_prune_ranges": [vp, vp, vp, ci, ci, vp, opt]},
     "lm": {s + "_lm": _BASE[s] + [ctypes.POINTER(rnntLmGraph), vp] for s in _BEAM_STEPS},
 }
-# the libraries of build.MORE_LIBRARIES, in the same form (a second table for the reason given there)
+# the libraries of build.MORE_LIBRARIES, in the same form (a second table for the reason given there).  Both named tables are
+# frozen by the tests that pin them: a new library's row joins the merged table (_ALL_SIGNATURES) below.
 MORE_SIGNATURES = {
     "tdt": {
         "get_rnnt_tdt_workspace_size": [ci, ci, ci, ci, sz],
         "compute_rnnt_loss_tdt": [vp] * 6 + [ci, ctypes.POINTER(ci), ci, cf, ci, vp, vp, opt],
     },
 }
-_ALL_SIGNATURES = {**SIGNATURES, **MORE_SIGNATURES}
+_ALL_SIGNATURES = {
+    **SIGNATURES,
+    **MORE_SIGNATURES,
+    "tdtgreedy": {
+        "get_rnnt_tdt_greedy_workspace_size": [ci] * 6 + [sz],
+        "compute_rnnt_tdt_greedy_begin": [vp] * 5 + [ci, ci, ctypes.POINTER(ci), ci, ci, ci, ci, vp, opt],
+        "compute_rnnt_tdt_greedy_step": [vp] * 4 + [ci] + [vp] * 5 + [ci] * 5 + [vp, opt],
+    },
+}
 _RESTYPES = {"rnntGetStatusString": ctypes.c_char_p}
 del vp, ci, cu, cf, opt, sz, blk
 SYMBOLS, BIAS_SYMBOLS, LM_SYMBOLS = list(SIGNATURES["base"]), list(SIGNATURES["bias"]), list(SIGNATURES["lm"])
@@ -210,7 +219,7 @@ class RNNTLibraryError(RuntimeError):
 
 
 def _load(name: str):
-    """Load one library of build.LIBRARIES / MORE_LIBRARIES (once) and bind its row of SIGNATURES / MORE_SIGNATURES on it.
+    """Load one library of build.ALL_LIBRARIES (once) and bind its row of _ALL_SIGNATURES on it.
     Raises RNNTLibraryError loudly when it is absent, does not load or lacks a symbol: there is no fallback."""
     if name in _libs:
         return _libs[name]
@@ -282,6 +291,11 @@ def load_pruneranges():
 def load_tdt():
     """libwarprnnt_tdt.so: the token-and-duration (TDT) transducer loss, include/rnnt_tdt.h."""
     return _load("tdt")
+
+
+def load_tdtgreedy():
+    """libwarprnnt_tdtgreedy.so: batched greedy decoding of the TDT transducer, include/rnnt_tdt_greedy.h."""
+    return _load("tdtgreedy")
 
 
 def status_string(status: int) -> str:
@@ -401,3 +415,9 @@ def simple_workspace_bytes(maxT: int, maxU: int, minibatch: int) -> int:
 
 def tdt_workspace_bytes(maxT: int, maxU: int, minibatch: int, num_durations: int) -> int:
     return _size(load_tdt(), "get_rnnt_tdt_workspace_size", maxT, maxU, minibatch, num_durations)
+
+
+def tdt_greedy_workspace_bytes(maxT: int, minibatch: int, joint_size: int, alphabet_size: int, num_durations: int,
+                               joint_dtype: int) -> int:
+    return _size(load_tdtgreedy(), "get_rnnt_tdt_greedy_workspace_size", maxT, minibatch, joint_size, alphabet_size, num_durations,
+                 joint_dtype)

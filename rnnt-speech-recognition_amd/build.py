@@ -52,13 +52,21 @@ LIBRARIES = {
     # n-gram LM shallow fusion in the beam searches: built as "bias" is
     "lm": Library("rnnt_lm.h", ("beam_lm_kernels.hip", "rnnt_lm_entrypoint.hip"), _BASE_KERNELS, "rnnt_lm.map"),
 }
-# More rows of the same table.  tests/test_abi.py pins list(LIBRARIES) to its own nine names, so a library added since lives here
-# until that test lists it too; everything below works over both tables (ALL_LIBRARIES).
+# More rows of the same table.  tests/test_abi.py pins list(LIBRARIES) to its own nine names and tests/test_abi_tdt.py pins
+# list(MORE_LIBRARIES) to ["tdt"]: both named tables are frozen.  A new library joins the merged table (ALL_LIBRARIES) below, which
+# is what everything else works over.
 MORE_LIBRARIES = {
     # the token-and-duration (TDT) transducer loss on materialised logits
     "tdt": Library("rnnt_tdt.h", ("rnnt_tdt_kernels.hip", "rnnt_tdt_entrypoint.hip"), (), "rnnt_tdt.map"),
 }
-ALL_LIBRARIES = {**LIBRARIES, **MORE_LIBRARIES}
+ALL_LIBRARIES = {
+    **LIBRARIES,
+    **MORE_LIBRARIES,
+    # batched greedy decoding of the TDT transducer: its own step and update kernels on the greedy decoder's prepare path and
+    # per-hypothesis joint; built as "bias" is
+    "tdtgreedy": Library("rnnt_tdt_greedy.h", ("tdt_greedy_kernels.hip", "rnnt_tdt_greedy_entrypoint.hip"), _BASE_KERNELS,
+                         "rnnt_tdt_greedy.map"),
+}
 
 
 def lib_path(name: str) -> str:
@@ -75,6 +83,7 @@ PRUNEDJOINT_LIB_PATH = lib_path("prunedjoint")
 PRUNERANGES_LIB_PATH = lib_path("pruneranges")
 LM_LIB_PATH = lib_path("lm")
 TDT_LIB_PATH = lib_path("tdt")
+TDTGREEDY_LIB_PATH = lib_path("tdtgreedy")
 # -fvisibility=hidden: the library exports exactly the entry points include/rnnt.h marks RNNT_API (tests/test_abi.py)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-inline-asm"]
 # per-source extras.  -fno-slp-vectorize: no packed-f32 instructions (v_pk_fma_f32 ...) from the compiler -- in the linear sweeps
@@ -83,7 +92,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 # HBM-bound cell kernels of rnnt_kernels.hip keep the vectoriser (the op at config 5's shape: 16.4 against 17.0 ms).
 _NO_SLP = ["-fno-slp-vectorize"]
 EXTRA_FLAGS = {"rnnt_lin_kernels.hip": _NO_SLP, "joint_kernels.hip": _NO_SLP, "joint_f16_kernels.hip": _NO_SLP, "dense_kernels.hip": _NO_SLP,
-               "greedy_kernels.hip": _NO_SLP, "beam_kernels.hip": _NO_SLP, "beam_bias_kernels.hip": _NO_SLP,
+               "greedy_kernels.hip": _NO_SLP, "tdt_greedy_kernels.hip": _NO_SLP, "beam_kernels.hip": _NO_SLP, "beam_bias_kernels.hip": _NO_SLP,
                "beam_lm_kernels.hip": _NO_SLP,
                "prednet_kernels.hip": _NO_SLP, "encoder_kernels.hip": _NO_SLP, "lstm_train_kernels.hip": _NO_SLP,
                "rnnt_pruned_joint_kernels.hip": _NO_SLP}
@@ -112,7 +121,7 @@ def _compile_one(args):
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    """Compile every source of LIBRARIES and MORE_LIBRARIES once (one hipcc per source, in parallel) and link each library from the
+    """Compile every source of ALL_LIBRARIES once (one hipcc per source, in parallel) and link each library from the
     objects its entry names, the extensions first and libwarprnnt.so last (needs_build() goes by the oldest of them).  Returns the path of
     libwarprnnt.so."""
     if not force and not needs_build():

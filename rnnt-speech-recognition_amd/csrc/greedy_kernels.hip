@@ -29,6 +29,7 @@
 // kExpTabLimit) when this hypothesis's enc_proj row or pred_proj row leaves the table range -- exactly when the single-hypothesis
 // logits call would raise its flag.  The h / r form depends on W2 alone and is the same for every hypothesis.
 #include "rnnt_decode.h"
+#include "greedy_common.h"  // GreedyLayout, make_greedy_layout, greedy_bind
 
 #include <limits.h>
 #include <math.h>
@@ -225,13 +226,7 @@ __global__ __launch_bounds__(256) void greedy_update_timed_kernel(const GreedyAr
 // host side
 // ---------------------------------------------------------------------------------------------
 bool joint_dtype_supported(int joint_dtype, int J, int V);
-size_t joint_w2_image_bytes(int J, int V);
 hipError_t launch_joint_w2_image(const float *W2, const float *b2, int J, int V, float *tflag, void *W2s, hipStream_t s);
-
-struct GreedyLayout {
-    size_t st, pm, ps, pi, rowflag, expE, encraw, img, btab, tflag, total;
-    int NC, NS, DT;
-};
 
 // DT of the step kernel for (joint_dtype, J, V), or -1 when the shape is not taken: joint_dtype 0 on the shapes of the f32-grade
 // joint (joint_dtype_supported), joint_dtype 1 on J a multiple of 128 up to 640 and 1 <= V <= 8192 (the vocabulary is padded to
@@ -240,42 +235,6 @@ int greedy_dt(int joint_dtype, int J, int V) {
     if (joint_dtype == 0) return joint_dtype_supported(0, J, V) ? (J > 640 ? 2 : 0) : -1;
     if (joint_dtype == 1) return (J >= 128 && J <= 640 && J % 128 == 0 && V >= 1 && V <= 8192) ? 1 : -1;
     return -1;
-}
-
-static bool make_greedy_layout(int T, int B, int J, int V, int joint_dtype, GreedyLayout &L) {
-    L.DT = greedy_dt(joint_dtype, J, V);
-    if (L.DT < 0 || T <= 0 || B <= 0) return false;
-    if ((unsigned long long)B * T * J >= (1ull << 31)) return false;
-    L.NC = (V + 31) / 32;
-    L.NS = (L.NC + kGrWaves - 1) / kGrWaves;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
-    L.st = take((size_t)B * sizeof(GreedyState));
-    L.pm = take((size_t)L.NS * B * sizeof(float));
-    L.ps = take((size_t)L.NS * B * sizeof(float));
-    L.pi = take((size_t)L.NS * B * sizeof(int));
-    L.rowflag = take((size_t)B * T * sizeof(int));
-    L.expE = take((size_t)B * T * J * sizeof(float));
-    L.encraw = take((size_t)B * T * J * sizeof(float));
-    L.img = take(L.DT == 1 ? (size_t)L.NC * 32 * J * sizeof(gf16) : joint_w2_image_bytes(J, V));
-    L.btab = take((size_t)L.NC * 32 * sizeof(float));
-    L.tflag = take(256 + 1024);  // joint_prep_kernel's flag words + b2s (64 words per tile, up to 4 tiles)
-    L.total = off;
-    return true;
-}
-
-static void greedy_bind(GreedyArgs &a, const GreedyLayout &L, void *workspace) {
-    char *ws = (char *)workspace;
-    a.st = (GreedyState *)(ws + L.st);
-    a.part_m = (float *)(ws + L.pm), a.part_s = (float *)(ws + L.ps), a.part_i = (int *)(ws + L.pi);
-    a.rowflag = (int *)(ws + L.rowflag);
-    a.expE = (float *)(ws + L.expE), a.encraw = (float *)(ws + L.encraw);
-    a.img = (gf16 *)(ws + L.img), a.btab = (float *)(ws + L.btab), a.tflag = (const float *)(ws + L.tflag);
-    a.NC = L.NC, a.NS = L.NS;
 }
 
 hipError_t greedy_workspace_bytes(int T, int B, int J, int V, int joint_dtype, size_t *bytes) {

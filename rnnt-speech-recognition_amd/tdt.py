@@ -1,5 +1,6 @@
-"""The token-and-duration (TDT) transducer loss (include/rnnt_tdt.h compute_rnnt_loss_tdt, libwarprnnt_tdt.so) and a greedy TDT
-decoder.
+"""The token-and-duration (TDT) transducer loss (include/rnnt_tdt.h compute_rnnt_loss_tdt, libwarprnnt_tdt.so) and greedy TDT
+decoding: batched (TDTGreedyJoint / tdt_greedy_search_batch on include/rnnt_tdt_greedy.h, libwarprnnt_tdtgreedy.so) and as a host
+loop over one utterance (tdt_greedy_decode).
 
 The joint of a TDT model emits V token logits and D duration logits per lattice cell: acts [B, T, U, V + D].  An edge of the lattice
 consumes d frames, d from `durations`; tokens and durations have a log-softmax each; `sigma` (>= 0) is subtracted from every token
@@ -21,6 +22,7 @@ import math
 import torch
 
 from . import _lib
+from . import joint as _joint
 from .loss import _as_i32
 
 MAX_DURATIONS = 8  # include/rnnt_tdt.h: 1 <= D <= 8
@@ -251,7 +253,10 @@ def tdt_greedy_decode(logits_fn, T: int, durations, blank_label: int = 0, max_sy
     logits_fn(t, tokens) -> [V + D] logits of frame t after the tokens emitted so far (the joint of the caller's model).  The token is
     the argmax of the first V entries, the duration d the one at the argmax of the last D.  A non-blank token is appended.  A blank
     with d == 0 advances by one frame (it would not move otherwise), and so does the max_symbols_per_frame-th emission in a row on
-    one frame with d == 0.  Then t += d, until t >= T (the last jump may pass T)."""
+    one frame with d == 0.  Then t += d, until t >= T (the last jump may pass T).
+
+    One call of logits_fn and one host read per decision, one utterance at a time: tdt_greedy_search_batch is the same rule for a
+    whole batch with the joint, both argmaxes and the state update in the library."""
     dur = check_durations(durations)
     if int(max_symbols_per_frame) < 1:
         raise ValueError(f"max_symbols_per_frame must be at least 1, got {max_symbols_per_frame!r}")
@@ -276,3 +281,258 @@ def tdt_greedy_decode(logits_fn, T: int, durations, blank_label: int = 0, max_sy
             on_frame = 0
         t += d
     return tokens, frames
+
+
+# ---- batched greedy decoding --------------------------------------------------------------------------------------------
+CHECK_EVERY = 32  # decode steps between two reads of the all-done word (the only host reads of the loop)
+LAST_STEPS = 0    # decode steps the last tdt_greedy_search_batch took (timing tools)
+_WORKSPACES = {}  # (device, stream) -> the workspace of the last batched decode there
+
+
+def _cell_logits(joint, e, pred, pred_proj):
+    """One joint cell per row in torch: e [B, H] against pred [B, H], or against pred_proj [B, >= J] = pred @ W1 already."""
+    W1, b1, W2, b2 = (x.detach() for x in (joint.W1, joint.b1, joint.W2, joint.b2))
+    if pred_proj is None:
+        z = (e + pred.to(e.dtype)) @ W1 + b1
+    else:
+        z = e @ W1 + b1 + pred_proj[:, : W1.shape[1]].to(e.dtype)
+    return torch.tanh(z) @ W2 + b2
+
+
+class TDTGreedyJoint:
+    """The joint of the batched greedy TDT decoder (tdt_greedy_search_batch), with the interface of joint.GreedyJoint: one lattice
+    cell per hypothesis and step, the argmax of the token head and of the duration head, the two log-softmaxes of the decision and
+    the decoder state in one pass.
+
+    joint: any object with W1 [H, J], b1 [J], W2 [J, V + D], b2 [V + D] and blank_label -- the first V columns of W2 are the token
+    head, the last D = len(durations) the duration head.  A joint.JointLoss built with vocab_size = V + D qualifies, and its
+    .logits feed rnnt_loss_tdt.
+
+    Device tensors on shapes the library takes run the ENGINE (include/rnnt_tdt_greedy.h compute_rnnt_tdt_greedy_begin / _step):
+    the object owns the workspace and the joint-unit padding of W1 / b1 / W2, as GreedyJoint does.  CPU tensors, and shapes the
+    library refuses, run the same state machine in torch, vectorised over the batch.
+
+    begin(enc [B, T, H], frame_lengths [B], max_symbols [B] or None, max_per_frame >= 1, max_hyp_len) allocates the outputs (`hyps`
+    [B, max_hyp_len] zero-filled, `lengths`, `scores`, `emitted`, `all_done`); step(pred [B, H]) or step(pred_proj=[B, Jp]) advances
+    every hypothesis by one decision and returns `emitted` (the token per row, or -1).  all_done[0]: 0 running, 1 finished, 2 paused
+    on a full `hyps` buffer (grow_hyps() resumes them).  token_times=True: `frames` int32 [B, max_hyp_len] (-1 where no token is)
+    and `logp` [B, max_hyp_len] (0 there): per token the frame of its decision and the token plus the duration log-probability."""
+
+    def __init__(self, joint, durations, joint_dtype: str = "auto", token_times: bool = False):
+        self.joint = joint
+        self.durations = check_durations(durations)
+        self.token_times = bool(token_times)
+        self.blank = int(joint.blank_label)
+        W1, b1, W2, b2 = (x.detach() for x in (joint.W1, joint.b1, joint.W2, joint.b2))
+        J, R = W2.shape
+        self.D = len(self.durations)
+        self.V = R - self.D
+        if self.V < 2 or not 0 <= self.blank < self.V:
+            raise ValueError(f"TDTGreedyJoint: W2 must have V + D = V + {self.D} columns with V >= 2 and the blank inside [0, V), "
+                             f"got {R} columns and blank_label = {self.blank}")
+        self.engine = W2.is_cuda
+        if self.engine:
+            if joint_dtype == "auto":
+                joint_dtype = _joint._auto_joint_dtype(J, R)
+            try:
+                Jp, _ = _joint.padded_joint_shape(J, R, joint_dtype)
+            except ValueError:
+                self.engine = False
+        if self.engine:
+            self.dtype = _joint.JOINT_DTYPES[joint_dtype]
+            self.Jp = Jp
+            pad = lambda x, p: torch.nn.functional.pad(x.float(), p).contiguous()  # noqa: E731
+            self.W1, self.b1 = pad(W1, (0, Jp - J)), pad(b1, (0, Jp - J))
+            self.W2, self.b2 = pad(W2, (0, 0, 0, Jp - J)), b2.float().contiguous()
+        self._ws = None
+
+    # ---- engine
+    def begin(self, enc, frame_lengths, max_symbols, max_per_frame: int, max_hyp_len: int):
+        if int(max_per_frame) < 1:
+            raise ValueError(f"max_per_frame must be at least 1, got {max_per_frame!r}")
+        B, T = enc.shape[0], enc.shape[1]
+        dev = enc.device
+        self.B, self.T = B, T
+        self.hyps = torch.zeros(B, max_hyp_len, dtype=torch.int32, device=dev)
+        self.lengths = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.emitted = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        self.all_done = torch.zeros(1, dtype=torch.int32, device=dev)
+        frames = frame_lengths.to(device=dev, dtype=torch.int32)
+        maxsym = None if max_symbols is None else max_symbols.to(device=dev, dtype=torch.int32)
+        if not self.engine:
+            self._torch_begin(enc, frames, maxsym, int(max_per_frame))
+            return self._new_times(B, max_hyp_len, dev)
+        lib = _lib.load_tdtgreedy()
+        self.scores = torch.zeros(B, dtype=torch.float32, device=dev)
+        self._new_times(B, max_hyp_len, dev)
+        ep = (torch.matmul(enc.float(), self.W1) + self.b1).contiguous()
+        frames = frames.contiguous()
+        self._keep = (frames, maxsym.contiguous() if maxsym is not None else None)
+        dur = (ctypes.c_int * self.D)(*self.durations)
+        with torch.cuda.device(dev):
+            nbytes = _lib.tdt_greedy_workspace_bytes(T, B, self.Jp, self.V, self.D, self.dtype)
+            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
+                self._ws = _joint._new_workspace(nbytes, dev)
+            elif _joint._WORKSPACE_FILL is not None:
+                self._ws.fill_(int(_joint._WORKSPACE_FILL))
+            self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
+            ms = self._keep[1]
+            st = lib.compute_rnnt_tdt_greedy_begin(ep.data_ptr(), self._keep[0].data_ptr(), None if ms is None else ms.data_ptr(),
+                                                   self.W2.data_ptr(), self.b2.data_ptr(), self.Jp, self.V, dur, self.D, B,
+                                                   int(max_per_frame), self.dtype, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_tdt_greedy_begin")
+
+    def _new_times(self, B, max_hyp_len, dev):
+        self.frames = self.logp = None
+        if self.token_times:
+            self.frames = torch.full((B, max_hyp_len), -1, dtype=torch.int32, device=dev)
+            self.logp = torch.zeros(B, max_hyp_len, dtype=self.scores.dtype, device=dev)
+
+    def step(self, pred=None, logit_stats=None, *, pred_proj=None):
+        """pred [B, H]: the prediction network's output of every row -> emitted [B] (int32, -1 where nothing was emitted).
+        pred_proj [B, Jp] instead of pred: that output already through W1 (joint.PredictionStep); the step skips its matmul."""
+        if not self.engine:
+            return self._torch_step(pred, pred_proj)
+        pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _joint._projected_operand(pred_proj, self.Jp)
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        st = _lib.load_tdtgreedy().compute_rnnt_tdt_greedy_step(
+            pp.data_ptr(), self.hyps.data_ptr(), ptr(self.frames), ptr(self.logp), self.hyps.shape[1], self.lengths.data_ptr(),
+            self.scores.data_ptr(), self.emitted.data_ptr(), self.all_done.data_ptr(), ptr(logit_stats), self.Jp, self.V, self.D,
+            self.B, self.dtype, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_tdt_greedy_step")
+        return self.emitted
+
+    def grow_hyps(self):
+        """Double the hyps buffer (contents kept; `frames` and `logp` with it): paused hypotheses resume at the next step."""
+        h = self.hyps
+        self.hyps = torch.zeros(h.shape[0], 2 * h.shape[1], dtype=h.dtype, device=h.device)
+        self.hyps[:, : h.shape[1]] = h
+        if self.token_times:
+            f, l = self.frames, self.logp
+            self.frames = torch.full((h.shape[0], 2 * h.shape[1]), -1, dtype=f.dtype, device=f.device)
+            self.logp = torch.zeros(h.shape[0], 2 * h.shape[1], dtype=l.dtype, device=l.device)
+            self.frames[:, : h.shape[1]], self.logp[:, : h.shape[1]] = f, l
+
+    # ---- torch composition: the same state machine (tdt_greedy_update_kernel)
+    def _torch_begin(self, enc, frames, maxsym, max_per_frame):
+        B, T = enc.shape[0], enc.shape[1]
+        dev = enc.device
+        self._enc = enc
+        self.scores = torch.zeros(B, dtype=torch.promote_types(enc.dtype, torch.float32), device=dev)
+        self._Tb = frames.clamp(0, T).long()
+        self._maxsym = (torch.full((B,), 2**31 - 1, dtype=torch.long, device=dev) if maxsym is None else maxsym.clamp(min=0).long())
+        self._cap = max_per_frame
+        self._dur = torch.tensor(self.durations, dtype=torch.long, device=dev)
+        self._t = torch.zeros(B, dtype=torch.long, device=dev)
+        self._n = torch.zeros(B, dtype=torch.long, device=dev)
+        self._nf = torch.zeros(B, dtype=torch.long, device=dev)
+        self._done = (self._Tb == 0) | (self._maxsym == 0)
+
+    @staticmethod
+    def _head(x):
+        """argmax (lowest index on ties; -1 when no logit is above -inf: a NaN never wins), the logit there, logsumexp."""
+        clean = torch.where(torch.isnan(x), torch.full_like(x, _NEG_INF), x)
+        k = torch.argmax(clean, dim=-1)
+        M = x.gather(1, k[:, None])[:, 0]
+        none = ~(clean > _NEG_INF).any(dim=-1)
+        lse = torch.logsumexp(x, dim=-1)
+        lp = torch.where(none, torch.full_like(M, float("nan")), M - lse)
+        return torch.where(none, torch.full_like(k, -1), k), lp
+
+    def _torch_step(self, pred, pred_proj=None):
+        B, T, N, V = self.B, self.T, self.hyps.shape[1], self.V
+        ar = torch.arange(B, device=self._enc.device)
+        live = ~self._done & (self._n < self._maxsym.clamp(max=N))
+        e = self._enc[ar, self._t.clamp(0, T - 1)]
+        logits = _cell_logits(self.joint, e, pred, pred_proj)
+        k, lpt = self._head(logits[:, :V])
+        i, lpd = self._head(logits[:, V:])
+        lp = (lpt + lpd).to(self.scores.dtype)
+        self.scores = torch.where(live, self.scores + lp, self.scores)
+        d = torch.where(i >= 0, self._dur[i.clamp(min=0)], torch.ones_like(i))
+        emit = live & (k >= 0) & (k != self.blank)
+        pos = self._n.clamp(max=N - 1)[:, None]
+        self.hyps.scatter_(1, pos, torch.where(emit, k.to(torch.int32), self.hyps.gather(1, pos)[:, 0])[:, None])
+        if self.token_times:  # (the frame of this decision: before the cursor moves on)
+            self.frames.scatter_(1, pos, torch.where(emit, self._t.to(torch.int32), self.frames.gather(1, pos)[:, 0])[:, None])
+            self.logp.scatter_(1, pos, torch.where(emit, lp.to(self.logp.dtype), self.logp.gather(1, pos)[:, 0])[:, None])
+        self._n = self._n + emit.long()
+        self._nf = torch.where(emit, self._nf + 1, self._nf)
+        forced = (d == 0) & (~emit | (self._nf >= self._cap))  # a blank with d = 0, or the cap reached on this frame: one frame on
+        d = torch.where(forced, torch.ones_like(d), d)
+        self._nf = torch.where(live & (d > 0), torch.zeros_like(self._nf), self._nf)
+        self._t = torch.where(live, self._t + d, self._t)
+        self._done = self._done | (live & ((self._t >= self._Tb) | (self._n >= self._maxsym)))
+        self.lengths.copy_(self._n.to(torch.int32))
+        self.emitted.copy_(torch.where(emit, k, torch.full_like(k, -1)).to(torch.int32))
+        running, paused = ~self._done & (self._n < N), ~self._done & (self._n >= N)
+        self.all_done.copy_(torch.where(running.any(), 0, torch.where(paused.any(), 2, 1)).to(torch.int32).reshape(1))
+        return self.emitted
+
+
+@torch.no_grad()
+def tdt_greedy_search_batch(prediction, joint, enc: torch.Tensor, frame_lengths: torch.Tensor, durations, max_length=None,
+                            max_symbols_per_frame: int = 10, check_every: int = CHECK_EVERY, prediction_route: str = "torch",
+                            token_times: bool = False):
+    """Greedy TDT search over encoder outputs enc [B, T', H] with frame_lengths [B]: (hyps [B, N] int32 zero-padded, lengths [B],
+    scores [B][, frames [B, N], logp [B, N]]).  The loop of decoding.greedy_search_batch: one TDTGreedyJoint step per decision of
+    every utterance, one host read per `check_every` steps, grow_hyps when every running hypothesis has filled the buffer.
+
+    prediction: the prediction network (model.PredictionNetwork: an embedding and LSTM blocks), advanced for the rows that emitted
+    a token; prediction_route "engine" steps it in the library (joint.PredictionStep).  joint / durations: as for TDTGreedyJoint.
+    max_length: None (no bound), an int or a tensor [B]: tokens per utterance at most.  max_symbols_per_frame >= 1."""
+    global LAST_STEPS
+    from .decoding import _check_prediction, _pred_step, read_flag
+
+    _check_prediction(prediction_route)
+    B, T = enc.shape[0], enc.shape[1]
+    dev = enc.device
+    if max_length is None:
+        maxsym, N = None, T + 16  # no bound: the buffer grows when a hypothesis fills it
+    elif isinstance(max_length, torch.Tensor):
+        maxsym = max_length.to(device=dev, dtype=torch.int32).reshape(B)
+        N = max(1, read_flag(maxsym.max().reshape(1)))
+    else:
+        maxsym = torch.full((B,), int(max_length), dtype=torch.int32, device=dev)
+        N = max(1, int(max_length))
+    jg = TDTGreedyJoint(joint, durations, token_times=token_times)
+    done = lambda: (jg.hyps, jg.lengths, jg.scores, jg.frames, jg.logp) if token_times else (jg.hyps, jg.lengths, jg.scores)  # noqa: E731
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream) if enc.is_cuda else None
+    jg._ws = _WORKSPACES.get(key)  # the workspace of the last decode on this stream, when it is large enough
+    jg.begin(enc, frame_lengths, maxsym, int(max_symbols_per_frame), N)
+    if jg._ws is not None:
+        _WORKSPACES[key] = jg._ws
+    steps = 0
+    if prediction_route == "engine":  # the loop body is library calls alone: the joint step, then the prediction-network step
+        ps = _joint.PredictionStep(prediction, jg.W1 if jg.engine else joint.W1.detach())
+        pp = ps.begin(B)
+        while True:
+            emitted = jg.step(pred_proj=pp)
+            steps += 1
+            if steps % check_every == 0:
+                flag = read_flag(jg.all_done)
+                if flag == 1:
+                    break
+                if flag == 2:
+                    jg.grow_hyps()
+            pp = ps.step(emitted)
+        LAST_STEPS = steps
+        return done()
+    g, states = _pred_step(prediction, torch.zeros(B, dtype=torch.int32, device=dev), [None] * len(prediction.blocks))
+    while True:
+        emitted = jg.step(g)
+        steps += 1
+        if steps % check_every == 0:
+            flag = read_flag(jg.all_done)
+            if flag == 1:
+                break
+            if flag == 2:
+                jg.grow_hyps()
+        # rows that emitted a token advance their prediction network; the others keep their state
+        mask = emitted >= 0
+        g2, states2 = _pred_step(prediction, emitted.clamp(min=0), states)
+        g = torch.where(mask[:, None], g2, g)
+        states = [(torch.where(mask[None, :, None], h2, h), torch.where(mask[None, :, None], c2, c))
+                  for (h2, c2), (h, c) in zip(states2, states)]
+    LAST_STEPS = steps
+    return done()
