@@ -6,14 +6,14 @@ from __future__ import annotations
 import ctypes
 import os
 
-from .build import ALL_LIBRARIES, lib_path
+from .build import EVERY_LIBRARY, lib_path
 
 # dev knob: load an experimental build of the library instead (scripts/build_variant.sh)
 LIB_PATH = os.environ.get("RNNT_LIBWARPRNNT", lib_path("base"))
 # where each library of build.LIBRARIES is loaded from.  The bias and LM extensions go with the base library: a variant base library
 # is paired with the libwarprnnt_bias.so / libwarprnnt_lm.so beside it, never with the stock ones (they step each other's
 # workspaces).  Every other extension shares nothing with the base library (its own kernels and workspace): always this tree's build.
-_PATHS = {name: lib_path(name) for name in ALL_LIBRARIES}
+_PATHS = {name: lib_path(name) for name in EVERY_LIBRARY}
 if LIB_PATH != _PATHS["base"]:
     _PATHS["base"] = LIB_PATH
     for _n in ("bias", "lm"):
@@ -193,7 +193,7 @@ SIGNATURES = {
     "lm": {s + "_lm": _BASE[s] + [ctypes.POINTER(rnntLmGraph), vp] for s in _BEAM_STEPS},
 }
 # the libraries of build.MORE_LIBRARIES, in the same form (a second table for the reason given there).  Both named tables are
-# frozen by the tests that pin them: a new library's row joins the merged table (_ALL_SIGNATURES) below.
+# frozen by the tests that pin them, as is the merged table (_ALL_SIGNATURES) below: a new library's row joins _LATER_SIGNATURES.
 MORE_SIGNATURES = {
     "tdt": {
         "get_rnnt_tdt_workspace_size": [ci, ci, ci, ci, sz],
@@ -209,6 +209,16 @@ _ALL_SIGNATURES = {
         "compute_rnnt_tdt_greedy_step": [vp] * 4 + [ci] + [vp] * 5 + [ci] * 5 + [vp, opt],
     },
 }
+# the libraries of build.LATER_LIBRARIES (the three tables above are frozen by the tests that pin them; this one is open)
+_LATER_SIGNATURES = {
+    "tdtstream": {
+        "get_rnnt_tdt_greedy_stream_workspace_size": [ci] * 7 + [sz],
+        "compute_rnnt_tdt_greedy_stream_begin": [vp] * 4 + [ci, ci, ci, ctypes.POINTER(ci), ci, ci, ci, vp, opt],
+        "compute_rnnt_tdt_greedy_stream_feed": [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp] + [ci] * 6 + [vp, opt],
+        "compute_rnnt_tdt_greedy_stream_step": [vp] * 4 + [ci] + [vp] * 5 + [ci] * 5 + [vp, opt],
+    },
+}
+_EVERY_SIGNATURE = {**_ALL_SIGNATURES, **_LATER_SIGNATURES}
 _RESTYPES = {"rnntGetStatusString": ctypes.c_char_p}
 del vp, ci, cu, cf, opt, sz, blk
 SYMBOLS, BIAS_SYMBOLS, LM_SYMBOLS = list(SIGNATURES["base"]), list(SIGNATURES["bias"]), list(SIGNATURES["lm"])
@@ -219,20 +229,20 @@ class RNNTLibraryError(RuntimeError):
 
 
 def _load(name: str):
-    """Load one library of build.ALL_LIBRARIES (once) and bind its row of _ALL_SIGNATURES on it.
+    """Load one library of build.EVERY_LIBRARY (once) and bind its row of _EVERY_SIGNATURE on it.
     Raises RNNTLibraryError loudly when it is absent, does not load or lacks a symbol: there is no fallback."""
     if name in _libs:
         return _libs[name]
     path = _PATHS[name]
     if not os.path.exists(path):
         raise RNNTLibraryError(f"{path} not found: the HIP extension has not been built. Run scripts/build_rnnt.sh (or "
-                               f"__graft_entry__.build()). There is no eager fallback for include/{ALL_LIBRARIES[name].header}.")
+                               f"__graft_entry__.build()). There is no eager fallback for include/{EVERY_LIBRARY[name].header}.")
     try:
         lib = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
         raise RNNTLibraryError(f"failed to load {path}: {e}") from e
     variant = name == "base" and path != lib_path("base")  # an older revision (scripts/build_variant.sh) may lack the newer symbols
-    for symbol, argtypes in _ALL_SIGNATURES[name].items():
+    for symbol, argtypes in _EVERY_SIGNATURE[name].items():
         if not hasattr(lib, symbol):
             if variant:
                 continue
@@ -296,6 +306,11 @@ def load_tdt():
 def load_tdtgreedy():
     """libwarprnnt_tdtgreedy.so: batched greedy decoding of the TDT transducer, include/rnnt_tdt_greedy.h."""
     return _load("tdtgreedy")
+
+
+def load_tdtstream():
+    """libwarprnnt_tdtstream.so: streaming greedy decoding of the TDT transducer over slots, include/rnnt_tdt_stream.h."""
+    return _load("tdtstream")
 
 
 def status_string(status: int) -> str:
@@ -421,3 +436,9 @@ def tdt_greedy_workspace_bytes(maxT: int, minibatch: int, joint_size: int, alpha
                                joint_dtype: int) -> int:
     return _size(load_tdtgreedy(), "get_rnnt_tdt_greedy_workspace_size", maxT, minibatch, joint_size, alphabet_size, num_durations,
                  joint_dtype)
+
+
+def tdt_greedy_stream_workspace_bytes(max_chunk_frames: int, slots: int, enc_width: int, joint_size: int, alphabet_size: int,
+                                      num_durations: int, joint_dtype: int) -> int:
+    return _size(load_tdtstream(), "get_rnnt_tdt_greedy_stream_workspace_size", max_chunk_frames, slots, enc_width, joint_size,
+                 alphabet_size, num_durations, joint_dtype)

@@ -53,8 +53,8 @@ LIBRARIES = {
     "lm": Library("rnnt_lm.h", ("beam_lm_kernels.hip", "rnnt_lm_entrypoint.hip"), _BASE_KERNELS, "rnnt_lm.map"),
 }
 # More rows of the same table.  tests/test_abi.py pins list(LIBRARIES) to its own nine names and tests/test_abi_tdt.py pins
-# list(MORE_LIBRARIES) to ["tdt"]: both named tables are frozen.  A new library joins the merged table (ALL_LIBRARIES) below, which
-# is what everything else works over.
+# list(MORE_LIBRARIES) to ["tdt"]: both named tables are frozen, and so is the merged table (ALL_LIBRARIES) below
+# with the one row of its own.  A new library is a row of LATER_LIBRARIES further down.
 MORE_LIBRARIES = {
     # the token-and-duration (TDT) transducer loss on materialised logits
     "tdt": Library("rnnt_tdt.h", ("rnnt_tdt_kernels.hip", "rnnt_tdt_entrypoint.hip"), (), "rnnt_tdt.map"),
@@ -67,6 +67,15 @@ ALL_LIBRARIES = {
     "tdtgreedy": Library("rnnt_tdt_greedy.h", ("tdt_greedy_kernels.hip", "rnnt_tdt_greedy_entrypoint.hip"), _BASE_KERNELS,
                          "rnnt_tdt_greedy.map"),
 }
+# Later rows.  tests/test_abi_tdt_greedy.py pins list(ALL_LIBRARIES) too, so the three tables above are frozen as they stand; this one
+# is open: a new library is a new row here, and no test pins its keys.  EVERY_LIBRARY is what the build and the binding work over.
+LATER_LIBRARIES = {
+    # greedy decoding of the TDT transducer over a stream of chunks per slot: its own feed and update kernels on the greedy
+    # stream's projection and on the step kernel of "tdtgreedy", whose kernel object it links beside the base kernels'
+    "tdtstream": Library("rnnt_tdt_stream.h", ("tdt_stream_kernels.hip", "rnnt_tdt_stream_entrypoint.hip"),
+                         _BASE_KERNELS + ("tdt_greedy_kernels.hip",), "rnnt_tdt_stream.map"),
+}
+EVERY_LIBRARY = {**ALL_LIBRARIES, **LATER_LIBRARIES}
 
 
 def lib_path(name: str) -> str:
@@ -84,6 +93,7 @@ PRUNERANGES_LIB_PATH = lib_path("pruneranges")
 LM_LIB_PATH = lib_path("lm")
 TDT_LIB_PATH = lib_path("tdt")
 TDTGREEDY_LIB_PATH = lib_path("tdtgreedy")
+TDTSTREAM_LIB_PATH = lib_path("tdtstream")
 # -fvisibility=hidden: the library exports exactly the entry points include/rnnt.h marks RNNT_API (tests/test_abi.py)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-inline-asm"]
 # per-source extras.  -fno-slp-vectorize: no packed-f32 instructions (v_pk_fma_f32 ...) from the compiler -- in the linear sweeps
@@ -92,7 +102,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 # HBM-bound cell kernels of rnnt_kernels.hip keep the vectoriser (the op at config 5's shape: 16.4 against 17.0 ms).
 _NO_SLP = ["-fno-slp-vectorize"]
 EXTRA_FLAGS = {"rnnt_lin_kernels.hip": _NO_SLP, "joint_kernels.hip": _NO_SLP, "joint_f16_kernels.hip": _NO_SLP, "dense_kernels.hip": _NO_SLP,
-               "greedy_kernels.hip": _NO_SLP, "tdt_greedy_kernels.hip": _NO_SLP, "beam_kernels.hip": _NO_SLP, "beam_bias_kernels.hip": _NO_SLP,
+               "greedy_kernels.hip": _NO_SLP, "tdt_greedy_kernels.hip": _NO_SLP, "tdt_stream_kernels.hip": _NO_SLP, "beam_kernels.hip": _NO_SLP, "beam_bias_kernels.hip": _NO_SLP,
                "beam_lm_kernels.hip": _NO_SLP,
                "prednet_kernels.hip": _NO_SLP, "encoder_kernels.hip": _NO_SLP, "lstm_train_kernels.hip": _NO_SLP,
                "rnnt_pruned_joint_kernels.hip": _NO_SLP}
@@ -100,11 +110,11 @@ EXTRA_FLAGS = {"rnnt_lin_kernels.hip": _NO_SLP, "joint_kernels.hip": _NO_SLP, "j
 
 def _deps():
     files = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".map"))]
-    return files + [os.path.join(os.path.dirname(_HERE), "include", lib.header) for lib in ALL_LIBRARIES.values()]
+    return files + [os.path.join(os.path.dirname(_HERE), "include", lib.header) for lib in EVERY_LIBRARY.values()]
 
 
 def needs_build() -> bool:
-    libs = [lib_path(name) for name in ALL_LIBRARIES]
+    libs = [lib_path(name) for name in EVERY_LIBRARY]
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
@@ -121,7 +131,7 @@ def _compile_one(args):
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    """Compile every source of ALL_LIBRARIES once (one hipcc per source, in parallel) and link each library from the
+    """Compile every source of EVERY_LIBRARY once (one hipcc per source, in parallel) and link each library from the
     objects its entry names, the extensions first and libwarprnnt.so last (needs_build() goes by the oldest of them).  Returns the path of
     libwarprnnt.so."""
     if not force and not needs_build():
@@ -131,15 +141,15 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("hipcc not found: cannot build libwarprnnt.so (ROCm toolchain required)")
     os.makedirs(LIB_DIR, exist_ok=True)
     tag = f".tmp{os.getpid()}"  # several ranks may arrive here at once
-    sources = list(dict.fromkeys(s for lib in ALL_LIBRARIES.values() for s in lib.sources))
+    sources = list(dict.fromkeys(s for lib in EVERY_LIBRARY.values() for s in lib.sources))
     jobs = [(hipcc, os.path.join(CSRC, s), os.path.join(LIB_DIR, s[:-4] + tag + ".o"), verbose) for s in sources]
     try:
         from concurrent.futures import ThreadPoolExecutor
 
         with ThreadPoolExecutor(max_workers=len(jobs)) as ex:
             obj = dict(zip(sources, ex.map(_compile_one, jobs)))
-        for name in [n for n in ALL_LIBRARIES if n != "base"] + ["base"]:
-            lib = ALL_LIBRARIES[name]
+        for name in [n for n in EVERY_LIBRARY if n != "base"] + ["base"]:
+            lib = EVERY_LIBRARY[name]
             extra = ["-Wl,--version-script=" + os.path.join(CSRC, lib.version_script)] if lib.version_script else []
             tmp = lib_path(name) + tag
             cmd = [hipcc] + HIPCC_FLAGS + extra + [obj[s] for s in lib.borrowed + lib.sources] + ["-o", tmp]

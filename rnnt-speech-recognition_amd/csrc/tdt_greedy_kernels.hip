@@ -18,33 +18,12 @@
 // Workspace: the greedy workspace at alphabet_size = R, then the duration head's partials [NS][B] (max, sum, argmax) and the
 // duration set.  The token head's partials live where the greedy decoder keeps its own.
 #include "rnnt_decode.h"
-#include "greedy_common.h"
-
-#include <limits.h>
-#include <math.h>
+#include "tdt_greedy_common.h"  // TdtGreedyArgs, TdtGreedyLayout, the update kernel's body
 
 namespace rnnt {
 
-constexpr int kTdtGreedyMaxD = 8;
-
-struct TdtDurations {
-    int d[kTdtGreedyMaxD];
-};
-
-struct TdtGreedyArgs {
-    GreedyArgs g;  // V = R = Vt + D, NC / NS over R; part_m / part_s / part_i: the token head's partials
-    float *dpart_m, *dpart_s;  // [NS][B] the duration head's partials
-    int *dpart_i;
-    int *durset;  // [kTdtGreedyMaxD] the duration set
-    int Vt, D;
-};
-
 __global__ __launch_bounds__(64) void tdt_greedy_begin_kernel(int *durset, const TdtDurations dur) {
     if (threadIdx.x < kTdtGreedyMaxD) durset[threadIdx.x] = dur.d[threadIdx.x];
-}
-
-__device__ __forceinline__ bool tg_live(const GreedyState &s, const int max_hyp_len) {
-    return !s.done && s.n < min(s.maxsym, max_hyp_len);  // (a full hyps buffer pauses a hypothesis)
 }
 
 // one column into a running (max, argmax, sum) triple: the arithmetic of greedy_step_kernel's epilogue
@@ -141,103 +120,13 @@ __global__ __launch_bounds__(kGrWaves * 64) void tdt_greedy_step_kernel(const Td
 // ---------------------------------------------------------------------------------------------
 // update: one workgroup over all hypotheses
 // ---------------------------------------------------------------------------------------------
-// the NS partials of hypothesis b in slice order -> argmax (lowest index on ties), max, logsumexp in float64
-__device__ __forceinline__ void tg_head(const float *pm, const float *ps, const int *pi, const int NS, const int B, const int b, float &M,
-                                        int &k, double &lse) {
-    M = -INFINITY, k = INT_MAX;
-    for (int q = 0; q < NS; ++q) {
-        const float m = pm[(size_t)q * B + b];
-        const int i = pi[(size_t)q * B + b];
-        if (m > M || (m == M && i < k)) M = m, k = i;
-    }
-    double S = 0.0;
-    for (int q = 0; q < NS; ++q) {
-        const float s = ps[(size_t)q * B + b];
-        if (s > 0.f) S += (double)s * exp((double)pm[(size_t)q * B + b] - (double)M);
-    }
-    lse = (double)M + log(S);
-}
-
 __global__ __launch_bounds__(256) void tdt_greedy_update_kernel(const TdtGreedyArgs ta) {
-    const GreedyArgs &a = ta.g;
-    bool running = false, paused = false;
-    for (int b = threadIdx.x; b < a.B; b += 256) {
-        GreedyState s = a.st[b];
-        int em = -1;
-        if (tg_live(s, a.max_hyp_len)) {
-            float M, Md;
-            int k, i;
-            double lse, lsed;
-            tg_head(a.part_m, a.part_s, a.part_i, a.NS, a.B, b, M, k, lse);
-            tg_head(ta.dpart_m, ta.dpart_s, ta.dpart_i, a.NS, a.B, b, Md, i, lsed);
-            if (a.stats) {
-                float *st = a.stats + 4 * (size_t)b;
-                st[0] = M, st[1] = (float)lse, st[2] = Md, st[3] = (float)lsed;
-            }
-            const double lp = ((double)M - lse) + ((double)Md - lsed);
-            s.score += lp;
-            int d = (i >= 0 && i < ta.D) ? ta.durset[i] : 1;  // (a duration head without a finite logit: d = 1)
-            if (k == a.blank || k < 0 || k >= ta.Vt) {  // blank (or no finite token logit at all)
-                if (d == 0) d = 1;
-            } else {
-                const size_t o = (size_t)b * a.max_hyp_len + s.n;
-                a.hyps[o] = k;
-                if (a.hyp_frames) {  // (s.t: the frame of this decision, before the state moves on)
-                    a.hyp_frames[o] = s.t;
-                    a.hyp_logp[o] = (float)lp;
-                }
-                s.n += 1, s.nf += 1, em = k;
-                if (d == 0 && s.nf >= s.cap) d = 1;
-            }
-            if (d > 0) s.nf = 0;
-            s.t += d;  // (the last jump may pass Tb)
-            if (s.t >= s.Tb || s.n >= s.maxsym) s.done = 1;
-            a.st[b] = s;
-        }
-        a.emitted[b] = em;
-        a.hyp_lengths[b] = s.n;
-        a.scores[b] = (float)s.score;
-        if (!s.done) {
-            if (s.n < a.max_hyp_len) running = true;
-            else paused = true;
-        }
-    }
-    const int any_running = __syncthreads_or(running), any_paused = __syncthreads_or(paused);
-    if (threadIdx.x == 0) a.all_done[0] = any_running ? 0 : (any_paused ? 2 : 1);
+    tdt_greedy_update_body<false>(ta, nullptr);  // (tdt_greedy_common.h)
 }
 
 // ---------------------------------------------------------------------------------------------
-// host side
+// host side (the layout and its binding: tdt_greedy_common.h)
 // ---------------------------------------------------------------------------------------------
-struct TdtGreedyLayout {
-    GreedyLayout g;
-    size_t dpm, dps, dpi, durset, total;
-};
-
-static bool make_tdt_greedy_layout(int T, int B, int J, int Vt, int D, int joint_dtype, TdtGreedyLayout &L) {
-    if (Vt < 2 || D < 1 || D > kTdtGreedyMaxD) return false;
-    if (!make_greedy_layout(T, B, J, Vt + D, joint_dtype, L.g)) return false;
-    size_t off = L.g.total;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
-    L.dpm = take((size_t)L.g.NS * B * sizeof(float));
-    L.dps = take((size_t)L.g.NS * B * sizeof(float));
-    L.dpi = take((size_t)L.g.NS * B * sizeof(int));
-    L.durset = take(kTdtGreedyMaxD * sizeof(int));
-    L.total = off;
-    return true;
-}
-
-static void tdt_greedy_bind(TdtGreedyArgs &ta, const TdtGreedyLayout &L, void *workspace) {
-    char *ws = (char *)workspace;
-    greedy_bind(ta.g, L.g, workspace);
-    ta.dpart_m = (float *)(ws + L.dpm), ta.dpart_s = (float *)(ws + L.dps), ta.dpart_i = (int *)(ws + L.dpi);
-    ta.durset = (int *)(ws + L.durset);
-}
-
 hipError_t tdt_greedy_workspace_bytes(int T, int B, int J, int Vt, int D, int joint_dtype, size_t *bytes) {
     TdtGreedyLayout L;
     if (!make_tdt_greedy_layout(T, B, J, Vt, D, joint_dtype, L)) return hipErrorInvalidValue;
@@ -271,6 +160,14 @@ static hipError_t launch_tdt_step_dt(const TdtGreedyArgs &ta, size_t shm, hipStr
     return hipGetLastError();
 }
 
+// the step kernel alone (the stream's translation unit runs an update kernel of its own after it)
+hipError_t launch_tdt_greedy_step_kernel(const TdtGreedyArgs &ta, int DT, hipStream_t s) {
+    const size_t shm = (size_t)ta.g.J * 32 * sizeof(gf16) * (DT == 1 ? 1 : 2);
+    if (DT == 1) return launch_tdt_step_dt<1>(ta, shm, s);
+    if (DT == 0) return launch_tdt_step_dt<0>(ta, shm, s);
+    return launch_tdt_step_dt<2>(ta, shm, s);
+}
+
 // hyp_frames / hyp_logp: both given or both NULL
 hipError_t launch_tdt_greedy_step(const float *pred_proj, int *hyps, int *hyp_frames, float *hyp_logp, int max_hyp_len,
                                   int *hyp_lengths, float *scores, int *emitted, int *all_done, float *stats, int J, int Vt, int D,
@@ -285,11 +182,7 @@ hipError_t launch_tdt_greedy_step(const float *pred_proj, int *hyps, int *hyp_fr
     a.all_done = all_done, a.stats = stats;
     a.hyp_frames = hyp_frames, a.hyp_logp = hyp_logp;
     a.B = B, a.T = T, a.J = J, a.V = Vt + D, a.blank = blank, a.max_hyp_len = max_hyp_len;
-    hipError_t e;
-    const size_t shm = (size_t)J * 32 * sizeof(gf16) * (L.g.DT == 1 ? 1 : 2);
-    if (L.g.DT == 1) e = launch_tdt_step_dt<1>(ta, shm, s);
-    else if (L.g.DT == 0) e = launch_tdt_step_dt<0>(ta, shm, s);
-    else e = launch_tdt_step_dt<2>(ta, shm, s);
+    const hipError_t e = launch_tdt_greedy_step_kernel(ta, L.g.DT, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(tdt_greedy_update_kernel, dim3(1), dim3(256), 0, s, ta);
     return hipGetLastError();

@@ -503,14 +503,18 @@ class StreamingGreedyDecoder(_StreamingSlots):
         self.max_length = None if max_length is None else int(max_length)
         self.token_times = bool(token_times)
         with self._eval():
-            self.gj = GreedyStreamJoint(model.joint, token_times=True) if token_times else GreedyStreamJoint(model.joint)
+            self.gj = self._make_joint(model)
             dev = next(model.parameters()).device
             N = max(1, self.max_length) if self.max_length is not None else self.Te + 16
             self.gj.begin(S, self.Te, int(max_symbols_per_frame or 0), N, device=dev)
-            W1 = self.gj.W1 if self.gj.engine else model.joint.W1
+            W1 = self.gj.W1 if self.gj.engine else self.gj.joint.W1
             self.ps = PredictionStep(model.prediction, W1)
             self.pp = self.ps.begin(S)
         self.dev = self.gj.hyps.device
+
+    def _make_joint(self, model):
+        """The stream joint the decoder steps (a subclass decodes another kind of joint: tdt.StreamingTDTGreedyDecoder)."""
+        return GreedyStreamJoint(model.joint, token_times=True) if self.token_times else GreedyStreamJoint(model.joint)
 
     @torch.no_grad()
     def start(self, slots) -> None:
@@ -723,6 +727,9 @@ class StreamingTranscriber:
     of a StreamingBeamDecoder when `beam` is given.  The decoder is sized by the front end's max_rows; decoder_kwargs go to it
     (max_length, max_symbols_per_frame, check_every for greedy; max_length for beam).  context=biasing.ContextGraph (beam search
     only): contextual biasing, as StreamingBeamDecoder takes it; lm=lm.NgramLM (beam search only): LM shallow fusion, likewise.
+    tdt_durations=[...] (greedy only; together with beam: ValueError): the model is a token-and-duration transducer with that
+    duration set, and the decoder is a tdt.StreamingTDTGreedyDecoder (decoder_kwargs: joint, max_length, max_symbols_per_frame,
+    check_every).
 
     start(slots) starts a stream in the given slots of both; feed(audio [slots, N], samples [slots], final [slots]) (N <=
     max_chunk_samples; samples and final are host data) returns what the decoder's feed returns for the rows this audio
@@ -731,8 +738,11 @@ class StreamingTranscriber:
     features.running_mean_log_mel for it.  A stream's result is bitwise independent of how its audio was chunked."""
 
     def __init__(self, model, hp, sample_rate, slots: int, max_chunk_samples: int, beam: Optional[int] = None,
-                 norm: str = "running", context=None, lm=None, **decoder_kwargs):
+                 norm: str = "running", context=None, lm=None, tdt_durations=None, **decoder_kwargs):
         from .features import StreamingFrontEnd
+
+        if tdt_durations is not None and beam is not None:
+            raise ValueError("tdt_durations= is greedy decoding: there is no TDT beam search, build the StreamingTranscriber without beam=")
 
         if context is not None and beam is None:
             raise ValueError("context= needs beam search: build the StreamingTranscriber with beam=")
@@ -742,7 +752,11 @@ class StreamingTranscriber:
         dev = next(model.parameters()).device
         self.hp, self.sample_rate = hp, sample_rate
         self.front = StreamingFrontEnd(hp, sample_rate, slots, max_chunk_samples, int(model.encoder.reduce.factor), norm, device=dev)
-        if beam is None:
+        if tdt_durations is not None:
+            from .tdt import StreamingTDTGreedyDecoder
+
+            self.decoder = StreamingTDTGreedyDecoder(model, tdt_durations, slots, self.front.max_rows, **decoder_kwargs)
+        elif beam is None:
             self.decoder = StreamingGreedyDecoder(model, slots, self.front.max_rows, **decoder_kwargs)
         else:
             self.decoder = StreamingBeamDecoder(model, slots, self.front.max_rows, beam=beam, context=context, lm=lm, **decoder_kwargs)

@@ -1,6 +1,7 @@
 """The token-and-duration (TDT) transducer loss (include/rnnt_tdt.h compute_rnnt_loss_tdt, libwarprnnt_tdt.so) and greedy TDT
-decoding: batched (TDTGreedyJoint / tdt_greedy_search_batch on include/rnnt_tdt_greedy.h, libwarprnnt_tdtgreedy.so) and as a host
-loop over one utterance (tdt_greedy_decode).
+decoding: batched (TDTGreedyJoint / tdt_greedy_search_batch on include/rnnt_tdt_greedy.h, libwarprnnt_tdtgreedy.so), over live
+streams fed chunk by chunk (TDTGreedyStreamJoint / StreamingTDTGreedyDecoder on include/rnnt_tdt_stream.h, libwarprnnt_tdtstream.so)
+and as a host loop over one utterance (tdt_greedy_decode).
 
 The joint of a TDT model emits V token logits and D duration logits per lattice cell: acts [B, T, U, V + D].  An edge of the lattice
 consumes d frames, d from `durations`; tokens and durations have a log-softmax each; `sigma` (>= 0) is subtracted from every token
@@ -22,6 +23,7 @@ import math
 import torch
 
 from . import _lib
+from . import decoding as _decoding
 from . import joint as _joint
 from .loss import _as_i32
 
@@ -322,6 +324,7 @@ class TDTGreedyJoint:
         self.joint = joint
         self.durations = check_durations(durations)
         self.token_times = bool(token_times)
+        self._frame_base = None  # (the stream: frames of the chunks a slot has left behind)
         self.blank = int(joint.blank_label)
         W1, b1, W2, b2 = (x.detach() for x in (joint.W1, joint.b1, joint.W2, joint.b2))
         J, R = W2.shape
@@ -454,7 +457,8 @@ class TDTGreedyJoint:
         pos = self._n.clamp(max=N - 1)[:, None]
         self.hyps.scatter_(1, pos, torch.where(emit, k.to(torch.int32), self.hyps.gather(1, pos)[:, 0])[:, None])
         if self.token_times:  # (the frame of this decision: before the cursor moves on)
-            self.frames.scatter_(1, pos, torch.where(emit, self._t.to(torch.int32), self.frames.gather(1, pos)[:, 0])[:, None])
+            fr = self._t if self._frame_base is None else self._t + self._frame_base
+            self.frames.scatter_(1, pos, torch.where(emit, fr.to(torch.int32), self.frames.gather(1, pos)[:, 0])[:, None])
             self.logp.scatter_(1, pos, torch.where(emit, lp.to(self.logp.dtype), self.logp.gather(1, pos)[:, 0])[:, None])
         self._n = self._n + emit.long()
         self._nf = torch.where(emit, self._nf + 1, self._nf)
@@ -536,3 +540,149 @@ def tdt_greedy_search_batch(prediction, joint, enc: torch.Tensor, frame_lengths:
                   for (h2, c2), (h, c) in zip(states2, states)]
     LAST_STEPS = steps
     return done()
+
+
+# ---- streaming greedy decoding ------------------------------------------------------------------------------------------
+class TDTGreedyStreamJoint(TDTGreedyJoint):
+    """The joint of the streaming greedy TDT decoder (StreamingTDTGreedyDecoder): TDTGreedyJoint's step over `slots` streams whose
+    encoder frames arrive chunk by chunk, as joint.GreedyStreamJoint is GreedyJoint's.
+
+    Device tensors on shapes the library takes run the ENGINE (include/rnnt_tdt_stream.h compute_rnnt_tdt_greedy_stream_begin /
+    _feed / _step): the object owns the workspace (reused by the next begin when it is large enough); W1 / b1 and every slot's frame
+    base live in it.  Otherwise the same state machine runs in torch.  `frames` and `logp` are always kept.
+
+    begin(slots, max_chunk_frames (encoder frames per feed), max_per_frame >= 1, max_hyp_len) leaves every slot finished;
+    feed(enc [slots, Te, H], frames [slots], reset, final, max_symbols) hands every slot its chunk (device int32 vectors, lists or
+    None); then step(pred_proj=...) until all_done[0] is 1 (2: grow_hyps(), then go on), as for TDTGreedyJoint.  What a duration
+    jump reaches beyond the chunk a slot holds is carried into its next chunks; `frames` count from the slot's reset."""
+
+    def __init__(self, joint, durations, joint_dtype: str = "auto"):
+        super().__init__(joint, durations, joint_dtype, token_times=True)
+
+    def begin(self, slots: int, max_chunk_frames: int, max_per_frame: int, max_hyp_len: int, device=None):
+        if int(max_per_frame) < 1:
+            raise ValueError(f"max_per_frame must be at least 1, got {max_per_frame!r}")
+        S, T = int(slots), int(max_chunk_frames)
+        dev = self.W2.device if self.engine else (device if device is not None else self.joint.W2.device)
+        self.B, self.T, self.Tc = S, T, T
+        self.hyps = torch.zeros(S, max_hyp_len, dtype=torch.int32, device=dev)
+        self.lengths = torch.zeros(S, dtype=torch.int32, device=dev)
+        self.emitted = torch.full((S,), -1, dtype=torch.int32, device=dev)
+        self.all_done = torch.ones(1, dtype=torch.int32, device=dev)
+        self._cap = int(max_per_frame)
+        if not self.engine:
+            self.scores = torch.zeros(S, dtype=torch.promote_types(self.joint.W2.dtype, torch.float32), device=dev)
+            self._new_times(S, max_hyp_len, dev)
+            z = torch.zeros(S, dtype=torch.long, device=dev)
+            self._frame_base = z.clone()
+            self._t, self._n, self._nf, self._Tb, self._maxsym = z.clone(), z.clone(), z.clone(), z.clone(), z.clone()
+            self._done = torch.ones(S, dtype=torch.bool, device=dev)
+            self._fin = torch.ones(S, dtype=torch.bool, device=dev)
+            self._dur = torch.tensor(self.durations, dtype=torch.long, device=dev)
+            return
+        self.H = int(self.W1.shape[0])
+        self.scores = torch.zeros(S, dtype=torch.float32, device=dev)
+        self._new_times(S, max_hyp_len, dev)
+        dur = (ctypes.c_int * self.D)(*self.durations)
+        with torch.cuda.device(dev):
+            nbytes = _lib.tdt_greedy_stream_workspace_bytes(T, S, self.H, self.Jp, self.V, self.D, self.dtype)
+            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
+                self._ws = _joint._new_workspace(nbytes, dev)
+            elif _joint._WORKSPACE_FILL is not None:
+                self._ws.fill_(int(_joint._WORKSPACE_FILL))
+            self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
+            st = _lib.load_tdtstream().compute_rnnt_tdt_greedy_stream_begin(
+                self.W1.data_ptr(), self.b1.data_ptr(), self.W2.data_ptr(), self.b2.data_ptr(), self.H, self.Jp, self.V, dur, self.D,
+                S, self.dtype, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_tdt_greedy_stream_begin")
+
+    def feed(self, enc, frames, reset=None, final=None, max_symbols=None):
+        """enc [slots, Te, H] (None or Te = 0: no frames), frames [slots] encoder frames per slot, reset / final [slots] or None,
+        max_symbols [slots] or None (the budget of the streams reset here)."""
+        S = self.B
+        Te = 0 if enc is None else int(enc.shape[1])
+        if Te > self.Tc:
+            raise ValueError(f"a feed takes at most {self.Tc} encoder frames, got {Te}")
+        if not self.engine:
+            return self._torch_feed(enc, Te, frames, reset, final, max_symbols)
+        dev = self.hyps.device
+        if Te > 0:
+            enc = _joint._aligned16(enc.to(device=dev, dtype=torch.float32))
+            if tuple(enc.shape) != (S, Te, self.H):
+                raise ValueError(f"enc must be [{S}, frames, {self.H}], got {tuple(enc.shape)}")
+        cv = lambda x: None if x is None else _joint._device_i32(x, dev).reshape(S)  # noqa: E731
+        fr, rs, fi, ms = cv(frames), cv(reset), cv(final), cv(max_symbols)
+        self._feed_args = (enc, fr, rs, fi, ms)  # (alive until the launches have read them)
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        st = _lib.load_tdtstream().compute_rnnt_tdt_greedy_stream_feed(
+            ptr(enc) if Te > 0 else None, Te, fr.data_ptr(), ptr(rs), ptr(fi), ptr(ms), self._cap, self.lengths.data_ptr(),
+            self.scores.data_ptr(), self.all_done.data_ptr(), self.H, self.Jp, self.V, self.D, S, self.dtype, self._ws.data_ptr(),
+            self._opts)
+        _lib.check(st, "compute_rnnt_tdt_greedy_stream_feed")
+
+    def step(self, pred=None, logit_stats=None, *, pred_proj=None):
+        if not self.engine:
+            return self._torch_step(pred, pred_proj)
+        pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _joint._projected_operand(pred_proj, self.Jp)
+        st = _lib.load_tdtstream().compute_rnnt_tdt_greedy_stream_step(
+            pp.data_ptr(), self.hyps.data_ptr(), self.frames.data_ptr(), self.logp.data_ptr(), self.hyps.shape[1],
+            self.lengths.data_ptr(), self.scores.data_ptr(), self.emitted.data_ptr(), self.all_done.data_ptr(),
+            None if logit_stats is None else logit_stats.data_ptr(), self.Jp, self.V, self.D, self.B, self.dtype, self._ws.data_ptr(),
+            self._opts)
+        _lib.check(st, "compute_rnnt_tdt_greedy_stream_step")
+        return self.emitted
+
+    def _torch_feed(self, enc, Te, frames, reset, final, max_symbols):
+        """tdt_stream_feed_kernel's state machine: the rule of include/rnnt_tdt_stream.h in its order."""
+        S = self.B
+        dev = self.hyps.device
+        vec = lambda x, d: torch.full((S,), d, dtype=torch.long, device=dev) if x is None else torch.as_tensor(x).to(dev).reshape(S).long()  # noqa: E731
+        rs, fi = vec(reset, 0) != 0, vec(final, 0) != 0
+        ms = vec(max_symbols, 2**31 - 1).clamp(min=0)
+        zero = torch.zeros_like(self._t)
+        self._frame_base = torch.where(rs, zero, self._frame_base + self._Tb)
+        skip = torch.where(rs, zero, (self._t - self._Tb).clamp(min=0))  # what the last jump reached beyond the chunk
+        self._n = torch.where(rs, zero, self._n)
+        self.scores = torch.where(rs, torch.zeros_like(self.scores), self.scores)
+        self._maxsym = torch.where(rs, ms, self._maxsym)
+        self._fin = self._fin & ~rs
+        finished = self._fin | (self._n >= self._maxsym)
+        self._Tb = torch.where(finished, zero, vec(frames, 0).clamp(0, Te))
+        self._t = torch.where(finished, zero, skip)
+        self._fin = finished | fi  # (after this chunk: a carry beyond a final chunk is dropped)
+        self._nf = zero.clone()
+        self._done = finished | (self._t >= self._Tb)
+        H = self.joint.W1.shape[0]
+        self._enc = enc if Te > 0 else torch.zeros(S, 1, H, dtype=self.joint.W1.dtype, device=dev)
+        self.T = max(Te, 1)
+        self.lengths.copy_(self._n.to(torch.int32))
+        self.all_done.fill_(0 if bool((~self._done).any()) else 1)
+
+
+class StreamingTDTGreedyDecoder(_decoding.StreamingGreedyDecoder):
+    """Greedy TDT decoding of up to `slots` live audio streams at once, fed chunk by chunk (include/rnnt_tdt_stream.h): a
+    decoding._StreamingSlots with the contract of decoding.StreamingGreedyDecoder -- start(slots), feed(mel_chunk, frames, final) ->
+    (ids, counts), hypotheses(), timed_hypotheses(); non-final feeds bring multiples of the encoder's reduction factor; a feed
+    reads the host for the all-done word every `check_every` steps and once for N -- and the step rule of tdt_greedy_search_batch.
+    Its constructor, feed loop, slot handling and results ARE StreamingGreedyDecoder's; only the joint differs (_make_joint): a
+    TDTGreedyStreamJoint.
+
+    durations: the duration set of the model.  joint: an object with W1, b1, W2 [J, V + D], b2 and blank_label (TDTGreedyJoint's
+    `joint`); None: model.joint.  max_symbols_per_frame >= 1 (mandatory for TDT: with a duration 0 an uncapped decode need not end).
+
+    A duration jump that reaches beyond the frames a slot has so far is carried into its next feeds, and token frames count from
+    the slot's start, so a stream fed through any chunking, in any slot, beside any other traffic ends with the ids, frames,
+    log-probabilities, length and score of the same stream fed in one call to a 1-slot decoder (bitwise on an MI355X), and with the
+    ids and frames of tdt_greedy_search_batch of the stream alone.  A jump beyond a stream's final frame is dropped."""
+
+    def __init__(self, model, durations, slots: int, max_chunk_frames: int, joint=None, max_length=None,
+                 max_symbols_per_frame: int = 10, check_every: int = CHECK_EVERY):
+        if int(max_symbols_per_frame) < 1:
+            raise ValueError(f"max_symbols_per_frame must be at least 1, got {max_symbols_per_frame!r}")
+        self.durations = check_durations(durations)
+        self._joint = model.joint if joint is None else joint
+        super().__init__(model, slots, max_chunk_frames, max_length=max_length, max_symbols_per_frame=int(max_symbols_per_frame),
+                         check_every=check_every, token_times=True)
+
+    def _make_joint(self, model):
+        return TDTGreedyStreamJoint(self._joint, self.durations)
