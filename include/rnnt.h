@@ -320,6 +320,11 @@ RNNT_API rnntStatus_t compute_rnnt_joint_loss_bwd_fastemit(const float *enc_proj
  *   logits[b,t,u,:] = tanh((enc[b,t,:] + pred[b,u,:]) @ W1 + b1) @ W2 + b2, never materialised; the layer is factored exactly
  *   as (enc @ W1 + b1) + pred @ W1 (three GEMMs over B (maxT + maxU) rows with their operands split into binary16 hi + lo
  *   parts, as for joint_dtype 0: csrc/dense_kernels.hip) and the rest is compute_rnnt_joint_loss on those projections.
+ *   Precision of those GEMMs: each of enc, pred, W1 and the two projection gradients is kept to 22 significand bits relative to
+ *   ITS largest magnitude m, for 2^-49 <= m < 2^77 (the per-tensor power-of-two scale is held within 2^-63 .. 2^63, so that
+ *   every product rescales by a normal f32 number).  A tensor with m < 2^-49 -- a pred of 1e-36 throughout, a gradient under a
+ *   vanishing cost_scale -- keeps an absolute resolution of 2^-87 and reads as zero below 2^-88; results stay finite.  A tensor
+ *   that reaches 2^79 overflows its binary16 image and gives inf / NaN, as a tensor that holds inf or NaN does.
  *   d_enc [B,maxT,H], d_pred [B,maxU,H], dW1 [H,J], db1 [J], dW2 [J,V], db2 [V]: gradients of sum_b cost_scale[b] * cost_b
  *   (all six or none; fully overwritten; padded frames / label positions get exact zeros in d_enc / d_pred).
  * hidden_size a multiple of 32, joint_size a multiple of 64 (both <= 4096), then the (joint_size, alphabet_size, joint_dtype)

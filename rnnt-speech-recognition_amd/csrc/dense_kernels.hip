@@ -106,11 +106,17 @@ __device__ __forceinline__ unsigned dense_max_of(const unsigned *arr, const int 
     return max(max(red2[0], red2[1]), max(red2[2], red2[3]));
 }
 
-// S = 2^(14 - e) with max|x| < 2^e (1 for an all-zero or non-finite tensor: the products then carry the inf / NaN through)
+// S = 2^(14 - e) with max|x| < 2^e (1 for an all-zero or non-finite tensor: the products then carry the inf / NaN through).
+// The exponent of S stays within +-kDenseScaleCapLog2, so that every S, every S_A S_B and its reciprocal (the rescale of a
+// product) are finite NORMAL f32 numbers.  Unbounded, a tensor of denormals or of 1e-36 throughout got S = +inf (images of
+// inf / NaN), and two tensors of 2^-60 each got 1 / (S_A S_B) = 0.  With the cap, a tensor whose largest magnitude is below
+// 2^-49 keeps an absolute resolution of 2^-87 instead of 22 relative bits (below 2^-88 it reads as zero), and one that reaches
+// 2^79 overflows its binary16 image and gives inf / NaN, as a non-finite tensor does (include/rnnt.h).
+constexpr int kDenseScaleCapLog2 = 63;
 __device__ __forceinline__ float dense_scale_from_bits(const unsigned bits) {
     const float m = __uint_as_float(bits);
     if (!(m > 0.f) || !(m < 3.0e38f)) return 1.0f;
-    return ldexpf(1.0f, kDenseScaleLog2 - (ilogbf(m) + 1));
+    return ldexpf(1.0f, min(max(kDenseScaleLog2 - (ilogbf(m) + 1), -kDenseScaleCapLog2), kDenseScaleCapLog2));
 }
 
 // four values -> their binary16 hi / lo parts
