@@ -217,6 +217,12 @@ _LATER_SIGNATURES = {
         "compute_rnnt_tdt_greedy_stream_feed": [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp] + [ci] * 6 + [vp, opt],
         "compute_rnnt_tdt_greedy_stream_step": [vp] * 4 + [ci] + [vp] * 5 + [ci] * 5 + [vp, opt],
     },
+    "tdtalign": {
+        "get_rnnt_tdt_align_workspace_size": [ci, ci, ci, ci, sz],
+        "compute_rnnt_tdt_align_cells": [vp, ci, ci, vp, vp, vp, ci, ctypes.POINTER(ci), ci, cf, ci, vp, opt],
+        "compute_rnnt_tdt_align_path": [vp] * 6 + [ctypes.POINTER(ci), ci, ci, vp, opt],
+        "compute_rnnt_tdt_align": [vp] * 4 + [ci, ctypes.POINTER(ci), ci, cf, ci] + [vp] * 5 + [opt],
+    },
 }
 _EVERY_SIGNATURE = {**_ALL_SIGNATURES, **_LATER_SIGNATURES}
 _RESTYPES = {"rnntGetStatusString": ctypes.c_char_p}
@@ -311,6 +317,11 @@ def load_tdtgreedy():
 def load_tdtstream():
     """libwarprnnt_tdtstream.so: streaming greedy decoding of the TDT transducer over slots, include/rnnt_tdt_stream.h."""
     return _load("tdtstream")
+
+
+def load_tdtalign():
+    """libwarprnnt_tdtalign.so: forced alignment on the TDT lattice, include/rnnt_tdt_align.h."""
+    return _load("tdtalign")
 
 
 def status_string(status: int) -> str:
@@ -436,6 +447,10 @@ def tdt_greedy_workspace_bytes(maxT: int, minibatch: int, joint_size: int, alpha
                                joint_dtype: int) -> int:
     return _size(load_tdtgreedy(), "get_rnnt_tdt_greedy_workspace_size", maxT, minibatch, joint_size, alphabet_size, num_durations,
                  joint_dtype)
+
+
+def tdt_align_workspace_bytes(maxT: int, maxU: int, minibatch: int, num_durations: int) -> int:
+    return _size(load_tdtalign(), "get_rnnt_tdt_align_workspace_size", maxT, maxU, minibatch, num_durations)
 
 
 def tdt_greedy_stream_workspace_bytes(max_chunk_frames: int, slots: int, enc_width: int, joint_size: int, alphabet_size: int,

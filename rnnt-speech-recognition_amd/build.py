@@ -74,6 +74,8 @@ LATER_LIBRARIES = {
     # stream's projection and on the step kernel of "tdtgreedy", whose kernel object it links beside the base kernels'
     "tdtstream": Library("rnnt_tdt_stream.h", ("tdt_stream_kernels.hip", "rnnt_tdt_stream_entrypoint.hip"),
                          _BASE_KERNELS + ("tdt_greedy_kernels.hip",), "rnnt_tdt_stream.map"),
+    # forced alignment on the TDT lattice: its own cell pass, sweep and back-trace; it borrows nothing
+    "tdtalign": Library("rnnt_tdt_align.h", ("rnnt_tdtalign_kernels.hip", "rnnt_tdtalign_entrypoint.hip"), (), "rnnt_tdtalign.map"),
 }
 EVERY_LIBRARY = {**ALL_LIBRARIES, **LATER_LIBRARIES}
 
@@ -94,6 +96,7 @@ LM_LIB_PATH = lib_path("lm")
 TDT_LIB_PATH = lib_path("tdt")
 TDTGREEDY_LIB_PATH = lib_path("tdtgreedy")
 TDTSTREAM_LIB_PATH = lib_path("tdtstream")
+TDTALIGN_LIB_PATH = lib_path("tdtalign")
 # -fvisibility=hidden: the library exports exactly the entry points include/rnnt.h marks RNNT_API (tests/test_abi.py)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-inline-asm"]
 # per-source extras.  -fno-slp-vectorize: no packed-f32 instructions (v_pk_fma_f32 ...) from the compiler -- in the linear sweeps

@@ -1,7 +1,8 @@
 """The token-and-duration (TDT) transducer loss (include/rnnt_tdt.h compute_rnnt_loss_tdt, libwarprnnt_tdt.so) and greedy TDT
 decoding: batched (TDTGreedyJoint / tdt_greedy_search_batch on include/rnnt_tdt_greedy.h, libwarprnnt_tdtgreedy.so), over live
 streams fed chunk by chunk (TDTGreedyStreamJoint / StreamingTDTGreedyDecoder on include/rnnt_tdt_stream.h, libwarprnnt_tdtstream.so)
-and as a host loop over one utterance (tdt_greedy_decode).
+and as a host loop over one utterance (tdt_greedy_decode); and forced alignment on the same lattice (rnnt_align_tdt / tdt_align_joint
+on include/rnnt_tdt_align.h, libwarprnnt_tdtalign.so): per label of a given transcript the frame that emits it and the frames it claims.
 
 The joint of a TDT model emits V token logits and D duration logits per lattice cell: acts [B, T, U, V + D].  An edge of the lattice
 consumes d frames, d from `durations`; tokens and durations have a log-softmax each; `sigma` (>= 0) is subtracted from every token
@@ -23,6 +24,7 @@ import math
 import torch
 
 from . import _lib
+from . import alignment as _alignment
 from . import decoding as _decoding
 from . import joint as _joint
 from .loss import _as_i32
@@ -686,3 +688,216 @@ class StreamingTDTGreedyDecoder(_decoding.StreamingGreedyDecoder):
 
     def _make_joint(self, model):
         return TDTGreedyStreamJoint(self._joint, self.durations)
+
+
+# ---- forced alignment on the TDT lattice --------------------------------------------------------------------------------
+def _align_cells_torch(acts, labels, dur, blank, sigma):
+    """The float32 edge weights of include/rnnt_tdt_align.h from float32 logits, each operation rounded once: (wb, wl, raw), each
+    [B, T, U, D]; raw = lp(label) + ld, the token_logp of a label edge (no sigma).  Labels are clamped into [0, V)."""
+    x = acts.detach().to(torch.float32)
+    B, T, U, R = x.shape
+    V = R - len(dur)
+    lp, ld = torch.log_softmax(x[..., :V], dim=-1), torch.log_softmax(x[..., V:], dim=-1)
+    y = torch.zeros((B, U), dtype=torch.int64, device=x.device)
+    y[:, : labels.shape[1]] = labels.to(torch.int64).clamp(0, V - 1)[:, :U]
+    lpb, lpl = lp[..., blank], lp.gather(3, y[:, None, :, None].expand(B, T, U, 1))[..., 0]
+    s = torch.tensor(sigma, dtype=torch.float32, device=x.device)
+    return ((lpb - s)[..., None] + ld), ((lpl - s)[..., None] + ld), (lpl[..., None] + ld)
+
+
+def _align_path_torch(wb, wl, raw, input_lengths, label_lengths, dur):
+    """The recurrence, the tie rule and the back-trace of include/rnnt_tdt_align.h on float32 weights [B, T, U, D]: float64 values,
+    one skewed row n = t + u per step with every utterance and column at once; per node the candidates in increasing i, the blank
+    arrival before the label arrival, a candidate replacing the incumbent only if STRICTLY greater.  The weight of an edge that does
+    not exist is selected away before it is added."""
+    B, T, U, D = wb.shape
+    dev = wb.device
+    il, ll = input_lengths.to(torch.int64), label_lengths.to(torch.int64)
+    bad = (il < 1) | (il > T) | (ll < 0) | (ll > U - 1)
+    Tb, Lb = il.clamp(1, T)[:, None, None], ll.clamp(0, U - 1)[:, None, None]
+    t = torch.arange(T, device=dev)[None, :, None]
+    u = torch.arange(U, device=dev)[None, None, :]
+    live = (t < Tb) & (u <= Lb)
+    N = T + U
+    rows, cols = (t + u).expand(1, T, U)[0], u.expand(1, T, U)[0]
+    ninf = torch.full((), _NEG_INF, dtype=torch.float64, device=dev)
+
+    def skew(w, exists):  # the weights at their SOURCE on skewed rows, -inf where the edge does not exist
+        out = torch.full((B, N, U), _NEG_INF, dtype=torch.float64, device=dev)
+        out[:, rows, cols] = torch.where(exists, w.to(torch.float64), ninf)
+        return out
+
+    wbs = [skew(wb[..., i], live & (d > 0) & ((t + d < Tb) | ((t + d == Tb) & (u == Lb)))) for i, d in enumerate(dur)]
+    wls = [skew(wl[..., i], live & (u < Lb) & (t + d < Tb)) for i, d in enumerate(dur)]
+    first = torch.full((B, U), _NEG_INF, dtype=torch.float64, device=dev)
+    first[:, 0] = 0.0
+    pad = torch.full((B, 1), _NEG_INF, dtype=torch.float64, device=dev)
+    v = [first]
+    codes = torch.full((B, N, U), -1, dtype=torch.int16, device=dev)
+    for n in range(1, N):
+        best = torch.full((B, U), _NEG_INF, dtype=torch.float64, device=dev)
+        code = torch.full((B, U), -1, dtype=torch.int16, device=dev)
+        for i, d in enumerate(dur):
+            cands = []
+            if d > 0 and n - d >= 0:
+                cands.append((2 * i, v[n - d] + wbs[i][:, n - d]))
+            if n - d - 1 >= 0:
+                cands.append((2 * i + 1, torch.cat([pad, (v[n - d - 1] + wls[i][:, n - d - 1])[:, :-1]], dim=1)))
+            for c, cand in cands:
+                take = cand > best  # (a NaN never wins)
+                best = torch.where(take, cand, best)
+                code = torch.where(take, torch.full_like(code, c), code)
+        v.append(best)
+        codes[:, n] = code
+    v = torch.stack(v, dim=1)  # [B, N, U]
+    b = torch.arange(B, device=dev)
+    Tn, Ln = Tb[:, 0, 0], Lb[:, 0, 0]
+    scores = v[b, Tn + Ln, Ln]
+    n_out = max(U - 1, 0)
+    frames = torch.full((B, n_out), -1, dtype=torch.int32)
+    durs = torch.full((B, n_out), -1, dtype=torch.int32)
+    logp = torch.zeros(B, n_out, dtype=torch.float32)
+    cd, raw_c = codes.cpu().numpy(), raw.cpu()
+    for k in range(B):
+        if bool(bad[k]) or not bool(scores[k] > _NEG_INF):
+            continue
+        uu, n = int(Ln[k]), int(Tn[k] + Ln[k])
+        while n > 0:
+            c = int(cd[k, n, uu])
+            i, label = c >> 1, c & 1
+            d = dur[i]
+            if label:
+                frames[k, uu - 1], durs[k, uu - 1] = n - uu - d, d
+                logp[k, uu - 1] = raw_c[k, n - uu - d, uu - 1, i]
+                uu -= 1
+            n -= d + label
+    scores = torch.where(bad, torch.full_like(scores, float("nan")), scores).float()
+    return frames.to(dev), durs.to(dev), logp.to(dev), scores
+
+
+class _TDTAligner:
+    """One TDT alignment in flight on the engine (libwarprnnt_tdtalign.so): the workspace, the outputs and the slab feed."""
+
+    def __init__(self, B, T, U, V, labels, input_lengths, label_lengths, dur, blank, sigma, dev):
+        self.lib = _lib.load_tdtalign()
+        self.B, self.T, self.U, self.V, self.dur, self.blank, self.sigma, self.dev = B, T, U, V, dur, int(blank), sigma, dev
+        self.labels, self.il, self.ll = labels, input_lengths, label_lengths
+        self.d = (ctypes.c_int * len(dur))(*dur)
+        with torch.cuda.device(dev):
+            self.ws = torch.empty(_lib.tdt_align_workspace_bytes(T, U, B, len(dur)), dtype=torch.uint8, device=dev)
+
+    def _opts(self):
+        return _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, self.T, self.U)
+
+    def _outputs(self):
+        n = max(self.U - 1, 1)
+        frames = torch.empty(self.B, n, dtype=torch.int32, device=self.dev)
+        durs = torch.empty(self.B, n, dtype=torch.int32, device=self.dev)
+        logp = torch.empty(self.B, n, dtype=torch.float32, device=self.dev)
+        scores = torch.empty(self.B, dtype=torch.float32, device=self.dev)
+        return frames, durs, logp, scores
+
+    def _trim(self, out):
+        return out[0][:, : self.U - 1], out[1][:, : self.U - 1], out[2][:, : self.U - 1], out[3]
+
+    def cells(self, slab: torch.Tensor, frame_offset: int) -> None:
+        R = self.V + len(self.dur)
+        if slab.dtype != torch.float32 or slab.dim() != 4 or slab.shape[0] != self.B or tuple(slab.shape[2:]) != (self.U, R):
+            raise ValueError(f"tdt align: a slab must be float32 [{self.B}, frames, {self.U}, {R}], got {tuple(slab.shape)}")
+        slab = slab.contiguous()
+        with torch.cuda.device(self.dev):
+            st = self.lib.compute_rnnt_tdt_align_cells(slab.data_ptr(), slab.shape[1], int(frame_offset), self.labels.data_ptr(),
+                                                       self.ll.data_ptr(), self.il.data_ptr(), self.V, self.d, len(self.dur),
+                                                       self.sigma, self.B, self.ws.data_ptr(), self._opts())
+        _lib.check(st, "compute_rnnt_tdt_align_cells")
+
+    def path(self):
+        with torch.cuda.device(self.dev):
+            out = self._outputs()
+            st = self.lib.compute_rnnt_tdt_align_path(out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(),
+                                                      self.ll.data_ptr(), self.il.data_ptr(), self.d, len(self.dur), self.B,
+                                                      self.ws.data_ptr(), self._opts())
+        _lib.check(st, "compute_rnnt_tdt_align_path")
+        return self._trim(out)
+
+    def whole(self, acts):
+        with torch.cuda.device(self.dev):
+            out = self._outputs()
+            st = self.lib.compute_rnnt_tdt_align(acts.data_ptr(), self.labels.data_ptr(), self.ll.data_ptr(), self.il.data_ptr(),
+                                                 self.V, self.d, len(self.dur), self.sigma, self.B, out[0].data_ptr(),
+                                                 out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), self.ws.data_ptr(),
+                                                 self._opts())
+        _lib.check(st, "compute_rnnt_tdt_align")
+        return self._trim(out)
+
+
+@torch.no_grad()
+def rnnt_align_tdt(acts, labels, input_lengths, label_lengths, durations, blank_label: int = 0, sigma: float = 0.0):
+    """Best path through the TDT lattice of `acts` (RAW LOGITS [B, T, U, V + D] float32, the convention of rnnt_loss_tdt):
+    (token_frames i32 [B, U-1], token_durations i32 [B, U-1], token_logp f32 [B, U-1], scores f32 [B]) -- per label the frame that
+    emits it and the frames it claims (-1 past the utterance's labels), the log-probability of the token and of its duration there,
+    without sigma (0 past them), and the path's log-probability (sigma included; never above -rnnt_loss_tdt).  Frames are
+    non-decreasing, equal only across duration 0.  An utterance without a path: score -inf, -1 and 0 elsewhere; out-of-range lengths:
+    a NaN score for that utterance alone.  Device tensors run libwarprnnt_tdtalign.so (include/rnnt_tdt_align.h; a missing library
+    is an error); CPU tensors run the same equations in torch: float32 log-softmaxes, float64 sweep, the same tie rule."""
+    labels, il, ll, dur, blank, sigma = _inputs("rnnt_align_tdt", acts, labels, input_lengths, label_lengths, durations, blank_label,
+                                                sigma)
+    B, T, U, R = acts.shape
+    if not acts.is_cuda:
+        wb, wl, raw = _align_cells_torch(acts, labels, dur, blank, sigma)
+        return _align_path_torch(wb, wl, raw, il, ll, dur)
+    al = _TDTAligner(B, T, U, R - len(dur), labels, il, ll, dur, blank, sigma, acts.device)
+    return al.whole(acts.detach().contiguous())
+
+
+@torch.no_grad()
+def tdt_align_joint(joint, enc, pred, labels, input_lengths, label_lengths, durations, slab_frames=None,
+                    slab_bytes=_alignment.SLAB_BYTES, sigma: float = 0.0):
+    """rnnt_align_tdt on the logits of `joint` for enc [B, T, H] / pred [B, U, H] without holding [B, T, U, V + D].  joint: any joint
+    with V + D columns, cell_logits and blank_label -- a joint.JointLoss with vocab_size = V + D, as TDTGreedyJoint documents.  The
+    logits come from joint.cell_logits one slab of frames at a time, each slab is reduced to 2 D floats per lattice cell
+    (compute_rnnt_tdt_align_cells), one slab is alive at a time and the sweep runs once.  slab_frames=None picks the largest slab
+    whose logits stay under slab_bytes (default alignment.SLAB_BYTES).  The outputs are bitwise those of rnnt_align_tdt on
+    joint.cell_logits(enc, pred)."""
+    dur, sigma = check_durations(durations), check_sigma(sigma)
+    if enc.dim() != 3 or pred.dim() != 3 or enc.shape[0] != pred.shape[0]:
+        raise ValueError("tdt_align_joint: enc must be [B, T, H] and pred [B, U, H]")
+    B, T, _ = enc.shape
+    U = pred.shape[1]
+    R = int(joint.W2.shape[1])
+    V = R - len(dur)
+    blank = int(joint.blank_label)
+    if T < 1 or V < 2 or not 0 <= blank < V:
+        raise ValueError(f"tdt_align_joint: the joint must have V + D = V + {len(dur)} columns with V >= 2 and the blank inside "
+                         f"[0, V), got {R} columns and blank_label = {blank}")
+    if not 1 <= U <= MAX_U:
+        raise ValueError(f"tdt_align_joint: pred must have 1 ... {MAX_U} label positions, got {U}")
+    labels = torch.as_tensor(labels)
+    if labels.dim() != 2 or labels.shape[0] != B or labels.shape[1] != U - 1 and (U, labels.shape[1]) != (1, 1):
+        raise ValueError(f"tdt_align_joint: labels must be [B, U - 1] = [{B}, {U - 1}], got {tuple(labels.shape)}")
+    dev = enc.device
+    labels = _as_i32(labels, dev)
+    if labels.numel() == 0:
+        labels = torch.zeros((B, 1), dtype=torch.int32, device=dev)
+    il, ll = _as_i32(input_lengths, dev).reshape(-1), _as_i32(label_lengths, dev).reshape(-1)
+    if il.numel() != B or ll.numel() != B:
+        raise ValueError("tdt_align_joint: input_lengths and label_lengths must be [B]")
+    S = _alignment.slab_frames_for(B, T, U, R, int(slab_bytes)) if slab_frames is None else int(slab_frames)
+    if S < 1:
+        raise ValueError("tdt_align_joint: slab_frames must be positive")
+    if not enc.is_cuda:
+        parts = [_align_cells_torch(joint.cell_logits(enc[:, t0:t0 + S], pred), labels, dur, blank, sigma) for t0 in range(0, T, S)]
+        wb, wl, raw = (torch.cat([p[k] for p in parts], dim=1) for k in range(3))
+        return _align_path_torch(wb, wl, raw, il, ll, dur)
+    al = _TDTAligner(B, T, U, V, labels, il, ll, dur, blank, sigma, dev)
+    for t0 in range(0, T, S):
+        slab = joint.cell_logits(enc[:, t0:t0 + S].contiguous(), pred)
+        al.cells(slab, t0)
+        del slab  # back to the allocator before the next slab is asked for: one slab of logits is alive at a time
+    return al.path()
+
+
+def token_end_frames(token_frames, token_durations) -> torch.Tensor:
+    """The first frame after the ones each token claims: token_frames + token_durations, -1 where token_frames is -1."""
+    f, d = torch.as_tensor(token_frames), torch.as_tensor(token_durations)
+    return torch.where(f < 0, torch.full_like(f, -1), f + d)
