@@ -223,6 +223,12 @@ _LATER_SIGNATURES = {
         "compute_rnnt_tdt_align_path": [vp] * 6 + [ctypes.POINTER(ci), ci, ci, vp, opt],
         "compute_rnnt_tdt_align": [vp] * 4 + [ci, ctypes.POINTER(ci), ci, cf, ci] + [vp] * 5 + [opt],
     },
+    "tdtbeam": {
+        "get_rnnt_tdt_beam_workspace_size": [ci] * 8 + [sz],
+        "compute_rnnt_tdt_beam_begin": [vp] * 4 + [ci, ci, ctypes.POINTER(ci)] + [ci] * 5 + [vp, opt],
+        "compute_rnnt_tdt_beam_step": [vp] * 7 + [ci] * 7 + [vp, opt],
+        "compute_rnnt_tdt_beam_results": [vp] * 6 + [ci] * 7 + [vp, opt],
+    },
 }
 _EVERY_SIGNATURE = {**_ALL_SIGNATURES, **_LATER_SIGNATURES}
 _RESTYPES = {"rnntGetStatusString": ctypes.c_char_p}
@@ -322,6 +328,11 @@ def load_tdtstream():
 def load_tdtalign():
     """libwarprnnt_tdtalign.so: forced alignment on the TDT lattice, include/rnnt_tdt_align.h."""
     return _load("tdtalign")
+
+
+def load_tdtbeam():
+    """libwarprnnt_tdtbeam.so: batched beam search of the TDT transducer, include/rnnt_tdt_beam.h."""
+    return _load("tdtbeam")
 
 
 def status_string(status: int) -> str:
@@ -451,6 +462,12 @@ def tdt_greedy_workspace_bytes(maxT: int, minibatch: int, joint_size: int, alpha
 
 def tdt_align_workspace_bytes(maxT: int, maxU: int, minibatch: int, num_durations: int) -> int:
     return _size(load_tdtalign(), "get_rnnt_tdt_align_workspace_size", maxT, maxU, minibatch, num_durations)
+
+
+def tdt_beam_workspace_bytes(maxT: int, minibatch: int, beam: int, joint_size: int, alphabet_size: int, num_durations: int,
+                             joint_dtype: int, timed: bool = False) -> int:
+    return _size(load_tdtbeam(), "get_rnnt_tdt_beam_workspace_size", maxT, minibatch, beam, joint_size, alphabet_size, num_durations,
+                 joint_dtype, int(bool(timed)))
 
 
 def tdt_greedy_stream_workspace_bytes(max_chunk_frames: int, slots: int, enc_width: int, joint_size: int, alphabet_size: int,

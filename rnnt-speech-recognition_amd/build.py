@@ -76,6 +76,9 @@ LATER_LIBRARIES = {
                          _BASE_KERNELS + ("tdt_greedy_kernels.hip",), "rnnt_tdt_stream.map"),
     # forced alignment on the TDT lattice: its own cell pass, sweep and back-trace; it borrows nothing
     "tdtalign": Library("rnnt_tdt_align.h", ("rnnt_tdtalign_kernels.hip", "rnnt_tdtalign_entrypoint.hip"), (), "rnnt_tdtalign.map"),
+    # batched beam search of the TDT transducer: its own step, select, begin and results kernels on the greedy decoder's prepare
+    # path and per-hypothesis joint; built as "bias" is (nothing of tdt_greedy_kernels.hip is linked)
+    "tdtbeam": Library("rnnt_tdt_beam.h", ("tdt_beam_kernels.hip", "rnnt_tdt_beam_entrypoint.hip"), _BASE_KERNELS, "rnnt_tdtbeam.map"),
 }
 EVERY_LIBRARY = {**ALL_LIBRARIES, **LATER_LIBRARIES}
 
@@ -97,6 +100,7 @@ TDT_LIB_PATH = lib_path("tdt")
 TDTGREEDY_LIB_PATH = lib_path("tdtgreedy")
 TDTSTREAM_LIB_PATH = lib_path("tdtstream")
 TDTALIGN_LIB_PATH = lib_path("tdtalign")
+TDTBEAM_LIB_PATH = lib_path("tdtbeam")
 # -fvisibility=hidden: the library exports exactly the entry points include/rnnt.h marks RNNT_API (tests/test_abi.py)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-inline-asm"]
 # per-source extras.  -fno-slp-vectorize: no packed-f32 instructions (v_pk_fma_f32 ...) from the compiler -- in the linear sweeps
@@ -106,7 +110,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 _NO_SLP = ["-fno-slp-vectorize"]
 EXTRA_FLAGS = {"rnnt_lin_kernels.hip": _NO_SLP, "joint_kernels.hip": _NO_SLP, "joint_f16_kernels.hip": _NO_SLP, "dense_kernels.hip": _NO_SLP,
                "greedy_kernels.hip": _NO_SLP, "tdt_greedy_kernels.hip": _NO_SLP, "tdt_stream_kernels.hip": _NO_SLP, "beam_kernels.hip": _NO_SLP, "beam_bias_kernels.hip": _NO_SLP,
-               "beam_lm_kernels.hip": _NO_SLP,
+               "beam_lm_kernels.hip": _NO_SLP, "tdt_beam_kernels.hip": _NO_SLP,
                "prednet_kernels.hip": _NO_SLP, "encoder_kernels.hip": _NO_SLP, "lstm_train_kernels.hip": _NO_SLP,
                "rnnt_pruned_joint_kernels.hip": _NO_SLP}
 

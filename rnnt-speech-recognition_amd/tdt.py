@@ -1,7 +1,8 @@
 """The token-and-duration (TDT) transducer loss (include/rnnt_tdt.h compute_rnnt_loss_tdt, libwarprnnt_tdt.so) and greedy TDT
 decoding: batched (TDTGreedyJoint / tdt_greedy_search_batch on include/rnnt_tdt_greedy.h, libwarprnnt_tdtgreedy.so), over live
 streams fed chunk by chunk (TDTGreedyStreamJoint / StreamingTDTGreedyDecoder on include/rnnt_tdt_stream.h, libwarprnnt_tdtstream.so)
-and as a host loop over one utterance (tdt_greedy_decode); and forced alignment on the same lattice (rnnt_align_tdt / tdt_align_joint
+and as a host loop over one utterance (tdt_greedy_decode); batched beam search with n-best lists (TDTBeamJoint /
+tdt_beam_search_batch on include/rnnt_tdt_beam.h, libwarprnnt_tdtbeam.so); and forced alignment on the same lattice (rnnt_align_tdt / tdt_align_joint
 on include/rnnt_tdt_align.h, libwarprnnt_tdtalign.so): per label of a given transcript the frame that emits it and the frames it claims.
 
 The joint of a TDT model emits V token logits and D duration logits per lattice cell: acts [B, T, U, V + D].  An edge of the lattice
@@ -20,6 +21,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+import types
 
 import torch
 
@@ -542,6 +544,275 @@ def tdt_greedy_search_batch(prediction, joint, enc: torch.Tensor, frame_lengths:
                   for (h2, c2), (h, c) in zip(states2, states)]
     LAST_STEPS = steps
     return done()
+
+
+# ---- batched beam search ------------------------------------------------------------------------------------------------
+_BEAM_WORKSPACES = {}  # (device, stream[, "timed"]) -> the workspace of the last tdt_beam_search_batch there
+LAST_ACTIVE_ROWS = None  # tdt_beam_search_batch(count_active=True): joint rows evaluated per utterance (timing tools)
+
+
+class TDTBeamJoint:
+    """The joint of the batched TDT beam search (tdt_beam_search_batch), with the interface of joint.BeamJoint: per frame the joint
+    of every ACTIVE hypothesis of every beam (cursor == frame; a waiting hypothesis costs nothing), the token top-`beam` x durations
+    candidates, ranking, merging on (sequence, cursor) and the new beams in one pass.  The rule: include/rnnt_tdt_beam.h.
+
+    joint / durations: as for TDTGreedyJoint.  Device tensors on shapes the library takes run the ENGINE
+    (compute_rnnt_tdt_beam_begin / _step / _results, libwarprnnt_tdtbeam.so); the object owns the workspace and the joint-unit
+    padding of W1 / b1 / W2.  CPU tensors, and shapes the library refuses, run the same rule in torch: float64 scores, the same key
+    order (per-utterance bookkeeping on the host).
+
+    begin(enc [B, T, H], frame_lengths [B]); step(pred [B beam, H]) or step(pred_proj=[B beam, Jp]) -> (parents, emitted) int32
+    [B beam]; results() -> (hyps [B, beam, T] int32 zero-padded, lengths [B, beam] int32, scores [B, beam]), best first, and with
+    token_times=True two more: frames and durations int32 [B, beam, T] (-1 padded), per token the frame that emitted it and the
+    frames it claims.  cursors() -> int32 [B, beam], the next frame every hypothesis reads (-1: empty slot).  step takes the
+    diagnostics keywords topk_logits / topk_symbols [B beam, beam], dur_logits [B beam, D], lse [B beam, 2]: written for the rows
+    that were active."""
+
+    def __init__(self, joint, durations, beam: int = 4, joint_dtype: str = "auto", token_times: bool = False):
+        if not 1 <= int(beam) <= 16:
+            raise ValueError("TDTBeamJoint: beam must be in 1 ... 16")
+        self.K = int(beam)
+        g = TDTGreedyJoint(joint, durations, joint_dtype)  # (the same checks, engine / torch decision and padding)
+        self.joint, self.durations, self.blank, self.V, self.D, self.engine = joint, g.durations, g.blank, g.V, g.D, g.engine
+        self.token_times = bool(token_times)
+        if self.engine:
+            self.dtype, self.Jp, self.W1, self.b1, self.W2, self.b2 = g.dtype, g.Jp, g.W1, g.b1, g.W2, g.b2
+        self._ws = None
+
+    def _args(self):
+        return self.Jp, self.V, self.D, self.B, self.K, self.dtype, int(self.token_times), self._ws.data_ptr(), self._opts
+
+    def begin(self, enc, frame_lengths):
+        B, T = enc.shape[0], enc.shape[1]
+        dev = enc.device
+        self.B, self.T = B, T
+        R = B * self.K
+        self.parents = torch.arange(R, dtype=torch.int32, device=dev)
+        self.emitted = torch.full((R,), -1, dtype=torch.int32, device=dev)
+        frames = frame_lengths.to(device=dev, dtype=torch.int32).contiguous()
+        if not self.engine:
+            return self._torch_begin(enc, frames)
+        ep = (torch.matmul(enc.float(), self.W1) + self.b1).contiguous()
+        self._keep = frames
+        dur = (ctypes.c_int * self.D)(*self.durations)
+        with torch.cuda.device(dev):
+            nbytes = _lib.tdt_beam_workspace_bytes(T, B, self.K, self.Jp, self.V, self.D, self.dtype, self.token_times)
+            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
+                self._ws = _joint._new_workspace(nbytes, dev)
+            elif _joint._WORKSPACE_FILL is not None:
+                self._ws.fill_(int(_joint._WORKSPACE_FILL))
+            self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
+            st = _lib.load_tdtbeam().compute_rnnt_tdt_beam_begin(ep.data_ptr(), frames.data_ptr(), self.W2.data_ptr(), self.b2.data_ptr(),
+                                                                 self.Jp, self.V, dur, self.D, B, self.K, self.dtype,
+                                                                 int(self.token_times), self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_tdt_beam_begin")
+
+    def step(self, pred=None, topk_logits=None, topk_symbols=None, dur_logits=None, lse=None, *, pred_proj=None):
+        """pred [B beam, H]: the prediction network's output of every slot -> (parents, emitted), int32 [B beam].
+        pred_proj [B beam, Jp] instead of pred: that output already through W1 (joint.PredictionStep); the step skips its matmul."""
+        if not self.engine:
+            return self._torch_step(pred, pred_proj, topk_logits, topk_symbols, dur_logits, lse)
+        pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _joint._projected_operand(pred_proj, self.Jp)
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        st = _lib.load_tdtbeam().compute_rnnt_tdt_beam_step(pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(),
+                                                            ptr(topk_logits), ptr(topk_symbols), ptr(dur_logits), ptr(lse), *self._args())
+        _lib.check(st, "compute_rnnt_tdt_beam_step")
+        return self.parents, self.emitted
+
+    def results(self):
+        out = self._results()
+        return out[:3] + out[4:] if self.token_times else out[:3]
+
+    def cursors(self):
+        """int32 [B, beam]: the next frame every hypothesis of the current beams reads (-1: empty slot)."""
+        return self._results()[3]
+
+    def _results(self):
+        B, K, T = self.B, self.K, self.T
+        if not self.engine:
+            return self._torch_results()
+        dev = self.parents.device
+        hyps = torch.empty(B, K, T, dtype=torch.int32, device=dev)
+        lengths = torch.empty(B, K, dtype=torch.int32, device=dev)
+        scores = torch.empty(B, K, dtype=torch.float32, device=dev)
+        cursors = torch.empty(B, K, dtype=torch.int32, device=dev)
+        frames = torch.empty(B, K, T, dtype=torch.int32, device=dev) if self.token_times else None
+        durs = torch.empty(B, K, T, dtype=torch.int32, device=dev) if self.token_times else None
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        st = _lib.load_tdtbeam().compute_rnnt_tdt_beam_results(hyps.data_ptr(), lengths.data_ptr(), scores.data_ptr(), cursors.data_ptr(),
+                                                               ptr(frames), ptr(durs), *self._args())
+        _lib.check(st, "compute_rnnt_tdt_beam_results")
+        return (hyps, lengths, scores, cursors, frames, durs)
+
+    # ---- torch composition: the rule of include/rnnt_tdt_beam.h with its two shortcuts (token top-K, then pair top-K)
+    def _torch_begin(self, enc, frames):
+        self._enc = enc
+        self._Tb = [int(x) for x in frames.clamp(0, enc.shape[1]).tolist()]
+        self._t = 0
+        self._beams = [[((), 0, 0.0, ())] for _ in range(self.B)]  # (tokens, cursor, float64 score, (frame, duration) pairs)
+        self._sdtype = torch.promote_types(enc.dtype, torch.float32)
+
+    def _torch_step(self, pred, pred_proj, topk_logits, topk_symbols, dur_logits, lse_out):
+        B, K, V, D = self.B, self.K, self.V, self.D
+        t = self._t
+        self._t += 1
+        parents, emitted = list(range(B * K)), [-1] * (B * K)
+        active = [b * K + i for b in range(B) if t < self._Tb[b] for i, h in enumerate(self._beams[b]) if h[1] == t]
+        rows = {}
+        if active:
+            idx = torch.tensor(active, device=self._enc.device)
+            e = self._enc[:, min(t, self.T - 1)][idx // K]
+            lg = _cell_logits(self.joint, e, None if pred is None else pred[idx], None if pred_proj is None else pred_proj[idx])
+            tok, dur = lg[:, :V], lg[:, V:]
+            lt, ld = torch.logsumexp(tok.double(), -1).tolist(), torch.logsumexp(dur.double(), -1).tolist()
+            clean = torch.where(torch.isnan(tok) | (tok == _NEG_INF), torch.full_like(tok, _NEG_INF), tok)
+            top_l, top_v = torch.sort(clean, dim=-1, descending=True, stable=True)  # (logit descending, symbol ascending)
+            top_l, top_v = top_l[:, :K], top_v[:, :K]
+            top_v = torch.where(top_l > _NEG_INF, top_v, torch.full_like(top_v, -1))
+            if K > V:
+                top_l = torch.nn.functional.pad(top_l, (0, K - V), value=_NEG_INF)
+                top_v = torch.nn.functional.pad(top_v, (0, K - V), value=-1)
+            for out, val in ((topk_logits, top_l), (topk_symbols, top_v), (dur_logits, dur)):
+                if out is not None:
+                    out[idx] = val.to(out.dtype)
+            if lse_out is not None:
+                lse_out[idx] = torch.tensor(list(zip(lt, ld)), dtype=lse_out.dtype, device=lse_out.device)
+            for n, r in enumerate(active):
+                rows[r] = (top_l[n].tolist(), top_v[n].tolist(), dur[n].tolist(), lt[n], ld[n])
+        for b in range(B):
+            if t < self._Tb[b]:
+                self._torch_rank(b, t, rows, parents, emitted)
+        dev = self.parents.device
+        self.parents = torch.tensor(parents, dtype=torch.int32, device=dev)
+        self.emitted = torch.tensor(emitted, dtype=torch.int32, device=dev)
+        return self.parents, self.emitted
+
+    def _torch_rank(self, b, t, rows, parents, emitted):
+        K, blank = self.K, self.blank
+        beam = self._beams[b]
+        cands = []  # (score, i, v or -1 for a stay, j)
+        for i, (y, c, s, tt) in enumerate(beam):
+            if c != t:
+                cands.append((s, i, -1, 0))
+                continue
+            top_l, top_v, dur, lt, ld = rows[b * K + i]
+            mine = []
+            for l, v in zip(top_l, top_v):
+                if v < 0:
+                    continue
+                for j, dl in enumerate(dur):
+                    sc = s + ((float(l) - lt) + (float(dl) - ld))
+                    if sc == sc and sc > -math.inf:
+                        mine.append((sc, i, v, j))
+            mine.sort(key=lambda x: (-x[0], x[2], x[3]))
+            cands += mine[:K]
+        cands.sort(key=lambda x: (-x[0], x[1], x[2], x[3]))
+        taken = cands[:K]
+        if not taken:  # the beam is carried over, one frame on
+            self._beams[b] = [(y, t + 1, s, tt) for y, c, s, tt in beam]
+            return
+        merged = []  # [tokens, cursor, score, pairs, parent, emitted]
+        for sc, i, v, j in taken:
+            y, c, _, tt = beam[i]
+            em = -1
+            if v >= 0:
+                d = self.durations[j] or 1
+                c = t + d
+                if v != blank:
+                    y, tt, em = y + (v,), tt + ((t, d),), v
+            hit = next((m for m in merged if m[0] == y and m[1] == c), None)
+            if hit is None:
+                merged.append([y, c, sc, tt, i, em])
+            else:
+                hi, lo = max(hit[2], sc), min(hit[2], sc)
+                hit[2] = hi + math.log1p(math.exp(lo - hi))
+        merged.sort(key=lambda m: -m[2])  # (stable)
+        self._beams[b] = [tuple(m[:4]) for m in merged]
+        for k, m in enumerate(merged):
+            parents[b * K + k], emitted[b * K + k] = b * K + m[4], m[5]
+
+    def _torch_results(self):
+        B, K, T = self.B, self.K, self.T
+        hyps = torch.zeros(B, K, T, dtype=torch.int32)
+        lengths = torch.zeros(B, K, dtype=torch.int32)
+        scores = torch.full((B, K), -math.inf, dtype=torch.float64)
+        cursors = torch.full((B, K), -1, dtype=torch.int32)
+        frames = torch.full((B, K, T), -1, dtype=torch.int32)
+        durs = torch.full((B, K, T), -1, dtype=torch.int32)
+        for b, beam in enumerate(self._beams):
+            for k, (y, c, s, tt) in enumerate(beam):
+                n = len(y)
+                lengths[b, k], scores[b, k], cursors[b, k] = n, s, c
+                if n:
+                    hyps[b, k, :n] = torch.tensor(y, dtype=torch.int32)
+                    frames[b, k, :n] = torch.tensor([f for f, _ in tt], dtype=torch.int32)
+                    durs[b, k, :n] = torch.tensor([d for _, d in tt], dtype=torch.int32)
+        dev = self.parents.device
+        out = (hyps.to(dev), lengths.to(dev), scores.to(device=dev, dtype=self._sdtype), cursors.to(dev))
+        return out + ((frames.to(dev), durs.to(dev)) if self.token_times else (None, None))
+
+
+@torch.no_grad()
+def tdt_beam_search_batch(prediction, joint, enc: torch.Tensor, frame_lengths: torch.Tensor, durations, beam: int = 4,
+                          prediction_route: str = "torch", token_times: bool = False, count_active: bool = False):
+    """TDT beam search (one symbol per frame, include/rnnt_tdt_beam.h) over encoder outputs enc [B, T', H] with frame_lengths [B]
+    -> (hyps int32 [B, beam, T'] zero-padded, lengths int32 [B, beam], scores [B, beam][, frames, durations int32 [B, beam, T']]):
+    every utterance's n-best, best first (empty slots: length 0, score -inf).  beam = 1 is tdt_greedy_search_batch with
+    max_symbols_per_frame = 1.
+
+    The loop of decoding.beam_search_batch: T' steps without reading the host; per step the prediction network runs on all B beam
+    rows, its output and LSTM state are gathered by `parents`, and the rows that emitted a token advance.  prediction /
+    prediction_route / joint / durations: as for tdt_greedy_search_batch.  count_active (timing tools): LAST_ACTIVE_ROWS becomes a
+    device tensor [B] of the joint rows evaluated per utterance (one more small torch op per step, still no host read)."""
+    global LAST_ACTIVE_ROWS
+    from .decoding import _check_prediction, _pred_step
+
+    _check_prediction(prediction_route)
+    B, T = enc.shape[0], enc.shape[1]
+    K = int(beam)
+    dev = enc.device
+    jb = TDTBeamJoint(joint, durations, K, token_times=bool(token_times))
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream) if enc.is_cuda else None
+    if token_times and key is not None:
+        key = key + ("timed",)  # (a timed decode keeps a workspace of its own)
+    jb._ws = _BEAM_WORKSPACES.get(key)
+    jb.begin(enc, frame_lengths)
+    if jb._ws is not None:
+        _BEAM_WORKSPACES[key] = jb._ws
+    active = torch.zeros(B, dtype=torch.int64, device=dev) if count_active else None
+    Tb = frame_lengths.to(dev).clamp(0, T) if count_active else None
+
+    def count(t):
+        if active is not None:
+            active.add_(((jb.cursors() == t) & (t < Tb)[:, None]).sum(1))
+
+    if prediction_route == "engine":
+        # (the prediction-network workspace of the last engine-route decode on this stream is reused, as beam_search_batch does)
+        ps, pp = _decoding._prediction_step(types.SimpleNamespace(prediction=prediction, joint=joint), jb, B * K, dev)
+        for t in range(T):
+            count(t)
+            parents, emitted = jb.step(pred_proj=pp)
+            if t + 1 == T:
+                break
+            pp = ps.step(emitted, parents)
+        LAST_ACTIVE_ROWS = active
+        return jb.results()
+    g, states = _pred_step(prediction, torch.zeros(B * K, dtype=torch.int32, device=dev), [None] * len(prediction.blocks))
+    for t in range(T):
+        count(t)
+        parents, emitted = jb.step(g)
+        if t + 1 == T:
+            break
+        idx = parents.long()
+        g = g[idx]
+        states = [(h[:, idx], c[:, idx]) for h, c in states]
+        mask = emitted >= 0
+        g2, states2 = _pred_step(prediction, emitted.clamp(min=0), states)
+        g = torch.where(mask[:, None], g2, g)
+        states = [(torch.where(mask[None, :, None], h2, h), torch.where(mask[None, :, None], c2, c))
+                  for (h2, c2), (h, c) in zip(states2, states)]
+    LAST_ACTIVE_ROWS = active
+    return jb.results()
 
 
 # ---- streaming greedy decoding ------------------------------------------------------------------------------------------
