@@ -229,6 +229,10 @@ _LATER_SIGNATURES = {
         "compute_rnnt_tdt_beam_step": [vp] * 7 + [ci] * 7 + [vp, opt],
         "compute_rnnt_tdt_beam_results": [vp] * 6 + [ci] * 7 + [vp, opt],
     },
+    "tdtjoint": {
+        "get_rnnt_tdt_joint_workspace_size": [ci] * 5 + [sz],
+        "compute_rnnt_joint_loss_tdt": [vp] * 8 + [ci, ci, ctypes.POINTER(ci), ci, cf, ci] + [vp] * 6 + [opt],
+    },
 }
 _EVERY_SIGNATURE = {**_ALL_SIGNATURES, **_LATER_SIGNATURES}
 _RESTYPES = {"rnntGetStatusString": ctypes.c_char_p}
@@ -333,6 +337,11 @@ def load_tdtalign():
 def load_tdtbeam():
     """libwarprnnt_tdtbeam.so: batched beam search of the TDT transducer, include/rnnt_tdt_beam.h."""
     return _load("tdtbeam")
+
+
+def load_tdtjoint():
+    """libwarprnnt_tdtjoint.so: the fused TDT joint, include/rnnt_tdt_joint.h."""
+    return _load("tdtjoint")
 
 
 def status_string(status: int) -> str:
@@ -468,6 +477,10 @@ def tdt_beam_workspace_bytes(maxT: int, minibatch: int, beam: int, joint_size: i
                              joint_dtype: int, timed: bool = False) -> int:
     return _size(load_tdtbeam(), "get_rnnt_tdt_beam_workspace_size", maxT, minibatch, beam, joint_size, alphabet_size, num_durations,
                  joint_dtype, int(bool(timed)))
+
+
+def tdt_joint_workspace_bytes(maxT: int, maxU: int, minibatch: int, num_durations: int, joint_size: int) -> int:
+    return _size(load_tdtjoint(), "get_rnnt_tdt_joint_workspace_size", maxT, maxU, minibatch, num_durations, joint_size)
 
 
 def tdt_greedy_stream_workspace_bytes(max_chunk_frames: int, slots: int, enc_width: int, joint_size: int, alphabet_size: int,

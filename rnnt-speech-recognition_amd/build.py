@@ -79,6 +79,9 @@ LATER_LIBRARIES = {
     # batched beam search of the TDT transducer: its own step, select, begin and results kernels on the greedy decoder's prepare
     # path and per-hypothesis joint; built as "bias" is (nothing of tdt_greedy_kernels.hip is linked)
     "tdtbeam": Library("rnnt_tdt_beam.h", ("tdt_beam_kernels.hip", "rnnt_tdt_beam_entrypoint.hip"), _BASE_KERNELS, "rnnt_tdtbeam.map"),
+    # the fused TDT joint: its own kernels and the lattice sweeps of the TDT loss, unchanged
+    "tdtjoint": Library("rnnt_tdt_joint.h", ("rnnt_tdt_joint_kernels.hip", "rnnt_tdt_joint_entrypoint.hip"),
+                        ("rnnt_tdt_kernels.hip",), "rnnt_tdt_joint.map"),
 }
 EVERY_LIBRARY = {**ALL_LIBRARIES, **LATER_LIBRARIES}
 
@@ -101,6 +104,7 @@ TDTGREEDY_LIB_PATH = lib_path("tdtgreedy")
 TDTSTREAM_LIB_PATH = lib_path("tdtstream")
 TDTALIGN_LIB_PATH = lib_path("tdtalign")
 TDTBEAM_LIB_PATH = lib_path("tdtbeam")
+TDTJOINT_LIB_PATH = lib_path("tdtjoint")
 # -fvisibility=hidden: the library exports exactly the entry points include/rnnt.h marks RNNT_API (tests/test_abi.py)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-inline-asm"]
 # per-source extras.  -fno-slp-vectorize: no packed-f32 instructions (v_pk_fma_f32 ...) from the compiler -- in the linear sweeps
@@ -112,7 +116,7 @@ EXTRA_FLAGS = {"rnnt_lin_kernels.hip": _NO_SLP, "joint_kernels.hip": _NO_SLP, "j
                "greedy_kernels.hip": _NO_SLP, "tdt_greedy_kernels.hip": _NO_SLP, "tdt_stream_kernels.hip": _NO_SLP, "beam_kernels.hip": _NO_SLP, "beam_bias_kernels.hip": _NO_SLP,
                "beam_lm_kernels.hip": _NO_SLP, "tdt_beam_kernels.hip": _NO_SLP,
                "prednet_kernels.hip": _NO_SLP, "encoder_kernels.hip": _NO_SLP, "lstm_train_kernels.hip": _NO_SLP,
-               "rnnt_pruned_joint_kernels.hip": _NO_SLP}
+               "rnnt_pruned_joint_kernels.hip": _NO_SLP, "rnnt_tdt_joint_kernels.hip": _NO_SLP}
 
 
 def _deps():
