@@ -22,6 +22,7 @@ from .tdt import (TDTGreedyJoint, TDTLoss, rnnt_loss_tdt, rnnt_loss_tdt_and_grad
 from .tdt import StreamingTDTGreedyDecoder, TDTGreedyStreamJoint  # noqa: F401
 from .tdt import rnnt_align_tdt, tdt_align_joint, token_end_frames  # noqa: F401
 from .tdt import TDTBeamJoint, tdt_beam_search_batch  # noqa: F401
+from .tdt import StreamingTDTBeamDecoder, TDTBeamStreamJoint  # noqa: F401
 from .tdt_joint import TDTJointLoss, rnnt_joint_loss_tdt, rnnt_joint_loss_tdt_and_grad  # noqa: F401
 
 __all__ = ["rnnt_loss", "rnnt_loss_and_grad", "RNNTLoss", "get_loss_fn", "reduced_lengths", "rnnt_joint_loss",
@@ -32,4 +33,5 @@ __all__ = ["rnnt_loss", "rnnt_loss_and_grad", "RNNTLoss", "get_loss_fn", "reduce
            "rnnt_loss_tdt", "rnnt_loss_tdt_and_grad", "TDTLoss", "tdt_greedy_decode",
            "TDTGreedyJoint", "tdt_greedy_search_batch", "TDTGreedyStreamJoint", "StreamingTDTGreedyDecoder",
            "rnnt_align_tdt", "tdt_align_joint", "token_end_frames", "TDTBeamJoint", "tdt_beam_search_batch",
-           "rnnt_joint_loss_tdt", "rnnt_joint_loss_tdt_and_grad", "TDTJointLoss"]
+           "rnnt_joint_loss_tdt", "rnnt_joint_loss_tdt_and_grad", "TDTJointLoss",
+           "TDTBeamStreamJoint", "StreamingTDTBeamDecoder"]

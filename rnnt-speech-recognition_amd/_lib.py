@@ -233,6 +233,13 @@ _LATER_SIGNATURES = {
         "get_rnnt_tdt_joint_workspace_size": [ci] * 5 + [sz],
         "compute_rnnt_joint_loss_tdt": [vp] * 8 + [ci, ci, ctypes.POINTER(ci), ci, cf, ci] + [vp] * 6 + [opt],
     },
+    "tdtbeamstream": {
+        "get_rnnt_tdt_beam_stream_workspace_size": [ci] * 10 + [sz],
+        "compute_rnnt_tdt_beam_stream_begin": [vp] * 4 + [ci, ci, ci, ctypes.POINTER(ci)] + [ci] * 6 + [vp, opt],
+        "compute_rnnt_tdt_beam_stream_feed": [vp, ci, vp, vp, vp] + [ci] * 9 + [vp, opt],
+        "compute_rnnt_tdt_beam_stream_step": [vp] * 7 + [ci] * 8 + [vp, opt],
+        "compute_rnnt_tdt_beam_stream_results": [vp] * 8 + [ci] * 8 + [vp, opt],
+    },
 }
 _EVERY_SIGNATURE = {**_ALL_SIGNATURES, **_LATER_SIGNATURES}
 _RESTYPES = {"rnntGetStatusString": ctypes.c_char_p}
@@ -342,6 +349,11 @@ def load_tdtbeam():
 def load_tdtjoint():
     """libwarprnnt_tdtjoint.so: the fused TDT joint, include/rnnt_tdt_joint.h."""
     return _load("tdtjoint")
+
+
+def load_tdtbeamstream():
+    """libwarprnnt_tdtbeamstream.so: streaming beam search of the TDT transducer over slots, include/rnnt_tdt_beam_stream.h."""
+    return _load("tdtbeamstream")
 
 
 def status_string(status: int) -> str:
@@ -487,3 +499,9 @@ def tdt_greedy_stream_workspace_bytes(max_chunk_frames: int, slots: int, enc_wid
                                       num_durations: int, joint_dtype: int) -> int:
     return _size(load_tdtstream(), "get_rnnt_tdt_greedy_stream_workspace_size", max_chunk_frames, slots, enc_width, joint_size,
                  alphabet_size, num_durations, joint_dtype)
+
+
+def tdt_beam_stream_workspace_bytes(max_chunk_frames: int, slots: int, beam: int, max_hyp_len: int, enc_width: int, joint_size: int,
+                                    alphabet_size: int, num_durations: int, joint_dtype: int, timed: bool = False) -> int:
+    return _size(load_tdtbeamstream(), "get_rnnt_tdt_beam_stream_workspace_size", max_chunk_frames, slots, beam, max_hyp_len, enc_width,
+                 joint_size, alphabet_size, num_durations, joint_dtype, int(bool(timed)))

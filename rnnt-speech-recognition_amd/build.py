@@ -82,6 +82,11 @@ LATER_LIBRARIES = {
     # the fused TDT joint: its own kernels and the lattice sweeps of the TDT loss, unchanged
     "tdtjoint": Library("rnnt_tdt_joint.h", ("rnnt_tdt_joint_kernels.hip", "rnnt_tdt_joint_entrypoint.hip"),
                         ("rnnt_tdt_kernels.hip",), "rnnt_tdt_joint.map"),
+    # beam search of the TDT transducer over a stream of chunks per slot: its own begin, feed, step, select and results kernels (step
+    # and select compiled from the text "tdtbeam" compiles: tdt_beam_step_body.h, tdt_beam_select_body.h) on the greedy stream's
+    # projection; built as "bias" is (no object of "tdtbeam" is linked)
+    "tdtbeamstream": Library("rnnt_tdt_beam_stream.h", ("tdt_nbest_stream_kernels.hip", "rnnt_tdt_nbest_stream_entrypoint.hip"),
+                             _BASE_KERNELS, "rnnt_tdtbeamstream.map"),
 }
 EVERY_LIBRARY = {**ALL_LIBRARIES, **LATER_LIBRARIES}
 
@@ -105,6 +110,7 @@ TDTSTREAM_LIB_PATH = lib_path("tdtstream")
 TDTALIGN_LIB_PATH = lib_path("tdtalign")
 TDTBEAM_LIB_PATH = lib_path("tdtbeam")
 TDTJOINT_LIB_PATH = lib_path("tdtjoint")
+TDTBEAMSTREAM_LIB_PATH = lib_path("tdtbeamstream")
 # -fvisibility=hidden: the library exports exactly the entry points include/rnnt.h marks RNNT_API (tests/test_abi.py)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-inline-asm"]
 # per-source extras.  -fno-slp-vectorize: no packed-f32 instructions (v_pk_fma_f32 ...) from the compiler -- in the linear sweeps
@@ -114,7 +120,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 _NO_SLP = ["-fno-slp-vectorize"]
 EXTRA_FLAGS = {"rnnt_lin_kernels.hip": _NO_SLP, "joint_kernels.hip": _NO_SLP, "joint_f16_kernels.hip": _NO_SLP, "dense_kernels.hip": _NO_SLP,
                "greedy_kernels.hip": _NO_SLP, "tdt_greedy_kernels.hip": _NO_SLP, "tdt_stream_kernels.hip": _NO_SLP, "beam_kernels.hip": _NO_SLP, "beam_bias_kernels.hip": _NO_SLP,
-               "beam_lm_kernels.hip": _NO_SLP, "tdt_beam_kernels.hip": _NO_SLP,
+               "beam_lm_kernels.hip": _NO_SLP, "tdt_beam_kernels.hip": _NO_SLP, "tdt_nbest_stream_kernels.hip": _NO_SLP,
                "prednet_kernels.hip": _NO_SLP, "encoder_kernels.hip": _NO_SLP, "lstm_train_kernels.hip": _NO_SLP,
                "rnnt_pruned_joint_kernels.hip": _NO_SLP, "rnnt_tdt_joint_kernels.hip": _NO_SLP}
 

@@ -8,13 +8,18 @@
 // duration set.  Two words of the beam's layout mean something else here:
 //   BeamSlot::pad   the hypothesis's CURSOR, the next frame it reads (the unbiased beam search keeps 0 there)
 //   BeamArgs::tt    timed: {emission frame, frames claimed} per token (the beam search: {frame, bits of the log-probability})
-// The region BeamArgs::bl (the blank's logit of a hypothesis with a full token row) is not used: offline a row is never full.
+// The region BeamArgs::bl (the blank's logit of a hypothesis with a full token row) is not used offline, where a row is never full.
+// The stream (tdt_nbest_stream_kernels.hip, include/rnnt_tdt_beam_stream.h) lays the same workspace out with token and pair rows of
+// stride N = max_hyp_len (the _n forms below; offline N = T), uses bl, and keeps the cursor relative to the chunk a slot holds.
 #pragma once
 #include "beam_common.h"
 
 namespace rnnt {
 
 constexpr int kTdtBeamMaxD = 8;  // include/rnnt_tdt.h: 1 <= D <= 8
+// the stream: the word after the duration set (its 256-byte region has room) holds the place of the frame bases, in words past
+// this workspace, for the calls that take no enc_width (tdt_stream_kernels.hip does the same)
+constexpr int kTdtBeamBaseWord = kTdtBeamMaxD;
 
 struct TdtBeamDurations {
     int d[kTdtBeamMaxD];
@@ -28,6 +33,7 @@ struct TdtBeamArgs {
     int Vt, D;
     float *durl;  // diagnostics: [B K][D] (NULL: not written)
     int *cursors, *hyp_durations;  // results
+    const int *tail;  // the stream alone: the end of this workspace; the frame bases [S] are at tail + durset[kTdtBeamBaseWord]
 };
 
 struct TdtBeamLayout {
@@ -35,9 +41,10 @@ struct TdtBeamLayout {
     size_t dpm, dps, dl, durset, total;
 };
 
-static bool make_tdt_beam_layout(int T, int B, int K, int J, int Vt, int D, int joint_dtype, bool timed, TdtBeamLayout &L) {
+// N: the token and pair row stride (offline: T)
+static bool make_tdt_beam_layout_n(int T, int B, int K, int N, int J, int Vt, int D, int joint_dtype, bool timed, TdtBeamLayout &L) {
     if (Vt < 2 || D < 1 || D > kTdtBeamMaxD) return false;
-    if (!make_beam_layout(T, B, K, T, J, Vt + D, joint_dtype, timed, L.b)) return false;
+    if (!make_beam_layout(T, B, K, N, J, Vt + D, joint_dtype, timed, L.b)) return false;
     size_t off = L.b.total;
     auto take = [&](size_t bytes) {
         const size_t o = off;
@@ -53,15 +60,24 @@ static bool make_tdt_beam_layout(int T, int B, int K, int J, int Vt, int D, int 
     return true;
 }
 
-static bool tdt_beam_bind(TdtBeamArgs &ta, int T, int B, int K, int J, int Vt, int D, int joint_dtype, bool timed, void *workspace,
-                          TdtBeamLayout &L) {
-    if (!make_tdt_beam_layout(T, B, K, J, Vt, D, joint_dtype, timed, L)) return false;
-    if (!beam_bind(ta.b, T, B, K, T, J, Vt + D, joint_dtype, timed, workspace, L.b)) return false;
+static bool make_tdt_beam_layout(int T, int B, int K, int J, int Vt, int D, int joint_dtype, bool timed, TdtBeamLayout &L) {
+    return make_tdt_beam_layout_n(T, B, K, T, J, Vt, D, joint_dtype, timed, L);
+}
+
+static bool tdt_beam_bind_n(TdtBeamArgs &ta, int T, int B, int K, int N, int J, int Vt, int D, int joint_dtype, bool timed,
+                            void *workspace, TdtBeamLayout &L) {
+    if (!make_tdt_beam_layout_n(T, B, K, N, J, Vt, D, joint_dtype, timed, L)) return false;
+    if (!beam_bind(ta.b, T, B, K, N, J, Vt + D, joint_dtype, timed, workspace, L.b)) return false;
     char *ws = (char *)workspace;
     ta.dpart_m = (float *)(ws + L.dpm), ta.dpart_s = (float *)(ws + L.dps);
     ta.dl = (float *)(ws + L.dl), ta.durset = (int *)(ws + L.durset);
     ta.Vt = Vt, ta.D = D;
     return true;
+}
+
+static bool tdt_beam_bind(TdtBeamArgs &ta, int T, int B, int K, int J, int Vt, int D, int joint_dtype, bool timed, void *workspace,
+                          TdtBeamLayout &L) {
+    return tdt_beam_bind_n(ta, T, B, K, T, J, Vt, D, joint_dtype, timed, workspace, L);
 }
 
 }  // namespace rnnt

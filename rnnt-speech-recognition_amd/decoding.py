@@ -636,13 +636,17 @@ class StreamingBeamDecoder(_StreamingSlots):
         S = self.S
         self.K, self.max_length = K, N
         with self._eval():
-            self.bj = BeamStreamJoint(model.joint, K, token_times=bool(token_times), context=context, lm=lm)
+            self.bj = self._make_joint(model, K, context, lm)
             dev = next(model.parameters()).device
             self.bj.begin(S, self.Te, N, device=dev)
-            W1 = self.bj.W1 if self.bj.engine else model.joint.W1
+            W1 = self.bj.W1 if self.bj.engine else self.bj.joint.W1
             self.ps = PredictionStep(model.prediction, W1)
             self.pp = self.ps.begin(S * K)
         self.dev = self.bj.parents.device
+
+    def _make_joint(self, model, K, context, lm):
+        """The stream joint the decoder steps (a subclass decodes another kind of joint: tdt.StreamingTDTBeamDecoder)."""
+        return BeamStreamJoint(model.joint, K, token_times=self.token_times, context=context, lm=lm)
 
     @torch.no_grad()
     def start(self, slots) -> None:
@@ -727,9 +731,10 @@ class StreamingTranscriber:
     of a StreamingBeamDecoder when `beam` is given.  The decoder is sized by the front end's max_rows; decoder_kwargs go to it
     (max_length, max_symbols_per_frame, check_every for greedy; max_length for beam).  context=biasing.ContextGraph (beam search
     only): contextual biasing, as StreamingBeamDecoder takes it; lm=lm.NgramLM (beam search only): LM shallow fusion, likewise.
-    tdt_durations=[...] (greedy only; together with beam: ValueError): the model is a token-and-duration transducer with that
-    duration set, and the decoder is a tdt.StreamingTDTGreedyDecoder (decoder_kwargs: joint, max_length, max_symbols_per_frame,
-    check_every).
+    tdt_durations=[...] (together with beam: ValueError): the model is a token-and-duration transducer with that duration set,
+    and the decoder is a tdt.StreamingTDTGreedyDecoder (decoder_kwargs: joint, max_length, max_symbols_per_frame, check_every) or,
+    with tdt_beam=K, a tdt.StreamingTDTBeamDecoder of beam K (decoder_kwargs: joint, max_length, token_times; no context= / lm=,
+    and no words(): its beams keep frames and durations, not per-token log-probabilities).
 
     start(slots) starts a stream in the given slots of both; feed(audio [slots, N], samples [slots], final [slots]) (N <=
     max_chunk_samples; samples and final are host data) returns what the decoder's feed returns for the rows this audio
@@ -738,11 +743,16 @@ class StreamingTranscriber:
     features.running_mean_log_mel for it.  A stream's result is bitwise independent of how its audio was chunked."""
 
     def __init__(self, model, hp, sample_rate, slots: int, max_chunk_samples: int, beam: Optional[int] = None,
-                 norm: str = "running", context=None, lm=None, tdt_durations=None, **decoder_kwargs):
+                 norm: str = "running", context=None, lm=None, tdt_durations=None, tdt_beam: Optional[int] = None, **decoder_kwargs):
         from .features import StreamingFrontEnd
 
         if tdt_durations is not None and beam is not None:
-            raise ValueError("tdt_durations= is greedy decoding: there is no TDT beam search, build the StreamingTranscriber without beam=")
+            raise ValueError("tdt_durations= does not go with beam=: the TDT beam search is tdt_beam=K, build the StreamingTranscriber "
+                             "without beam=")
+        if tdt_beam is not None and tdt_durations is None:
+            raise ValueError("tdt_beam= needs the model's duration set: build the StreamingTranscriber with tdt_durations=")
+        if tdt_beam is not None and (context is not None or lm is not None):
+            raise ValueError("context= and lm= are not taken by the TDT beam search (tdt_beam=)")
 
         if context is not None and beam is None:
             raise ValueError("context= needs beam search: build the StreamingTranscriber with beam=")
@@ -752,7 +762,11 @@ class StreamingTranscriber:
         dev = next(model.parameters()).device
         self.hp, self.sample_rate = hp, sample_rate
         self.front = StreamingFrontEnd(hp, sample_rate, slots, max_chunk_samples, int(model.encoder.reduce.factor), norm, device=dev)
-        if tdt_durations is not None:
+        if tdt_beam is not None:
+            from .tdt import StreamingTDTBeamDecoder
+
+            self.decoder = StreamingTDTBeamDecoder(model, tdt_durations, slots, self.front.max_rows, beam=tdt_beam, **decoder_kwargs)
+        elif tdt_durations is not None:
             from .tdt import StreamingTDTGreedyDecoder
 
             self.decoder = StreamingTDTGreedyDecoder(model, tdt_durations, slots, self.front.max_rows, **decoder_kwargs)
@@ -793,6 +807,8 @@ class StreamingTranscriber:
         from .features import CharEncoder
 
         dec = self.decoder
+        if getattr(dec, "durations", None) is not None and hasattr(dec, "nbest"):
+            raise RuntimeError("words() needs per-token log-probabilities, which the TDT beam search (tdt_beam=) does not keep")
         if hasattr(dec, "timed_stable_lengths"):  # beam: one results call gives the best hypothesis and the timed stable length
             r = dec._timed()
             ids, frames, logp, stable = r[0][slot, 0].cpu(), r[4][slot, 0].cpu(), r[5][slot, 0].cpu(), int(r[6][slot])

@@ -2,7 +2,8 @@
 decoding: batched (TDTGreedyJoint / tdt_greedy_search_batch on include/rnnt_tdt_greedy.h, libwarprnnt_tdtgreedy.so), over live
 streams fed chunk by chunk (TDTGreedyStreamJoint / StreamingTDTGreedyDecoder on include/rnnt_tdt_stream.h, libwarprnnt_tdtstream.so)
 and as a host loop over one utterance (tdt_greedy_decode); batched beam search with n-best lists (TDTBeamJoint /
-tdt_beam_search_batch on include/rnnt_tdt_beam.h, libwarprnnt_tdtbeam.so); and forced alignment on the same lattice (rnnt_align_tdt / tdt_align_joint
+tdt_beam_search_batch on include/rnnt_tdt_beam.h, libwarprnnt_tdtbeam.so) and the same search over live streams (TDTBeamStreamJoint /
+StreamingTDTBeamDecoder on include/rnnt_tdt_beam_stream.h, libwarprnnt_tdtbeamstream.so); and forced alignment on the same lattice (rnnt_align_tdt / tdt_align_joint
 on include/rnnt_tdt_align.h, libwarprnnt_tdtalign.so): per label of a given transcript the frame that emits it and the frames it claims.
 
 The joint of a TDT model emits V token logits and D duration logits per lattice cell: acts [B, T, U, V + D].  An edge of the lattice
@@ -578,6 +579,7 @@ class TDTBeamJoint:
         if self.engine:
             self.dtype, self.Jp, self.W1, self.b1, self.W2, self.b2 = g.dtype, g.Jp, g.W1, g.b1, g.W2, g.b2
         self._ws = None
+        self._N = None  # (the stream: the tokens a hypothesis may hold)
 
     def _args(self):
         return self.Jp, self.V, self.D, self.B, self.K, self.dtype, int(self.token_times), self._ws.data_ptr(), self._opts
@@ -661,24 +663,8 @@ class TDTBeamJoint:
         rows = {}
         if active:
             idx = torch.tensor(active, device=self._enc.device)
-            e = self._enc[:, min(t, self.T - 1)][idx // K]
-            lg = _cell_logits(self.joint, e, None if pred is None else pred[idx], None if pred_proj is None else pred_proj[idx])
-            tok, dur = lg[:, :V], lg[:, V:]
-            lt, ld = torch.logsumexp(tok.double(), -1).tolist(), torch.logsumexp(dur.double(), -1).tolist()
-            clean = torch.where(torch.isnan(tok) | (tok == _NEG_INF), torch.full_like(tok, _NEG_INF), tok)
-            top_l, top_v = torch.sort(clean, dim=-1, descending=True, stable=True)  # (logit descending, symbol ascending)
-            top_l, top_v = top_l[:, :K], top_v[:, :K]
-            top_v = torch.where(top_l > _NEG_INF, top_v, torch.full_like(top_v, -1))
-            if K > V:
-                top_l = torch.nn.functional.pad(top_l, (0, K - V), value=_NEG_INF)
-                top_v = torch.nn.functional.pad(top_v, (0, K - V), value=-1)
-            for out, val in ((topk_logits, top_l), (topk_symbols, top_v), (dur_logits, dur)):
-                if out is not None:
-                    out[idx] = val.to(out.dtype)
-            if lse_out is not None:
-                lse_out[idx] = torch.tensor(list(zip(lt, ld)), dtype=lse_out.dtype, device=lse_out.device)
-            for n, r in enumerate(active):
-                rows[r] = (top_l[n].tolist(), top_v[n].tolist(), dur[n].tolist(), lt[n], ld[n])
+            rows = self._torch_rows(active, idx, self._enc[:, min(t, self.T - 1)][idx // K], pred, pred_proj, topk_logits,
+                                    topk_symbols, dur_logits, lse_out)
         for b in range(B):
             if t < self._Tb[b]:
                 self._torch_rank(b, t, rows, parents, emitted)
@@ -686,6 +672,31 @@ class TDTBeamJoint:
         self.parents = torch.tensor(parents, dtype=torch.int32, device=dev)
         self.emitted = torch.tensor(emitted, dtype=torch.int32, device=dev)
         return self.parents, self.emitted
+
+    def _torch_rows(self, active, idx, e, pred, pred_proj, topk_logits, topk_symbols, dur_logits, lse_out):
+        """The joint of the active rows `active` (idx: the same as a tensor; e [rows, H]: each row's encoder frame) -> per row its
+        token top-K, duration logits, both logsumexps and the blank's logit; the diagnostics are written on the way."""
+        K, V = self.K, self.V
+        rows = {}
+        lg = _cell_logits(self.joint, e, None if pred is None else pred[idx], None if pred_proj is None else pred_proj[idx])
+        tok, dur = lg[:, :V], lg[:, V:]
+        lt, ld = torch.logsumexp(tok.double(), -1).tolist(), torch.logsumexp(dur.double(), -1).tolist()
+        clean = torch.where(torch.isnan(tok) | (tok == _NEG_INF), torch.full_like(tok, _NEG_INF), tok)
+        top_l, top_v = torch.sort(clean, dim=-1, descending=True, stable=True)  # (logit descending, symbol ascending)
+        top_l, top_v = top_l[:, :K], top_v[:, :K]
+        top_v = torch.where(top_l > _NEG_INF, top_v, torch.full_like(top_v, -1))
+        if K > V:
+            top_l = torch.nn.functional.pad(top_l, (0, K - V), value=_NEG_INF)
+            top_v = torch.nn.functional.pad(top_v, (0, K - V), value=-1)
+        for out, val in ((topk_logits, top_l), (topk_symbols, top_v), (dur_logits, dur)):
+            if out is not None:
+                out[idx] = val.to(out.dtype)
+        if lse_out is not None:
+            lse_out[idx] = torch.tensor(list(zip(lt, ld)), dtype=lse_out.dtype, device=lse_out.device)
+        bl = tok[:, self.blank].tolist()
+        for n, r in enumerate(active):
+            rows[r] = (top_l[n].tolist(), top_v[n].tolist(), dur[n].tolist(), lt[n], ld[n], bl[n])
+        return rows
 
     def _torch_rank(self, b, t, rows, parents, emitted):
         K, blank = self.K, self.blank
@@ -695,7 +706,9 @@ class TDTBeamJoint:
             if c != t:
                 cands.append((s, i, -1, 0))
                 continue
-            top_l, top_v, dur, lt, ld = rows[b * K + i]
+            top_l, top_v, dur, lt, ld, bl = rows[b * K + i]
+            if self._N is not None and len(y) >= self._N:  # the stream: a full hypothesis offers its blank alone
+                top_l, top_v = [bl], [blank]
             mine = []
             for l, v in zip(top_l, top_v):
                 if v < 0:
@@ -732,7 +745,7 @@ class TDTBeamJoint:
             parents[b * K + k], emitted[b * K + k] = b * K + m[4], m[5]
 
     def _torch_results(self):
-        B, K, T = self.B, self.K, self.T
+        B, K, T = self.B, self.K, (self.T if self._N is None else self._N)
         hyps = torch.zeros(B, K, T, dtype=torch.int32)
         lengths = torch.zeros(B, K, dtype=torch.int32)
         scores = torch.full((B, K), -math.inf, dtype=torch.float64)
@@ -959,6 +972,233 @@ class StreamingTDTGreedyDecoder(_decoding.StreamingGreedyDecoder):
 
     def _make_joint(self, model):
         return TDTGreedyStreamJoint(self._joint, self.durations)
+
+
+# ---- streaming beam search ----------------------------------------------------------------------------------------------
+class TDTBeamStreamJoint(TDTBeamJoint):
+    """The joint of the streaming TDT beam search (StreamingTDTBeamDecoder): TDTBeamJoint's step over `slots` streams whose encoder
+    frames arrive chunk by chunk, each slot keeping its beam from one feed to the next, as joint.BeamStreamJoint is BeamJoint's.
+    The rule: include/rnnt_tdt_beam_stream.h.
+
+    Device tensors on shapes the library takes run the ENGINE (compute_rnnt_tdt_beam_stream_begin / _feed / _step / _results,
+    libwarprnnt_tdtbeamstream.so): the object owns the workspace; W1 / b1, every slot's frame base and every hypothesis's cursor
+    live in it.  CPU tensors, and shapes the library refuses (at construction or at begin), run the same rule in torch with float64
+    scores: TDTBeamJoint's rank and merge code, the capacity rule and both stable lengths included.
+
+    begin(slots, max_chunk_frames (encoder frames per feed), max_hyp_len (the tokens a stream's hypothesis may hold)) leaves every
+    slot finished with an empty beam; feed(enc [slots, Te, H], frames [slots], reset, final) hands every slot its chunk (int
+    vectors, lists or None); then step(pred_proj=...) once per encoder frame of the longest chunk (host data: nothing is polled),
+    each followed by a prediction-network step -- after the last frame too.  What a hypothesis's duration jump reaches beyond the
+    chunk its slot holds is carried into the slot's next chunks.  results() -> (hyps [slots, beam, max_hyp_len] zero-padded,
+    lengths [slots, beam], scores [slots, beam], stable [slots], cursors [slots, beam]) at any time, and with token_times=True
+    three more: frames, durations int32 [slots, beam, max_hyp_len] (-1 padded) and timed_stable [slots].  Cursors and frames count
+    from the slot's reset; stable is the common token prefix of a slot's hypotheses, timed_stable the prefix on which they agree
+    in frame and duration too."""
+
+    MAX_ROWS, MAX_WIDTH = 1024, 4096  # slots * beam: the prediction network's rows; the encoder width
+
+    def _args(self):
+        return self.Jp, self.V, self.D, self.B, self.K, self.N, self.dtype, int(self.token_times), self._ws.data_ptr(), self._opts
+
+    def begin(self, slots: int, max_chunk_frames: int, max_hyp_len: int, device=None):
+        S, T, N, K = int(slots), int(max_chunk_frames), int(max_hyp_len), self.K
+        if S < 1 or S * K > self.MAX_ROWS:
+            raise ValueError(f"slots * beam must be in 1 ... {self.MAX_ROWS}, got {S} * {K}")
+        if T < 1 or N < 1:
+            raise ValueError("max_chunk_frames and max_hyp_len must be >= 1")
+        dev = self.W2.device if self.engine else (device if device is not None else self.joint.W2.device)
+        self.B, self.T, self.Tc, self.N, self._N = S, T, T, N, N
+        self.parents = torch.arange(S * K, dtype=torch.int32, device=dev)
+        self.emitted = torch.full((S * K,), -1, dtype=torch.int32, device=dev)
+        if self.engine:
+            self.H = int(self.W1.shape[0])
+            words = (6 if self.token_times else 2) * S * K * N
+            if self.H > self.MAX_WIDTH or words >= 2**31 or S * T * self.Jp >= 2**31:
+                self.engine = False  # (what only the stream refuses: the torch route takes it)
+        if not self.engine:
+            self._sdtype = torch.promote_types(self.joint.W2.dtype, torch.float32)
+            self._beams = [[] for _ in range(S)]
+            self._base, self._ct, self._Tb, self._fin = [0] * S, [0] * S, [0] * S, [True] * S
+            self._enc = None
+            return
+        dur = (ctypes.c_int * self.D)(*self.durations)
+        with torch.cuda.device(dev):
+            nbytes = _lib.tdt_beam_stream_workspace_bytes(T, S, K, N, self.H, self.Jp, self.V, self.D, self.dtype, self.token_times)
+            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
+                self._ws = _joint._new_workspace(nbytes, dev)
+            elif _joint._WORKSPACE_FILL is not None:
+                self._ws.fill_(int(_joint._WORKSPACE_FILL))
+            self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
+            st = _lib.load_tdtbeamstream().compute_rnnt_tdt_beam_stream_begin(
+                self.W1.data_ptr(), self.b1.data_ptr(), self.W2.data_ptr(), self.b2.data_ptr(), self.H, self.Jp, self.V, dur, self.D,
+                S, K, N, self.dtype, int(self.token_times), self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_tdt_beam_stream_begin")
+
+    def feed(self, enc, frames, reset=None, final=None):
+        """enc [slots, Te, H] (None or Te = 0: no frames), frames [slots] encoder frames per slot, reset / final [slots] or None."""
+        S = self.B
+        Te = 0 if enc is None else int(enc.shape[1])
+        if Te > self.Tc:
+            raise ValueError(f"a feed takes at most {self.Tc} encoder frames, got {Te}")
+        if not self.engine:
+            return self._torch_feed(enc, Te, frames, reset, final)
+        dev = self.parents.device
+        if Te > 0:
+            enc = _joint._aligned16(enc.to(device=dev, dtype=torch.float32))
+            if tuple(enc.shape) != (S, Te, self.H):
+                raise ValueError(f"enc must be [{S}, frames, {self.H}], got {tuple(enc.shape)}")
+        cv = lambda x: None if x is None else _joint._device_i32(x, dev).reshape(S)  # noqa: E731
+        fr, rs, fi = cv(frames), cv(reset), cv(final)
+        self._feed_args = (enc, fr, rs, fi)  # (alive until the launches have read them)
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        st = _lib.load_tdtbeamstream().compute_rnnt_tdt_beam_stream_feed(
+            ptr(enc) if Te > 0 else None, Te, fr.data_ptr(), ptr(rs), ptr(fi), self.H, self.Jp, self.V, self.D, S, self.K, self.N,
+            self.dtype, int(self.token_times), self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_tdt_beam_stream_feed")
+
+    def step(self, pred=None, topk_logits=None, topk_symbols=None, dur_logits=None, lse=None, *, pred_proj=None):
+        """One frame of every slot that has one left -> (parents, emitted), int32 [slots beam]; the other slots are frozen."""
+        if not self.engine:
+            return self._torch_step(pred, pred_proj, topk_logits, topk_symbols, dur_logits, lse)
+        pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _joint._projected_operand(pred_proj, self.Jp)
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        st = _lib.load_tdtbeamstream().compute_rnnt_tdt_beam_stream_step(
+            pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(), ptr(topk_logits), ptr(topk_symbols), ptr(dur_logits),
+            ptr(lse), *self._args())
+        _lib.check(st, "compute_rnnt_tdt_beam_stream_step")
+        return self.parents, self.emitted
+
+    def results(self):
+        S, K, N = self.B, self.K, self.N
+        if not self.engine:
+            return self._torch_stream_results()
+        dev = self.parents.device
+        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)  # noqa: E731
+        hyps, lengths, cursors, stable = i32(S, K, N), i32(S, K), i32(S, K), i32(S)
+        scores = torch.empty(S, K, dtype=torch.float32, device=dev)
+        frames, durs, tstable = (i32(S, K, N), i32(S, K, N), i32(S)) if self.token_times else (None, None, None)
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        st = _lib.load_tdtbeamstream().compute_rnnt_tdt_beam_stream_results(
+            hyps.data_ptr(), lengths.data_ptr(), scores.data_ptr(), cursors.data_ptr(), stable.data_ptr(), ptr(frames), ptr(durs),
+            ptr(tstable), *self._args())
+        _lib.check(st, "compute_rnnt_tdt_beam_stream_results")
+        out = (hyps, lengths, scores, stable, cursors)
+        return out + (frames, durs, tstable) if self.token_times else out
+
+    def cursors(self):
+        return self.results()[4]
+
+    # ---- torch composition: cursors and frames are kept from the slot's reset (frame base + chunk-local), which is the rule of
+    # include/rnnt_tdt_beam_stream.h read from outside: nothing needs rebasing at a feed
+    def _torch_feed(self, enc, Te, frames, reset, final):
+        S = self.B
+        vec = lambda x: [0] * S if x is None else [int(v) for v in torch.as_tensor(x).reshape(S).tolist()]  # noqa: E731
+        fr, rs, fi = vec(frames), vec(reset), vec(final)
+        for s in range(S):
+            if rs[s]:
+                self._beams[s], self._base[s], self._fin[s] = [((), 0, 0.0, ())], 0, False
+            elif not self._fin[s]:
+                self._base[s] += self._Tb[s]
+            self._ct[s] = 0
+            if self._fin[s]:
+                self._Tb[s] = 0
+            else:
+                self._Tb[s] = min(max(fr[s], 0), Te)
+                self._fin[s] = bool(fi[s])  # (after this chunk; a carry beyond it is dropped)
+        self._enc = enc
+
+    def _torch_step(self, pred, pred_proj, topk_logits, topk_symbols, dur_logits, lse_out):
+        S, K = self.B, self.K
+        parents, emitted = list(range(S * K)), [-1] * (S * K)
+        live = [s for s in range(S) if self._ct[s] < self._Tb[s]]
+        now = {s: self._base[s] + self._ct[s] for s in live}  # the frame since the slot's reset
+        active = [s * K + i for s in live for i, h in enumerate(self._beams[s]) if h[1] == now[s]]
+        rows = {}
+        if active:
+            idx = torch.tensor(active, device=self._enc.device)
+            at = torch.tensor([self._ct[r // K] for r in active], device=self._enc.device)
+            rows = self._torch_rows(active, idx, self._enc[idx // K, at], pred, pred_proj, topk_logits, topk_symbols, dur_logits,
+                                    lse_out)
+        for s in live:
+            self._torch_rank(s, now[s], rows, parents, emitted)
+            self._ct[s] += 1
+        dev = self.parents.device
+        self.parents = torch.tensor(parents, dtype=torch.int32, device=dev)
+        self.emitted = torch.tensor(emitted, dtype=torch.int32, device=dev)
+        return self.parents, self.emitted
+
+    def _torch_stream_results(self):
+        hyps, lengths, scores, cursors, frames, durs = self._torch_results()
+        stable, tstable = [], []
+        for beam in self._beams:
+            n = m = min((len(h[0]) for h in beam), default=0)
+            for p in range(n - 1, -1, -1):
+                if any(h[0][p] != beam[0][0][p] for h in beam):
+                    n = p
+                if any(h[0][p] != beam[0][0][p] or h[3][p] != beam[0][3][p] for h in beam):
+                    m = p
+            stable.append(n)
+            tstable.append(m)
+        dev = self.parents.device
+        out = (hyps, lengths, scores, torch.tensor(stable, dtype=torch.int32, device=dev), cursors)
+        return out + (frames, durs, torch.tensor(tstable, dtype=torch.int32, device=dev)) if self.token_times else out
+
+
+class StreamingTDTBeamDecoder(_decoding.StreamingBeamDecoder):
+    """TDT beam search (one symbol per frame, include/rnnt_tdt_beam_stream.h) of up to `slots` live audio streams at once, fed chunk
+    by chunk: the streaming counterpart of tdt_beam_search_batch.  Its constructor, slot handling, feed loop and results ARE
+    decoding.StreamingBeamDecoder's -- start(slots), feed(mel_chunk, frames, final) -> (ids, lengths, stable), hypotheses(),
+    nbest() --; only the joint differs (_make_joint): a TDTBeamStreamJoint.  context= and lm= are not taken.
+
+    durations: the duration set of the model.  joint: an object with W1, b1, W2 [J, V + D], b2 and blank_label (TDTGreedyJoint's
+    `joint`); None: model.joint.  max_length: the tokens a stream's hypothesis may hold (StreamingBeamDecoder's rule: a full
+    hypothesis goes on through blanks alone).
+
+    token_times=True: timed_nbest() -> (ids, lengths, scores, frames, durations), frames and durations int32 [slots, beam, N] (-1
+    padded; per token the encoder frame since the slot's start that emitted it and the frames it claims) in place of
+    StreamingBeamDecoder's log-probabilities, which the TDT beams do not keep; timed_hypotheses() -> the best (ids, frames,
+    durations); timed_stable_lengths() -> the prefix of every slot on which its hypotheses agree in token, frame and duration.
+    cursors() -> int32 [slots, beam]: the next frame since the slot's start every hypothesis reads.
+
+    A hypothesis's duration jump beyond the frames its slot has so far is carried into the slot's next feeds, so a stream fed
+    through any chunking, in any slot, beside any other traffic ends with the n-best (ids, lengths, scores, cursors, frames,
+    durations) and both stable lengths of the same stream fed in one call to a 1-slot decoder: bitwise on an MI355X.  beam = 1
+    gives the ids and frames of StreamingTDTGreedyDecoder with max_symbols_per_frame = 1."""
+
+    def __init__(self, model, durations, slots: int, max_chunk_frames: int, beam: int = 4, joint=None, max_length=None,
+                 token_times: bool = False):
+        self.durations = check_durations(durations)
+        self._joint = model.joint if joint is None else joint
+        super().__init__(model, slots, max_chunk_frames, beam=beam, max_length=max_length, token_times=token_times)
+
+    def _make_joint(self, model, K, context, lm):
+        return TDTBeamStreamJoint(self._joint, self.durations, K, token_times=self.token_times)
+
+    def cursors(self):
+        return self.bj.results()[4]
+
+    def bias_states(self):
+        raise RuntimeError("the TDT beam search takes no context graph")
+
+    def lm_states(self):
+        raise RuntimeError("the TDT beam search takes no language model")
+
+    def timed_hypotheses(self):
+        """The best hypothesis of each slot with its times: (ids int32 [slots, N] zero-padded, frames, durations int32 [slots, N]
+        -1 padded).  Needs token_times=True."""
+        r = self._timed()
+        return r[0][:, 0], r[5][:, 0], r[6][:, 0]
+
+    def timed_nbest(self):
+        """(ids [slots, beam, N], lengths [slots, beam], scores [slots, beam], frames [slots, beam, N], durations [slots, beam, N]),
+        best first.  Needs token_times=True."""
+        r = self._timed()
+        return r[0], r[1], r[2], r[5], r[6]
+
+    def timed_stable_lengths(self):
+        """int32 [slots]: the leading tokens of a slot on which every hypothesis of its beam agrees in token, emission frame AND
+        duration.  Never more than feed()'s `stable`.  Needs token_times=True."""
+        return self._timed()[7]
 
 
 # ---- forced alignment on the TDT lattice --------------------------------------------------------------------------------
