@@ -13,7 +13,9 @@ namespace rnnt {
 // (written to `out`, zeros for padded cells; the patch kernels pass out = xs: the LDS image is rewritten in place).
 // LIN: the linear-domain lattice (rnnt_lin.h): edge probabilities instead of log2 weights and no lse store in the lsm pass;
 // in the gradient pass the softmax numerators are recomputed and scaled by occupancies formed from mantissas + frames: `lg`, the
-// cell's lin_grad_setup, which the caller forms (and certifies) before it stages the logits.
+// cell's lin_grad_setup, which the caller forms (and certifies) before it stages the logits.  In the lsm pass `lg` carries one thing:
+// lg->lab, the cell's label as stored (clamped here), which the patch kernels fetch before they stage the logits (LIN: required; log
+// domain: the label is loaded here when lg is null).
 // FE: FastEmit (DESIGN.md "FastEmit"): the label edge's gradient times 1 + lambda through the fused log-softmax -- the softmax term
 // takes occupancy + lambda e_label, the label correction (1 + lambda) e_label; lambda = p.fe_lambda.  FE = false is the plain gradient.
 template <int VP, bool V4, bool GRAD, bool LIN = false, bool SC1 = false, bool FE = false>
@@ -39,7 +41,7 @@ __device__ __forceinline__ float cell_body(const LossParams &p, const Cell &cl, 
         }
 
         if (!GRAD && LIN) {
-            stat = lin_cell_lsm<VP>(p, cl, x, xs);
+            stat = lin_cell_lsm<VP>(p, cl, x, xs, clamp_label(lg->lab, V));
         } else if (GRAD && LIN) {
             const LinGrad &g = *lg;
             float m = x[0];
@@ -80,7 +82,8 @@ __device__ __forceinline__ float cell_body(const LossParams &p, const Cell &cl, 
             const float ob = blank_stays ? fmaf(xs[p.blank] - m, kLog2e, -lg2s) : kNeg;
             float ol = kNeg;
             if (cl.u < cl.Ub - 1) {
-                const int lab = clamp_label(p.labels[(size_t)cl.b * (p.U - 1) + cl.u], V);
+                // (the patch kernels fetched the label before they staged the logits; the hand-back team passes no `lg`)
+                const int lab = clamp_label(lg ? lg->lab : p.labels[(size_t)cl.b * (p.U - 1) + cl.u], V);
                 ol = fmaf(xs[lab] - m, kLog2e, -lg2s);
             }
             const size_t wi = ((size_t)cl.b * p.Nr + (cl.t + cl.u)) * p.Up + cl.u;

@@ -109,8 +109,26 @@ __global__ __launch_bounds__(256) void cell_tile_kernel(const LossParams p) {
     const uint32_t tt = q1 - bb * (uint32_t)tg.tiles_t;
     const int b = p.b0 + (int)bb;
     const int t0 = (int)tt * tg.TT, u0 = (int)tu * tg.UU;
-    const int Tb = length_T(p, b), Ub = length_U(p, b);
-    if (GRAD && LIN && lin_skip(p, b)) return;  // handed back to the log-domain path: lin_redo_kernel writes this utterance's gradients
+    // Everything the workgroup reads per utterance is asked for in ONE batch of scalar loads and waited for once: the two lengths
+    // and, in the gradient pass of the linear lattice, the four flag words (one 16-byte load), the block length, the likelihood and
+    // cost_scale -- in front of the skip decision.  (One length, then the other, the flags in two trips, then lshift, then lik were
+    // dependent trips in front of the first vector load.)  The empty asm statement takes every loaded word as a read-write
+    // operand: all of them have to be there at that point, and nothing that uses one can be scheduled in front of it.
+    int len_t = p.input_lengths[b], len_l = p.label_lengths[b];
+    LinUtt ut = {};
+    if (GRAD && LIN) {
+        int4 fl = lin_flag_words(p, b);
+        ut.sh = p.lshift[b];
+        ut.mL = p.lik[4 * b];
+        ut.EL = ((const int *)p.lik)[4 * b + 1];
+        float sc = *(p.cost_scale ? p.cost_scale + b : p.lik + 4 * b);  // (no cost_scale: some readable word, replaced below)
+        asm volatile("" : "+s"(len_t), "+s"(len_l), "+s"(fl.x), "+s"(fl.y), "+s"(fl.w), "+s"(ut.sh), "+s"(ut.mL), "+s"(ut.EL), "+s"(sc));
+        ut.scale = p.cost_scale ? sc : 1.0f;
+        if (lin_skip_words(fl)) return;  // handed back to the log-domain path: lin_redo_kernel writes this utterance's gradients
+    } else {
+        asm volatile("" : "+s"(len_t), "+s"(len_l));
+    }
+    const int Tb = min(max(len_t, 1), p.T), Ub = min(max(len_l + 1, 1), p.U);  // length_T / length_U (rnnt_cell.h) of the words above
 
     // The valid part of a patch is a rectangle known to the whole workgroup: no per-cell bookkeeping.
     const int rows_valid = max(0, min(tg.TT, Tb - t0));         // lattice rows with t < T_b
@@ -151,13 +169,14 @@ __global__ __launch_bounds__(256) void cell_tile_kernel(const LossParams p) {
         }
     };
 
-    // LIN lsm: every wave of every patch leaves {sum of the cells' decay statistic, cells} for the sweeps (rnnt_lin.h)
+    // LIN lsm: wave 0 of every patch leaves {sum of its cells' decay statistic, cells} for the sweeps (rnnt_lin.h); the slots of
+    // waves 1 .. 3 keep their place in the table and stay unwritten (the sweeps' stride skips them)
     float2 *const pslot = p.pstat + (size_t)b * p.nPstat + ((size_t)tt * tg.tiles_u + tu) * 4 + wave;
     if (rows_valid == 0 || cols_valid == 0) {
         if (GRAD) {  // an all-padding patch: exact zeros, no reads
             for (int r = wave; r < rows_in; r += 4) store_row(r, nullptr);
         }
-        if (!GRAD && LIN && lane == 0) *pslot = make_float2(0.f, 0.f);
+        if (!GRAD && LIN && wave == 0 && lane == 0) *pslot = make_float2(0.f, 0.f);
         return;
     }
 
@@ -177,11 +196,15 @@ __global__ __launch_bounds__(256) void cell_tile_kernel(const LossParams p) {
     // the patch image, before any LDS-DMA lands there: one 32-bit word per 32 cells (ceil(TT UU / 32) words <= the TT UU V floats
     // of the image), so the LDS allocation -- and with it the workgroups per CU -- stays what it was.
     LinGrad lg = {};
+    // lsm pass: the cell's label depends on (b, u) alone, so it is asked for HERE, in front of the logits, and has arrived with them
+    // (cell_body finds it in lg.lab and clamps it there: clamped here, the load would be waited for on the spot).
+    // u < U_b - 1 <= U - 1: with U == 1 there is no label array and nothing is read.
+    if (!GRAD && cl.valid && cl.u < Ub - 1) lg.lab = p.labels[(size_t)b * (p.U - 1) + cl.u];
     uint32_t lword = ~0u;  // lane j < 8: the liveness word of cells [32 j, 32 j + 32) of the patch
     if (GRAD && LIN) {
         bool live = false;
         if (cl.valid) {
-            lg = lin_grad_setup(p, cl);
+            lg = lin_grad_setup(p, cl, ut);
             if (lg.bad) atomicOr(p.flags + 4 * cl.b + kFlagG, 1);  // (rare) the utterance is redone in the log domain
             live = p.visit_all || !(lg.l2occ <= (float)-kOccFloorWave);
             cl.valid = live;  // a dead cell takes cell_body's padding route: zeros into its slot
@@ -230,6 +253,7 @@ __global__ __launch_bounds__(256) void cell_tile_kernel(const LossParams p) {
     }
     wait_vm0();
     __syncthreads();
+    if (!GRAD) asm volatile("" : "+v"(lg.lab));  // the label fetched above is not looked at (so not waited for) before this point
 
     float stat = 0.f;
     if (AL) {
@@ -238,12 +262,23 @@ __global__ __launch_bounds__(256) void cell_tile_kernel(const LossParams p) {
         const int a = (int)((patch0 + r * row_f) & 3);
         if (GRAD || cl.valid) stat = cell_body<VP, false, GRAD, LIN, false, FE>(p, cl, c, lds + r * row_lds + a + cu * V, lds + r * row_lds + a + cu * V, &lg);
     }
-    if (!GRAD && LIN) {  // wave sums by butterfly (no LDS: the patch image is still being read by other waves)
-        float cnt = cl.valid ? 1.f : 0.f;
-        stat = cl.valid ? stat : 0.f;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) stat += __shfl_xor(stat, off), cnt += __shfl_xor(cnt, off);
-        if (lane == 0) *pslot = make_float2(stat, cnt);
+    if (!GRAD && LIN) {
+        // The sweeps sample wave 0's slot of every patch (pstatStride = 4): only that wave forms its sum, on DPP row operations and
+        // four v_readlane, as joint_fwd_kernel's fwd_put_stat does.  (Every wave ran a six-step __shfl_xor butterfly on the statistic
+        // and on the count -- 12 ds_bpermute round trips in a dependent chain in front of the barrier below -- and stored a slot
+        // that three times out of four nothing reads.)  The count is the wave's valid lanes.
+        if (wave == 0) {
+            const float cnt = (float)__popcll(__ballot(cl.valid));
+            stat = cl.valid ? stat : 0.f;
+            stat += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(stat), 0xB1 /*quad_perm:[1,0,3,2]*/, 0xf, 0xf, true));
+            stat += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(stat), 0x4E /*quad_perm:[2,3,0,1]*/, 0xf, 0xf, true));
+            stat += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(stat), 0x141 /*row_half_mirror*/, 0xf, 0xf, true));
+            stat += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(stat), 0x140 /*row_mirror*/, 0xf, 0xf, true));
+            // every lane of a 16-lane row now holds its row's sum
+            const float sum = (__builtin_amdgcn_readlane(stat, 0) + __builtin_amdgcn_readlane(stat, 16)) +
+                              (__builtin_amdgcn_readlane(stat, 32) + __builtin_amdgcn_readlane(stat, 48));
+            if (lane == 0) *pslot = make_float2(sum, cnt);
+        }
         // The edge probabilities, from the cells' LDS slots to the skewed array DIAGONAL by diagonal: thread j takes row j % TT of
         // patch diagonal j / TT, so TT consecutive lanes store TT consecutive (descending) positions of one row of W -- 64-byte
         // runs at TT = 8 -- where a lane per cell scattered every wave-store over 64 rows (2.9 M 8-byte requests per step at

@@ -40,15 +40,56 @@ __device__ __forceinline__ int frexp_e(float x) { return __builtin_amdgcn_frexp_
 __device__ __forceinline__ float ldexp_f(float x, int e) { return __builtin_ldexpf(x, e); }     // v_ldexp_f32
 
 // True when the utterance's lattice is not (or no longer) in the linear format: the fast gradient pass leaves it alone.
-__device__ __forceinline__ bool lin_skip(const LossParams &p, const int b) {
-    const int *fl = p.flags + 4 * b;
-    return (fl[kFlagA] | fl[kFlagB]) != 0 || fl[kFlagState] == 2;
+// The four flag words of an utterance are one 16-byte (scalar) load: `a || b` on single words was two dependent trips.
+__device__ __forceinline__ bool lin_skip_words(const int4 fl) { return (fl.x | fl.y) != 0 || fl.w == 2; }  // kFlagA, kFlagB, kFlagState
+__device__ __forceinline__ int4 lin_flag_words(const LossParams &p, const int b) { return *(const int4 *)(p.flags + 4 * b); }
+__device__ __forceinline__ bool lin_skip(const LossParams &p, const int b) { return lin_skip_words(lin_flag_words(p, b)); }
+
+// What the gradient pass reads per UTTERANCE (workgroup-uniform: scalar loads), fetched in one batch with the flag words and the
+// lengths at the top of the patch kernel, in front of the decision whether the utterance is skipped.
+struct LinUtt {
+    int sh;       // log2 of the diagonals per frame block the sweeps chose
+    float mL;     // the likelihood: mantissa ...
+    int EL;       // ... and frame
+    float scale;  // cost_scale[b], 1 without one
+};
+
+// ---- where the gradient set-up of cell (b, n = t + u, u) reads: index arithmetic alone, checked on the host over whole lattices
+// (tests/test_cell_prologue_host.py).  The set-up fetches all of it unconditionally, so every index is clamped into its array;
+// a clamp is only ever active for an edge the cell does not have, whose value a select then discards. ----
+struct LinIdx {
+    size_t sk;                  // A, Bt: the cell
+    size_t down;                // Bt: (t + 1, u), row n + 1 (row Nr does not exist: clamped to the cell's own row)
+    size_t diag;                // Bt: (t, u + 1), row n + 1, column u + 1 (column Up does not exist)
+    size_t e00, e10, e11;       // frame tables [B][NCl][64]: (kc, l0), (kc1, l0), (kc1, l1)
+    size_t lab;                 // labels [B][U - 1]: (b, u), u clamped to U - 2; not to be used when U == 1 (no label array)
+};
+__host__ __device__ __forceinline__ LinIdx lin_grad_indices(const int b, const int n, const int u, const int sh, const int l0, const int l1,
+                                                            const int Nr, const int Up, const int NCl, const int U) {
+    LinIdx x;
+    const int n1 = n + 1 < Nr ? n + 1 : Nr - 1, u1 = u + 1 < Up ? u + 1 : Up - 1;
+    x.sk = ((size_t)b * Nr + n) * Up + u;
+    x.down = ((size_t)b * Nr + n1) * Up + u;
+    x.diag = ((size_t)b * Nr + n1) * Up + u1;
+    const int kc = n >> sh, kc1 = (n + 1) >> sh;
+    const int kcc = kc < NCl ? kc : NCl - 1, kc1c = kc1 < NCl ? kc1 : NCl - 1;
+    const int l1c = l1 < 64 ? l1 : 63;
+    const size_t tb = (size_t)b * NCl * 64;
+    x.e00 = tb + (size_t)kcc * 64 + l0;
+    x.e10 = tb + (size_t)kc1c * 64 + l0;
+    x.e11 = tb + (size_t)kc1c * 64 + l1c;
+    const int ul = u < U - 2 ? u : U - 2;
+    x.lab = (size_t)b * (U - 1) + (ul > 0 ? ul : 0);
+    return x;
 }
 
 // ---- lsm: one valid cell, its V logits in x[] (registers) and at xs (its slot of the patch image in LDS) ----
 // Returns -log2 max(p_blank, p_label) of the cell (the decay statistic; 200 where an edge had to be refused).
+// `lab`: the cell's clamped label, fetched by the caller BEFORE it staged the logits (it depends on (b, u) alone; loaded here,
+// between the staging barrier and the edge-store barrier, it cost every workgroup a global-memory round trip with its LDS held);
+// looked at only where u < U_b - 1.
 template <int VP>
-__device__ __forceinline__ float lin_cell_lsm(const LossParams &p, const Cell &cl, const float (&x)[VP], const float *xs) {
+__device__ __forceinline__ float lin_cell_lsm(const LossParams &p, const Cell &cl, const float (&x)[VP], const float *xs, const int lab) {
     float m = x[0];
 #pragma unroll
     for (int i = 1; i < VP; ++i) m = fmaxf(m, x[i]);
@@ -65,7 +106,6 @@ __device__ __forceinline__ float lin_cell_lsm(const LossParams &p, const Cell &c
         if (!(pb >= kTinyEdge)) pb = NAN;  // (also a NaN logit): not representable here -> the sweeps hand the utterance back
     }
     if (cl.u < cl.Ub - 1) {
-        const int lab = clamp_label(p.labels[(size_t)cl.b * (p.U - 1) + cl.u], p.V);
         pl = ex2(fmaf(xs[lab], kLog2e, nml)) * inv;
         if (!(pl >= kTinyEdge)) pl = NAN;
     }
@@ -88,19 +128,27 @@ struct LinGrad {
     int lab;
 };
 
-__device__ __forceinline__ LinGrad lin_grad_setup(const LossParams &p, const Cell &cl) {
+// Everything the cell needs from global memory is asked for in ONE batch -- the cell, both neighbours of the next diagonal, the four
+// frames, the label -- unconditionally and with clamped indices (lin_grad_indices), and waited for once: fetched inside the
+// `t < T_b - 1` / `has_label` branches they were three dependent round trips (to values another XCD wrote write-through) in front of
+// the first logit of every patch -- and the whole life of a dead one.  What was fetched for an edge the cell does not have is
+// replaced by zero BEFORE any arithmetic (the workspace may hold NaN there).
+__device__ __forceinline__ LinGrad lin_grad_setup(const LossParams &p, const Cell &cl, const LinUtt &ut) {
     LinGrad g;
     const int n = cl.t + cl.u;
-    const size_t sk = ((size_t)cl.b * p.Nr + n) * p.Up + cl.u;
-    const float ma = p.A[sk], mb = p.Bt[sk];
-    const int sh = p.lshift[cl.b];  // the block length the sweeps chose for this utterance
-    const int kc = n >> sh, kc1 = (n + 1) >> sh;
     const int l0 = (int)fdiv((uint32_t)cl.u, p.divOG), l1 = (int)fdiv((uint32_t)cl.u + 1u, p.divOG);
-    const size_t tb = (size_t)cl.b * p.NCl * 64;
-    const int ea = p.EA[tb + (size_t)kc * 64 + l0], eb = p.EB[tb + (size_t)kc * 64 + l0];
-    const float mL = p.lik[4 * cl.b];
-    const int EL = ((const int *)p.lik)[4 * cl.b + 1];
-    const float scale = p.cost_scale ? p.cost_scale[cl.b] : 1.0f;
+    const LinIdx ix = lin_grad_indices(cl.b, n, cl.u, ut.sh, l0, l1, p.Nr, p.Up, p.NCl, p.U);
+    const float ma = p.A[ix.sk], mb = p.Bt[ix.sk];
+    const float m_dn = p.Bt[ix.down], m_dg = p.Bt[ix.diag];
+    const int ea = p.EA[ix.e00], eb = p.EB[ix.e00];
+    const int e_dn = p.EB[ix.e10], e_dg = p.EB[ix.e11];
+    // (U == 1: there is no label array and no cell has a label -- some readable word instead of a branch, which would close the batch)
+    const int labw = *(p.U > 1 ? p.labels + ix.lab : (const int *)p.lshift + cl.b);
+    const bool down = cl.t < cl.Tb - 1;
+    g.has_label = cl.u < cl.Ub - 1;
+    const float mL = ut.mL;
+    const int EL = ut.EL;
+    const float scale = ut.scale;
     // alpha / L as (qa, base): mantissas may sit anywhere in the f32 range (a dragged frame), so split before multiplying
     const int xa = frexp_e(ma), xb = frexp_e(mb);
     const float qa = scale * frexp_m(ma) * __builtin_amdgcn_rcpf(mL);
@@ -108,23 +156,20 @@ __device__ __forceinline__ LinGrad lin_grad_setup(const LossParams &p, const Cel
     g.h0 = ldexp_f(qa * frexp_m(mb), base + eb + xb);
     // (a zero mantissa gives -inf: dead; a NaN or infinite likelihood / mantissa gives NaN or +inf: live)
     g.l2occ = lg2(frexp_m(ma) * frexp_m(mb) * __builtin_amdgcn_rcpf(mL)) + (float)(ea + xa + eb + xb - EL);
-    g.has_blank_corr = true;
-    g.hb = 0.f;
-    if (cl.t < cl.Tb - 1) {
-        const float m1 = p.Bt[sk + p.Up];
-        g.hb = ldexp_f(qa * frexp_m(m1), base + p.EB[tb + (size_t)kc1 * 64 + l0] + frexp_e(m1));
-    } else if (cl.u == cl.Ub - 1) {
-        g.hb = ldexp_f(qa, base);  // the terminal transition: beta of the virtual end node is 1
-    } else {
-        g.has_blank_corr = false;
+    {
+        const float m1 = down ? m_dn : 0.f;
+        const int e1 = down ? e_dn : 0;
+        const float via = ldexp_f(qa * frexp_m(m1), base + e1 + frexp_e(m1));
+        const bool term = cl.u == cl.Ub - 1;  // the terminal transition: beta of the virtual end node is 1
+        g.has_blank_corr = down || term;
+        g.hb = down ? via : (term ? ldexp_f(qa, base) : 0.f);
     }
-    g.has_label = cl.u < cl.Ub - 1;
-    g.lab = 0;
-    g.hl = 0.f;
-    if (g.has_label) {
-        g.lab = clamp_label(p.labels[(size_t)cl.b * (p.U - 1) + cl.u], p.V);
-        const float m1 = p.Bt[sk + p.Up + 1];
-        g.hl = ldexp_f(qa * frexp_m(m1), base + p.EB[tb + (size_t)kc1 * 64 + l1] + frexp_e(m1));
+    {
+        const float m1 = g.has_label ? m_dg : 0.f;
+        const int e1 = g.has_label ? e_dg : 0;
+        const float via = ldexp_f(qa * frexp_m(m1), base + e1 + frexp_e(m1));
+        g.lab = g.has_label ? clamp_label(labw, p.V) : 0;
+        g.hl = g.has_label ? via : 0.f;
     }
     // Certificate.  A product or sum below 2^-126 of its frame is flushed (or loses bits as a denormal): alpha^ of this cell is
     // short of alpha by at most ~2^(ea-126), which can reach the likelihood through at most beta(cell); the same for beta^; and
