@@ -32,8 +32,8 @@ _BASE_KERNELS = ("rnnt_kernels.hip", "rnnt_lin_kernels.hip", "joint_kernels.hip"
 # version script exports its own entry points alone: libwarprnnt.so holds nothing of any extension.
 LIBRARIES = {
     "base": Library("rnnt.h", _BASE_KERNELS + ("rnnt_entrypoint.hip",)),
-    # contextual biasing in the beam searches.  The host side of the beam search rests on the base kernels: it links their objects,
-    # with rnnt_bias_entrypoint.hip in place of rnnt_entrypoint.hip
+    # contextual biasing in the beam searches.  The host side of the beam search rests on the base kernels: it links their objects
+    # and its own entry points (the argument checks both boundaries share are in rnnt_decode_host.h)
     "bias": Library("rnnt_bias.h", ("beam_bias_kernels.hip", "rnnt_bias_entrypoint.hip"), _BASE_KERNELS, "rnnt_bias.map"),
     # the loss op on the modified (one symbol per frame) lattice
     "mod": Library("rnnt_modified.h", ("rnnt_mod_kernels.hip", "rnnt_mod_entrypoint.hip"), (), "rnnt_mod.map"),
@@ -49,7 +49,7 @@ LIBRARIES = {
     # the band positions between the two passes of the pruned loss, with a defined order of additions (no workspace)
     "pruneranges": Library("rnnt_prune_ranges.h", ("rnnt_prune_ranges_kernels.hip", "rnnt_prune_ranges_entrypoint.hip"), (),
                            "rnnt_prune_ranges.map"),
-    # n-gram LM shallow fusion in the beam searches: built as "bias" is
+    # n-gram LM shallow fusion in the beam searches: the base kernel objects and its own entry points, as "bias"
     "lm": Library("rnnt_lm.h", ("beam_lm_kernels.hip", "rnnt_lm_entrypoint.hip"), _BASE_KERNELS, "rnnt_lm.map"),
 }
 # More rows of the same table.  tests/test_abi.py pins list(LIBRARIES) to its own nine names and tests/test_abi_tdt.py pins
@@ -63,7 +63,7 @@ ALL_LIBRARIES = {
     **LIBRARIES,
     **MORE_LIBRARIES,
     # batched greedy decoding of the TDT transducer: its own step and update kernels on the greedy decoder's prepare path and
-    # per-hypothesis joint; built as "bias" is
+    # per-hypothesis joint; the base kernel objects and its own entry points, as "bias"
     "tdtgreedy": Library("rnnt_tdt_greedy.h", ("tdt_greedy_kernels.hip", "rnnt_tdt_greedy_entrypoint.hip"), _BASE_KERNELS,
                          "rnnt_tdt_greedy.map"),
 }
@@ -77,14 +77,15 @@ LATER_LIBRARIES = {
     # forced alignment on the TDT lattice: its own cell pass, sweep and back-trace; it borrows nothing
     "tdtalign": Library("rnnt_tdt_align.h", ("rnnt_tdtalign_kernels.hip", "rnnt_tdtalign_entrypoint.hip"), (), "rnnt_tdtalign.map"),
     # batched beam search of the TDT transducer: its own step, select, begin and results kernels on the greedy decoder's prepare
-    # path and per-hypothesis joint; built as "bias" is (nothing of tdt_greedy_kernels.hip is linked)
+    # path and per-hypothesis joint; the base kernel objects and its own entry points, as "bias" (nothing of
+    # tdt_greedy_kernels.hip is linked)
     "tdtbeam": Library("rnnt_tdt_beam.h", ("tdt_beam_kernels.hip", "rnnt_tdt_beam_entrypoint.hip"), _BASE_KERNELS, "rnnt_tdtbeam.map"),
     # the fused TDT joint: its own kernels and the lattice sweeps of the TDT loss, unchanged
     "tdtjoint": Library("rnnt_tdt_joint.h", ("rnnt_tdt_joint_kernels.hip", "rnnt_tdt_joint_entrypoint.hip"),
                         ("rnnt_tdt_kernels.hip",), "rnnt_tdt_joint.map"),
     # beam search of the TDT transducer over a stream of chunks per slot: its own begin, feed, step, select and results kernels (step
     # and select compiled from the text "tdtbeam" compiles: tdt_beam_step_body.h, tdt_beam_select_body.h) on the greedy stream's
-    # projection; built as "bias" is (no object of "tdtbeam" is linked)
+    # projection; the base kernel objects and its own entry points, as "bias" (no object of "tdtbeam" is linked)
     "tdtbeamstream": Library("rnnt_tdt_beam_stream.h", ("tdt_nbest_stream_kernels.hip", "rnnt_tdt_nbest_stream_entrypoint.hip"),
                              _BASE_KERNELS, "rnnt_tdtbeamstream.map"),
 }

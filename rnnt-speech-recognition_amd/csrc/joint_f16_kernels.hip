@@ -1551,9 +1551,6 @@ hipError_t joint_f16_workspace_bytes(int T, int U, int B, int J, int V, size_t *
     return hipSuccess;
 }
 
-bool fill_loss_params(LossParams &p, const float *acts, float *grads, const int *labels, const int *label_lengths,
-                      const int *input_lengths, const float *cost_scale, int V, int B, float *costs, void *workspace,
-                      int maxT, int maxU, int blank);
 hipError_t launch_reduce_f16_backward(float *d_enc, const float *dApart, int n_ut, const LossParams &lp, int J, unsigned *bm_enc, const uint8_t *live8,
                                       float *d_pred, const float *dCpart, int nC, unsigned *bm_pred, float *dW2, const float *dWpart, float *db2,
                                       const float *dbpart, int nR, int V, hipStream_t s);

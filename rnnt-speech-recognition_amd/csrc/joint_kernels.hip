@@ -2252,11 +2252,6 @@ hipError_t joint_workspace_bytes(int T, int U, int B, int J, int V, int joint_dt
     return hipSuccess;
 }
 
-// provided by rnnt_entrypoint.hip
-bool fill_loss_params(LossParams &p, const float *acts, float *grads, const int *labels, const int *label_lengths,
-                      const int *input_lengths, const float *cost_scale, int V, int B, float *costs, void *workspace,
-                      int maxT, int maxU, int blank);
-
 // logits[c][0..V) <- the parked tiles dl[c][0..Vp) (bias included; Vp = 32 or 64)
 __global__ __launch_bounds__(256) void joint_logits_copy_kernel(float *out, const float *dl, const uint32_t cells, const int V, const int Vp) {
     const size_t n = (size_t)cells * (size_t)V;

@@ -190,6 +190,56 @@ inline TileGeom make_tile(int T, int U, int V) {
     return g;
 }
 
+// The loss op's parameter block on a workspace of make_layout(maxT, maxU, B): every pointer into the workspace, the geometry
+// and the dividers.  false: the lattice has 2^31 cells or more, or the workspace is not 256-byte aligned.  Host code, shared by
+// the loss op's entry points and the fused joints (joint_kernels.hip, joint_f16_kernels.hip), whose objects several libraries link.
+inline bool fill_loss_params(LossParams &p, const float *acts, float *grads, const int *labels, const int *label_lengths,
+                             const int *input_lengths, const float *cost_scale, int V, int B, float *costs, void *workspace,
+                             int maxT, int maxU, int blank) {
+    const long long cells = (long long)B * maxT * maxU;
+    if (cells <= 0 || cells >= (1ll << 31)) return false;
+    if (((uintptr_t)workspace & 255) != 0) return false;
+    const WsLayout w = make_layout(maxT, maxU, B);
+    char *ws = (char *)workspace;
+    p.acts = acts;
+    p.grads = grads;
+    p.labels = labels;
+    p.label_lengths = label_lengths;
+    p.input_lengths = input_lengths;
+    p.cost_scale = cost_scale;
+    p.costs = costs;
+    p.lse = (float *)(ws + w.lse);
+    p.W = (float *)(ws + w.W);
+    p.A = (float *)(ws + w.A);
+    p.Bt = (float *)(ws + w.Bt);
+    p.offA = (float *)(ws + w.offA);
+    p.offB = (float *)(ws + w.offB);
+    p.ll = (double *)(ws + w.ll);
+    p.EA = (int *)(ws + w.EA);
+    p.EB = (int *)(ws + w.EB);
+    p.lik = (float *)(ws + w.lik);
+    p.flags = (int *)(ws + w.flags);
+    p.NCl = w.NCl;
+    p.pstat = (float2 *)(ws + w.pstat);
+    p.lshift = (int *)(ws + w.lshift);
+    p.bar = (int *)(ws + w.bar);
+    p.nPstat = w.nPstat;
+    p.pstatStride = 4;
+    p.B = B, p.T = maxT, p.U = maxU, p.V = V, p.blank = blank;
+    p.b0 = 0, p.nb = B;
+    p.precise = 0;
+    p.visit_all = 0;
+    p.fe_lambda = 0.f;
+    p.tile = make_tile(maxT, maxU, V);
+    p.N = w.N, p.Nr = w.Nr, p.Up = w.Up, p.NC = w.NC, p.NG = w.NG;
+    p.cells = (uint32_t)cells;
+    p.divU = make_fastdiv((uint32_t)maxU);
+    p.divT = make_fastdiv((uint32_t)maxT);
+    p.divV = make_fastdiv((uint32_t)V);
+    p.divOG = make_fastdiv((uint32_t)w.OG);
+    return true;
+}
+
 // The fused joints' tanh tables (joint_kernels.hip, joint_f16_kernels.hip; also written by the dense layer's GEMM epilogue,
 // dense_kernels.hip): tab(x) = e^{2x} = 2^(x * kExpTab2Log2e), valid while |x| <= kExpTabLimit (beyond that the table-range flag
 // sends the kernels to the exact tanh on the raw projections).  One definition for the three files that must agree.

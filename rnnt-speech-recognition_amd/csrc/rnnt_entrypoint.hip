@@ -8,7 +8,7 @@
 #include "rnnt_common.h"
 #include "rnnt_lin.h"
 #include "rnnt_align.h"
-#include "rnnt_host.h"
+#include "rnnt_decode_host.h"
 
 using namespace rnnt;
 
@@ -41,36 +41,14 @@ hipError_t launch_joint_logits(const float *enc_proj, const float *pred_proj, co
 hipError_t joint_f16_workspace_bytes(int T, int U, int B, int J, int V, size_t *bytes);
 hipError_t launch_joint_logits_f16(const float *enc_proj, const float *pred_proj, const float *W2, const float *b2, int J, int V,
                                    int B, int T, int U, float *logits, void *workspace, hipStream_t s);
-// greedy_kernels.hip (batched greedy decoding)
-hipError_t greedy_workspace_bytes(int T, int B, int J, int V, int joint_dtype, size_t *bytes);
-hipError_t launch_greedy_begin(const float *enc_proj, const int *frame_lengths, const int *max_symbols, const float *W2,
-                               const float *b2, int J, int V, int B, int T, int max_per_frame, int joint_dtype, void *workspace,
-                               hipStream_t s);
-hipError_t launch_greedy_step(const float *pred_proj, int *hyps, int max_hyp_len, int *hyp_lengths, float *scores, int *emitted,
-                              int *all_done, float *stats, int *hyp_frames, float *hyp_logp, const int *frame_base, int J, int V,
-                              int B, int T, int blank, int joint_dtype, void *workspace, hipStream_t s);
-// beam_kernels.hip (batched modified beam search)
-// (timed: the workspace layout with the {frame, log-probability} rows, and the kernels that keep them)
-hipError_t beam_workspace_bytes(int T, int B, int K, int J, int V, int joint_dtype, bool timed, size_t *bytes);
-hipError_t launch_beam_begin(const float *enc_proj, const int *frame_lengths, const float *W2, const float *b2, int J, int V, int B,
-                             int T, int K, int joint_dtype, bool timed, void *workspace, hipStream_t s);
-hipError_t launch_beam_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits, int *topk_symbols, float *lse,
-                            int J, int V, int B, int T, int K, int N, int blank, int joint_dtype, bool timed, void *workspace,
-                            hipStream_t s);
-hipError_t launch_beam_results(int *hyps, int *hyp_lengths, float *scores, int *stable_lengths, int *hyp_frames, float *hyp_logp,
-                               int *timed_stable_lengths, int J, int V, int B, int T, int K, int N, int joint_dtype, void *workspace,
-                               hipStream_t s);
-hipError_t beam_stream_workspace_bytes(int Tc, int S, int K, int N, int H, int J, int V, int joint_dtype, bool timed, size_t *bytes);
-hipError_t launch_beam_stream_begin(const float *W1, const float *b1, const float *W2, const float *b2, int H, int J, int V, int S,
-                                    int Tc, int K, int N, int joint_dtype, bool timed, void *workspace, hipStream_t s);
-hipError_t launch_beam_stream_feed(const float *enc, int Te, const int *chunk_frames, const int *reset, const int *final_, int H, int J,
-                                   int V, int S, int Tc, int K, int N, int joint_dtype, bool timed, void *workspace, hipStream_t s);
 // prednet_kernels.hip (the prediction-network step of the decoders)
 bool prednet_layout_ok(const rnntPrednetBlock *blocks, int L, int E, int V, int Jp, int R, size_t *bytes);
 hipError_t launch_prednet_begin(const float *emb, const rnntPrednetBlock *blocks, int L, int E, int V, const float *W1, int Jp, int R,
                                 float *out, void *workspace, hipStream_t s);
 hipError_t launch_prednet_step(const int *emitted, const int *parents, float *out, const rnntPrednetBlock *blocks, int L, int E,
                                int V, int Jp, int R, void *workspace, hipStream_t s);
+hipError_t launch_prednet_reset(const int *reset, float *out, const rnntPrednetBlock *blocks, int L, int E, int V, int Jp, int R,
+                                void *workspace, hipStream_t s);
 // encoder_kernels.hip (the encoder's forward pass, state carried across runs)
 bool encoder_layout_ok(const rnntPrednetBlock *blocks, int L, int F, float bn_eps, int ridx, int f, int R, int Tmax, size_t *bytes);
 hipError_t launch_encoder_begin(const rnntPrednetBlock *blocks, int L, int F, const float *bn_mean, const float *bn_var,
@@ -87,16 +65,6 @@ hipError_t launch_lstm_train_fwd(float *gates, const float *W_hh, const float *W
                                  int P, void *workspace, hipStream_t s);
 hipError_t launch_lstm_train_bwd(float *gates, const float *c, const float *dy, const float *W_hh, const float *W_hr, float *dr, int R,
                                  int T, int H, int P, void *workspace, hipStream_t s);
-// prednet_kernels.hip / greedy_kernels.hip (streaming greedy decoding)
-hipError_t launch_prednet_reset(const int *reset, float *out, const rnntPrednetBlock *blocks, int L, int E, int V, int Jp, int R,
-                                void *workspace, hipStream_t s);
-hipError_t greedy_stream_workspace_bytes(int Tc, int S, int H, int J, int V, int joint_dtype, size_t *bytes);
-hipError_t launch_greedy_stream_begin(const float *W1, const float *b1, const float *W2, const float *b2, int H, int J, int V, int S,
-                                      int Tc, int joint_dtype, void *workspace, hipStream_t s);
-hipError_t launch_greedy_stream_feed(const float *enc, int Te, const int *chunk_frames, const int *reset, const int *final_,
-                                     const int *max_symbols, int max_per_frame, int *hyp_lengths, float *scores, int *all_done,
-                                     int *frame_base, int H, int J, int V, int S, int Tc, int joint_dtype, void *workspace,
-                                     hipStream_t s);
 // frontend_kernels.hip (the streaming log-mel front end)
 bool frontend_layout_ok(int K, int S, int L, int step, int M, int stack, int rm, size_t *bytes, int *max_rows);
 hipError_t launch_frontend_begin(const float *window, const float *mel_weights, int K, int S, int L, int step, int M, int stack,
@@ -104,71 +72,6 @@ hipError_t launch_frontend_begin(const float *window, const float *mel_weights, 
 hipError_t launch_frontend_feed(const float *audio, int cs, const int *samples, const int *reset, const int *final_, int norm,
                                 float *rows, int *counts, int K, int S, int L, int step, int M, int stack, int rm, void *workspace,
                                 hipStream_t s);
-}  // namespace rnnt
-
-static rnntStatus_t check_options(const rnntOptions &o) {
-    if (o.loc != RNNT_GPU) return RNNT_STATUS_INVALID_VALUE;  // device-only library: no CPU fallback
-    if (!o.batch_first) return RNNT_STATUS_INVALID_VALUE;
-    if (o.maxT <= 0 || o.maxU <= 0 || o.blank_label < 0) return RNNT_STATUS_INVALID_VALUE;
-    if (o.maxU > kMaxU) return RNNT_STATUS_INVALID_VALUE;  // the wide sweep keeps two diagonals in LDS (include/rnnt.h)
-    return RNNT_STATUS_SUCCESS;
-}
-
-static bool fill_params(LossParams &p, const float *acts, float *grads, const int *labels,
-                        const int *label_lengths, const int *input_lengths, const float *cost_scale, int V,
-                        int B, float *costs, void *workspace, const rnntOptions &o) {
-    const long long cells = (long long)B * o.maxT * o.maxU;
-    if (cells <= 0 || cells >= (1ll << 31)) return false;
-    if (((uintptr_t)workspace & 255) != 0) return false;
-    const WsLayout w = make_layout(o.maxT, o.maxU, B);
-    char *ws = (char *)workspace;
-    p.acts = acts;
-    p.grads = grads;
-    p.labels = labels;
-    p.label_lengths = label_lengths;
-    p.input_lengths = input_lengths;
-    p.cost_scale = cost_scale;
-    p.costs = costs;
-    p.lse = (float *)(ws + w.lse);
-    p.W = (float *)(ws + w.W);
-    p.A = (float *)(ws + w.A);
-    p.Bt = (float *)(ws + w.Bt);
-    p.offA = (float *)(ws + w.offA);
-    p.offB = (float *)(ws + w.offB);
-    p.ll = (double *)(ws + w.ll);
-    p.EA = (int *)(ws + w.EA);
-    p.EB = (int *)(ws + w.EB);
-    p.lik = (float *)(ws + w.lik);
-    p.flags = (int *)(ws + w.flags);
-    p.NCl = w.NCl;
-    p.pstat = (float2 *)(ws + w.pstat);
-    p.lshift = (int *)(ws + w.lshift);
-    p.bar = (int *)(ws + w.bar);
-    p.nPstat = w.nPstat;
-    p.pstatStride = 4;
-    p.B = B, p.T = o.maxT, p.U = o.maxU, p.V = V, p.blank = o.blank_label;
-    p.b0 = 0, p.nb = B;
-    p.precise = 0;
-    p.visit_all = 0;
-    p.fe_lambda = 0.f;
-    p.tile = make_tile(o.maxT, o.maxU, V);
-    p.N = w.N, p.Nr = w.Nr, p.Up = w.Up, p.NC = w.NC, p.NG = w.NG;
-    p.cells = (uint32_t)cells;
-    p.divU = make_fastdiv((uint32_t)o.maxU);
-    p.divT = make_fastdiv((uint32_t)o.maxT);
-    p.divV = make_fastdiv((uint32_t)V);
-    p.divOG = make_fastdiv((uint32_t)w.OG);
-    return true;
-}
-
-namespace rnnt {
-bool fill_loss_params(LossParams &p, const float *acts, float *grads, const int *labels, const int *label_lengths,
-                      const int *input_lengths, const float *cost_scale, int V, int B, float *costs, void *workspace,
-                      int maxT, int maxU, int blank) {
-    rnntOptions o;
-    o.loc = RNNT_GPU, o.stream = nullptr, o.blank_label = blank, o.maxT = maxT, o.maxU = maxU, o.batch_first = true;
-    return fill_params(p, acts, grads, labels, label_lengths, input_lengths, cost_scale, V, B, costs, workspace, o);
-}
 }  // namespace rnnt
 
 extern "C" {
@@ -228,8 +131,8 @@ rnntStatus_t compute_rnnt_loss_fwd(const float *acts, const int *flat_labels, co
                                options);
     if (st != RNNT_STATUS_SUCCESS) return st;
     LossParams p;
-    if (!fill_params(p, acts, nullptr, flat_labels, label_lengths, input_lengths, nullptr, alphabet_size,
-                     minibatch, costs, workspace, options))
+    if (!fill_loss_params(p, acts, nullptr, flat_labels, label_lengths, input_lengths, nullptr, alphabet_size, minibatch, costs,
+                          workspace, options.maxT, options.maxU, options.blank_label))
         return RNNT_STATUS_INVALID_VALUE;
     hipStream_t s = (hipStream_t)options.stream;
     const WsLayout w = make_layout(options.maxT, options.maxU, minibatch);
@@ -258,8 +161,8 @@ rnntStatus_t compute_rnnt_loss_bwd(const float *acts, float *grads, const int *f
                                options);
     if (st != RNNT_STATUS_SUCCESS) return st;
     LossParams p;
-    if (!fill_params(p, acts, grads, flat_labels, label_lengths, input_lengths, cost_scale, alphabet_size,
-                     minibatch, nullptr, workspace, options))
+    if (!fill_loss_params(p, acts, grads, flat_labels, label_lengths, input_lengths, cost_scale, alphabet_size, minibatch, nullptr,
+                          workspace, options.maxT, options.maxU, options.blank_label))
         return RNNT_STATUS_INVALID_VALUE;
     return run_backward(p, (hipStream_t)options.stream);
 }
@@ -281,8 +184,8 @@ static rnntStatus_t loss_flags_call(const float *acts, float *grads, const int *
                                options);
     if (st != RNNT_STATUS_SUCCESS) return st;
     LossParams p;
-    if (!fill_params(p, acts, grads, flat_labels, label_lengths, input_lengths, cost_scale, alphabet_size,
-                     minibatch, costs, workspace, options))
+    if (!fill_loss_params(p, acts, grads, flat_labels, label_lengths, input_lengths, cost_scale, alphabet_size, minibatch, costs,
+                          workspace, options.maxT, options.maxU, options.blank_label))
         return RNNT_STATUS_INVALID_VALUE;
     p.visit_all = (flags & RNNT_VISIT_ALL) ? 1 : 0;
     p.fe_lambda = fastemit_lambda;  // (0: the plain gradient kernels)
@@ -589,18 +492,7 @@ rnntStatus_t compute_rnnt_joint_net_logits(const float *enc, const float *pred, 
 }
 
 
-// Batched greedy decoding (include/rnnt.h).  Everything is checked before anything is enqueued.
-static rnntStatus_t check_greedy(int maxT, int joint_size, int alphabet_size, int minibatch, int joint_dtype, const rnntOptions &o) {
-    if (joint_size <= 0 || alphabet_size <= 0 || minibatch <= 0 || maxT <= 0) return RNNT_STATUS_INVALID_VALUE;
-    if (joint_dtype != 0 && joint_dtype != 1) return RNNT_STATUS_INVALID_VALUE;  // (RNNT_VISIT_ALL means nothing here: refused)
-    const rnntStatus_t st = check_options(o);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    if (o.blank_label >= alphabet_size) return RNNT_STATUS_INVALID_VALUE;
-    size_t n = 0;
-    if (greedy_workspace_bytes(maxT, minibatch, joint_size, alphabet_size, joint_dtype, &n) != hipSuccess) return RNNT_STATUS_INVALID_VALUE;
-    return RNNT_STATUS_SUCCESS;
-}
-
+// Batched greedy decoding (include/rnnt.h).  Everything is checked before anything is enqueued (rnnt_decode_host.h: check_greedy).
 rnntStatus_t get_rnnt_greedy_workspace_size(int maxT, int minibatch, int joint_size, int alphabet_size, int joint_dtype,
                                             size_t *size_bytes) {
     if (!size_bytes) return RNNT_STATUS_INVALID_VALUE;
@@ -652,20 +544,8 @@ rnntStatus_t compute_rnnt_greedy_step_timed(const float *pred_proj, int *hyps, i
 }
 
 
-// Batched beam search (include/rnnt.h).  The checks of the greedy decoder, plus 1 <= beam <= 16; everything is checked before
-// anything is enqueued.
-static rnntStatus_t check_beam(int maxT, int joint_size, int alphabet_size, int minibatch, int beam, int joint_dtype,
-                               const void *workspace, const rnntOptions &o, bool timed = false) {
-    if (!workspace || ((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
-    if (beam < 1 || beam > 16) return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st = check_greedy(maxT, joint_size, alphabet_size, minibatch, joint_dtype, o);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    size_t n = 0;
-    if (beam_workspace_bytes(maxT, minibatch, beam, joint_size, alphabet_size, joint_dtype, timed, &n) != hipSuccess)
-        return RNNT_STATUS_INVALID_VALUE;
-    return RNNT_STATUS_SUCCESS;
-}
-
+// Batched beam search (include/rnnt.h).  Everything is checked before anything is enqueued (rnnt_decode_host.h: check_beam).
+// Kept as it was: the untimed begin, step and results check no alignment, their timed twins further down do.
 rnntStatus_t get_rnnt_beam_workspace_size(int maxT, int minibatch, int beam, int joint_size, int alphabet_size, int joint_dtype,
                                           size_t *size_bytes) {
     if (!size_bytes) return RNNT_STATUS_INVALID_VALUE;
@@ -679,7 +559,8 @@ rnntStatus_t compute_rnnt_beam_begin(const float *enc_proj, const int *frame_len
                                      int joint_size, int alphabet_size, int minibatch, int beam, int joint_dtype, void *workspace,
                                      rnntOptions options) {
     if (!enc_proj || !frame_lengths || !W2 || !b2) return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st = check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options);
+    const rnntStatus_t st =
+        check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options, false);
     if (st != RNNT_STATUS_SUCCESS) return st;
     return from_hip(launch_beam_begin(enc_proj, frame_lengths, W2, b2, joint_size, alphabet_size, minibatch, options.maxT, beam,
                                       joint_dtype, false, workspace, (hipStream_t)options.stream));
@@ -688,18 +569,15 @@ rnntStatus_t compute_rnnt_beam_begin(const float *enc_proj, const int *frame_len
 rnntStatus_t compute_rnnt_beam_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits, int *topk_symbols,
                                     float *lse, int joint_size, int alphabet_size, int minibatch, int beam, int joint_dtype,
                                     void *workspace, rnntOptions options) {
-    if (!pred_proj || !parents || !emitted) return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st = check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    return from_hip(launch_beam_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size,
-                                     minibatch, options.maxT, beam, options.maxT, options.blank_label, joint_dtype, false, workspace,
-                                     (hipStream_t)options.stream));
+    return beam_step_call(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, minibatch, beam,
+                          joint_dtype, workspace, options, false);
 }
 
 rnntStatus_t compute_rnnt_beam_results(int *hyps, int *hyp_lengths, float *scores, int joint_size, int alphabet_size, int minibatch,
                                        int beam, int joint_dtype, void *workspace, rnntOptions options) {
     if (!hyps || !hyp_lengths || !scores) return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st = check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options);
+    const rnntStatus_t st =
+        check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options, false);
     if (st != RNNT_STATUS_SUCCESS) return st;
     return from_hip(launch_beam_results(hyps, hyp_lengths, scores, nullptr, nullptr, nullptr, nullptr, joint_size, alphabet_size,
                                         minibatch, options.maxT, beam, options.maxT, joint_dtype, workspace,
@@ -834,17 +712,6 @@ rnntStatus_t compute_rnnt_prednet_reset(const int *reset, float *pred_proj_out, 
                                          (hipStream_t)options.stream));
 }
 
-static rnntStatus_t check_greedy_stream(int max_chunk_frames, int slots, int enc_width, int joint_size, int alphabet_size,
-                                        int joint_dtype, const void *workspace, const rnntOptions &o) {
-    if (!workspace || ((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st = check_greedy(max_chunk_frames, joint_size, alphabet_size, slots, joint_dtype, o);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    size_t n = 0;
-    if (greedy_stream_workspace_bytes(max_chunk_frames, slots, enc_width, joint_size, alphabet_size, joint_dtype, &n) != hipSuccess)
-        return RNNT_STATUS_INVALID_VALUE;
-    return RNNT_STATUS_SUCCESS;
-}
-
 rnntStatus_t get_rnnt_greedy_stream_workspace_size(int max_chunk_frames, int slots, int enc_width, int joint_size, int alphabet_size,
                                                    int joint_dtype, size_t *size_bytes) {
     if (!size_bytes) return RNNT_STATUS_INVALID_VALUE;
@@ -896,21 +763,8 @@ rnntStatus_t compute_rnnt_greedy_stream_feed_timed(const float *enc, int enc_fra
                                               options.maxT, joint_dtype, workspace, (hipStream_t)options.stream));
 }
 
-// The beam stream (include/rnnt.h).  enc_width 1: step and results do not reach W1 / b1, which follow the beam workspace.
-static rnntStatus_t check_beam_stream(int max_chunk_frames, int slots, int beam, int max_hyp_len, int enc_width, int joint_size,
-                                      int alphabet_size, int joint_dtype, const void *workspace, const rnntOptions &o,
-                                      bool timed = false) {
-    if (!workspace || ((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
-    if (beam < 1 || beam > 16 || slots < 1 || (long long)slots * beam > 1024 || max_hyp_len < 1) return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st = check_greedy(max_chunk_frames, joint_size, alphabet_size, slots, joint_dtype, o);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    size_t n = 0;
-    if (beam_stream_workspace_bytes(max_chunk_frames, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype,
-                                    timed, &n) != hipSuccess)
-        return RNNT_STATUS_INVALID_VALUE;
-    return RNNT_STATUS_SUCCESS;
-}
-
+// The beam stream (include/rnnt.h; rnnt_decode_host.h: check_beam_stream).  The timed entry points further down are the same
+// bodies on the workspace layout that also holds the {frame, log-probability} rows.
 rnntStatus_t get_rnnt_beam_stream_workspace_size(int max_chunk_frames, int slots, int beam, int max_hyp_len, int enc_width,
                                                  int joint_size, int alphabet_size, int joint_dtype, size_t *size_bytes) {
     if (!size_bytes) return RNNT_STATUS_INVALID_VALUE;
@@ -921,56 +775,75 @@ rnntStatus_t get_rnnt_beam_stream_workspace_size(int max_chunk_frames, int slots
                : RNNT_STATUS_INVALID_VALUE;
 }
 
+static rnntStatus_t beam_stream_begin_call(const float *W1, const float *b1, const float *W2, const float *b2, int enc_width,
+                                           int joint_size, int alphabet_size, int slots, int beam, int max_hyp_len, int joint_dtype,
+                                           void *workspace, const rnntOptions &options, bool timed) {
+    if (!W1 || !b1 || !W2 || !b2 || !aligned4(W1) || !aligned4(b1) || !aligned4(W2) || !aligned4(b2)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_beam_stream(options.maxT, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype,
+                                              workspace, options, timed);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_stream_begin(W1, b1, W2, b2, enc_width, joint_size, alphabet_size, slots, options.maxT, beam,
+                                             max_hyp_len, joint_dtype, timed, workspace, (hipStream_t)options.stream));
+}
+
+static rnntStatus_t beam_stream_feed_call(const float *enc, int enc_frames, const int *chunk_frames, const int *reset,
+                                          const int *final_chunk, int enc_width, int joint_size, int alphabet_size, int slots,
+                                          int beam, int max_hyp_len, int joint_dtype, void *workspace, const rnntOptions &options,
+                                          bool timed) {
+    if (!chunk_frames || !aligned4(enc) || !aligned4(chunk_frames) || !aligned4(reset) || !aligned4(final_chunk))
+        return RNNT_STATUS_INVALID_VALUE;
+    if (enc_frames < 0 || enc_frames > options.maxT || (enc_frames > 0 && !enc)) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_beam_stream(options.maxT, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype,
+                                              workspace, options, timed);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_stream_feed(enc, enc_frames, chunk_frames, reset, final_chunk, enc_width, joint_size, alphabet_size,
+                                            slots, options.maxT, beam, max_hyp_len, joint_dtype, timed, workspace,
+                                            (hipStream_t)options.stream));
+}
+
+// timed: hyp_frames and hyp_logp are required; untimed: the three timed outputs are NULL
+static rnntStatus_t beam_stream_results_call(int *hyps, int *hyp_lengths, float *scores, int *stable_lengths, int *hyp_frames,
+                                             float *hyp_logp, int *timed_stable_lengths, int joint_size, int alphabet_size, int slots,
+                                             int beam, int max_hyp_len, int joint_dtype, void *workspace, const rnntOptions &options,
+                                             bool timed) {
+    if (!hyps || !hyp_lengths || !scores || (timed && (!hyp_frames || !hyp_logp))) return RNNT_STATUS_INVALID_VALUE;
+    if (!aligned4(hyps) || !aligned4(hyp_lengths) || !aligned4(scores) || !aligned4(stable_lengths) || !aligned4(hyp_frames) ||
+        !aligned4(hyp_logp) || !aligned4(timed_stable_lengths))
+        return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_beam_stream(options.maxT, slots, beam, max_hyp_len, 1, joint_size, alphabet_size, joint_dtype,
+                                              workspace, options, timed);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return from_hip(launch_beam_results(hyps, hyp_lengths, scores, stable_lengths, hyp_frames, hyp_logp, timed_stable_lengths,
+                                        joint_size, alphabet_size, slots, options.maxT, beam, max_hyp_len, joint_dtype, workspace,
+                                        (hipStream_t)options.stream));
+}
+
 rnntStatus_t compute_rnnt_beam_stream_begin(const float *W1, const float *b1, const float *W2, const float *b2, int enc_width,
                                             int joint_size, int alphabet_size, int slots, int beam, int max_hyp_len, int joint_dtype,
                                             void *workspace, rnntOptions options) {
-    if (!W1 || !b1 || !W2 || !b2 || !aligned4(W1) || !aligned4(b1) || !aligned4(W2) || !aligned4(b2)) return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st = check_beam_stream(options.maxT, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype,
-                                              workspace, options);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    return from_hip(launch_beam_stream_begin(W1, b1, W2, b2, enc_width, joint_size, alphabet_size, slots, options.maxT, beam,
-                                             max_hyp_len, joint_dtype, false, workspace, (hipStream_t)options.stream));
+    return beam_stream_begin_call(W1, b1, W2, b2, enc_width, joint_size, alphabet_size, slots, beam, max_hyp_len, joint_dtype, workspace,
+                                  options, false);
 }
 
 rnntStatus_t compute_rnnt_beam_stream_feed(const float *enc, int enc_frames, const int *chunk_frames, const int *reset,
                                            const int *final_chunk, int enc_width, int joint_size, int alphabet_size, int slots,
                                            int beam, int max_hyp_len, int joint_dtype, void *workspace, rnntOptions options) {
-    if (!chunk_frames || !aligned4(enc) || !aligned4(chunk_frames) || !aligned4(reset) || !aligned4(final_chunk))
-        return RNNT_STATUS_INVALID_VALUE;
-    if (enc_frames < 0 || enc_frames > options.maxT || (enc_frames > 0 && !enc)) return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st = check_beam_stream(options.maxT, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype,
-                                              workspace, options);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    return from_hip(launch_beam_stream_feed(enc, enc_frames, chunk_frames, reset, final_chunk, enc_width, joint_size, alphabet_size,
-                                            slots, options.maxT, beam, max_hyp_len, joint_dtype, false, workspace,
-                                            (hipStream_t)options.stream));
+    return beam_stream_feed_call(enc, enc_frames, chunk_frames, reset, final_chunk, enc_width, joint_size, alphabet_size, slots, beam,
+                                 max_hyp_len, joint_dtype, workspace, options, false);
 }
 
 rnntStatus_t compute_rnnt_beam_stream_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits, int *topk_symbols,
                                            float *lse, int joint_size, int alphabet_size, int slots, int beam, int max_hyp_len,
                                            int joint_dtype, void *workspace, rnntOptions options) {
-    if (!pred_proj || !parents || !emitted) return RNNT_STATUS_INVALID_VALUE;
-    if (!aligned4(pred_proj) || !aligned4(parents) || !aligned4(emitted) || !aligned4(topk_logits) || !aligned4(topk_symbols) ||
-        !aligned4(lse))
-        return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st =
-        check_beam_stream(options.maxT, slots, beam, max_hyp_len, 1, joint_size, alphabet_size, joint_dtype, workspace, options);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    return from_hip(launch_beam_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, slots,
-                                     options.maxT, beam, max_hyp_len, options.blank_label, joint_dtype, false, workspace,
-                                     (hipStream_t)options.stream));
+    return beam_stream_step_call(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, slots, beam,
+                                 max_hyp_len, joint_dtype, workspace, options, false);
 }
 
 rnntStatus_t compute_rnnt_beam_stream_results(int *hyps, int *hyp_lengths, float *scores, int *stable_lengths, int joint_size,
                                               int alphabet_size, int slots, int beam, int max_hyp_len, int joint_dtype,
                                               void *workspace, rnntOptions options) {
-    if (!hyps || !hyp_lengths || !scores) return RNNT_STATUS_INVALID_VALUE;
-    if (!aligned4(hyps) || !aligned4(hyp_lengths) || !aligned4(scores) || !aligned4(stable_lengths)) return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st =
-        check_beam_stream(options.maxT, slots, beam, max_hyp_len, 1, joint_size, alphabet_size, joint_dtype, workspace, options);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    return from_hip(launch_beam_results(hyps, hyp_lengths, scores, stable_lengths, nullptr, nullptr, nullptr, joint_size, alphabet_size,
-                                        slots, options.maxT, beam, max_hyp_len, joint_dtype, workspace, (hipStream_t)options.stream));
+    return beam_stream_results_call(hyps, hyp_lengths, scores, stable_lengths, nullptr, nullptr, nullptr, joint_size, alphabet_size,
+                                    slots, beam, max_hyp_len, joint_dtype, workspace, options, false);
 }
 
 // The timed beam searches (include/rnnt.h): the same checks and launches on the workspace layout that also holds the
@@ -999,16 +872,8 @@ rnntStatus_t compute_rnnt_beam_timed_begin(const float *enc_proj, const int *fra
 rnntStatus_t compute_rnnt_beam_timed_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits, int *topk_symbols,
                                           float *lse, int joint_size, int alphabet_size, int minibatch, int beam, int joint_dtype,
                                           void *workspace, rnntOptions options) {
-    if (!pred_proj || !parents || !emitted) return RNNT_STATUS_INVALID_VALUE;
-    if (!aligned4(pred_proj) || !aligned4(parents) || !aligned4(emitted) || !aligned4(topk_logits) || !aligned4(topk_symbols) ||
-        !aligned4(lse))
-        return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st =
-        check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options, true);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    return from_hip(launch_beam_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size,
-                                     minibatch, options.maxT, beam, options.maxT, options.blank_label, joint_dtype, true, workspace,
-                                     (hipStream_t)options.stream));
+    return beam_step_call(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, minibatch, beam,
+                          joint_dtype, workspace, options, true);
 }
 
 rnntStatus_t compute_rnnt_beam_timed_results(int *hyps, int *hyp_lengths, float *scores, int *hyp_frames, float *hyp_logp,
@@ -1038,57 +903,30 @@ rnntStatus_t get_rnnt_beam_stream_timed_workspace_size(int max_chunk_frames, int
 rnntStatus_t compute_rnnt_beam_stream_timed_begin(const float *W1, const float *b1, const float *W2, const float *b2, int enc_width,
                                                   int joint_size, int alphabet_size, int slots, int beam, int max_hyp_len,
                                                   int joint_dtype, void *workspace, rnntOptions options) {
-    if (!W1 || !b1 || !W2 || !b2 || !aligned4(W1) || !aligned4(b1) || !aligned4(W2) || !aligned4(b2)) return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st = check_beam_stream(options.maxT, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype,
-                                              workspace, options, true);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    return from_hip(launch_beam_stream_begin(W1, b1, W2, b2, enc_width, joint_size, alphabet_size, slots, options.maxT, beam,
-                                             max_hyp_len, joint_dtype, true, workspace, (hipStream_t)options.stream));
+    return beam_stream_begin_call(W1, b1, W2, b2, enc_width, joint_size, alphabet_size, slots, beam, max_hyp_len, joint_dtype, workspace,
+                                  options, true);
 }
 
 rnntStatus_t compute_rnnt_beam_stream_timed_feed(const float *enc, int enc_frames, const int *chunk_frames, const int *reset,
                                                  const int *final_chunk, int enc_width, int joint_size, int alphabet_size, int slots,
                                                  int beam, int max_hyp_len, int joint_dtype, void *workspace, rnntOptions options) {
-    if (!chunk_frames || !aligned4(enc) || !aligned4(chunk_frames) || !aligned4(reset) || !aligned4(final_chunk))
-        return RNNT_STATUS_INVALID_VALUE;
-    if (enc_frames < 0 || enc_frames > options.maxT || (enc_frames > 0 && !enc)) return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st = check_beam_stream(options.maxT, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype,
-                                              workspace, options, true);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    return from_hip(launch_beam_stream_feed(enc, enc_frames, chunk_frames, reset, final_chunk, enc_width, joint_size, alphabet_size,
-                                            slots, options.maxT, beam, max_hyp_len, joint_dtype, true, workspace,
-                                            (hipStream_t)options.stream));
+    return beam_stream_feed_call(enc, enc_frames, chunk_frames, reset, final_chunk, enc_width, joint_size, alphabet_size, slots, beam,
+                                 max_hyp_len, joint_dtype, workspace, options, true);
 }
 
 rnntStatus_t compute_rnnt_beam_stream_timed_step(const float *pred_proj, int *parents, int *emitted, float *topk_logits,
                                                  int *topk_symbols, float *lse, int joint_size, int alphabet_size, int slots, int beam,
                                                  int max_hyp_len, int joint_dtype, void *workspace, rnntOptions options) {
-    if (!pred_proj || !parents || !emitted) return RNNT_STATUS_INVALID_VALUE;
-    if (!aligned4(pred_proj) || !aligned4(parents) || !aligned4(emitted) || !aligned4(topk_logits) || !aligned4(topk_symbols) ||
-        !aligned4(lse))
-        return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st =
-        check_beam_stream(options.maxT, slots, beam, max_hyp_len, 1, joint_size, alphabet_size, joint_dtype, workspace, options, true);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    return from_hip(launch_beam_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, slots,
-                                     options.maxT, beam, max_hyp_len, options.blank_label, joint_dtype, true, workspace,
-                                     (hipStream_t)options.stream));
+    return beam_stream_step_call(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, slots, beam,
+                                 max_hyp_len, joint_dtype, workspace, options, true);
 }
 
 rnntStatus_t compute_rnnt_beam_stream_timed_results(int *hyps, int *hyp_lengths, float *scores, int *stable_lengths, int *hyp_frames,
                                                     float *hyp_logp, int *timed_stable_lengths, int joint_size, int alphabet_size,
                                                     int slots, int beam, int max_hyp_len, int joint_dtype, void *workspace,
                                                     rnntOptions options) {
-    if (!hyps || !hyp_lengths || !scores || !hyp_frames || !hyp_logp) return RNNT_STATUS_INVALID_VALUE;
-    if (!aligned4(hyps) || !aligned4(hyp_lengths) || !aligned4(scores) || !aligned4(stable_lengths) || !aligned4(hyp_frames) ||
-        !aligned4(hyp_logp) || !aligned4(timed_stable_lengths))
-        return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st =
-        check_beam_stream(options.maxT, slots, beam, max_hyp_len, 1, joint_size, alphabet_size, joint_dtype, workspace, options, true);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    return from_hip(launch_beam_results(hyps, hyp_lengths, scores, stable_lengths, hyp_frames, hyp_logp, timed_stable_lengths,
-                                        joint_size, alphabet_size, slots, options.maxT, beam, max_hyp_len, joint_dtype, workspace,
-                                        (hipStream_t)options.stream));
+    return beam_stream_results_call(hyps, hyp_lengths, scores, stable_lengths, hyp_frames, hyp_logp, timed_stable_lengths, joint_size,
+                                    alphabet_size, slots, beam, max_hyp_len, joint_dtype, workspace, options, true);
 }
 
 // The LSTM layer for training (include/rnnt.h).  Everything is checked before anything is enqueued.

@@ -1,9 +1,9 @@
 // rnnt_lm_entrypoint.hip -- the extern "C" boundary of libwarprnnt_lm.so (declared in include/rnnt_lm.h): the LM steps
-// of the four beam searches.  libwarprnnt.so and include/rnnt.h, the base interface, stay as they are.  This translation unit
-// includes rnnt_entrypoint.hip for the base steps' argument checks (they are static there) and for the graph == NULL forward;
-// build.py links it with the kernel objects and beam_lm_kernels.hip, and rnnt_lm.map keeps everything but the four twins
-// local, so the library defines no base entry point a second time.
-#include "rnnt_entrypoint.hip"
+// of the four beam searches.  libwarprnnt.so and include/rnnt.h, the base interface, stay as they are.  The base steps'
+// argument checks and the body of the graph == NULL forward come from rnnt_decode_host.h, shared with rnnt_entrypoint.hip; this
+// unit defines the four twins and nothing else.  build.py links it with the base kernel objects and beam_lm_kernels.hip, and
+// rnnt_lm.map exports the four twins alone.
+#include "rnnt_decode_host.h"
 #include "../../include/rnnt_lm.h"
 
 #include <cmath>
@@ -14,6 +14,8 @@ hipError_t launch_beam_step_lm(const float *pred_proj, int *parents, int *emitte
                                    float *lse, int J, int V, int B, int T, int K, int N, int blank, int joint_dtype, bool timed,
                                    void *workspace, hipStream_t s, const rnntLmGraph *graph, int *lm_states);
 }  // namespace rnnt
+
+using namespace rnnt;
 
 extern "C" {
 
@@ -35,9 +37,7 @@ static rnntStatus_t beam_step_lm(const float *pred_proj, int *parents, int *emit
                                      void *workspace, const rnntOptions &options, bool timed, const rnntLmGraph *graph,
                                      int *lm_states) {
     if (!pred_proj || !parents || !emitted) return RNNT_STATUS_INVALID_VALUE;
-    if (!aligned4(pred_proj) || !aligned4(parents) || !aligned4(emitted) || !aligned4(topk_logits) || !aligned4(topk_symbols) ||
-        !aligned4(lse))
-        return RNNT_STATUS_INVALID_VALUE;
+    if (!beam_step_pointers_aligned(pred_proj, parents, emitted, topk_logits, topk_symbols, lse)) return RNNT_STATUS_INVALID_VALUE;
     rnntStatus_t st = check_lm(graph, lm_states);
     if (st != RNNT_STATUS_SUCCESS) return st;
     st = check_beam(options.maxT, joint_size, alphabet_size, minibatch, beam, joint_dtype, workspace, options, timed);
@@ -52,9 +52,7 @@ static rnntStatus_t beam_stream_step_lm(const float *pred_proj, int *parents, in
                                             int max_hyp_len, int joint_dtype, void *workspace, const rnntOptions &options, bool timed,
                                             const rnntLmGraph *graph, int *lm_states) {
     if (!pred_proj || !parents || !emitted) return RNNT_STATUS_INVALID_VALUE;
-    if (!aligned4(pred_proj) || !aligned4(parents) || !aligned4(emitted) || !aligned4(topk_logits) || !aligned4(topk_symbols) ||
-        !aligned4(lse))
-        return RNNT_STATUS_INVALID_VALUE;
+    if (!beam_step_pointers_aligned(pred_proj, parents, emitted, topk_logits, topk_symbols, lse)) return RNNT_STATUS_INVALID_VALUE;
     rnntStatus_t st = check_lm(graph, lm_states);
     if (st != RNNT_STATUS_SUCCESS) return st;
     st = check_beam_stream(options.maxT, slots, beam, max_hyp_len, 1, joint_size, alphabet_size, joint_dtype, workspace, options, timed);
@@ -68,8 +66,8 @@ rnntStatus_t compute_rnnt_beam_step_lm(const float *pred_proj, int *parents, int
                                            float *lse, int joint_size, int alphabet_size, int minibatch, int beam, int joint_dtype,
                                            void *workspace, rnntOptions options, const rnntLmGraph *graph, int *lm_states) {
     if (!graph)
-        return compute_rnnt_beam_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, minibatch,
-                                      beam, joint_dtype, workspace, options);
+        return beam_step_call(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, minibatch, beam,
+                              joint_dtype, workspace, options, false);
     return beam_step_lm(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, minibatch, beam,
                             joint_dtype, workspace, options, false, graph, lm_states);
 }
@@ -79,8 +77,8 @@ rnntStatus_t compute_rnnt_beam_timed_step_lm(const float *pred_proj, int *parent
                                                  int beam, int joint_dtype, void *workspace, rnntOptions options,
                                                  const rnntLmGraph *graph, int *lm_states) {
     if (!graph)
-        return compute_rnnt_beam_timed_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size,
-                                            minibatch, beam, joint_dtype, workspace, options);
+        return beam_step_call(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, minibatch, beam,
+                              joint_dtype, workspace, options, true);
     return beam_step_lm(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, minibatch, beam,
                             joint_dtype, workspace, options, true, graph, lm_states);
 }
@@ -90,8 +88,8 @@ rnntStatus_t compute_rnnt_beam_stream_step_lm(const float *pred_proj, int *paren
                                                   int max_hyp_len, int joint_dtype, void *workspace, rnntOptions options,
                                                   const rnntLmGraph *graph, int *lm_states) {
     if (!graph)
-        return compute_rnnt_beam_stream_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size,
-                                             slots, beam, max_hyp_len, joint_dtype, workspace, options);
+        return beam_stream_step_call(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, slots,
+                                     beam, max_hyp_len, joint_dtype, workspace, options, false);
     return beam_stream_step_lm(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, slots, beam,
                                    max_hyp_len, joint_dtype, workspace, options, false, graph, lm_states);
 }
@@ -101,8 +99,8 @@ rnntStatus_t compute_rnnt_beam_stream_timed_step_lm(const float *pred_proj, int 
                                                         int beam, int max_hyp_len, int joint_dtype, void *workspace,
                                                         rnntOptions options, const rnntLmGraph *graph, int *lm_states) {
     if (!graph)
-        return compute_rnnt_beam_stream_timed_step(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size,
-                                                   alphabet_size, slots, beam, max_hyp_len, joint_dtype, workspace, options);
+        return beam_stream_step_call(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, slots,
+                                     beam, max_hyp_len, joint_dtype, workspace, options, true);
     return beam_stream_step_lm(pred_proj, parents, emitted, topk_logits, topk_symbols, lse, joint_size, alphabet_size, slots, beam,
                                    max_hyp_len, joint_dtype, workspace, options, true, graph, lm_states);
 }

@@ -21,12 +21,14 @@
 // Everything a kernel reads was written by the kernel in front of it: the workspace may hold anything on entry.
 #pragma once
 #include "rnnt_common.h"
+#include "tdt_host.h"
 
 namespace rnnt {
 
 constexpr int kTdtMaxU = 1024;      // one lattice column per thread of the sweep
 constexpr int kTdtMaxD = 8;         // durations per set
 constexpr int kTdtMaxDuration = 8;  // the largest duration: the sweep's ring holds kTdtMaxDuration + 2 rows
+static_assert(kTdtMaxD == kTdtHostMaxD && kTdtMaxDuration == kTdtHostMaxDuration, "tdt_host.h holds the limits the boundary checks");
 
 struct TdtLayout {
     size_t w, lse, alpha, beta, lnP, total;

@@ -1,9 +1,9 @@
 // rnnt_tdt_beam_entrypoint.hip -- the extern "C" boundary of libwarprnnt_tdtbeam.so (declared in include/rnnt_tdt_beam.h): batched beam
-// search of the token-and-duration (TDT) transducer.  libwarprnnt.so and include/rnnt.h, the base interface, stay as they are.  This
-// translation unit includes rnnt_entrypoint.hip for the beam search's argument checks (they are static there); build.py links it
-// with the base kernel objects and tdt_beam_kernels.hip, and rnnt_tdtbeam.map keeps everything but the four entry points local, so
-// the library defines no base entry point a second time.
-#include "rnnt_entrypoint.hip"
+// search of the token-and-duration (TDT) transducer.  libwarprnnt.so and include/rnnt.h, the base interface, stay as they are.  The
+// argument checks come from rnnt_decode_host.h (the beam search's) and tdt_host.h (the TDT rules); this unit defines the four entry
+// points and nothing else.  build.py links it with the base kernel objects and tdt_beam_kernels.hip, and rnnt_tdtbeam.map exports
+// the four entry points alone.
+#include "tdt_host.h"
 #include "../../include/rnnt_tdt_beam.h"
 
 namespace rnnt {
@@ -20,25 +20,12 @@ hipError_t launch_tdt_beam_results(int *hyps, int *hyp_lengths, float *scores, i
                                    hipStream_t s);
 }  // namespace rnnt
 
-constexpr int kTdtBeamMaxD = 8, kTdtBeamMaxDuration = 8;  // include/rnnt_tdt.h's limits on the duration set
-
-// 2 <= V, 1 <= D <= 8 (V + D cannot overflow: the decoders take no alphabet beyond 8192)
-static bool tdt_beam_heads_ok(int alphabet_size, int num_durations) {
-    return alphabet_size >= 2 && alphabet_size <= (1 << 24) && num_durations >= 1 && num_durations <= kTdtBeamMaxD;
-}
-
-// strictly increasing, durations[0] in {0, 1}, some d > 0, the largest <= 8
-static bool tdt_beam_durations_ok(const int *durations, int num_durations) {
-    if (durations[0] != 0 && durations[0] != 1) return false;
-    for (int i = 1; i < num_durations; ++i)
-        if (durations[i] <= durations[i - 1]) return false;
-    return durations[num_durations - 1] > 0 && durations[num_durations - 1] <= kTdtBeamMaxDuration;
-}
+using namespace rnnt;
 
 // the checks of the beam search at alphabet_size = R, then the blank inside the token head and the workspace's own layout
 static rnntStatus_t check_tdt_beam(int maxT, int joint_size, int alphabet_size, int num_durations, int minibatch, int beam,
                                    int joint_dtype, bool timed, const void *workspace, const rnntOptions &o) {
-    if (!tdt_beam_heads_ok(alphabet_size, num_durations)) return RNNT_STATUS_INVALID_VALUE;
+    if (!tdt_heads_ok(alphabet_size, num_durations)) return RNNT_STATUS_INVALID_VALUE;
     const rnntStatus_t st = check_beam(maxT, joint_size, alphabet_size + num_durations, minibatch, beam, joint_dtype, workspace, o, timed);
     if (st != RNNT_STATUS_SUCCESS) return st;
     if (o.blank_label >= alphabet_size) return RNNT_STATUS_INVALID_VALUE;
@@ -52,7 +39,7 @@ extern "C" {
 
 rnntStatus_t get_rnnt_tdt_beam_workspace_size(int maxT, int minibatch, int beam, int joint_size, int alphabet_size, int num_durations,
                                               int joint_dtype, int timed, size_t *size_bytes) {
-    if (!size_bytes || !tdt_beam_heads_ok(alphabet_size, num_durations)) return RNNT_STATUS_INVALID_VALUE;
+    if (!size_bytes || !tdt_heads_ok(alphabet_size, num_durations)) return RNNT_STATUS_INVALID_VALUE;
     if (joint_dtype != 0 && joint_dtype != 1) return RNNT_STATUS_INVALID_VALUE;
     if (joint_size <= 0 || minibatch <= 0 || maxT <= 0 || beam < 1 || beam > 16) return RNNT_STATUS_INVALID_VALUE;
     return tdt_beam_workspace_bytes(maxT, minibatch, beam, joint_size, alphabet_size, num_durations, joint_dtype, timed != 0,
@@ -68,7 +55,7 @@ rnntStatus_t compute_rnnt_tdt_beam_begin(const float *enc_proj, const int *frame
     const rnntStatus_t st = check_tdt_beam(options.maxT, joint_size, alphabet_size, num_durations, minibatch, beam, joint_dtype,
                                            timed != 0, workspace, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
-    if (!tdt_beam_durations_ok(durations, num_durations)) return RNNT_STATUS_INVALID_VALUE;
+    if (!tdt_durations_ok(durations, num_durations)) return RNNT_STATUS_INVALID_VALUE;
     return from_hip(launch_tdt_beam_begin(enc_proj, frame_lengths, W2, b2, joint_size, alphabet_size, durations, num_durations,
                                           minibatch, options.maxT, beam, joint_dtype, timed != 0, workspace,
                                           (hipStream_t)options.stream));

@@ -1,14 +1,13 @@
 // rnnt_tdt_greedy_entrypoint.hip -- the extern "C" boundary of libwarprnnt_tdtgreedy.so (declared in include/rnnt_tdt_greedy.h):
 // batched greedy decoding of the token-and-duration (TDT) transducer.  libwarprnnt.so and include/rnnt.h, the base interface, stay
-// as they are.  This translation unit includes rnnt_entrypoint.hip for the greedy decoder's argument checks (they are static
-// there); build.py links it with the base kernel objects and tdt_greedy_kernels.hip, and rnnt_tdt_greedy.map keeps everything but
-// the three entry points local, so the library defines no base entry point a second time.
-#include "rnnt_entrypoint.hip"
+// as they are.  The argument checks come from tdt_host.h (the TDT rules, check_tdt_greedy) and, through it, rnnt_decode_host.h
+// (the greedy decoder's); this unit defines the three entry points and nothing else.  build.py links it with the base kernel
+// objects and tdt_greedy_kernels.hip, and rnnt_tdt_greedy.map exports the three entry points alone.
+#include "tdt_host.h"
 #include "../../include/rnnt_tdt_greedy.h"
 
 namespace rnnt {
-// tdt_greedy_kernels.hip
-hipError_t tdt_greedy_workspace_bytes(int T, int B, int J, int Vt, int D, int joint_dtype, size_t *bytes);
+// tdt_greedy_kernels.hip (tdt_host.h: tdt_greedy_workspace_bytes)
 hipError_t launch_tdt_greedy_begin(const float *enc_proj, const int *frame_lengths, const int *max_symbols, const float *W2,
                                    const float *b2, int J, int Vt, const int *durations, int D, int B, int T, int max_per_frame,
                                    int joint_dtype, void *workspace, hipStream_t s);
@@ -17,33 +16,7 @@ hipError_t launch_tdt_greedy_step(const float *pred_proj, int *hyps, int *hyp_fr
                                   int B, int T, int blank, int joint_dtype, void *workspace, hipStream_t s);
 }  // namespace rnnt
 
-constexpr int kTdtGreedyMaxD = 8, kTdtGreedyMaxDuration = 8;  // include/rnnt_tdt.h's limits on the duration set
-
-// 2 <= V, 1 <= D <= 8 (V + D cannot overflow: the greedy decoder takes no alphabet beyond 8192)
-static bool tdt_heads_ok(int alphabet_size, int num_durations) {
-    return alphabet_size >= 2 && alphabet_size <= (1 << 24) && num_durations >= 1 && num_durations <= kTdtGreedyMaxD;
-}
-
-// strictly increasing, durations[0] in {0, 1}, some d > 0, the largest <= 8
-static bool tdt_durations_ok(const int *durations, int num_durations) {
-    if (durations[0] != 0 && durations[0] != 1) return false;
-    for (int i = 1; i < num_durations; ++i)
-        if (durations[i] <= durations[i - 1]) return false;
-    return durations[num_durations - 1] > 0 && durations[num_durations - 1] <= kTdtGreedyMaxDuration;
-}
-
-// the checks of the greedy decoder at alphabet_size = R, then the blank inside the token head and the workspace's own layout
-static rnntStatus_t check_tdt_greedy(int maxT, int joint_size, int alphabet_size, int num_durations, int minibatch, int joint_dtype,
-                                     const rnntOptions &o) {
-    if (!tdt_heads_ok(alphabet_size, num_durations)) return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st = check_greedy(maxT, joint_size, alphabet_size + num_durations, minibatch, joint_dtype, o);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    if (o.blank_label >= alphabet_size) return RNNT_STATUS_INVALID_VALUE;
-    size_t n = 0;
-    if (tdt_greedy_workspace_bytes(maxT, minibatch, joint_size, alphabet_size, num_durations, joint_dtype, &n) != hipSuccess)
-        return RNNT_STATUS_INVALID_VALUE;
-    return RNNT_STATUS_SUCCESS;
-}
+using namespace rnnt;
 
 extern "C" {
 

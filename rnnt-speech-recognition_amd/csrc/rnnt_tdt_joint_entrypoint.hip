@@ -5,7 +5,7 @@
 // caller's stream.
 #include "../../include/rnnt_tdt_joint.h"
 #include "rnnt_tdt_joint.h"
-#include "rnnt_host.h"
+#include "tdt_host.h"
 
 #include <math.h>
 
@@ -18,14 +18,6 @@ static bool shape_ok(int maxT, int maxU, int minibatch, int num_durations, int j
     if (num_durations < 1 || num_durations > kTdtMaxD) return false;
     if (joint_size < 64 || joint_size > kTJMaxJ || joint_size % 64 != 0) return false;
     return (long long)minibatch * maxT * maxU < (1ll << 31);
-}
-
-// strictly increasing, durations[0] in {0, 1}, some d > 0, the largest <= 8
-static bool durations_ok(const int *durations, int num_durations) {
-    if (durations[0] != 0 && durations[0] != 1) return false;
-    for (int i = 1; i < num_durations; ++i)
-        if (durations[i] <= durations[i - 1]) return false;
-    return durations[num_durations - 1] > 0 && durations[num_durations - 1] <= kTdtMaxDuration;
 }
 
 extern "C" {
@@ -55,7 +47,7 @@ rnntStatus_t compute_rnnt_joint_loss_tdt(const float *enc_proj, const float *pre
     if (!shape_ok(options.maxT, options.maxU, minibatch, num_durations, joint_size)) return RNNT_STATUS_INVALID_VALUE;
     if (alphabet_size < 2 || alphabet_size > kTJMaxR - num_durations || options.blank_label < 0 || options.blank_label >= alphabet_size)
         return RNNT_STATUS_INVALID_VALUE;
-    if (!durations_ok(durations, num_durations)) return RNNT_STATUS_INVALID_VALUE;
+    if (!tdt_durations_ok(durations, num_durations)) return RNNT_STATUS_INVALID_VALUE;
     if (((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
     const TdtJointLayout w = make_tdt_joint_layout(options.maxT, options.maxU, minibatch, num_durations, joint_size);
     char *ws = (char *)workspace;

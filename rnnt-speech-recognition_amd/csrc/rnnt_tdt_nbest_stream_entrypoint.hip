@@ -1,9 +1,9 @@
 // rnnt_tdt_nbest_stream_entrypoint.hip -- the extern "C" boundary of libwarprnnt_tdtbeamstream.so (declared in
 // include/rnnt_tdt_beam_stream.h): chunked streaming beam search of the token-and-duration (TDT) transducer.  libwarprnnt.so and
-// include/rnnt.h, the base interface, stay as they are.  This translation unit includes rnnt_entrypoint.hip for the beam stream's
-// argument checks (they are static there); build.py links it with the base kernel objects and tdt_nbest_stream_kernels.hip, and
-// rnnt_tdtbeamstream.map keeps everything but the five entry points local, so the library defines no base entry point a second time.
-#include "rnnt_entrypoint.hip"
+// include/rnnt.h, the base interface, stay as they are.  The argument checks come from rnnt_decode_host.h (the beam
+// stream's) and tdt_host.h (the TDT rules); this unit defines the five entry points and nothing else.  build.py links it with the
+// base kernel objects and tdt_nbest_stream_kernels.hip, and rnnt_tdtbeamstream.map exports the five entry points alone.
+#include "tdt_host.h"
 #include "../../include/rnnt_tdt_beam_stream.h"
 
 namespace rnnt {
@@ -24,27 +24,14 @@ hipError_t launch_tdt_beam_stream_results(int *hyps, int *hyp_lengths, float *sc
                                           int Tc, int K, int N, int joint_dtype, bool timed, void *workspace, hipStream_t s);
 }  // namespace rnnt
 
-constexpr int kTbsMaxD = 8, kTbsMaxDuration = 8;  // include/rnnt_tdt.h's limits on the duration set
-
-// 2 <= V, 1 <= D <= 8 (V + D cannot overflow: the decoders take no alphabet beyond 8192)
-static bool tbs_heads_ok(int alphabet_size, int num_durations) {
-    return alphabet_size >= 2 && alphabet_size <= (1 << 24) && num_durations >= 1 && num_durations <= kTbsMaxD;
-}
-
-// strictly increasing, durations[0] in {0, 1}, some d > 0, the largest <= 8
-static bool tbs_durations_ok(const int *durations, int num_durations) {
-    if (durations[0] != 0 && durations[0] != 1) return false;
-    for (int i = 1; i < num_durations; ++i)
-        if (durations[i] <= durations[i - 1]) return false;
-    return durations[num_durations - 1] > 0 && durations[num_durations - 1] <= kTbsMaxDuration;
-}
+using namespace rnnt;
 
 // the checks of the beam stream at alphabet_size = R, then the blank inside the token head and the workspace's own layout.
 // enc_width 1: step and results do not reach W1 / b1.
-static rnntStatus_t check_tbs(int max_chunk_frames, int slots, int beam, int max_hyp_len, int enc_width, int joint_size,
-                              int alphabet_size, int num_durations, int joint_dtype, bool timed, const void *workspace,
-                              const rnntOptions &o) {
-    if (!tbs_heads_ok(alphabet_size, num_durations)) return RNNT_STATUS_INVALID_VALUE;
+static rnntStatus_t check_tdt_beam_stream(int max_chunk_frames, int slots, int beam, int max_hyp_len, int enc_width, int joint_size,
+                                          int alphabet_size, int num_durations, int joint_dtype, bool timed, const void *workspace,
+                                          const rnntOptions &o) {
+    if (!tdt_heads_ok(alphabet_size, num_durations)) return RNNT_STATUS_INVALID_VALUE;
     const rnntStatus_t st = check_beam_stream(max_chunk_frames, slots, beam, max_hyp_len, enc_width, joint_size,
                                               alphabet_size + num_durations, joint_dtype, workspace, o, timed);
     if (st != RNNT_STATUS_SUCCESS) return st;
@@ -61,7 +48,7 @@ extern "C" {
 rnntStatus_t get_rnnt_tdt_beam_stream_workspace_size(int max_chunk_frames, int slots, int beam, int max_hyp_len, int enc_width,
                                                      int joint_size, int alphabet_size, int num_durations, int joint_dtype, int timed,
                                                      size_t *size_bytes) {
-    if (!size_bytes || !tbs_heads_ok(alphabet_size, num_durations)) return RNNT_STATUS_INVALID_VALUE;
+    if (!size_bytes || !tdt_heads_ok(alphabet_size, num_durations)) return RNNT_STATUS_INVALID_VALUE;
     if (joint_dtype != 0 && joint_dtype != 1) return RNNT_STATUS_INVALID_VALUE;
     if (joint_size <= 0 || slots <= 0 || max_chunk_frames <= 0 || beam < 1 || beam > 16 || max_hyp_len < 1)
         return RNNT_STATUS_INVALID_VALUE;
@@ -77,10 +64,10 @@ rnntStatus_t compute_rnnt_tdt_beam_stream_begin(const float *W1, const float *b1
                                                 rnntOptions options) {
     if (!W1 || !b1 || !W2 || !b2 || !durations) return RNNT_STATUS_INVALID_VALUE;
     if (!aligned4(W1) || !aligned4(b1) || !aligned4(W2) || !aligned4(b2)) return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st = check_tbs(options.maxT, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, num_durations,
-                                      joint_dtype, timed != 0, workspace, options);
+    const rnntStatus_t st = check_tdt_beam_stream(options.maxT, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size,
+                                                  num_durations, joint_dtype, timed != 0, workspace, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
-    if (!tbs_durations_ok(durations, num_durations)) return RNNT_STATUS_INVALID_VALUE;
+    if (!tdt_durations_ok(durations, num_durations)) return RNNT_STATUS_INVALID_VALUE;
     return from_hip(launch_tdt_beam_stream_begin(W1, b1, W2, b2, enc_width, joint_size, alphabet_size, durations, num_durations, slots,
                                                  options.maxT, beam, max_hyp_len, joint_dtype, timed != 0, workspace,
                                                  (hipStream_t)options.stream));
@@ -93,8 +80,8 @@ rnntStatus_t compute_rnnt_tdt_beam_stream_feed(const float *enc, int enc_frames,
     if (!chunk_frames || !aligned4(enc) || !aligned4(chunk_frames) || !aligned4(reset) || !aligned4(final_chunk))
         return RNNT_STATUS_INVALID_VALUE;
     if (enc_frames < 0 || enc_frames > options.maxT || (enc_frames > 0 && !enc)) return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st = check_tbs(options.maxT, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size, num_durations,
-                                      joint_dtype, timed != 0, workspace, options);
+    const rnntStatus_t st = check_tdt_beam_stream(options.maxT, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size,
+                                                  num_durations, joint_dtype, timed != 0, workspace, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
     return from_hip(launch_tdt_beam_stream_feed(enc, enc_frames, chunk_frames, reset, final_chunk, enc_width, joint_size, alphabet_size,
                                                 num_durations, slots, options.maxT, beam, max_hyp_len, joint_dtype, timed != 0,
@@ -109,8 +96,8 @@ rnntStatus_t compute_rnnt_tdt_beam_stream_step(const float *pred_proj, int *pare
     if (!aligned4(pred_proj) || !aligned4(parents) || !aligned4(emitted) || !aligned4(topk_logits) || !aligned4(topk_symbols) ||
         !aligned4(dur_logits) || !aligned4(lse))
         return RNNT_STATUS_INVALID_VALUE;
-    const rnntStatus_t st = check_tbs(options.maxT, slots, beam, max_hyp_len, 1, joint_size, alphabet_size, num_durations, joint_dtype,
-                                      timed != 0, workspace, options);
+    const rnntStatus_t st = check_tdt_beam_stream(options.maxT, slots, beam, max_hyp_len, 1, joint_size, alphabet_size,
+                                                  num_durations, joint_dtype, timed != 0, workspace, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
     return from_hip(launch_tdt_beam_stream_step(pred_proj, parents, emitted, topk_logits, topk_symbols, dur_logits, lse, joint_size,
                                                 alphabet_size, num_durations, slots, options.maxT, beam, max_hyp_len,
@@ -128,8 +115,8 @@ rnntStatus_t compute_rnnt_tdt_beam_stream_results(int *hyps, int *hyp_lengths, f
         return RNNT_STATUS_INVALID_VALUE;
     if ((hyp_frames == nullptr) != (hyp_durations == nullptr)) return RNNT_STATUS_INVALID_VALUE;
     if ((hyp_frames || timed_stable_lengths) && timed == 0) return RNNT_STATUS_INVALID_VALUE;  // (a timed workspace alone holds the rows)
-    const rnntStatus_t st = check_tbs(options.maxT, slots, beam, max_hyp_len, 1, joint_size, alphabet_size, num_durations, joint_dtype,
-                                      timed != 0, workspace, options);
+    const rnntStatus_t st = check_tdt_beam_stream(options.maxT, slots, beam, max_hyp_len, 1, joint_size, alphabet_size,
+                                                  num_durations, joint_dtype, timed != 0, workspace, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
     return from_hip(launch_tdt_beam_stream_results(hyps, hyp_lengths, scores, cursors, stable_lengths, hyp_frames, hyp_durations,
                                                    timed_stable_lengths, joint_size, alphabet_size, num_durations, slots, options.maxT,

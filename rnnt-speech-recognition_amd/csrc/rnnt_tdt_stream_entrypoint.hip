@@ -1,10 +1,10 @@
 // rnnt_tdt_stream_entrypoint.hip -- the extern "C" boundary of libwarprnnt_tdtstream.so (declared in include/rnnt_tdt_stream.h):
 // greedy decoding of the token-and-duration (TDT) transducer over a stream of chunks per slot.  The other libraries and their
-// headers stay as they are.  This translation unit includes rnnt_tdt_greedy_entrypoint.hip (and through it rnnt_entrypoint.hip)
-// for the argument checks of the greedy stream and of the batched TDT greedy decoder (they are static there); build.py links it
-// with the base kernel objects, tdt_greedy_kernels.hip's object and tdt_stream_kernels.hip, and rnnt_tdt_stream.map keeps
-// everything but the four entry points local, so the library defines no other library's entry point a second time.
-#include "rnnt_tdt_greedy_entrypoint.hip"
+// headers stay as they are.  The argument checks of the greedy stream come from rnnt_decode_host.h and those of the batched TDT
+// greedy decoder from tdt_host.h; this unit defines the four entry points and nothing else.  build.py links it with the base
+// kernel objects, tdt_greedy_kernels.hip's object and tdt_stream_kernels.hip, and rnnt_tdt_stream.map exports the four entry
+// points alone.
+#include "tdt_host.h"
 #include "../../include/rnnt_tdt_stream.h"
 
 namespace rnnt {
@@ -19,6 +19,8 @@ hipError_t launch_tdt_stream_step(const float *pred_proj, int *hyps, int *hyp_fr
                                   int *hyp_lengths, float *scores, int *emitted, int *all_done, float *stats, int J, int Vt, int D,
                                   int S, int Tc, int blank, int joint_dtype, void *workspace, hipStream_t s);
 }  // namespace rnnt
+
+using namespace rnnt;
 
 // the checks of the greedy stream at alphabet_size = R (the workspace pointer, the slots, the encoder width, the greedy decoder's
 // own), then those of the TDT greedy decoder (the heads, the blank inside the token head) and the workspace's own layout

@@ -18,12 +18,14 @@
 // Everything a kernel reads was written by the kernel in front of it: the workspace may hold anything on entry.
 #pragma once
 #include "rnnt_common.h"
+#include "tdt_host.h"
 
 namespace rnnt {
 
 constexpr int kTdtAlignMaxU = 1024;      // one lattice column per thread of the sweep
 constexpr int kTdtAlignMaxD = 8;         // durations per set
 constexpr int kTdtAlignMaxDuration = 8;  // the largest duration: the sweep's ring holds kTdtAlignMaxDuration + 2 rows
+static_assert(kTdtAlignMaxD == kTdtHostMaxD && kTdtAlignMaxDuration == kTdtHostMaxDuration, "tdt_host.h holds the limits the boundary checks");
 
 struct TdtAlignLayout {
     size_t sigma, w, dec, total;

@@ -5,7 +5,7 @@
 // enqueued, nothing is allocated, everything is enqueued on the caller's stream.
 #include "../../include/rnnt_tdt_align.h"
 #include "rnnt_tdtalign.h"
-#include "rnnt_host.h"
+#include "tdt_host.h"
 
 #include <math.h>
 
@@ -18,14 +18,6 @@ static bool shape_ok(int maxT, int maxU, int minibatch, int num_durations) {
     return (long long)minibatch * maxT * maxU < (1ll << 31);
 }
 
-// strictly increasing, durations[0] in {0, 1}, some d > 0, the largest <= 8
-static bool durations_ok(const int *durations, int num_durations) {
-    if (durations[0] != 0 && durations[0] != 1) return false;
-    for (int i = 1; i < num_durations; ++i)
-        if (durations[i] <= durations[i - 1]) return false;
-    return durations[num_durations - 1] > 0 && durations[num_durations - 1] <= kTdtAlignMaxDuration;
-}
-
 // what _cells and _path share: V = the token vocabulary (_path: anything that holds the blank)
 static rnntStatus_t check_common(const void *ll, const void *il, const int *durations, int D, const void *ws, int V, int B,
                                  const rnntOptions &o) {
@@ -34,7 +26,7 @@ static rnntStatus_t check_common(const void *ll, const void *il, const int *dura
     if (o.loc != RNNT_GPU || !o.batch_first) return RNNT_STATUS_INVALID_VALUE;  // device-only library: no CPU fallback
     if (V < 2 || o.blank_label < 0 || o.blank_label >= V) return RNNT_STATUS_INVALID_VALUE;
     if (!shape_ok(o.maxT, o.maxU, B, D)) return RNNT_STATUS_INVALID_VALUE;
-    if (!durations_ok(durations, D)) return RNNT_STATUS_INVALID_VALUE;
+    if (!tdt_durations_ok(durations, D)) return RNNT_STATUS_INVALID_VALUE;
     if (((uintptr_t)ws & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
     return RNNT_STATUS_SUCCESS;
 }

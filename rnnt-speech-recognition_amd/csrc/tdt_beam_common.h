@@ -13,10 +13,12 @@
 // stride N = max_hyp_len (the _n forms below; offline N = T), uses bl, and keeps the cursor relative to the chunk a slot holds.
 #pragma once
 #include "beam_common.h"
+#include "tdt_host.h"
 
 namespace rnnt {
 
 constexpr int kTdtBeamMaxD = 8;  // include/rnnt_tdt.h: 1 <= D <= 8
+static_assert(kTdtBeamMaxD == kTdtHostMaxD, "tdt_host.h holds the limit the boundary checks");
 // the stream: the word after the duration set (its 256-byte region has room) holds the place of the frame bases, in words past
 // this workspace, for the calls that take no enc_width (tdt_stream_kernels.hip does the same)
 constexpr int kTdtBeamBaseWord = kTdtBeamMaxD;

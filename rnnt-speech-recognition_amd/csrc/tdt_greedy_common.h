@@ -6,6 +6,7 @@
 #pragma once
 #include "rnnt_decode.h"
 #include "greedy_common.h"
+#include "tdt_host.h"
 
 #include <limits.h>
 #include <math.h>
@@ -13,6 +14,7 @@
 namespace rnnt {
 
 constexpr int kTdtGreedyMaxD = 8;
+static_assert(kTdtGreedyMaxD == kTdtHostMaxD, "tdt_host.h holds the limit the boundary checks");
 constexpr int kTdtStreamBaseWord = kTdtGreedyMaxD;  // durset[this]: where the stream's frame bases lie (tdt_stream_kernels.hip)
 
 struct TdtDurations {
