@@ -365,6 +365,11 @@ def check(status: int, what: str):
         raise RuntimeError(f"{what} failed: rnntStatus_t={status} ({status_string(status)})")
 
 
+def ptr(x):
+    """An optional tensor as a C ABI argument: its address, or None (a null pointer) for None."""
+    return None if x is None else x.data_ptr()
+
+
 def make_options(stream: int, blank: int, maxT: int, maxU: int, loc: int = RNNT_GPU) -> rnntOptions:
     o = rnntOptions()
     o.loc = loc

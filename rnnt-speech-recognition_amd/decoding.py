@@ -24,7 +24,8 @@ from typing import List, Optional
 
 import torch
 
-from .joint import BeamJoint, BeamStreamJoint, EncoderStream, GreedyJoint, GreedyStreamJoint, PredictionStep
+from .joint import (BeamJoint, BeamStreamJoint, EncoderStream, GreedyJoint, GreedyStreamJoint, PredictionStep, TorchPredictionStep,
+                    _pred_step)  # noqa: F401  (_pred_step: one symbol through the prediction network, for callers of this module)
 from .loss import reduced_lengths
 
 
@@ -103,20 +104,86 @@ def read_flag(x: torch.Tensor) -> int:
             torch.cuda.set_sync_debug_mode(mode)
 
 
+def _stream_key(x: torch.Tensor, *extra):
+    """The key of the per-stream workspace caches: (device, stream) + extra for a device tensor, None for a CPU tensor."""
+    return (x.device, torch.cuda.current_stream(x.device).cuda_stream) + extra if x.is_cuda else None
+
+
+def _begin_cached(cache: dict, key, obj, *args):
+    """obj.begin(*args) on the workspace that `cache` holds under `key` -- the one of the last decode on this stream, which
+    begin keeps when it is large enough (joint._workspace); the workspace obj has afterwards is held for the next one."""
+    obj._ws = cache.get(key)
+    out = obj.begin(*args)
+    if key is not None and obj._ws is not None:
+        cache[key] = obj._ws
+    return out
+
+
 _PRED_WORKSPACES = {}  # (device, stream) -> the prediction-network workspace of the last engine-route decode there
 PREDICTIONS = ("torch", "engine")
 
 
-def _prediction_step(model, joint, rows: int, dev):
-    """The engine route's PredictionStep for `joint` (a GreedyJoint / BeamJoint), begun for `rows` rows -> (step, pred_proj)."""
-    W1 = joint.W1 if joint.engine else model.joint.W1  # (the joint-unit padding of the engine joint; the torch joint takes J)
-    ps = PredictionStep(model.prediction, W1)
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream) if W1.is_cuda else None
-    ps._ws = _PRED_WORKSPACES.get(key)
-    pp = ps.begin(rows)
-    if ps._ws is not None:
-        _PRED_WORKSPACES[key] = ps._ws
-    return ps, pp
+def _joint_W1(jx):
+    """The first Dense layer a PredictionStep for the joint jx projects through: the engine joint's, padded to its joint units;
+    the torch joint takes the model's J."""
+    return jx.W1 if jx.engine else jx.joint.W1
+
+
+def _prediction_step(pred_net, W1: torch.Tensor, rows: int):
+    """The engine route's PredictionStep of the prediction network pred_net through W1, begun for `rows` rows -> (step, pred_proj)."""
+    ps = PredictionStep(pred_net, W1)
+    return ps, _begin_cached(_PRED_WORKSPACES, _stream_key(ps.W1), ps, rows)
+
+
+def _begin_prediction(route: str, pred_net, jx, rows: int, dev):
+    """The prediction network of the joint jx's `rows` rows after the start token -> (stepper, its output).  "engine": a
+    PredictionStep, the output through W1 (the joint step's pred_proj=); "torch": the model's own modules, the output as it is
+    (the joint step's pred, which projects it itself)."""
+    if route == "engine":
+        return _prediction_step(pred_net, _joint_W1(jx), rows)
+    ps = TorchPredictionStep(pred_net, dev)
+    return ps, ps.begin(rows)
+
+
+def _joint_step(jx, ps):
+    return (lambda x: jx.step(pred_proj=x)) if ps.projected else jx.step
+
+
+def _greedy_loop(jg, ps, x, check_every: int, carry: bool):
+    """The greedy decoders' loop on a begun joint jg and a begun prediction stepper ps with the output x: joint step,
+    prediction-network step for the rows that emitted, and every `check_every` joint steps one read of the all-done word -- 1 ends
+    the loop, 2 (every running hypothesis has filled the buffer) grows the buffer.  carry False (a batch): the prediction network
+    steps after the read, and not after the last joint step.  carry True (a stream): it steps before the read, after the last
+    joint step too: the next feed goes on from it.  -> (joint steps, the stepper's last output)."""
+    step = _joint_step(jg, ps)
+    steps = 0
+    while True:
+        emitted = step(x)
+        steps += 1
+        if carry:
+            x = ps.step(emitted)
+        if steps % check_every == 0:
+            flag = read_flag(jg.all_done)
+            if flag == 1:
+                return steps, x
+            if flag == 2:
+                jg.grow_hyps()
+        if not carry:
+            x = ps.step(emitted)
+
+
+def _beam_loop(jb, ps, x, steps: int, carry: bool, before_step=None):
+    """The beam decoders' loop, frame-synchronous (nothing is read from the host): `steps` joint steps, each followed by a
+    prediction-network step from the parents' states -- but for the last one unless carry (a stream: the next feed goes on from
+    it).  before_step(t), when given, runs before joint step t.  -> the stepper's last output."""
+    step = _joint_step(jb, ps)
+    for t in range(steps):
+        if before_step is not None:
+            before_step(t)
+        parents, emitted = step(x)
+        if carry or t + 1 < steps:
+            x = ps.step(emitted, parents)
+    return x
 
 
 def _check_prediction(prediction: str):
@@ -138,35 +205,12 @@ def _encode(model, mel_specs: torch.Tensor, encoder: str) -> torch.Tensor:
     if encoder == "torch":
         return model.encoder(mel_specs)
     es = EncoderStream(model.encoder)
-    dev = mel_specs.device
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream) if (es.engine and mel_specs.is_cuda) else None
-    es._ws = _ENC_WORKSPACES.get(key)
-    B, T = mel_specs.shape[0], mel_specs.shape[1]
-    es.begin(B, T)
-    enc = es.run(mel_specs)
-    if key is not None and es._ws is not None:
-        _ENC_WORKSPACES[key] = es._ws
-    return enc
+    _begin_cached(_ENC_WORKSPACES, _stream_key(mel_specs) if es.engine else None, es, mel_specs.shape[0], mel_specs.shape[1])
+    return es.run(mel_specs)
 
 
-def _pred_step(pred_net, tokens: torch.Tensor, states):
-    """One symbol through the prediction network for every row: tokens [B] -> (output [B, H], new states)."""
-    y = pred_net.embed(tokens.long()[:, None])
-    new = []
-    for blk, st in zip(pred_net.blocks, states):
-        y, hc = blk.lstm(y, st)
-        y = blk.norm(blk.drop(y))
-        new.append(hc)
-    return y[:, 0, :], new
-
-
-@torch.no_grad()
-def greedy_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, max_length=None,
-                        max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY, prediction: str = "torch",
-                        token_times: bool = False):
-    """Greedy search over encoder outputs enc [B, T', H] with frame_lengths [B] (the model in eval mode).  See greedy_decode_batch."""
-    global LAST_STEPS
-    _check_prediction(prediction)
+def _greedy_search(jg, cache: dict, pred_net, enc, frame_lengths, max_length, max_per_frame: int, check_every: int, prediction: str):
+    """The batched greedy search on the fresh joint jg (its workspace from `cache`) -> (jg's results, the decode steps)."""
     B, T = enc.shape[0], enc.shape[1]
     dev = enc.device
     if max_length is None:
@@ -177,49 +221,25 @@ def greedy_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, m
     else:
         maxsym = torch.full((B,), int(max_length), dtype=torch.int32, device=dev)
         N = max(1, int(max_length))
+    _begin_cached(cache, _stream_key(enc), jg, enc, frame_lengths, maxsym, max_per_frame, N)
+    ps, x = _begin_prediction(prediction, pred_net, jg, B, dev)
+    steps, _ = _greedy_loop(jg, ps, x, check_every, carry=False)
+    out = (jg.hyps, jg.lengths, jg.scores)
+    return (out + (jg.frames, jg.logp) if jg.token_times else out), steps
+
+
+@torch.no_grad()
+def greedy_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, max_length=None,
+                        max_symbols_per_frame: Optional[int] = None, check_every: int = CHECK_EVERY, prediction: str = "torch",
+                        token_times: bool = False):
+    """Greedy search over encoder outputs enc [B, T', H] with frame_lengths [B] (the model in eval mode).  See greedy_decode_batch."""
+    global LAST_STEPS
+    _check_prediction(prediction)
     # (the current weights: a model may be trained between two decodes)
     jg = GreedyJoint(model.joint, token_times=True) if token_times else GreedyJoint(model.joint)
-    done = lambda: (jg.hyps, jg.lengths, jg.scores, jg.frames, jg.logp) if token_times else (jg.hyps, jg.lengths, jg.scores)  # noqa: E731
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream) if enc.is_cuda else None
-    jg._ws = _WORKSPACES.get(key)  # the workspace of the last decode on this stream, when it is large enough
-    jg.begin(enc, frame_lengths, maxsym, int(max_symbols_per_frame or 0), N)
-    if jg._ws is not None:
-        _WORKSPACES[key] = jg._ws
-    if prediction == "engine":  # the loop body is library calls alone: the joint step, then the prediction-network step
-        ps, pp = _prediction_step(model, jg, B, dev)
-        steps = 0
-        while True:
-            emitted = jg.step(pred_proj=pp)
-            steps += 1
-            if steps % check_every == 0:
-                flag = read_flag(jg.all_done)
-                if flag == 1:
-                    break
-                if flag == 2:
-                    jg.grow_hyps()
-            pp = ps.step(emitted)
-        LAST_STEPS = steps
-        return done()
-    pred_net = model.prediction
-    g, states = _pred_step(pred_net, torch.zeros(B, dtype=torch.int32, device=dev), [None] * len(pred_net.blocks))
-    steps = 0
-    while True:
-        emitted = jg.step(g)
-        steps += 1
-        if steps % check_every == 0:
-            flag = read_flag(jg.all_done)
-            if flag == 1:
-                break
-            if flag == 2:
-                jg.grow_hyps()
-        # rows that emitted a symbol advance their prediction network; the others keep their state
-        mask = emitted >= 0
-        g2, states2 = _pred_step(pred_net, emitted.clamp(min=0), states)
-        g = torch.where(mask[:, None], g2, g)
-        states = [(torch.where(mask[None, :, None], h2, h), torch.where(mask[None, :, None], c2, c))
-                  for (h2, c2), (h, c) in zip(states2, states)]
-    LAST_STEPS = steps
-    return done()
+    out, LAST_STEPS = _greedy_search(jg, _WORKSPACES, model.prediction, enc, frame_lengths, max_length,
+                                     int(max_symbols_per_frame or 0), check_every, prediction)
+    return out
 
 
 @torch.no_grad()
@@ -281,6 +301,16 @@ def greedy_decode_batch_fn(model, prediction: str = "torch", encoder: str = "tor
 _BEAM_WORKSPACES = {}  # (device, stream) -> the beam workspace of the last decode there
 
 
+def _beam_search(jb, cache: dict, pred_net, enc, frame_lengths, prediction: str, before_step=None):
+    """The batched beam search on the fresh joint jb (its workspace from `cache`; a timed decode keeps one of its own) -> jb's
+    results.  before_step: _beam_loop's."""
+    key = _stream_key(enc, "timed") if jb.token_times else _stream_key(enc)
+    _begin_cached(cache, key, jb, enc, frame_lengths)
+    ps, x = _begin_prediction(prediction, pred_net, jb, enc.shape[0] * jb.K, enc.device)
+    _beam_loop(jb, ps, x, enc.shape[1], carry=False, before_step=before_step)
+    return jb.results()
+
+
 @torch.no_grad()
 def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, beam: int = 4, prediction: str = "torch",
                       token_times: bool = False, context=None, lm=None):
@@ -305,41 +335,9 @@ def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, bea
     with the LM's score of the token (already scaled by the LM weight), the scores include it, and the results are finalised with
     the LM's end-of-sentence score and re-sorted (stably).  logp stays the model's log-probability."""
     _check_prediction(prediction)
-    B, T = enc.shape[0], enc.shape[1]
-    K = int(beam)
-    dev = enc.device
     # (the current weights: a model may be trained between two decodes)
-    jb = BeamJoint(model.joint, K, token_times=bool(token_times), context=context, lm=lm)
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream) if enc.is_cuda else None
-    if token_times and key is not None:
-        key = key + ("timed",)  # (a timed decode keeps a workspace of its own)
-    jb._ws = _BEAM_WORKSPACES.get(key)
-    jb.begin(enc, frame_lengths)
-    if jb._ws is not None:
-        _BEAM_WORKSPACES[key] = jb._ws
-    if prediction == "engine":
-        ps, pp = _prediction_step(model, jb, B * K, dev)
-        for t in range(T):
-            parents, emitted = jb.step(pred_proj=pp)
-            if t + 1 == T:
-                break
-            pp = ps.step(emitted, parents)
-        return jb.results()
-    pred_net = model.prediction
-    g, states = _pred_step(pred_net, torch.zeros(B * K, dtype=torch.int32, device=dev), [None] * len(pred_net.blocks))
-    for t in range(T):
-        parents, emitted = jb.step(g)
-        if t + 1 == T:
-            break
-        idx = parents.long()
-        g = g[idx]
-        states = [(h[:, idx], c[:, idx]) for h, c in states]
-        mask = emitted >= 0
-        g2, states2 = _pred_step(pred_net, emitted.clamp(min=0), states)
-        g = torch.where(mask[:, None], g2, g)
-        states = [(torch.where(mask[None, :, None], h2, h), torch.where(mask[None, :, None], c2, c))
-                  for (h2, c2), (h, c) in zip(states2, states)]
-    return jb.results()
+    jb = BeamJoint(model.joint, int(beam), token_times=bool(token_times), context=context, lm=lm)
+    return _beam_search(jb, _BEAM_WORKSPACES, model.prediction, enc, frame_lengths, prediction)
 
 
 @torch.no_grad()
@@ -507,8 +505,7 @@ class StreamingGreedyDecoder(_StreamingSlots):
             dev = next(model.parameters()).device
             N = max(1, self.max_length) if self.max_length is not None else self.Te + 16
             self.gj.begin(S, self.Te, int(max_symbols_per_frame or 0), N, device=dev)
-            W1 = self.gj.W1 if self.gj.engine else self.gj.joint.W1
-            self.ps = PredictionStep(model.prediction, W1)
+            self.ps = PredictionStep(model.prediction, _joint_W1(self.gj))
             self.pp = self.ps.begin(S)
         self.dev = self.gj.hyps.device
 
@@ -549,20 +546,7 @@ class StreamingGreedyDecoder(_StreamingSlots):
         """Joint step, then prediction-network step, until every slot has consumed its chunk.  The prediction network always
         takes the last step's symbols: the next feed goes on from them."""
         global LAST_STEPS
-        gj, ps = self.gj, self.ps
-        pp, steps = self.pp, 0
-        while True:
-            emitted = gj.step(pred_proj=pp)
-            pp = ps.step(emitted)
-            steps += 1
-            if steps % self.check_every == 0:
-                flag = read_flag(gj.all_done)
-                if flag == 1:
-                    break
-                if flag == 2:
-                    gj.grow_hyps()
-        self.pp = pp
-        LAST_STEPS = steps
+        LAST_STEPS, self.pp = _greedy_loop(self.gj, self.ps, self.pp, self.check_every, carry=True)
 
     def hypotheses(self):
         """(ids int32 [slots, N] zero-padded, lengths int32 [slots], scores [slots]) of each slot's stream since its start."""
@@ -639,8 +623,7 @@ class StreamingBeamDecoder(_StreamingSlots):
             self.bj = self._make_joint(model, K, context, lm)
             dev = next(model.parameters()).device
             self.bj.begin(S, self.Te, N, device=dev)
-            W1 = self.bj.W1 if self.bj.engine else self.bj.joint.W1
-            self.ps = PredictionStep(model.prediction, W1)
+            self.ps = PredictionStep(model.prediction, _joint_W1(self.bj))
             self.pp = self.ps.begin(S * K)
         self.dev = self.bj.parents.device
 
@@ -668,11 +651,7 @@ class StreamingBeamDecoder(_StreamingSlots):
             enc = self._encode_chunk(mel_chunk, fr)
             self.bj.feed(enc, [-(-v // f) for v in fr], reset=None, final=[int(v) for v in fi])
             steps = -(-T // f)  # (host data: the search is frame-synchronous, so nothing is polled)
-            pp = self.pp
-            for _ in range(steps):
-                parents, emitted = self.bj.step(pred_proj=pp)
-                pp = self.ps.step(emitted, parents)  # (after the last frame too: the next feed goes on from it)
-            self.pp = pp
+            self.pp = _beam_loop(self.bj, self.ps, self.pp, steps, carry=True)
             LAST_STEPS = steps
             ids, lengths, _, stable = self.bj.results()[:4]
         return ids[:, 0], lengths[:, 0], stable

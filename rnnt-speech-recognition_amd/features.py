@@ -155,10 +155,10 @@ class StreamingFrontEnd:
             raise RuntimeError(f"StreamingFrontEnd: the engine was asked for but cannot run ({self.route})")
         if self.engine:
             from . import _lib
-            from .joint import _new_workspace
+            from .joint import _workspace
 
             with torch.cuda.device(dev):
-                self._ws = _new_workspace(int(n.value), dev)
+                self._ws = _workspace(None, int(n.value), dev)  # (a front end begins once: always a fresh one)
                 self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, 0, 1, 1)
                 st = _lib.load().compute_rnnt_frontend_begin(self.window.data_ptr(), self.mel_w.data_ptr(), K, S, L, step, M, stack,
                                                              rm, self._ws.data_ptr(), self._opts)

@@ -17,6 +17,7 @@ import math
 import torch
 
 from . import _lib
+from ._lib import ptr
 
 
 class _JointLossFunction(torch.autograd.Function):
@@ -199,6 +200,16 @@ _WORKSPACE_FILL = None
 
 def _new_workspace(nbytes: int, dev) -> torch.Tensor:
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if _WORKSPACE_FILL is not None:
+        ws.fill_(int(_WORKSPACE_FILL))
+    return ws
+
+
+def _workspace(ws, nbytes: int, dev) -> torch.Tensor:
+    """The workspace an object that owns one begins on: `ws`, the one it has, when that lives on dev and holds nbytes (filled
+    again under the test hook), else a fresh one."""
+    if ws is None or ws.device != dev or ws.numel() < nbytes:
+        return _new_workspace(nbytes, dev)
     if _WORKSPACE_FILL is not None:
         ws.fill_(int(_WORKSPACE_FILL))
     return ws
@@ -423,7 +434,113 @@ def _torch_cell_logits(joint: "JointLoss", e, pred, pred_proj):
     return torch.tanh(z) @ joint.W2 + joint.b2
 
 
-class GreedyJoint:
+class _EngineJoint:
+    """What the decoder joints share: the engine / torch decision and the engine's weights.  `engine`: the joint's tensors are
+    on a device and its shape is one the kernels take (the rule of JointLoss.cell_logits); then `dtype`, `Jp` and W1 / b1 / W2 / b2
+    as float32 with the joint units zero-padded to Jp (as joint_logits pads them; the output columns need none: the step kernels
+    skip padding columns themselves).  `V`: W2's columns (a TDT joint takes its duration head off them).  `_ws`: the workspace
+    the object owns, kept by _workspace from one begin to the next."""
+
+    def __init__(self, joint, joint_dtype: str = "auto", token_times: bool = False):
+        self.joint = joint
+        self.token_times = bool(token_times)
+        self.blank = int(joint.blank_label)
+        W1, b1, W2, b2 = (x.detach() for x in (joint.W1, joint.b1, joint.W2, joint.b2))
+        J, self.V = W2.shape
+        self.engine = W2.is_cuda
+        if self.engine:
+            if joint_dtype == "auto":
+                joint_dtype = _auto_joint_dtype(J, self.V)
+            try:
+                Jp, _ = padded_joint_shape(J, self.V, joint_dtype)
+            except ValueError:
+                self.engine = False
+        if self.engine:
+            self.dtype = JOINT_DTYPES[joint_dtype]
+            self.Jp = Jp
+            pad = lambda x, p: torch.nn.functional.pad(x.float(), p).contiguous()  # noqa: E731
+            self.W1, self.b1 = pad(W1, (0, Jp - J)), pad(b1, (0, Jp - J))
+            self.W2, self.b2 = pad(W2, (0, 0, 0, Jp - J)), b2.float().contiguous()
+        self._ws = None
+
+
+class _GreedyEngineJoint(_EngineJoint):
+    """What the greedy joints share beyond _EngineJoint: the output buffers (`hyps`, `lengths`, `emitted`, `all_done`, `scores`;
+    `frames` and `logp`, None without token_times), grow_hyps, and the torch mirror's cursors."""
+
+    def __init__(self, joint, joint_dtype: str = "auto", token_times: bool = False):
+        super().__init__(joint, joint_dtype, token_times)
+        self._frame_base = None  # (the stream: frames of the chunks a slot has left behind)
+
+    def _new_outputs(self, rows: int, max_hyp_len: int, dev, all_done: int, torch_dtype):
+        """scores: float32 on the engine, on the torch route torch_dtype where that is wider."""
+        self.hyps = torch.zeros(rows, max_hyp_len, dtype=torch.int32, device=dev)
+        self.lengths = torch.zeros(rows, dtype=torch.int32, device=dev)
+        self.emitted = torch.full((rows,), -1, dtype=torch.int32, device=dev)
+        self.all_done = torch.full((1,), all_done, dtype=torch.int32, device=dev)
+        sdtype = torch.float32 if self.engine else torch.promote_types(torch_dtype, torch.float32)
+        self.scores = torch.zeros(rows, dtype=sdtype, device=dev)
+        self.frames = self.logp = None
+        if self.token_times:
+            self.frames = torch.full((rows, max_hyp_len), -1, dtype=torch.int32, device=dev)
+            self.logp = torch.zeros(rows, max_hyp_len, dtype=sdtype, device=dev)
+
+    def grow_hyps(self):
+        """Double the hyps buffer (contents kept; `frames` and `logp` with it): paused hypotheses resume at the next step."""
+        h = self.hyps
+        self.hyps = torch.zeros(h.shape[0], 2 * h.shape[1], dtype=h.dtype, device=h.device)
+        self.hyps[:, : h.shape[1]] = h
+        if self.token_times:
+            f, l = self.frames, self.logp
+            self.frames = torch.full((h.shape[0], 2 * h.shape[1]), -1, dtype=f.dtype, device=f.device)
+            self.logp = torch.zeros(h.shape[0], 2 * h.shape[1], dtype=l.dtype, device=l.device)
+            self.frames[:, : h.shape[1]], self.logp[:, : h.shape[1]] = f, l
+
+    def _begin(self, enc, frame_lengths, max_symbols, max_per_frame: int, max_hyp_len: int):
+        """What the batched begins share: the outputs, then the torch mirror's state (-> None) or the engine's operands (->
+        enc @ W1 + b1; `_keep`: the frame lengths and the symbol budget or None, alive while the launches read them)."""
+        B, T = enc.shape[0], enc.shape[1]
+        dev = enc.device
+        self.B, self.T = B, T
+        self._new_outputs(B, max_hyp_len, dev, 0, enc.dtype)
+        frames = frame_lengths.to(device=dev, dtype=torch.int32)
+        maxsym = None if max_symbols is None else max_symbols.to(device=dev, dtype=torch.int32)
+        if not self.engine:
+            return self._torch_begin(enc, frames, maxsym, int(max_per_frame))
+        self._keep = (frames.contiguous(), maxsym.contiguous() if maxsym is not None else None)
+        return (torch.matmul(enc.float(), self.W1) + self.b1).contiguous()
+
+    def _begin_stream(self, slots: int, max_chunk_frames: int, max_per_frame: int, max_hyp_len: int, device):
+        """What the streams' begins share: every slot finished, its outputs, and the torch mirror's state -> the device."""
+        S, T = int(slots), int(max_chunk_frames)
+        dev = self.W2.device if self.engine else (device if device is not None else self.joint.W2.device)
+        self.B, self.T, self.Tc = S, T, T
+        self._cap = int(max_per_frame)
+        self._new_outputs(S, max_hyp_len, dev, 1, self.joint.W2.dtype)
+        if self.engine:
+            self.H = int(self.W1.shape[0])
+        else:
+            z = torch.zeros(S, dtype=torch.long, device=dev)
+            self._frame_base = z.clone() if self.token_times else None
+            self._t, self._n, self._nf, self._Tb, self._maxsym = z.clone(), z.clone(), z.clone(), z.clone(), z.clone()
+            self._done = torch.ones(S, dtype=torch.bool, device=dev)
+            self._fin = torch.ones(S, dtype=torch.bool, device=dev)
+        return dev
+
+    def _torch_begin(self, enc, frames, maxsym, max_per_frame):
+        B, T = enc.shape[0], enc.shape[1]
+        dev = enc.device
+        self._enc = enc
+        self._Tb = frames.clamp(0, T).long()
+        self._maxsym = (torch.full((B,), 2**31 - 1, dtype=torch.long, device=dev) if maxsym is None else maxsym.clamp(min=0).long())
+        self._cap = max_per_frame
+        self._t = torch.zeros(B, dtype=torch.long, device=dev)
+        self._n = torch.zeros(B, dtype=torch.long, device=dev)
+        self._nf = torch.zeros(B, dtype=torch.long, device=dev)
+        self._done = (self._Tb == 0) | (self._maxsym == 0)
+
+
+class GreedyJoint(_GreedyEngineJoint):
     """The joint of the batched greedy decoder (decoding.greedy_decode_batch): one lattice cell per hypothesis and step, argmax,
     log-softmax of the decision and the decoder state in one pass.
 
@@ -444,67 +561,20 @@ class GreedyJoint:
     that decision (float32 on the engine; the dtype of `scores` on the torch route).  ids, lengths and scores are bitwise those
     of the untimed step."""
 
-    def __init__(self, joint: "JointLoss", joint_dtype: str = "auto", token_times: bool = False):
-        self.joint = joint
-        self.token_times = bool(token_times)
-        self._frame_base = None  # (the stream: frames of a slot's earlier chunks)
-        self.blank = int(joint.blank_label)
-        W1, b1, W2, b2 = (x.detach() for x in (joint.W1, joint.b1, joint.W2, joint.b2))
-        J, V = W2.shape
-        self.V = V
-        self.engine = W2.is_cuda
-        if self.engine:
-            if joint_dtype == "auto":
-                joint_dtype = _auto_joint_dtype(J, V)
-            try:
-                Jp, _ = padded_joint_shape(J, V, joint_dtype)
-            except ValueError:  # (the same rule as JointLoss.cell_logits)
-                self.engine = False
-        if self.engine:
-            self.dtype = JOINT_DTYPES[joint_dtype]
-            self.Jp = Jp
-            pad = lambda x, p: torch.nn.functional.pad(x.float(), p).contiguous()  # noqa: E731
-            self.W1, self.b1 = pad(W1, (0, Jp - J)), pad(b1, (0, Jp - J))
-            self.W2, self.b2 = pad(W2, (0, 0, 0, Jp - J)), b2.float().contiguous()
-        self._ws = None
-
     # ---- engine
     def begin(self, enc, frame_lengths, max_symbols, max_per_frame: int, max_hyp_len: int):
-        B, T = enc.shape[0], enc.shape[1]
-        dev = enc.device
-        self.B, self.T = B, T
-        self.hyps = torch.zeros(B, max_hyp_len, dtype=torch.int32, device=dev)
-        self.lengths = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.emitted = torch.full((B,), -1, dtype=torch.int32, device=dev)
-        self.all_done = torch.zeros(1, dtype=torch.int32, device=dev)
-        frames = frame_lengths.to(device=dev, dtype=torch.int32)
-        maxsym = None if max_symbols is None else max_symbols.to(device=dev, dtype=torch.int32)
-        if not self.engine:
-            self._torch_begin(enc, frames, maxsym, max_per_frame)
-            return self._new_times(B, max_hyp_len, dev)
-        lib = _lib.load()
-        self.scores = torch.zeros(B, dtype=torch.float32, device=dev)
-        self._new_times(B, max_hyp_len, dev)
-        ep = (torch.matmul(enc.float(), self.W1) + self.b1).contiguous()
-        frames = frames.contiguous()
-        self._keep = (frames, maxsym.contiguous() if maxsym is not None else None)
-        with torch.cuda.device(dev):
-            nbytes = _lib.greedy_workspace_bytes(T, B, self.Jp, self.V, self.dtype)
-            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
-                self._ws = _new_workspace(nbytes, dev)
-            elif _WORKSPACE_FILL is not None:
-                self._ws.fill_(int(_WORKSPACE_FILL))
+        ep = self._begin(enc, frame_lengths, max_symbols, max_per_frame, max_hyp_len)
+        if ep is None:
+            return
+        B, T = self.B, self.T
+        frames, ms = self._keep
+        with torch.cuda.device(enc.device):
+            self._ws = _workspace(self._ws, _lib.greedy_workspace_bytes(T, B, self.Jp, self.V, self.dtype), enc.device)
             self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
-            ms = self._keep[1]
-            st = lib.compute_rnnt_greedy_begin(ep.data_ptr(), self._keep[0].data_ptr(), None if ms is None else ms.data_ptr(),
-                                               self.W2.data_ptr(), self.b2.data_ptr(), self.Jp, self.V, B, int(max_per_frame),
-                                               self.dtype, self._ws.data_ptr(), self._opts)
+            st = _lib.load().compute_rnnt_greedy_begin(ep.data_ptr(), frames.data_ptr(), ptr(ms), self.W2.data_ptr(),
+                                                       self.b2.data_ptr(), self.Jp, self.V, B, int(max_per_frame), self.dtype,
+                                                       self._ws.data_ptr(), self._opts)
         _lib.check(st, "compute_rnnt_greedy_begin")
-
-    def _new_times(self, B, max_hyp_len, dev):
-        if self.token_times:
-            self.frames = torch.full((B, max_hyp_len), -1, dtype=torch.int32, device=dev)
-            self.logp = torch.zeros(B, max_hyp_len, dtype=self.scores.dtype, device=dev)
 
     def step(self, pred=None, logit_stats=None, *, pred_proj=None):
         """pred [B, H]: the prediction network's output of every row -> emitted [B] (int32, -1 where nothing was emitted).
@@ -513,46 +583,20 @@ class GreedyJoint:
             return self._torch_step(pred, pred_proj)
         pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _projected_operand(pred_proj, self.Jp)
         if self.token_times:
-            fb = self._frame_base
             st = _lib.load().compute_rnnt_greedy_step_timed(
                 pp.data_ptr(), self.hyps.data_ptr(), self.frames.data_ptr(), self.logp.data_ptr(), self.hyps.shape[1],
                 self.lengths.data_ptr(), self.scores.data_ptr(), self.emitted.data_ptr(), self.all_done.data_ptr(),
-                None if logit_stats is None else logit_stats.data_ptr(), None if fb is None else fb.data_ptr(), self.Jp, self.V,
-                self.B, self.dtype, self._ws.data_ptr(), self._opts)
+                ptr(logit_stats), ptr(self._frame_base), self.Jp, self.V, self.B, self.dtype, self._ws.data_ptr(), self._opts)
             _lib.check(st, "compute_rnnt_greedy_step_timed")
             return self.emitted
         st = _lib.load().compute_rnnt_greedy_step(pp.data_ptr(), self.hyps.data_ptr(), self.hyps.shape[1], self.lengths.data_ptr(),
                                                   self.scores.data_ptr(), self.emitted.data_ptr(), self.all_done.data_ptr(),
-                                                  None if logit_stats is None else logit_stats.data_ptr(), self.Jp, self.V, self.B,
-                                                  self.dtype, self._ws.data_ptr(), self._opts)
+                                                  ptr(logit_stats), self.Jp, self.V, self.B, self.dtype, self._ws.data_ptr(),
+                                                  self._opts)
         _lib.check(st, "compute_rnnt_greedy_step")
         return self.emitted
 
-    def grow_hyps(self):
-        """Double the hyps buffer (contents kept; `frames` and `logp` with it): paused hypotheses resume at the next step."""
-        h = self.hyps
-        self.hyps = torch.zeros(h.shape[0], 2 * h.shape[1], dtype=h.dtype, device=h.device)
-        self.hyps[:, : h.shape[1]] = h
-        if self.token_times:
-            f, l = self.frames, self.logp
-            self.frames = torch.full((h.shape[0], 2 * h.shape[1]), -1, dtype=f.dtype, device=f.device)
-            self.logp = torch.zeros(h.shape[0], 2 * h.shape[1], dtype=l.dtype, device=l.device)
-            self.frames[:, : h.shape[1]], self.logp[:, : h.shape[1]] = f, l
-
     # ---- torch composition: the same state machine (greedy_update_kernel) on JointLoss.logits
-    def _torch_begin(self, enc, frames, maxsym, max_per_frame):
-        B, T = enc.shape[0], enc.shape[1]
-        dev = enc.device
-        self._enc = enc
-        self.scores = torch.zeros(B, dtype=torch.promote_types(enc.dtype, torch.float32), device=dev)
-        self._Tb = frames.clamp(0, T).long()
-        self._maxsym = (torch.full((B,), 2**31 - 1, dtype=torch.long, device=dev) if maxsym is None else maxsym.clamp(min=0).long())
-        self._cap = int(max_per_frame)
-        self._t = torch.zeros(B, dtype=torch.long, device=dev)
-        self._n = torch.zeros(B, dtype=torch.long, device=dev)
-        self._nf = torch.zeros(B, dtype=torch.long, device=dev)
-        self._done = (self._Tb == 0) | (self._maxsym == 0)
-
     def _torch_step(self, pred, pred_proj=None):
         B, T, N = self.B, self.T, self.hyps.shape[1]
         ar = torch.arange(B, device=self._enc.device)
@@ -599,33 +643,14 @@ class GreedyStreamJoint(GreedyJoint):
     None); then step(pred_proj=...) until all_done[0] is 1, as for GreedyJoint."""
 
     def begin(self, slots: int, max_chunk_frames: int, max_per_frame: int, max_hyp_len: int, device=None):
-        S, T = int(slots), int(max_chunk_frames)
-        dev = self.W2.device if self.engine else (device if device is not None else self.joint.W2.device)
-        self.B, self.T, self.Tc = S, T, T
-        self.hyps = torch.zeros(S, max_hyp_len, dtype=torch.int32, device=dev)
-        self.lengths = torch.zeros(S, dtype=torch.int32, device=dev)
-        self.emitted = torch.full((S,), -1, dtype=torch.int32, device=dev)
-        self.all_done = torch.ones(1, dtype=torch.int32, device=dev)
-        self._cap = int(max_per_frame)
+        dev = self._begin_stream(slots, max_chunk_frames, max_per_frame, max_hyp_len, device)
         if not self.engine:
-            self.scores = torch.zeros(S, dtype=torch.promote_types(self.joint.W2.dtype, torch.float32), device=dev)
-            self._new_times(S, max_hyp_len, dev)
-            z = torch.zeros(S, dtype=torch.long, device=dev)
-            self._frame_base = z.clone() if self.token_times else None
-            self._t, self._n, self._nf, self._Tb, self._maxsym = z.clone(), z.clone(), z.clone(), z.clone(), z.clone()
-            self._done = torch.ones(S, dtype=torch.bool, device=dev)
-            self._fin = torch.ones(S, dtype=torch.bool, device=dev)
             return
-        self.H = int(self.W1.shape[0])
-        self.scores = torch.zeros(S, dtype=torch.float32, device=dev)
-        self._new_times(S, max_hyp_len, dev)
+        S, T = self.B, self.T
         self._frame_base = torch.zeros(S, dtype=torch.int32, device=dev) if self.token_times else None
         with torch.cuda.device(dev):
             nbytes = _lib.greedy_stream_workspace_bytes(T, S, self.H, self.Jp, self.V, self.dtype)
-            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
-                self._ws = _new_workspace(nbytes, dev)
-            elif _WORKSPACE_FILL is not None:
-                self._ws.fill_(int(_WORKSPACE_FILL))
+            self._ws = _workspace(self._ws, nbytes, dev)
             self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
             st = _lib.load().compute_rnnt_greedy_stream_begin(self.W1.data_ptr(), self.b1.data_ptr(), self.W2.data_ptr(),
                                                               self.b2.data_ptr(), self.H, self.Jp, self.V, S, self.dtype,
@@ -649,7 +674,6 @@ class GreedyStreamJoint(GreedyJoint):
         cv = lambda x: None if x is None else _device_i32(x, dev).reshape(S)  # noqa: E731
         fr, rs, fi, ms = cv(frames), cv(reset), cv(final), cv(max_symbols)
         self._feed_args = (enc, fr, rs, fi, ms)  # (alive until the launches have read them)
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         if self.token_times:
             st = _lib.load().compute_rnnt_greedy_stream_feed_timed(
                 ptr(enc) if Te > 0 else None, Te, fr.data_ptr(), ptr(rs), ptr(fi), ptr(ms), self._cap, self.lengths.data_ptr(),
@@ -687,7 +711,7 @@ class GreedyStreamJoint(GreedyJoint):
         self.all_done.fill_(0 if bool((~self._done).any()) else 1)
 
 
-class BeamJoint:
+class BeamJoint(_EngineJoint):
     """The joint of the batched beam search (decoding.beam_search_batch): per frame, the joint of every hypothesis of every beam,
     the candidate ranking, merging and the new beams in one pass ("modified" beam search, include/rnnt.h).
 
@@ -717,7 +741,6 @@ class BeamJoint:
         if not 1 <= int(beam) <= 16:
             raise ValueError("BeamJoint: beam must be in 1 ... 16")
         self.K = int(beam)
-        self.token_times = bool(token_times)
         if lm is not None and context is not None:
             raise ValueError("lm= together with context=: a hypothesis carries one automaton state, take one of the two")
         self.context, self.lm = context, lm
@@ -728,11 +751,7 @@ class BeamJoint:
         if lm is not None and (lm.blank != joint.blank_label or lm.vocab_size != joint.W2.shape[1]):
             raise ValueError(f"LM built for blank {lm.blank} / {lm.vocab_size} symbols, the joint has blank "
                              f"{joint.blank_label} / {joint.W2.shape[1]} symbols")
-        g = GreedyJoint(joint, joint_dtype)  # (the same engine / torch decision and padding)
-        self.joint, self.blank, self.V, self.engine = joint, g.blank, g.V, g.engine
-        if self.engine:
-            self.dtype, self.Jp, self.W1, self.b1, self.W2, self.b2 = g.dtype, g.Jp, g.W1, g.b1, g.W2, g.b2
-        self._ws = None
+        super().__init__(joint, joint_dtype, token_times)
 
     def begin(self, enc, frame_lengths):
         B, T = enc.shape[0], enc.shape[1]
@@ -750,10 +769,7 @@ class BeamJoint:
         with torch.cuda.device(dev):
             size = _lib.beam_timed_workspace_bytes if self.token_times else _lib.beam_workspace_bytes
             nbytes = size(T, B, self.K, self.Jp, self.V, self.dtype)
-            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
-                self._ws = _new_workspace(nbytes, dev)
-            elif _WORKSPACE_FILL is not None:
-                self._ws.fill_(int(_WORKSPACE_FILL))
+            self._ws = _workspace(self._ws, nbytes, dev)
             self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
             lib = _lib.load()
             fn = lib.compute_rnnt_beam_timed_begin if self.token_times else lib.compute_rnnt_beam_begin
@@ -767,7 +783,6 @@ class BeamJoint:
         if not self.engine:
             return self._torch_step(pred, pred_proj)
         pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _projected_operand(pred_proj, self.Jp)
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         lib = _lib.load()
         if self.context is not None:
             lib = _lib.load_bias()  # (include/rnnt_bias.h)
@@ -1016,10 +1031,7 @@ class BeamStreamJoint(BeamJoint):
         with torch.cuda.device(dev):
             size = _lib.beam_stream_timed_workspace_bytes if self.token_times else _lib.beam_stream_workspace_bytes
             nbytes = size(T, S, K, N, self.H, self.Jp, self.V, self.dtype)
-            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
-                self._ws = _new_workspace(nbytes, dev)
-            elif _WORKSPACE_FILL is not None:
-                self._ws.fill_(int(_WORKSPACE_FILL))
+            self._ws = _workspace(self._ws, nbytes, dev)
             self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
             fn = lib.compute_rnnt_beam_stream_timed_begin if self.token_times else lib.compute_rnnt_beam_stream_begin
             st = fn(self.W1.data_ptr(), self.b1.data_ptr(), self.W2.data_ptr(), self.b2.data_ptr(), self.H, self.Jp, self.V, S, K, N,
@@ -1042,7 +1054,6 @@ class BeamStreamJoint(BeamJoint):
         cv = lambda x: None if x is None else _device_i32(x, dev).reshape(S)  # noqa: E731
         fr, rs, fi = cv(frames), cv(reset), cv(final)
         self._feed_args = (enc, fr, rs, fi)  # (alive until the launches have read them)
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         lib = _lib.load()
         fn = lib.compute_rnnt_beam_stream_timed_feed if self.token_times else lib.compute_rnnt_beam_stream_feed
         st = fn(ptr(enc) if Te > 0 else None, Te, fr.data_ptr(), ptr(rs), ptr(fi), self.H, self.Jp, self.V, S, self.K, self.N,
@@ -1054,7 +1065,6 @@ class BeamStreamJoint(BeamJoint):
         if not self.engine:
             return self._torch_step(pred, pred_proj)
         pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _projected_operand(pred_proj, self.Jp)
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         lib = _lib.load()
         if self.context is not None:
             lib = _lib.load_bias()  # (include/rnnt_bias.h)
@@ -1185,6 +1195,54 @@ def _device_i32(x, dev) -> torch.Tensor:
     return _aligned16(t.to(dev, non_blocking=True))
 
 
+def _pred_step(pred_net, tokens: torch.Tensor, states):
+    """One symbol through the prediction network for every row: tokens [B] -> (output [B, H], new states)."""
+    y = pred_net.embed(tokens.long()[:, None])
+    new = []
+    for blk, st in zip(pred_net.blocks, states):
+        y, hc = blk.lstm(y, st)
+        y = blk.norm(blk.drop(y))
+        new.append(hc)
+    return y[:, 0, :], new
+
+
+class TorchPredictionStep:
+    """The prediction network of every decoder row stepped with the model's own modules, in the shape of PredictionStep:
+    begin(rows) runs the start token 0 from zero state; step(emitted [rows], parents [rows] or None) gives every row the output
+    and LSTM state of row parents[r] (None: its own), then the rows that emitted a symbol (emitted >= 0) advance by it and the
+    others keep both.  Both return `g` [rows, H], the network's UNPROJECTED output: what a joint step takes as `pred`."""
+
+    projected = False  # (a joint step takes the output as pred=, not as pred_proj=)
+
+    def __init__(self, pred_net, device):
+        self.net, self.device = pred_net, device
+
+    def begin(self, rows: int, mask=None) -> torch.Tensor:
+        """mask [rows] given: only those rows restart; the others keep their output and state."""
+        g0, st0 = _pred_step(self.net, torch.zeros(rows, dtype=torch.int32, device=self.device), [None] * len(self.net.blocks))
+        if mask is None:
+            self.g, self.states = g0, st0
+        else:
+            self._take(mask, g0, st0, self.g, self.states)
+        return self.g
+
+    def step(self, emitted: torch.Tensor, parents=None) -> torch.Tensor:
+        g, states = self.g, self.states
+        if parents is not None:
+            idx = parents.to(g.device).long()
+            g = g[idx]
+            states = [(h[:, idx], c[:, idx]) for h, c in states]
+        emitted = emitted.to(g.device)
+        g2, states2 = _pred_step(self.net, emitted.clamp(min=0), states)
+        self._take(emitted >= 0, g2, states2, g, states)
+        return self.g
+
+    def _take(self, mask, g2, states2, g, states):
+        self.g = torch.where(mask[:, None], g2, g)
+        self.states = [(torch.where(mask[None, :, None], h2, h), torch.where(mask[None, :, None], c2, c))
+                       for (h2, c2), (h, c) in zip(states2, states)]
+
+
 class PredictionStep:
     """One prediction-network step for every decoder row, through the joint's first Dense layer: the `pred_proj` that
     GreedyJoint.step / BeamJoint.step take as `pred_proj=`.
@@ -1193,13 +1251,14 @@ class PredictionStep:
     the workspace (the object owns it; the next decode reuses it when it is large enough), zeroes every row's state and runs the
     start token 0; each step advances the rows with emitted >= 0 from row parents[r]'s state (parents None: their own) and
     carries the others over.  CPU tensors, models that are not float32 and shapes the kernels do not take run the same state
-    machine in torch (decoding._pred_step, then the parents gather and torch.where, then matmul(W1)).
+    machine in torch (a TorchPredictionStep, then matmul(W1)).
 
     pred_net: model.PredictionNetwork (embedding + single-layer LSTM blocks with LayerNorm); W1 [out, Jp]: the joint's first
     Dense layer zero-padded to the decoder's joint units (GreedyJoint.W1 on the engine).  begin(rows) -> pred_proj [rows, Jp];
     step(emitted [rows] int32, parents [rows] int32 or None) -> pred_proj (the same tensor, overwritten by the next step)."""
 
     MAX_ROWS, MAX_BLOCKS, MAX_WIDTH = 1024, 8, 4096
+    projected = True  # (a joint step takes the output as pred_proj=)
 
     def __init__(self, pred_net, W1: torch.Tensor):
         self.net = pred_net
@@ -1237,11 +1296,8 @@ class PredictionStep:
         self._use_engine = self.engine and 1 <= self.R <= self.MAX_ROWS
         dev = self.W1.device
         if not self._use_engine:
-            from .decoding import _pred_step
-
-            self._g, self._states = _pred_step(self.net, torch.zeros(self.R, dtype=torch.int32, device=dev),
-                                               [None] * len(self.net.blocks))
-            return self._project()
+            self._torch = TorchPredictionStep(self.net, dev)
+            return self._project(self._torch.begin(self.R))
         net = self.net
         keep = [_aligned16(net.embed.weight), _aligned16(self.W1)]
         blocks = (_lib.rnntPrednetBlock * len(net.blocks))()
@@ -1259,10 +1315,7 @@ class PredictionStep:
         self._n = 0
         with torch.cuda.device(dev):
             nbytes = _lib.prednet_workspace_bytes(blocks, self.E, self.V, self.Jp, self.R)
-            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
-                self._ws = _new_workspace(nbytes, dev)
-            elif _WORKSPACE_FILL is not None:
-                self._ws.fill_(int(_WORKSPACE_FILL))
+            self._ws = _workspace(self._ws, nbytes, dev)
             self.pred_proj = torch.empty(self.R, self.Jp, dtype=torch.float32, device=dev)
             self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, 0, 1, 1)
             st = _lib.load().compute_rnnt_prednet_begin(keep[0].data_ptr(), blocks, len(blocks), self.E, self.V, keep[1].data_ptr(),
@@ -1273,12 +1326,12 @@ class PredictionStep:
 
     def step(self, emitted: torch.Tensor, parents=None) -> torch.Tensor:
         if not self._use_engine:
-            return self._torch_step(emitted, parents)
+            return self._project(self._torch.step(emitted, parents))
         dev = self.pred_proj.device
         em = emitted.to(device=dev, dtype=torch.int32).contiguous()
         pa = None if parents is None else parents.to(device=dev, dtype=torch.int32).contiguous()
         self._args = (em, pa)  # (alive until the launch has read them)
-        st = _lib.load().compute_rnnt_prednet_step(em.data_ptr(), None if pa is None else pa.data_ptr(), self.pred_proj.data_ptr(),
+        st = _lib.load().compute_rnnt_prednet_step(em.data_ptr(), ptr(pa), self.pred_proj.data_ptr(),
                                                    self._blocks, len(self._blocks), self.E, self.V, self.Jp, self.R,
                                                    self._ws.data_ptr(), self._opts)
         _lib.check(st, "compute_rnnt_prednet_step")
@@ -1289,15 +1342,8 @@ class PredictionStep:
         """Restart the rows where mask [rows] (bool or int) is set: zero state, then the start token 0 -- what begin runs for
         every row (compute_rnnt_prednet_reset on the engine).  The other rows keep their state and pred_proj.  -> pred_proj."""
         if not self._use_engine:
-            from .decoding import _pred_step
-
-            dev = self._g.device
-            m = torch.as_tensor(mask, device=dev).reshape(self.R).bool()
-            g0, st0 = _pred_step(self.net, torch.zeros(self.R, dtype=torch.int32, device=dev), [None] * len(self.net.blocks))
-            self._g = torch.where(m[:, None], g0, self._g)
-            self._states = [(torch.where(m[None, :, None], h0, h), torch.where(m[None, :, None], c0, c))
-                            for (h0, c0), (h, c) in zip(st0, self._states)]
-            return self._project()
+            m = torch.as_tensor(mask, device=self._torch.device).reshape(self.R).bool()
+            return self._project(self._torch.begin(self.R, m))
         m = _device_i32(mask, self.pred_proj.device).reshape(self.R)
         self._args = (m,)
         st = _lib.load().compute_rnnt_prednet_reset(m.data_ptr(), self.pred_proj.data_ptr(), self._blocks, len(self._blocks), self.E,
@@ -1310,7 +1356,7 @@ class PredictionStep:
         """Every block's current (r [rows, proj], c [rows, hidden]): torch's (h, c) of the LSTM (views on the engine, valid until
         the next step)."""
         if not self._use_engine:
-            return [(h[0], c[0]) for h, c in self._states]
+            return [(h[0], c[0]) for h, c in self._torch.states]
         R = self.R
         a64 = lambda n: (n + 63) // 64 * 64  # noqa: E731  (the workspace layout of include/rnnt.h)
         sizes = [(R * b.proj, R * b.hidden) for b in self._blocks]
@@ -1323,25 +1369,8 @@ class PredictionStep:
             off += a64(p) + a64(c)
         return out
 
-    # ---- torch composition
-    def _project(self):
-        return torch.matmul(self._g.to(self.W1.dtype), self.W1)
-
-    def _torch_step(self, emitted, parents):
-        from .decoding import _pred_step
-
-        g, states = self._g, self._states
-        if parents is not None:
-            idx = parents.to(g.device).long()
-            g = g[idx]
-            states = [(h[:, idx], c[:, idx]) for h, c in states]
-        emitted = emitted.to(g.device)
-        mask = emitted >= 0
-        g2, states2 = _pred_step(self.net, emitted.clamp(min=0), states)
-        self._g = torch.where(mask[:, None], g2, g)
-        self._states = [(torch.where(mask[None, :, None], h2, h), torch.where(mask[None, :, None], c2, c))
-                        for (h2, c2), (h, c) in zip(states2, states)]
-        return self._project()
+    def _project(self, g):
+        return torch.matmul(g.to(self.W1.dtype), self.W1)
 
 
 class EncoderStream:
@@ -1422,10 +1451,7 @@ class EncoderStream:
         self.F, self.bn_eps = bn.num_features, float(bn.eps)
         with torch.cuda.device(dev):
             nbytes = _lib.encoder_workspace_bytes(blocks, self.F, self.ridx, self.factor, self.R, self.Tmax)
-            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
-                self._ws = _new_workspace(nbytes, dev)
-            elif _WORKSPACE_FILL is not None:
-                self._ws.fill_(int(_WORKSPACE_FILL))
+            self._ws = _workspace(self._ws, nbytes, dev)
             self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, 0, 1, 1)
             st = _lib.load().compute_rnnt_encoder_begin(blocks, len(blocks), self.F, *(x.data_ptr() for x in keep[:4]), self.bn_eps,
                                                         self.ridx, self.factor, self.R, self.Tmax, self._ws.data_ptr(), self._opts)
@@ -1454,7 +1480,7 @@ class EncoderStream:
             rf = _device_i32([T] * self.R if row_frames is None else row_frames, dev).reshape(self.R)
             rs = None if reset is None else _device_i32(reset, dev).reshape(self.R)
             self._rows = (rf, rs)
-            st = _lib.load().compute_rnnt_encoder_run_rows(x.data_ptr(), T, rf.data_ptr(), None if rs is None else rs.data_ptr(),
+            st = _lib.load().compute_rnnt_encoder_run_rows(x.data_ptr(), T, rf.data_ptr(), ptr(rs),
                                                            out.data_ptr(), self._blocks, len(self._blocks), self.F, self.bn_eps,
                                                            self.ridx, self.factor, self.R, self.Tmax, self._ws.data_ptr(), self._opts)
             _lib.check(st, "compute_rnnt_encoder_run_rows")

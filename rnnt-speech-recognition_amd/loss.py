@@ -20,6 +20,7 @@ import math
 import torch
 
 from . import _lib
+from ._lib import ptr
 
 
 def _as_i32(x: torch.Tensor, device) -> torch.Tensor:
@@ -130,7 +131,6 @@ def _modified_inputs(what, acts, labels, input_lengths, label_lengths):
 def _modified_call(acts, grads, labels, input_lengths, label_lengths, scale, costs, ws, blank, lam):
     """compute_rnnt_loss_modified on the current stream (grads / scale / costs: tensors or None)."""
     B, T, U, V = acts.shape
-    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
     with torch.cuda.device(acts.device):
         opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, int(blank), T, U)
         st = _lib.load_mod().compute_rnnt_loss_modified(

@@ -20,6 +20,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._lib import ptr
 from .loss import _as_i32, check_fastemit_lambda, check_topology
 from .pruning import MAX_S_RANGE, _TOPOLOGY_ID, _check_blank, _mirror as _band_mirror, prune_ranges
 from .simple import rnnt_loss_simple
@@ -87,7 +88,6 @@ def _joint_call(enc, pred, W2, b2, sb, labels, il, ll, scale, costs, grads, ws, 
     """compute_rnnt_joint_loss_pruned on the current stream (scale / costs: tensors or None; grads: four tensors or None)."""
     B, T, J = enc.shape
     U, V = pred.shape[1], W2.shape[1]
-    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
     g = (None,) * 4 if grads is None else grads
     with torch.cuda.device(enc.device):
         opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, int(blank), T, U)

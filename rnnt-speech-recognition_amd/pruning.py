@@ -25,6 +25,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._lib import ptr
 from .loss import _as_i32, check_fastemit_lambda, check_topology
 
 MAX_S_RANGE = 64
@@ -76,7 +77,6 @@ def _check_blank(what, blank_label, V):
 def _pruned_call(acts, grads, s_begin, labels, input_lengths, label_lengths, scale, costs, ws, blank, lam, topology, maxU):
     """compute_rnnt_loss_pruned on the current stream (grads / scale / costs: tensors or None)."""
     B, T, S, V = acts.shape
-    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
     with torch.cuda.device(acts.device):
         opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, int(blank), T, maxU)
         st = _lib.load_pruned().compute_rnnt_loss_pruned(

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr
 from .loss import _as_i32, check_fastemit_lambda, check_topology
 from .pruning import prune_joint_inputs, prune_ranges, rnnt_loss_pruned
 
@@ -75,7 +76,6 @@ def _inputs(what, am, lm, labels, input_lengths, label_lengths, blank_label, cop
 def _simple_call(am, lm, grad_am, grad_lm, occupancy, labels, input_lengths, label_lengths, scale, costs, ws, blank, l, a, topology):
     """compute_rnnt_loss_simple on the current stream (grad_am / grad_lm / occupancy / scale / costs: tensors or None)."""
     B, T, V = am.shape
-    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
     with torch.cuda.device(am.device):
         opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, int(blank), T, lm.shape[1])
         st = _lib.load_simple().compute_rnnt_loss_simple(

@@ -22,11 +22,11 @@ from __future__ import annotations
 
 import ctypes
 import math
-import types
 
 import torch
 
 from . import _lib
+from ._lib import ptr
 from . import alignment as _alignment
 from . import decoding as _decoding
 from . import joint as _joint
@@ -92,7 +92,6 @@ def _inputs(what, acts, labels, input_lengths, label_lengths, durations, blank_l
 def _tdt_call(acts, grads, labels, input_lengths, label_lengths, scale, costs, ws, dur, blank, sigma):
     """compute_rnnt_loss_tdt on the current stream (grads / scale / costs: tensors or None)."""
     B, T, U, R = acts.shape
-    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
     d = (ctypes.c_int * len(dur))(*dur)
     with torch.cuda.device(acts.device):
         opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, int(blank), T, U)
@@ -306,7 +305,18 @@ def _cell_logits(joint, e, pred, pred_proj):
     return torch.tanh(z) @ W2 + b2
 
 
-class TDTGreedyJoint:
+def _heads(joint, durations):
+    """The two heads of a TDT joint's W2 [J, V + D] -> (durations, D, V); ValueError unless V >= 2 and the blank is a token."""
+    dur = check_durations(durations)
+    R, blank = joint.W2.shape[1], int(joint.blank_label)
+    V = R - len(dur)
+    if V < 2 or not 0 <= blank < V:
+        raise ValueError(f"TDTGreedyJoint: W2 must have V + D = V + {len(dur)} columns with V >= 2 and the blank inside [0, V), "
+                         f"got {R} columns and blank_label = {blank}")
+    return dur, len(dur), V
+
+
+class TDTGreedyJoint(_joint._GreedyEngineJoint):
     """The joint of the batched greedy TDT decoder (tdt_greedy_search_batch), with the interface of joint.GreedyJoint: one lattice
     cell per hypothesis and step, the argmax of the token head and of the duration head, the two log-softmaxes of the decision and
     the decoder state in one pass.
@@ -326,75 +336,28 @@ class TDTGreedyJoint:
     and `logp` [B, max_hyp_len] (0 there): per token the frame of its decision and the token plus the duration log-probability."""
 
     def __init__(self, joint, durations, joint_dtype: str = "auto", token_times: bool = False):
-        self.joint = joint
-        self.durations = check_durations(durations)
-        self.token_times = bool(token_times)
-        self._frame_base = None  # (the stream: frames of the chunks a slot has left behind)
-        self.blank = int(joint.blank_label)
-        W1, b1, W2, b2 = (x.detach() for x in (joint.W1, joint.b1, joint.W2, joint.b2))
-        J, R = W2.shape
-        self.D = len(self.durations)
-        self.V = R - self.D
-        if self.V < 2 or not 0 <= self.blank < self.V:
-            raise ValueError(f"TDTGreedyJoint: W2 must have V + D = V + {self.D} columns with V >= 2 and the blank inside [0, V), "
-                             f"got {R} columns and blank_label = {self.blank}")
-        self.engine = W2.is_cuda
-        if self.engine:
-            if joint_dtype == "auto":
-                joint_dtype = _joint._auto_joint_dtype(J, R)
-            try:
-                Jp, _ = _joint.padded_joint_shape(J, R, joint_dtype)
-            except ValueError:
-                self.engine = False
-        if self.engine:
-            self.dtype = _joint.JOINT_DTYPES[joint_dtype]
-            self.Jp = Jp
-            pad = lambda x, p: torch.nn.functional.pad(x.float(), p).contiguous()  # noqa: E731
-            self.W1, self.b1 = pad(W1, (0, Jp - J)), pad(b1, (0, Jp - J))
-            self.W2, self.b2 = pad(W2, (0, 0, 0, Jp - J)), b2.float().contiguous()
-        self._ws = None
+        self.durations, self.D, V = _heads(joint, durations)
+        super().__init__(joint, joint_dtype, token_times)
+        self.V = V
 
     # ---- engine
     def begin(self, enc, frame_lengths, max_symbols, max_per_frame: int, max_hyp_len: int):
         if int(max_per_frame) < 1:
             raise ValueError(f"max_per_frame must be at least 1, got {max_per_frame!r}")
-        B, T = enc.shape[0], enc.shape[1]
-        dev = enc.device
-        self.B, self.T = B, T
-        self.hyps = torch.zeros(B, max_hyp_len, dtype=torch.int32, device=dev)
-        self.lengths = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.emitted = torch.full((B,), -1, dtype=torch.int32, device=dev)
-        self.all_done = torch.zeros(1, dtype=torch.int32, device=dev)
-        frames = frame_lengths.to(device=dev, dtype=torch.int32)
-        maxsym = None if max_symbols is None else max_symbols.to(device=dev, dtype=torch.int32)
-        if not self.engine:
-            self._torch_begin(enc, frames, maxsym, int(max_per_frame))
-            return self._new_times(B, max_hyp_len, dev)
-        lib = _lib.load_tdtgreedy()
-        self.scores = torch.zeros(B, dtype=torch.float32, device=dev)
-        self._new_times(B, max_hyp_len, dev)
-        ep = (torch.matmul(enc.float(), self.W1) + self.b1).contiguous()
-        frames = frames.contiguous()
-        self._keep = (frames, maxsym.contiguous() if maxsym is not None else None)
+        ep = self._begin(enc, frame_lengths, max_symbols, max_per_frame, max_hyp_len)
+        if ep is None:
+            return
+        B, T = self.B, self.T
+        frames, ms = self._keep
         dur = (ctypes.c_int * self.D)(*self.durations)
-        with torch.cuda.device(dev):
+        with torch.cuda.device(enc.device):
             nbytes = _lib.tdt_greedy_workspace_bytes(T, B, self.Jp, self.V, self.D, self.dtype)
-            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
-                self._ws = _joint._new_workspace(nbytes, dev)
-            elif _joint._WORKSPACE_FILL is not None:
-                self._ws.fill_(int(_joint._WORKSPACE_FILL))
+            self._ws = _joint._workspace(self._ws, nbytes, enc.device)
             self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
-            ms = self._keep[1]
-            st = lib.compute_rnnt_tdt_greedy_begin(ep.data_ptr(), self._keep[0].data_ptr(), None if ms is None else ms.data_ptr(),
-                                                   self.W2.data_ptr(), self.b2.data_ptr(), self.Jp, self.V, dur, self.D, B,
-                                                   int(max_per_frame), self.dtype, self._ws.data_ptr(), self._opts)
+            st = _lib.load_tdtgreedy().compute_rnnt_tdt_greedy_begin(
+                ep.data_ptr(), frames.data_ptr(), ptr(ms), self.W2.data_ptr(), self.b2.data_ptr(), self.Jp, self.V, dur, self.D, B,
+                int(max_per_frame), self.dtype, self._ws.data_ptr(), self._opts)
         _lib.check(st, "compute_rnnt_tdt_greedy_begin")
-
-    def _new_times(self, B, max_hyp_len, dev):
-        self.frames = self.logp = None
-        if self.token_times:
-            self.frames = torch.full((B, max_hyp_len), -1, dtype=torch.int32, device=dev)
-            self.logp = torch.zeros(B, max_hyp_len, dtype=self.scores.dtype, device=dev)
 
     def step(self, pred=None, logit_stats=None, *, pred_proj=None):
         """pred [B, H]: the prediction network's output of every row -> emitted [B] (int32, -1 where nothing was emitted).
@@ -402,7 +365,6 @@ class TDTGreedyJoint:
         if not self.engine:
             return self._torch_step(pred, pred_proj)
         pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _joint._projected_operand(pred_proj, self.Jp)
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         st = _lib.load_tdtgreedy().compute_rnnt_tdt_greedy_step(
             pp.data_ptr(), self.hyps.data_ptr(), ptr(self.frames), ptr(self.logp), self.hyps.shape[1], self.lengths.data_ptr(),
             self.scores.data_ptr(), self.emitted.data_ptr(), self.all_done.data_ptr(), ptr(logit_stats), self.Jp, self.V, self.D,
@@ -410,31 +372,10 @@ class TDTGreedyJoint:
         _lib.check(st, "compute_rnnt_tdt_greedy_step")
         return self.emitted
 
-    def grow_hyps(self):
-        """Double the hyps buffer (contents kept; `frames` and `logp` with it): paused hypotheses resume at the next step."""
-        h = self.hyps
-        self.hyps = torch.zeros(h.shape[0], 2 * h.shape[1], dtype=h.dtype, device=h.device)
-        self.hyps[:, : h.shape[1]] = h
-        if self.token_times:
-            f, l = self.frames, self.logp
-            self.frames = torch.full((h.shape[0], 2 * h.shape[1]), -1, dtype=f.dtype, device=f.device)
-            self.logp = torch.zeros(h.shape[0], 2 * h.shape[1], dtype=l.dtype, device=l.device)
-            self.frames[:, : h.shape[1]], self.logp[:, : h.shape[1]] = f, l
-
     # ---- torch composition: the same state machine (tdt_greedy_update_kernel)
     def _torch_begin(self, enc, frames, maxsym, max_per_frame):
-        B, T = enc.shape[0], enc.shape[1]
-        dev = enc.device
-        self._enc = enc
-        self.scores = torch.zeros(B, dtype=torch.promote_types(enc.dtype, torch.float32), device=dev)
-        self._Tb = frames.clamp(0, T).long()
-        self._maxsym = (torch.full((B,), 2**31 - 1, dtype=torch.long, device=dev) if maxsym is None else maxsym.clamp(min=0).long())
-        self._cap = max_per_frame
-        self._dur = torch.tensor(self.durations, dtype=torch.long, device=dev)
-        self._t = torch.zeros(B, dtype=torch.long, device=dev)
-        self._n = torch.zeros(B, dtype=torch.long, device=dev)
-        self._nf = torch.zeros(B, dtype=torch.long, device=dev)
-        self._done = (self._Tb == 0) | (self._maxsym == 0)
+        super()._torch_begin(enc, frames, maxsym, max_per_frame)
+        self._dur = torch.tensor(self.durations, dtype=torch.long, device=enc.device)
 
     @staticmethod
     def _head(x):
@@ -491,60 +432,11 @@ def tdt_greedy_search_batch(prediction, joint, enc: torch.Tensor, frame_lengths:
     a token; prediction_route "engine" steps it in the library (joint.PredictionStep).  joint / durations: as for TDTGreedyJoint.
     max_length: None (no bound), an int or a tensor [B]: tokens per utterance at most.  max_symbols_per_frame >= 1."""
     global LAST_STEPS
-    from .decoding import _check_prediction, _pred_step, read_flag
-
-    _check_prediction(prediction_route)
-    B, T = enc.shape[0], enc.shape[1]
-    dev = enc.device
-    if max_length is None:
-        maxsym, N = None, T + 16  # no bound: the buffer grows when a hypothesis fills it
-    elif isinstance(max_length, torch.Tensor):
-        maxsym = max_length.to(device=dev, dtype=torch.int32).reshape(B)
-        N = max(1, read_flag(maxsym.max().reshape(1)))
-    else:
-        maxsym = torch.full((B,), int(max_length), dtype=torch.int32, device=dev)
-        N = max(1, int(max_length))
+    _decoding._check_prediction(prediction_route)
     jg = TDTGreedyJoint(joint, durations, token_times=token_times)
-    done = lambda: (jg.hyps, jg.lengths, jg.scores, jg.frames, jg.logp) if token_times else (jg.hyps, jg.lengths, jg.scores)  # noqa: E731
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream) if enc.is_cuda else None
-    jg._ws = _WORKSPACES.get(key)  # the workspace of the last decode on this stream, when it is large enough
-    jg.begin(enc, frame_lengths, maxsym, int(max_symbols_per_frame), N)
-    if jg._ws is not None:
-        _WORKSPACES[key] = jg._ws
-    steps = 0
-    if prediction_route == "engine":  # the loop body is library calls alone: the joint step, then the prediction-network step
-        ps = _joint.PredictionStep(prediction, jg.W1 if jg.engine else joint.W1.detach())
-        pp = ps.begin(B)
-        while True:
-            emitted = jg.step(pred_proj=pp)
-            steps += 1
-            if steps % check_every == 0:
-                flag = read_flag(jg.all_done)
-                if flag == 1:
-                    break
-                if flag == 2:
-                    jg.grow_hyps()
-            pp = ps.step(emitted)
-        LAST_STEPS = steps
-        return done()
-    g, states = _pred_step(prediction, torch.zeros(B, dtype=torch.int32, device=dev), [None] * len(prediction.blocks))
-    while True:
-        emitted = jg.step(g)
-        steps += 1
-        if steps % check_every == 0:
-            flag = read_flag(jg.all_done)
-            if flag == 1:
-                break
-            if flag == 2:
-                jg.grow_hyps()
-        # rows that emitted a token advance their prediction network; the others keep their state
-        mask = emitted >= 0
-        g2, states2 = _pred_step(prediction, emitted.clamp(min=0), states)
-        g = torch.where(mask[:, None], g2, g)
-        states = [(torch.where(mask[None, :, None], h2, h), torch.where(mask[None, :, None], c2, c))
-                  for (h2, c2), (h, c) in zip(states2, states)]
-    LAST_STEPS = steps
-    return done()
+    out, LAST_STEPS = _decoding._greedy_search(jg, _WORKSPACES, prediction, enc, frame_lengths, max_length, int(max_symbols_per_frame),
+                                               check_every, prediction_route)
+    return out
 
 
 # ---- batched beam search ------------------------------------------------------------------------------------------------
@@ -552,7 +444,7 @@ _BEAM_WORKSPACES = {}  # (device, stream[, "timed"]) -> the workspace of the las
 LAST_ACTIVE_ROWS = None  # tdt_beam_search_batch(count_active=True): joint rows evaluated per utterance (timing tools)
 
 
-class TDTBeamJoint:
+class TDTBeamJoint(_joint._EngineJoint):
     """The joint of the batched TDT beam search (tdt_beam_search_batch), with the interface of joint.BeamJoint: per frame the joint
     of every ACTIVE hypothesis of every beam (cursor == frame; a waiting hypothesis costs nothing), the token top-`beam` x durations
     candidates, ranking, merging on (sequence, cursor) and the new beams in one pass.  The rule: include/rnnt_tdt_beam.h.
@@ -573,12 +465,9 @@ class TDTBeamJoint:
         if not 1 <= int(beam) <= 16:
             raise ValueError("TDTBeamJoint: beam must be in 1 ... 16")
         self.K = int(beam)
-        g = TDTGreedyJoint(joint, durations, joint_dtype)  # (the same checks, engine / torch decision and padding)
-        self.joint, self.durations, self.blank, self.V, self.D, self.engine = joint, g.durations, g.blank, g.V, g.D, g.engine
-        self.token_times = bool(token_times)
-        if self.engine:
-            self.dtype, self.Jp, self.W1, self.b1, self.W2, self.b2 = g.dtype, g.Jp, g.W1, g.b1, g.W2, g.b2
-        self._ws = None
+        self.durations, self.D, V = _heads(joint, durations)
+        super().__init__(joint, joint_dtype, token_times)
+        self.V = V
         self._N = None  # (the stream: the tokens a hypothesis may hold)
 
     def _args(self):
@@ -599,10 +488,7 @@ class TDTBeamJoint:
         dur = (ctypes.c_int * self.D)(*self.durations)
         with torch.cuda.device(dev):
             nbytes = _lib.tdt_beam_workspace_bytes(T, B, self.K, self.Jp, self.V, self.D, self.dtype, self.token_times)
-            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
-                self._ws = _joint._new_workspace(nbytes, dev)
-            elif _joint._WORKSPACE_FILL is not None:
-                self._ws.fill_(int(_joint._WORKSPACE_FILL))
+            self._ws = _joint._workspace(self._ws, nbytes, dev)
             self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
             st = _lib.load_tdtbeam().compute_rnnt_tdt_beam_begin(ep.data_ptr(), frames.data_ptr(), self.W2.data_ptr(), self.b2.data_ptr(),
                                                                  self.Jp, self.V, dur, self.D, B, self.K, self.dtype,
@@ -615,7 +501,6 @@ class TDTBeamJoint:
         if not self.engine:
             return self._torch_step(pred, pred_proj, topk_logits, topk_symbols, dur_logits, lse)
         pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _joint._projected_operand(pred_proj, self.Jp)
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         st = _lib.load_tdtbeam().compute_rnnt_tdt_beam_step(pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(),
                                                             ptr(topk_logits), ptr(topk_symbols), ptr(dur_logits), ptr(lse), *self._args())
         _lib.check(st, "compute_rnnt_tdt_beam_step")
@@ -640,7 +525,6 @@ class TDTBeamJoint:
         cursors = torch.empty(B, K, dtype=torch.int32, device=dev)
         frames = torch.empty(B, K, T, dtype=torch.int32, device=dev) if self.token_times else None
         durs = torch.empty(B, K, T, dtype=torch.int32, device=dev) if self.token_times else None
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         st = _lib.load_tdtbeam().compute_rnnt_tdt_beam_results(hyps.data_ptr(), lengths.data_ptr(), scores.data_ptr(), cursors.data_ptr(),
                                                                ptr(frames), ptr(durs), *self._args())
         _lib.check(st, "compute_rnnt_tdt_beam_results")
@@ -778,54 +662,19 @@ def tdt_beam_search_batch(prediction, joint, enc: torch.Tensor, frame_lengths: t
     prediction_route / joint / durations: as for tdt_greedy_search_batch.  count_active (timing tools): LAST_ACTIVE_ROWS becomes a
     device tensor [B] of the joint rows evaluated per utterance (one more small torch op per step, still no host read)."""
     global LAST_ACTIVE_ROWS
-    from .decoding import _check_prediction, _pred_step
-
-    _check_prediction(prediction_route)
+    _decoding._check_prediction(prediction_route)
     B, T = enc.shape[0], enc.shape[1]
-    K = int(beam)
     dev = enc.device
-    jb = TDTBeamJoint(joint, durations, K, token_times=bool(token_times))
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream) if enc.is_cuda else None
-    if token_times and key is not None:
-        key = key + ("timed",)  # (a timed decode keeps a workspace of its own)
-    jb._ws = _BEAM_WORKSPACES.get(key)
-    jb.begin(enc, frame_lengths)
-    if jb._ws is not None:
-        _BEAM_WORKSPACES[key] = jb._ws
+    jb = TDTBeamJoint(joint, durations, int(beam), token_times=bool(token_times))
     active = torch.zeros(B, dtype=torch.int64, device=dev) if count_active else None
     Tb = frame_lengths.to(dev).clamp(0, T) if count_active else None
 
     def count(t):
-        if active is not None:
-            active.add_(((jb.cursors() == t) & (t < Tb)[:, None]).sum(1))
+        active.add_(((jb.cursors() == t) & (t < Tb)[:, None]).sum(1))
 
-    if prediction_route == "engine":
-        # (the prediction-network workspace of the last engine-route decode on this stream is reused, as beam_search_batch does)
-        ps, pp = _decoding._prediction_step(types.SimpleNamespace(prediction=prediction, joint=joint), jb, B * K, dev)
-        for t in range(T):
-            count(t)
-            parents, emitted = jb.step(pred_proj=pp)
-            if t + 1 == T:
-                break
-            pp = ps.step(emitted, parents)
-        LAST_ACTIVE_ROWS = active
-        return jb.results()
-    g, states = _pred_step(prediction, torch.zeros(B * K, dtype=torch.int32, device=dev), [None] * len(prediction.blocks))
-    for t in range(T):
-        count(t)
-        parents, emitted = jb.step(g)
-        if t + 1 == T:
-            break
-        idx = parents.long()
-        g = g[idx]
-        states = [(h[:, idx], c[:, idx]) for h, c in states]
-        mask = emitted >= 0
-        g2, states2 = _pred_step(prediction, emitted.clamp(min=0), states)
-        g = torch.where(mask[:, None], g2, g)
-        states = [(torch.where(mask[None, :, None], h2, h), torch.where(mask[None, :, None], c2, c))
-                  for (h2, c2), (h, c) in zip(states2, states)]
+    out = _decoding._beam_search(jb, _BEAM_WORKSPACES, prediction, enc, frame_lengths, prediction_route, count if count_active else None)
     LAST_ACTIVE_ROWS = active
-    return jb.results()
+    return out
 
 
 # ---- streaming greedy decoding ------------------------------------------------------------------------------------------
@@ -848,34 +697,15 @@ class TDTGreedyStreamJoint(TDTGreedyJoint):
     def begin(self, slots: int, max_chunk_frames: int, max_per_frame: int, max_hyp_len: int, device=None):
         if int(max_per_frame) < 1:
             raise ValueError(f"max_per_frame must be at least 1, got {max_per_frame!r}")
-        S, T = int(slots), int(max_chunk_frames)
-        dev = self.W2.device if self.engine else (device if device is not None else self.joint.W2.device)
-        self.B, self.T, self.Tc = S, T, T
-        self.hyps = torch.zeros(S, max_hyp_len, dtype=torch.int32, device=dev)
-        self.lengths = torch.zeros(S, dtype=torch.int32, device=dev)
-        self.emitted = torch.full((S,), -1, dtype=torch.int32, device=dev)
-        self.all_done = torch.ones(1, dtype=torch.int32, device=dev)
-        self._cap = int(max_per_frame)
+        dev = self._begin_stream(slots, max_chunk_frames, max_per_frame, max_hyp_len, device)
         if not self.engine:
-            self.scores = torch.zeros(S, dtype=torch.promote_types(self.joint.W2.dtype, torch.float32), device=dev)
-            self._new_times(S, max_hyp_len, dev)
-            z = torch.zeros(S, dtype=torch.long, device=dev)
-            self._frame_base = z.clone()
-            self._t, self._n, self._nf, self._Tb, self._maxsym = z.clone(), z.clone(), z.clone(), z.clone(), z.clone()
-            self._done = torch.ones(S, dtype=torch.bool, device=dev)
-            self._fin = torch.ones(S, dtype=torch.bool, device=dev)
             self._dur = torch.tensor(self.durations, dtype=torch.long, device=dev)
             return
-        self.H = int(self.W1.shape[0])
-        self.scores = torch.zeros(S, dtype=torch.float32, device=dev)
-        self._new_times(S, max_hyp_len, dev)
+        S, T = self.B, self.T
         dur = (ctypes.c_int * self.D)(*self.durations)
         with torch.cuda.device(dev):
             nbytes = _lib.tdt_greedy_stream_workspace_bytes(T, S, self.H, self.Jp, self.V, self.D, self.dtype)
-            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
-                self._ws = _joint._new_workspace(nbytes, dev)
-            elif _joint._WORKSPACE_FILL is not None:
-                self._ws.fill_(int(_joint._WORKSPACE_FILL))
+            self._ws = _joint._workspace(self._ws, nbytes, dev)
             self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
             st = _lib.load_tdtstream().compute_rnnt_tdt_greedy_stream_begin(
                 self.W1.data_ptr(), self.b1.data_ptr(), self.W2.data_ptr(), self.b2.data_ptr(), self.H, self.Jp, self.V, dur, self.D,
@@ -899,7 +729,6 @@ class TDTGreedyStreamJoint(TDTGreedyJoint):
         cv = lambda x: None if x is None else _joint._device_i32(x, dev).reshape(S)  # noqa: E731
         fr, rs, fi, ms = cv(frames), cv(reset), cv(final), cv(max_symbols)
         self._feed_args = (enc, fr, rs, fi, ms)  # (alive until the launches have read them)
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         st = _lib.load_tdtstream().compute_rnnt_tdt_greedy_stream_feed(
             ptr(enc) if Te > 0 else None, Te, fr.data_ptr(), ptr(rs), ptr(fi), ptr(ms), self._cap, self.lengths.data_ptr(),
             self.scores.data_ptr(), self.all_done.data_ptr(), self.H, self.Jp, self.V, self.D, S, self.dtype, self._ws.data_ptr(),
@@ -913,8 +742,7 @@ class TDTGreedyStreamJoint(TDTGreedyJoint):
         st = _lib.load_tdtstream().compute_rnnt_tdt_greedy_stream_step(
             pp.data_ptr(), self.hyps.data_ptr(), self.frames.data_ptr(), self.logp.data_ptr(), self.hyps.shape[1],
             self.lengths.data_ptr(), self.scores.data_ptr(), self.emitted.data_ptr(), self.all_done.data_ptr(),
-            None if logit_stats is None else logit_stats.data_ptr(), self.Jp, self.V, self.D, self.B, self.dtype, self._ws.data_ptr(),
-            self._opts)
+            ptr(logit_stats), self.Jp, self.V, self.D, self.B, self.dtype, self._ws.data_ptr(), self._opts)
         _lib.check(st, "compute_rnnt_tdt_greedy_stream_step")
         return self.emitted
 
@@ -1024,10 +852,7 @@ class TDTBeamStreamJoint(TDTBeamJoint):
         dur = (ctypes.c_int * self.D)(*self.durations)
         with torch.cuda.device(dev):
             nbytes = _lib.tdt_beam_stream_workspace_bytes(T, S, K, N, self.H, self.Jp, self.V, self.D, self.dtype, self.token_times)
-            if self._ws is None or self._ws.device != dev or self._ws.numel() < nbytes:
-                self._ws = _joint._new_workspace(nbytes, dev)
-            elif _joint._WORKSPACE_FILL is not None:
-                self._ws.fill_(int(_joint._WORKSPACE_FILL))
+            self._ws = _joint._workspace(self._ws, nbytes, dev)
             self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
             st = _lib.load_tdtbeamstream().compute_rnnt_tdt_beam_stream_begin(
                 self.W1.data_ptr(), self.b1.data_ptr(), self.W2.data_ptr(), self.b2.data_ptr(), self.H, self.Jp, self.V, dur, self.D,
@@ -1050,7 +875,6 @@ class TDTBeamStreamJoint(TDTBeamJoint):
         cv = lambda x: None if x is None else _joint._device_i32(x, dev).reshape(S)  # noqa: E731
         fr, rs, fi = cv(frames), cv(reset), cv(final)
         self._feed_args = (enc, fr, rs, fi)  # (alive until the launches have read them)
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         st = _lib.load_tdtbeamstream().compute_rnnt_tdt_beam_stream_feed(
             ptr(enc) if Te > 0 else None, Te, fr.data_ptr(), ptr(rs), ptr(fi), self.H, self.Jp, self.V, self.D, S, self.K, self.N,
             self.dtype, int(self.token_times), self._ws.data_ptr(), self._opts)
@@ -1061,7 +885,6 @@ class TDTBeamStreamJoint(TDTBeamJoint):
         if not self.engine:
             return self._torch_step(pred, pred_proj, topk_logits, topk_symbols, dur_logits, lse)
         pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _joint._projected_operand(pred_proj, self.Jp)
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         st = _lib.load_tdtbeamstream().compute_rnnt_tdt_beam_stream_step(
             pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(), ptr(topk_logits), ptr(topk_symbols), ptr(dur_logits),
             ptr(lse), *self._args())
@@ -1077,7 +900,6 @@ class TDTBeamStreamJoint(TDTBeamJoint):
         hyps, lengths, cursors, stable = i32(S, K, N), i32(S, K), i32(S, K), i32(S)
         scores = torch.empty(S, K, dtype=torch.float32, device=dev)
         frames, durs, tstable = (i32(S, K, N), i32(S, K, N), i32(S)) if self.token_times else (None, None, None)
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         st = _lib.load_tdtbeamstream().compute_rnnt_tdt_beam_stream_results(
             hyps.data_ptr(), lengths.data_ptr(), scores.data_ptr(), cursors.data_ptr(), stable.data_ptr(), ptr(frames), ptr(durs),
             ptr(tstable), *self._args())

@@ -21,6 +21,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._lib import ptr
 from .loss import _as_i32
 from .tdt import MAX_U, _mirror as _lattice_mirror, check_durations, check_sigma
 
@@ -77,7 +78,6 @@ def _joint_call(enc, pred, W2, b2, labels, il, ll, scale, costs, grads, ws, dur,
     """compute_rnnt_joint_loss_tdt on the current stream (scale / costs: tensors or None; grads: four tensors or None)."""
     B, T, J = enc.shape
     U, R = pred.shape[1], W2.shape[1]
-    ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
     g = (None,) * 4 if grads is None else grads
     d = (ctypes.c_int * len(dur))(*dur)
     with torch.cuda.device(enc.device):
