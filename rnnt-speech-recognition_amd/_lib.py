@@ -6,7 +6,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-from .build import EVERY_LIBRARY, lib_path
+from .build import BUILT_LIBRARIES, EVERY_LIBRARY, NEXT_LIBRARIES, lib_path
 
 # dev knob: load an experimental build of the library instead (scripts/build_variant.sh)
 LIB_PATH = os.environ.get("RNNT_LIBWARPRNNT", lib_path("base"))
@@ -18,6 +18,7 @@ if LIB_PATH != _PATHS["base"]:
     _PATHS["base"] = LIB_PATH
     for _n in ("bias", "lm"):
         _PATHS[_n] = os.path.join(os.path.dirname(LIB_PATH), os.path.basename(_PATHS[_n]))
+_NEXT_PATHS = {name: lib_path(name) for name in NEXT_LIBRARIES}  # (tests pin the keys of _PATHS: the rows added since)
 _libs = {}  # name -> the loaded and bound library
 
 RNNT_CPU, RNNT_GPU = 0, 1
@@ -242,6 +243,16 @@ _LATER_SIGNATURES = {
     },
 }
 _EVERY_SIGNATURE = {**_ALL_SIGNATURES, **_LATER_SIGNATURES}
+# the libraries of build.NEXT_LIBRARIES (the tables above are frozen by the tests that pin them, their lengths included)
+_NEXT_SIGNATURES = {
+    "multibeam": {
+        "get_rnnt_multibeam_workspace_size": [ci] * 8 + [sz],
+        "compute_rnnt_multibeam_begin": [vp] * 4 + [ci] * 7 + [vp, opt],
+        "compute_rnnt_multibeam_step": [vp] * 3 + [ci] * 7 + [vp, opt],
+        "compute_rnnt_multibeam_results": [vp] * 3 + [ci] * 7 + [vp, opt],
+    },
+}
+_BUILT_SIGNATURES = {**_EVERY_SIGNATURE, **_NEXT_SIGNATURES}
 _RESTYPES = {"rnntGetStatusString": ctypes.c_char_p}
 del vp, ci, cu, cf, opt, sz, blk
 SYMBOLS, BIAS_SYMBOLS, LM_SYMBOLS = list(SIGNATURES["base"]), list(SIGNATURES["bias"]), list(SIGNATURES["lm"])
@@ -252,20 +263,20 @@ class RNNTLibraryError(RuntimeError):
 
 
 def _load(name: str):
-    """Load one library of build.EVERY_LIBRARY (once) and bind its row of _EVERY_SIGNATURE on it.
+    """Load one library of build.BUILT_LIBRARIES (once) and bind its row of _BUILT_SIGNATURES on it.
     Raises RNNTLibraryError loudly when it is absent, does not load or lacks a symbol: there is no fallback."""
     if name in _libs:
         return _libs[name]
-    path = _PATHS[name]
+    path = _PATHS[name] if name in _PATHS else _NEXT_PATHS[name]
     if not os.path.exists(path):
         raise RNNTLibraryError(f"{path} not found: the HIP extension has not been built. Run scripts/build_rnnt.sh (or "
-                               f"__graft_entry__.build()). There is no eager fallback for include/{EVERY_LIBRARY[name].header}.")
+                               f"__graft_entry__.build()). There is no eager fallback for include/{BUILT_LIBRARIES[name].header}.")
     try:
         lib = ctypes.CDLL(path)
     except OSError as e:  # pragma: no cover - depends on the ROCm runtime being present
         raise RNNTLibraryError(f"failed to load {path}: {e}") from e
     variant = name == "base" and path != lib_path("base")  # an older revision (scripts/build_variant.sh) may lack the newer symbols
-    for symbol, argtypes in _EVERY_SIGNATURE[name].items():
+    for symbol, argtypes in _BUILT_SIGNATURES[name].items():
         if not hasattr(lib, symbol):
             if variant:
                 continue
@@ -354,6 +365,11 @@ def load_tdtjoint():
 def load_tdtbeamstream():
     """libwarprnnt_tdtbeamstream.so: streaming beam search of the TDT transducer over slots, include/rnnt_tdt_beam_stream.h."""
     return _load("tdtbeamstream")
+
+
+def load_multibeam():
+    """libwarprnnt_multibeam.so: batched beam search with several symbols per frame, include/rnnt_beam_multi.h."""
+    return _load("multibeam")
 
 
 def status_string(status: int) -> str:
@@ -510,3 +526,9 @@ def tdt_beam_stream_workspace_bytes(max_chunk_frames: int, slots: int, beam: int
                                     alphabet_size: int, num_durations: int, joint_dtype: int, timed: bool = False) -> int:
     return _size(load_tdtbeamstream(), "get_rnnt_tdt_beam_stream_workspace_size", max_chunk_frames, slots, beam, max_hyp_len, enc_width,
                  joint_size, alphabet_size, num_durations, joint_dtype, int(bool(timed)))
+
+
+def multibeam_workspace_bytes(maxT: int, minibatch: int, beam: int, symbols_per_frame: int, max_hyp_len: int, joint_size: int,
+                              alphabet_size: int, joint_dtype: int) -> int:
+    return _size(load_multibeam(), "get_rnnt_multibeam_workspace_size", maxT, minibatch, beam, symbols_per_frame, max_hyp_len,
+                 joint_size, alphabet_size, joint_dtype)

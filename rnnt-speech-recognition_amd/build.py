@@ -68,7 +68,7 @@ ALL_LIBRARIES = {
                          "rnnt_tdt_greedy.map"),
 }
 # Later rows.  tests/test_abi_tdt_greedy.py pins list(ALL_LIBRARIES) too, so the three tables above are frozen as they stand; this one
-# is open: a new library is a new row here, and no test pins its keys.  EVERY_LIBRARY is what the build and the binding work over.
+# was open until a test pinned the merged table's length (see NEXT_LIBRARIES below, where a new library is a row now).
 LATER_LIBRARIES = {
     # greedy decoding of the TDT transducer over a stream of chunks per slot: its own feed and update kernels on the greedy
     # stream's projection and on the step kernel of "tdtgreedy", whose kernel object it links beside the base kernels'
@@ -90,6 +90,16 @@ LATER_LIBRARIES = {
                              _BASE_KERNELS, "rnnt_tdtbeamstream.map"),
 }
 EVERY_LIBRARY = {**ALL_LIBRARIES, **LATER_LIBRARIES}
+# tests/test_abi_tdt_beam_stream.py pins len(EVERY_LIBRARY) to 16, so LATER_LIBRARIES and EVERY_LIBRARY are frozen as well.  The rows
+# added since stand here, and BUILT_LIBRARIES is what the build and the binding work over.  No test pins the length of this table.
+NEXT_LIBRARIES = {
+    # batched beam search with several symbols per frame (time-synchronous, on the standard lattice): its own select, begin and
+    # results kernels and the beam search's step body at a flag value of its own; the base kernel objects and its own entry
+    # points, as "tdtbeam"
+    "multibeam": Library("rnnt_beam_multi.h", ("multibeam_kernels.hip", "rnnt_multibeam_entrypoint.hip"), _BASE_KERNELS,
+                         "rnnt_multibeam.map"),
+}
+BUILT_LIBRARIES = {**EVERY_LIBRARY, **NEXT_LIBRARIES}
 
 
 def lib_path(name: str) -> str:
@@ -112,6 +122,7 @@ TDTALIGN_LIB_PATH = lib_path("tdtalign")
 TDTBEAM_LIB_PATH = lib_path("tdtbeam")
 TDTJOINT_LIB_PATH = lib_path("tdtjoint")
 TDTBEAMSTREAM_LIB_PATH = lib_path("tdtbeamstream")
+MULTIBEAM_LIB_PATH = lib_path("multibeam")
 # -fvisibility=hidden: the library exports exactly the entry points include/rnnt.h marks RNNT_API (tests/test_abi.py)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-inline-asm"]
 # per-source extras.  -fno-slp-vectorize: no packed-f32 instructions (v_pk_fma_f32 ...) from the compiler -- in the linear sweeps
@@ -122,17 +133,18 @@ _NO_SLP = ["-fno-slp-vectorize"]
 EXTRA_FLAGS = {"rnnt_lin_kernels.hip": _NO_SLP, "joint_kernels.hip": _NO_SLP, "joint_f16_kernels.hip": _NO_SLP, "dense_kernels.hip": _NO_SLP,
                "greedy_kernels.hip": _NO_SLP, "tdt_greedy_kernels.hip": _NO_SLP, "tdt_stream_kernels.hip": _NO_SLP, "beam_kernels.hip": _NO_SLP, "beam_bias_kernels.hip": _NO_SLP,
                "beam_lm_kernels.hip": _NO_SLP, "tdt_beam_kernels.hip": _NO_SLP, "tdt_nbest_stream_kernels.hip": _NO_SLP,
+               "multibeam_kernels.hip": _NO_SLP,
                "prednet_kernels.hip": _NO_SLP, "encoder_kernels.hip": _NO_SLP, "lstm_train_kernels.hip": _NO_SLP,
                "rnnt_pruned_joint_kernels.hip": _NO_SLP, "rnnt_tdt_joint_kernels.hip": _NO_SLP}
 
 
 def _deps():
     files = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".map"))]
-    return files + [os.path.join(os.path.dirname(_HERE), "include", lib.header) for lib in EVERY_LIBRARY.values()]
+    return files + [os.path.join(os.path.dirname(_HERE), "include", lib.header) for lib in BUILT_LIBRARIES.values()]
 
 
 def needs_build() -> bool:
-    libs = [lib_path(name) for name in EVERY_LIBRARY]
+    libs = [lib_path(name) for name in BUILT_LIBRARIES]
     if not all(os.path.exists(p) for p in libs):
         return True
     t = min(os.path.getmtime(p) for p in libs)
@@ -149,7 +161,7 @@ def _compile_one(args):
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    """Compile every source of EVERY_LIBRARY once (one hipcc per source, in parallel) and link each library from the
+    """Compile every source of BUILT_LIBRARIES once (one hipcc per source, in parallel) and link each library from the
     objects its entry names, the extensions first and libwarprnnt.so last (needs_build() goes by the oldest of them).  Returns the path of
     libwarprnnt.so."""
     if not force and not needs_build():
@@ -159,15 +171,15 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("hipcc not found: cannot build libwarprnnt.so (ROCm toolchain required)")
     os.makedirs(LIB_DIR, exist_ok=True)
     tag = f".tmp{os.getpid()}"  # several ranks may arrive here at once
-    sources = list(dict.fromkeys(s for lib in EVERY_LIBRARY.values() for s in lib.sources))
+    sources = list(dict.fromkeys(s for lib in BUILT_LIBRARIES.values() for s in lib.sources))
     jobs = [(hipcc, os.path.join(CSRC, s), os.path.join(LIB_DIR, s[:-4] + tag + ".o"), verbose) for s in sources]
     try:
         from concurrent.futures import ThreadPoolExecutor
 
         with ThreadPoolExecutor(max_workers=len(jobs)) as ex:
             obj = dict(zip(sources, ex.map(_compile_one, jobs)))
-        for name in [n for n in EVERY_LIBRARY if n != "base"] + ["base"]:
-            lib = EVERY_LIBRARY[name]
+        for name in [n for n in BUILT_LIBRARIES if n != "base"] + ["base"]:
+            lib = BUILT_LIBRARIES[name]
             extra = ["-Wl,--version-script=" + os.path.join(CSRC, lib.version_script)] if lib.version_script else []
             tmp = lib_path(name) + tag
             cmd = [hipcc] + HIPCC_FLAGS + extra + [obj[s] for s in lib.borrowed + lib.sources] + ["-o", tmp]

@@ -4,10 +4,13 @@
 // unbiased one comes out of the compiler as it did before the biased one existed.  No include guard on purpose.
 // BEAM_STEP_BIAS 2 (beam_step_lm_kernel<DT>, beam_lm_kernels.hip): bg is the n-gram LM of include/rnnt_lm.h (LmArgs) and beta its
 // back-off transition; everything else is the biased kernel's.  The preprocessed text at 0 and at 1 is what it was.
+// BEAM_STEP_BIAS 3 (multibeam_step_kernel<DT>, multibeam_kernels.hip: the search of include/rnnt_beam_multi.h): the unbiased kernel
+// on 2 K rows per utterance, of which the first nslot[b] <= K (the open hypotheses) are live, with the blank kept out of the slice's
+// top-K (its logit still goes to bl).  The preprocessed text at 0, 1 and 2 is what it was.
 template <int DT>
 #if BEAM_STEP_BIAS == 2
 __global__ __launch_bounds__(kGrWaves * 64) void BEAM_STEP_KERNEL(const BeamArgs ba, const LmArgs bg) {
-#elif BEAM_STEP_BIAS
+#elif BEAM_STEP_BIAS == 1
 __global__ __launch_bounds__(kGrWaves * 64) void BEAM_STEP_KERNEL(const BeamArgs ba, const BiasArgs bg) {
 #else
 __global__ __launch_bounds__(kGrWaves * 64) void BEAM_STEP_KERNEL(const BeamArgs ba) {
@@ -18,7 +21,7 @@ __global__ __launch_bounds__(kGrWaves * 64) void BEAM_STEP_KERNEL(const BeamArgs
     __shared__ float r_m[kGrWaves * 64], r_s[kGrWaves * 64];
     __shared__ float stage[DT == 2 ? 32 * 33 : 1];
     __shared__ float lg[32 * (32 * kGrWaves + 1)];
-#if BEAM_STEP_BIAS
+#if BEAM_STEP_BIAS == 1 || BEAM_STEP_BIAS == 2
     __shared__ float bt[32 * (32 * kGrWaves + 1)];  // beta of the tile's symbols
 #endif
     constexpr int LW = 32 * kGrWaves + 1;
@@ -29,11 +32,19 @@ __global__ __launch_bounds__(kGrWaves * 64) void BEAM_STEP_KERNEL(const BeamArgs
 
     bool live = false;
     if (tid < 32) {
+#if BEAM_STEP_BIAS == 3
+        const int r = r0 + tid, b = r / (2 * K);
+#else
         const int r = r0 + tid, b = r / K;
+#endif
         int t = 0, slow = 0;
         if (r < ba.R) {
             const GreedyState s = a.st[b];
+#if BEAM_STEP_BIAS == 3
+            live = s.t < s.Tb && r - b * 2 * K < ba.nslot[b];
+#else
             live = s.t < s.Tb && r - b * K < ba.nslot[b];
+#endif
             t = min(max(s.t, 0), a.T - 1);
             if (live) slow = a.rowflag[(size_t)b * a.T + t];
         }
@@ -44,7 +55,11 @@ __global__ __launch_bounds__(kGrWaves * 64) void BEAM_STEP_KERNEL(const BeamArgs
     __syncthreads();
     gf16 *hA = (gf16 *)smem, *hL = hA + (size_t)J * 32;
     const bool hform = DT == 0 && a.tflag[1] != 0.f;
+#if BEAM_STEP_BIAS == 3
+    dec_build_h<DT>(a, J, r0, s_live, s_slow, [&](int n) { return (size_t)((r0 + n) / (2 * K)) * a.T + s_t[n]; }, hform, hA, hL, tid);
+#else
     dec_build_h<DT>(a, J, r0, s_live, s_slow, [&](int n) { return (size_t)((r0 + n) / K) * a.T + s_t[n]; }, hform, hA, hL, tid);
+#endif
     __syncthreads();
 
     // ---- this wave's chunk of 32 symbols: greedy's (max, sum) per lane, and the logits into lg (NaN: takes no part)
@@ -170,13 +185,18 @@ __global__ __launch_bounds__(kGrWaves * 64) void BEAM_STEP_KERNEL(const BeamArgs
     float val[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) val[i] = lg[n * LW + 16 * q + i];
-#if BEAM_STEP_BIAS
+#if BEAM_STEP_BIAS == 1 || BEAM_STEP_BIAS == 2
     if (s_live[n]) {  // the key
 #pragma unroll
         for (int i = 0; i < 16; ++i) val[i] += bt[n * LW + 16 * q + i];
     }
 #endif
     const int sym0 = slice * 32 * kGrWaves + 16 * q;
+#if BEAM_STEP_BIAS == 3
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        if (sym0 + i == a.blank) val[i] = __builtin_nanf("");  // the blank closes a hypothesis: it is no expansion
+#endif
     const size_t lo = ((size_t)slice * ba.R + r0 + n) * K;
     unsigned taken = 0;
     for (int k = 0; k < K; ++k) {  // (uniform trip count: every lane takes part in the shuffles)
@@ -195,7 +215,7 @@ __global__ __launch_bounds__(kGrWaves * 64) void BEAM_STEP_KERNEL(const BeamArgs
         }
         if (bv != INT_MAX && bv == mine) taken |= 1u << bj;
         if (q == 0 && s_live[n]) {
-#if BEAM_STEP_BIAS
+#if BEAM_STEP_BIAS == 1 || BEAM_STEP_BIAS == 2
             ba.pl[lo + k] = bv != INT_MAX ? lg[n * LW + bv - slice * 32 * kGrWaves] : -INFINITY;  // (raw, in key order)
 #else
             ba.pl[lo + k] = bv != INT_MAX ? bl : -INFINITY;

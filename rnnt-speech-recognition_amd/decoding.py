@@ -24,8 +24,8 @@ from typing import List, Optional
 
 import torch
 
-from .joint import (BeamJoint, BeamStreamJoint, EncoderStream, GreedyJoint, GreedyStreamJoint, PredictionStep, TorchPredictionStep,
-                    _pred_step)  # noqa: F401  (_pred_step: one symbol through the prediction network, for callers of this module)
+from .joint import (BeamJoint, BeamStreamJoint, EncoderStream, GreedyJoint, GreedyStreamJoint, MultiBeamJoint, PredictionStep,
+                    TorchPredictionStep, _pred_step)  # noqa: F401  (_pred_step: one symbol through the prediction network, for callers of this module)
 from .loss import reduced_lengths
 
 
@@ -311,9 +311,22 @@ def _beam_search(jb, cache: dict, pred_net, enc, frame_lengths, prediction: str,
     return jb.results()
 
 
+_MULTIBEAM_WORKSPACES = {}  # (device, stream) -> the workspace of the last several-symbols-per-frame decode there
+
+
+def _multibeam_search(jm, cache: dict, pred_net, enc, frame_lengths, prediction: str):
+    """The batched beam search with several symbols per frame on the fresh joint jm (its workspace from `cache`) -> jm's results:
+    T' (E + 1) steps of _beam_loop over B 2 beam rows."""
+    _begin_cached(cache, _stream_key(enc), jm, enc, frame_lengths)
+    ps, x = _begin_prediction(prediction, pred_net, jm, enc.shape[0] * 2 * jm.K, enc.device)
+    _beam_loop(jm, ps, x, enc.shape[1] * (jm.E + 1), carry=False)
+    return jm.results()
+
+
 @torch.no_grad()
 def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, beam: int = 4, prediction: str = "torch",
-                      token_times: bool = False, context=None, lm=None):
+                      token_times: bool = False, context=None, lm=None, symbols_per_frame: Optional[int] = None,
+                      max_length: Optional[int] = None):
     """Modified beam search (one symbol per frame) over encoder outputs enc [B, T', H] with frame_lengths [B] (the model in eval
     mode) -> (ids int32 [B, beam, T'] zero-padded, lengths int32 [B, beam], scores [B, beam]): every utterance's n-best, sorted
     by score (empty slots: length 0, score -inf).  See include/rnnt.h for the algorithm; beam = 1 is greedy_search_batch with
@@ -333,8 +346,21 @@ def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, bea
 
     lm=lm.NgramLM: shallow fusion of a back-off n-gram LM (in place of a context: both together raise).  Candidates are ranked
     with the LM's score of the token (already scaled by the LM weight), the scores include it, and the results are finalised with
-    the LM's end-of-sentence score and re-sorted (stably).  logp stays the model's log-probability."""
+    the LM's end-of-sentence score and re-sorted (stably).  logp stays the model's log-probability.
+
+    symbols_per_frame=E (an integer 1 ... 8; None: the search above, untouched): the time-synchronous search of
+    include/rnnt_beam_multi.h on the STANDARD lattice -- up to E symbols per frame, which is what a model trained with rnnt_loss may
+    need (more labels than frames included).  It runs T' (E + 1) steps on B 2 beam rows (MultiBeamJoint) and returns ids int32
+    [B, beam, max_hyp_len], max_hyp_len = max_length or T' E: a hypothesis of max_hyp_len tokens emits no more.  token_times,
+    context and lm raise together with it."""
     _check_prediction(prediction)
+    if symbols_per_frame is not None:
+        if token_times or context is not None or lm is not None:
+            raise ValueError("symbols_per_frame= takes no token_times, context or lm")
+        jm = MultiBeamJoint(model.joint, int(beam), int(symbols_per_frame), max_length)
+        return _multibeam_search(jm, _MULTIBEAM_WORKSPACES, model.prediction, enc, frame_lengths, prediction)
+    if max_length is not None:
+        raise ValueError("max_length= bounds the hypotheses of the search with symbols_per_frame= alone")
     # (the current weights: a model may be trained between two decodes)
     jb = BeamJoint(model.joint, int(beam), token_times=bool(token_times), context=context, lm=lm)
     return _beam_search(jb, _BEAM_WORKSPACES, model.prediction, enc, frame_lengths, prediction)
@@ -343,11 +369,12 @@ def beam_search_batch(model, enc: torch.Tensor, frame_lengths: torch.Tensor, bea
 @torch.no_grad()
 def beam_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[torch.Tensor] = None, beam: int = 4,
                       prediction: str = "torch", encoder: str = "torch", token_times: bool = False, context=None,
-                      lm=None):
+                      lm=None, symbols_per_frame: Optional[int] = None):
     """Beam search of EVERY utterance of a batch -> the best hypothesis of each: (ids int32 [B, T'] zero-padded, lengths int32
     [B], scores [B]).  spec_lengths are spectrogram frames, reduced as greedy_decode_batch reduces them; None: every frame.
     encoder= as in greedy_decode_batch.  token_times=True: (ids, lengths, scores, frames int32 [B, T'], logp [B, T']) of the
-    best hypothesis, as beam_search_batch defines them.  context= and lm= as in beam_search_batch."""
+    best hypothesis, as beam_search_batch defines them.  context= and lm= as in beam_search_batch.  symbols_per_frame=E: the
+    search with up to E symbols per frame (beam_search_batch); ids is then [B, T' E]."""
     _check_prediction(prediction)
     _check_encoder(encoder)
     was_training = model.training
@@ -359,6 +386,10 @@ def beam_decode_batch(model, mel_specs: torch.Tensor, spec_lengths: Optional[tor
             frames = torch.full((B,), T, dtype=torch.int32, device=enc.device)
         else:
             frames = reduced_lengths(spec_lengths.to(enc.device), model.hp.time_reduction_factor)
+        if symbols_per_frame is not None:
+            ids, lengths, scores = beam_search_batch(model, enc, frames, beam, prediction, token_times, context=context, lm=lm,
+                                                     symbols_per_frame=symbols_per_frame)
+            return ids[:, 0], lengths[:, 0], scores[:, 0]
         if token_times:
             return tuple(x[:, 0] for x in beam_search_batch(model, enc, frames, beam, prediction, True, context=context, lm=lm))
         ids, lengths, scores = beam_search_batch(model, enc, frames, beam, prediction, context=context, lm=lm)

@@ -1179,6 +1179,162 @@ class BeamStreamJoint(BeamJoint):
         return out + self._torch_times(N) + (tstable.to(dev),)
 
 
+class MultiBeamJoint(_EngineJoint):
+    """The joint of the batched beam search with SEVERAL symbols per frame (decoding.beam_search_batch(symbols_per_frame=E)): the
+    time-synchronous search of include/rnnt_beam_multi.h, which states the rule.  Rows are 2 beam per utterance: slot k of the
+    open list A is row b 2 beam + k, slot k of the closed list B row b 2 beam + beam + k.  One step is one round; a frame takes
+    E + 1 of them.
+
+    On an MI355X this is the ENGINE (compute_rnnt_multibeam_begin / _step / _results, libwarprnnt_multibeam.so).  CPU tensors and
+    shapes the library refuses (the joint's, or more than 1024 rows) run the same rule in torch with float64 scores.
+
+    begin(enc [B, T, H], frame_lengths [B]); step(pred [B 2 beam, H]) -> (parents, emitted) [B 2 beam] int32; results() ->
+    (hyps [B, beam, max_hyp_len] int32 zero-padded, lengths [B, beam] int32, scores [B, beam]), list A, best first."""
+
+    def __init__(self, joint: "JointLoss", beam: int = 4, symbols_per_frame: int = 2, max_hyp_len=None, joint_dtype: str = "auto"):
+        if not 1 <= int(beam) <= 16:
+            raise ValueError("MultiBeamJoint: beam must be in 1 ... 16")
+        if not 1 <= int(symbols_per_frame) <= 8:
+            raise ValueError("MultiBeamJoint: symbols_per_frame must be in 1 ... 8")
+        if max_hyp_len is not None and int(max_hyp_len) < 1:
+            raise ValueError("MultiBeamJoint: max_hyp_len must be at least 1")
+        self.K, self.E = int(beam), int(symbols_per_frame)
+        self.max_hyp_len = None if max_hyp_len is None else int(max_hyp_len)
+        super().__init__(joint, joint_dtype, False)
+        self._takes = self.engine  # (the joint's shape; begin adds the row limit)
+
+    @property
+    def rows_per_utterance(self) -> int:
+        return 2 * self.K
+
+    def begin(self, enc, frame_lengths):
+        B, T = enc.shape[0], enc.shape[1]
+        dev = enc.device
+        self.B, self.T = B, T
+        self.N = self.max_hyp_len if self.max_hyp_len is not None else max(1, T * self.E)
+        R = B * 2 * self.K
+        self.parents = torch.arange(R, dtype=torch.int32, device=dev)
+        self.emitted = torch.full((R,), -1, dtype=torch.int32, device=dev)
+        frames = frame_lengths.to(device=dev, dtype=torch.int32).contiguous()
+        self.engine = self._takes and R <= 1024
+        if not self.engine:
+            return self._torch_begin(enc, frames)
+        ep = (torch.matmul(enc.float(), self.W1) + self.b1).contiguous()
+        self._keep = frames
+        with torch.cuda.device(dev):
+            nbytes = _lib.multibeam_workspace_bytes(T, B, self.K, self.E, self.N, self.Jp, self.V, self.dtype)
+            self._ws = _workspace(self._ws, nbytes, dev)
+            self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
+            st = _lib.load_multibeam().compute_rnnt_multibeam_begin(
+                ep.data_ptr(), frames.data_ptr(), self.W2.data_ptr(), self.b2.data_ptr(), self.Jp, self.V, B, self.K, self.E, self.N,
+                self.dtype, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_multibeam_begin")
+
+    def step(self, pred=None, *, pred_proj=None):
+        """pred [B 2 beam, H]: the prediction network's output of every row -> (parents, emitted), int32 [B 2 beam].
+        pred_proj [B 2 beam, Jp] instead of pred: that output already through W1 (PredictionStep)."""
+        if not self.engine:
+            return self._torch_step(pred, pred_proj)
+        pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _projected_operand(pred_proj, self.Jp)
+        st = _lib.load_multibeam().compute_rnnt_multibeam_step(
+            pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(), self.Jp, self.V, self.B, self.K, self.E, self.N, self.dtype,
+            self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_multibeam_step")
+        return self.parents, self.emitted
+
+    def results(self):
+        B, K, N = self.B, self.K, self.N
+        if not self.engine:
+            return self._torch_results()
+        dev = self.parents.device
+        hyps = torch.empty(B, K, N, dtype=torch.int32, device=dev)
+        lengths = torch.empty(B, K, dtype=torch.int32, device=dev)
+        scores = torch.empty(B, K, dtype=torch.float32, device=dev)
+        st = _lib.load_multibeam().compute_rnnt_multibeam_results(
+            hyps.data_ptr(), lengths.data_ptr(), scores.data_ptr(), self.Jp, self.V, B, K, self.E, N, self.dtype, self._ws.data_ptr(),
+            self._opts)
+        _lib.check(st, "compute_rnnt_multibeam_results")
+        return hyps, lengths, scores
+
+    # ---- torch composition: the rule of include/rnnt_beam_multi.h on JointLoss.logits, float64 scores
+    def _torch_begin(self, enc, frames):
+        self._enc = enc
+        self._Tb = [int(x) for x in frames.clamp(0, enc.shape[1]).tolist()]
+        self._k = 0
+        self._open = [[((), 0.0)] for _ in range(self.B)]  # (tokens, float64 score), in list order
+        self._closed = [[] for _ in range(self.B)]
+        self._sdtype = torch.promote_types(enc.dtype, torch.float32)
+
+    def _torch_step(self, pred, pred_proj=None):
+        B, K, E, blank = self.B, self.K, self.E, self.blank
+        KR = 2 * K
+        t, rnd = divmod(self._k, E + 1)
+        self._k += 1
+        parents = list(range(B * KR))
+        emitted = [-1] * (B * KR)
+        e = self._enc[:, min(t, self.T - 1)]  # [B, H]
+        logits = _torch_cell_logits(self.joint, e.repeat_interleave(KR, 0), pred, pred_proj).double()  # [B 2K, V]
+        lp = (logits - torch.logsumexp(logits, dim=-1, keepdim=True)).tolist()
+        for b in range(B):
+            if t >= self._Tb[b]:
+                continue
+            rb = b * KR
+            A, Bl = self._open[b], self._closed[b]
+            # closings: [sequence, score, the slot that holds its state]
+            lst = [[y, s, K + j] for j, (y, s) in enumerate(Bl)]
+            for i, (y, s) in enumerate(A):
+                c = s + lp[rb + i][blank]
+                if c != c or c == -math.inf:
+                    continue
+                hit = next((x for x in lst if x[0] == y), None)
+                if hit is None:
+                    lst.append([y, c, i])
+                else:
+                    hi, lo = max(hit[1], c), min(hit[1], c)
+                    hit[1] = hi + math.log1p(math.exp(lo - hi))
+            lst.sort(key=lambda x: -x[1])  # (stable)
+            lst = lst[:K]
+            if rnd < E:
+                cands = []
+                for i, (y, s) in enumerate(A):
+                    if len(y) >= self.N:
+                        continue
+                    row = lp[rb + i]
+                    for v in range(self.V):
+                        sc = s + row[v]
+                        if v != blank and sc == sc and sc > -math.inf:
+                            cands.append((sc, i, v))
+                cands.sort(key=lambda c: (-c[0], c[1], c[2]))
+                cands = cands[:K]
+                for k, (sc, i, v) in enumerate(cands):
+                    parents[rb + k], emitted[rb + k] = rb + i, v
+                for k, x in enumerate(lst):
+                    parents[rb + K + k] = rb + x[2]
+                self._open[b] = [(A[i][0] + (v,), sc) for sc, i, v in cands]
+                self._closed[b] = [(x[0], x[1]) for x in lst]
+            else:  # the frame turn
+                for k, x in enumerate(lst):
+                    parents[rb + k] = rb + x[2]
+                self._open[b] = [(x[0], x[1]) for x in lst]
+                self._closed[b] = []
+        dev = self.parents.device
+        self.parents = torch.tensor(parents, dtype=torch.int32, device=dev)
+        self.emitted = torch.tensor(emitted, dtype=torch.int32, device=dev)
+        return self.parents, self.emitted
+
+    def _torch_results(self):
+        B, K, N = self.B, self.K, self.N
+        hyps = torch.zeros(B, K, N, dtype=torch.int32)
+        lengths = torch.zeros(B, K, dtype=torch.int32)
+        scores = torch.full((B, K), -math.inf, dtype=torch.float64)
+        for b, beam in enumerate(self._open):
+            for k, (y, s) in enumerate(beam):
+                hyps[b, k, : len(y)] = torch.tensor(y, dtype=torch.int32)
+                lengths[b, k], scores[b, k] = len(y), s
+        dev = self.parents.device
+        return hyps.to(dev), lengths.to(dev), scores.to(device=dev, dtype=self._sdtype)
+
+
 def _aligned16(x: torch.Tensor) -> torch.Tensor:
     x = x.detach().contiguous()
     return x if x.data_ptr() % 16 == 0 else x.clone()
