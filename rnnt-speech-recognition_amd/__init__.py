@@ -6,7 +6,7 @@ from .model import HParams, Transducer, TimeReduction, Encoder, PredictionNetwor
 from .train import TrainStep, run_evaluate, run_training, synthetic_batch, synthetic_trained_like_joint  # noqa: F401
 from .decoding import greedy_decode, greedy_decode_batch, greedy_decode_batch_fn, greedy_decode_fn  # noqa: F401
 from .decoding import beam_decode_batch, beam_decode_batch_fn, beam_search_batch  # noqa: F401
-from .decoding import StreamingBeamDecoder, StreamingGreedyDecoder, StreamingTranscriber  # noqa: F401
+from .decoding import StreamingBeamDecoder, StreamingGreedyDecoder, StreamingMultiBeamDecoder, StreamingTranscriber  # noqa: F401
 from .lstm import LSTMLayerFunction  # noqa: F401
 from .biasing import ContextGraph  # noqa: F401
 from .lm import NgramLM  # noqa: F401

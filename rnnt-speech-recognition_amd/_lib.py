@@ -251,6 +251,13 @@ _NEXT_SIGNATURES = {
         "compute_rnnt_multibeam_step": [vp] * 3 + [ci] * 7 + [vp, opt],
         "compute_rnnt_multibeam_results": [vp] * 3 + [ci] * 7 + [vp, opt],
     },
+    "multibeamstream": {
+        "get_rnnt_multibeam_stream_workspace_size": [ci] * 10 + [sz],
+        "compute_rnnt_multibeam_stream_begin": [vp] * 4 + [ci] * 9 + [vp, opt],
+        "compute_rnnt_multibeam_stream_feed": [vp, ci, vp, vp, vp] + [ci] * 9 + [vp, opt],
+        "compute_rnnt_multibeam_stream_step": [vp] * 3 + [ci] * 8 + [vp, opt],
+        "compute_rnnt_multibeam_stream_results": [vp] * 6 + [ci] * 8 + [vp, opt],
+    },
 }
 _BUILT_SIGNATURES = {**_EVERY_SIGNATURE, **_NEXT_SIGNATURES}
 _RESTYPES = {"rnntGetStatusString": ctypes.c_char_p}
@@ -370,6 +377,12 @@ def load_tdtbeamstream():
 def load_multibeam():
     """libwarprnnt_multibeam.so: batched beam search with several symbols per frame, include/rnnt_beam_multi.h."""
     return _load("multibeam")
+
+
+def load_multibeam_stream():
+    """libwarprnnt_multibeamstream.so: streaming beam search with several symbols per frame over slots,
+    include/rnnt_beam_multi_stream.h."""
+    return _load("multibeamstream")
 
 
 def status_string(status: int) -> str:
@@ -532,3 +545,9 @@ def multibeam_workspace_bytes(maxT: int, minibatch: int, beam: int, symbols_per_
                               alphabet_size: int, joint_dtype: int) -> int:
     return _size(load_multibeam(), "get_rnnt_multibeam_workspace_size", maxT, minibatch, beam, symbols_per_frame, max_hyp_len,
                  joint_size, alphabet_size, joint_dtype)
+
+
+def multibeam_stream_workspace_bytes(max_chunk_frames: int, slots: int, beam: int, symbols_per_frame: int, max_hyp_len: int,
+                                     enc_width: int, joint_size: int, alphabet_size: int, joint_dtype: int, timed: bool = False) -> int:
+    return _size(load_multibeam_stream(), "get_rnnt_multibeam_stream_workspace_size", max_chunk_frames, slots, beam,
+                 symbols_per_frame, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype, int(bool(timed)))

@@ -98,6 +98,11 @@ NEXT_LIBRARIES = {
     # points, as "tdtbeam"
     "multibeam": Library("rnnt_beam_multi.h", ("multibeam_kernels.hip", "rnnt_multibeam_entrypoint.hip"), _BASE_KERNELS,
                          "rnnt_multibeam.map"),
+    # "multibeam" over a stream of chunks per slot: its own begin, feed, step, select and results kernels (step and select compiled
+    # from the text "multibeam" compiles: beam_step_body.h at the same flag value, multibeam_select_body.h) on the greedy stream's
+    # projection; the base kernel objects and its own entry points (no object of "multibeam" is linked)
+    "multibeamstream": Library("rnnt_beam_multi_stream.h", ("tsd_stream_kernels.hip", "rnnt_tsd_stream_entrypoint.hip"), _BASE_KERNELS,
+                               "rnnt_tsdstream.map"),
 }
 BUILT_LIBRARIES = {**EVERY_LIBRARY, **NEXT_LIBRARIES}
 
@@ -123,6 +128,7 @@ TDTBEAM_LIB_PATH = lib_path("tdtbeam")
 TDTJOINT_LIB_PATH = lib_path("tdtjoint")
 TDTBEAMSTREAM_LIB_PATH = lib_path("tdtbeamstream")
 MULTIBEAM_LIB_PATH = lib_path("multibeam")
+MULTIBEAMSTREAM_LIB_PATH = lib_path("multibeamstream")
 # -fvisibility=hidden: the library exports exactly the entry points include/rnnt.h marks RNNT_API (tests/test_abi.py)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-inline-asm"]
 # per-source extras.  -fno-slp-vectorize: no packed-f32 instructions (v_pk_fma_f32 ...) from the compiler -- in the linear sweeps
@@ -133,7 +139,7 @@ _NO_SLP = ["-fno-slp-vectorize"]
 EXTRA_FLAGS = {"rnnt_lin_kernels.hip": _NO_SLP, "joint_kernels.hip": _NO_SLP, "joint_f16_kernels.hip": _NO_SLP, "dense_kernels.hip": _NO_SLP,
                "greedy_kernels.hip": _NO_SLP, "tdt_greedy_kernels.hip": _NO_SLP, "tdt_stream_kernels.hip": _NO_SLP, "beam_kernels.hip": _NO_SLP, "beam_bias_kernels.hip": _NO_SLP,
                "beam_lm_kernels.hip": _NO_SLP, "tdt_beam_kernels.hip": _NO_SLP, "tdt_nbest_stream_kernels.hip": _NO_SLP,
-               "multibeam_kernels.hip": _NO_SLP,
+               "multibeam_kernels.hip": _NO_SLP, "tsd_stream_kernels.hip": _NO_SLP,
                "prednet_kernels.hip": _NO_SLP, "encoder_kernels.hip": _NO_SLP, "lstm_train_kernels.hip": _NO_SLP,
                "rnnt_pruned_joint_kernels.hip": _NO_SLP, "rnnt_tdt_joint_kernels.hip": _NO_SLP}
 

@@ -39,6 +39,9 @@ hipError_t launch_greedy_stream_feed(const float *enc, int Te, const int *chunk_
                                      const int *max_symbols, int max_per_frame, int *hyp_lengths, float *scores, int *all_done,
                                      int *frame_base, int H, int J, int V, int S, int Tc, int joint_dtype, void *workspace,
                                      hipStream_t s);
+// tsd_stream_kernels.hip (the stream of the beam search with several symbols per frame; libwarprnnt_multibeamstream.so alone links it)
+hipError_t tsd_stream_workspace_bytes(int Tc, int S, int K, int E, int N, int H, int J, int V, int joint_dtype, bool timed,
+                                      size_t *bytes);
 }  // namespace rnnt
 
 static inline rnntStatus_t check_options(const rnntOptions &o) {
@@ -100,6 +103,24 @@ static inline rnntStatus_t check_beam_stream(int max_chunk_frames, int slots, in
     size_t n = 0;
     if (rnnt::beam_stream_workspace_bytes(max_chunk_frames, slots, beam, max_hyp_len, enc_width, joint_size, alphabet_size,
                                           joint_dtype, timed, &n) != hipSuccess)
+        return RNNT_STATUS_INVALID_VALUE;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// The stream of the beam search with several symbols per frame (include/rnnt_beam_multi_stream.h): the beam stream's checks on
+// 2 beam rows per slot, symbols_per_frame in [1, 8], and the workspace's own layout.  enc_width 1: step and results do not reach
+// W1 / b1, which stand last in the workspace.
+static inline rnntStatus_t check_multibeam_stream(int max_chunk_frames, int slots, int beam, int symbols_per_frame, int max_hyp_len,
+                                                  int enc_width, int joint_size, int alphabet_size, int joint_dtype,
+                                                  const void *workspace, const rnntOptions &o, bool timed) {
+    if (!workspace || ((uintptr_t)workspace & 255) != 0) return RNNT_STATUS_INVALID_VALUE;
+    if (beam < 1 || beam > 16 || slots < 1 || (long long)slots * 2 * beam > 1024 || max_hyp_len < 1) return RNNT_STATUS_INVALID_VALUE;
+    if (symbols_per_frame < 1 || symbols_per_frame > 8) return RNNT_STATUS_INVALID_VALUE;
+    const rnntStatus_t st = check_greedy(max_chunk_frames, joint_size, alphabet_size, slots, joint_dtype, o);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    size_t n = 0;
+    if (rnnt::tsd_stream_workspace_bytes(max_chunk_frames, slots, beam, symbols_per_frame, max_hyp_len, enc_width, joint_size,
+                                         alphabet_size, joint_dtype, timed, &n) != hipSuccess)
         return RNNT_STATUS_INVALID_VALUE;
     return RNNT_STATUS_SUCCESS;
 }

@@ -24,8 +24,8 @@ from typing import List, Optional
 
 import torch
 
-from .joint import (BeamJoint, BeamStreamJoint, EncoderStream, GreedyJoint, GreedyStreamJoint, MultiBeamJoint, PredictionStep,
-                    TorchPredictionStep, _pred_step)  # noqa: F401  (_pred_step: one symbol through the prediction network, for callers of this module)
+from .joint import (BeamJoint, BeamStreamJoint, EncoderStream, GreedyJoint, GreedyStreamJoint, MultiBeamJoint, MultiBeamStreamJoint,
+                    PredictionStep, TorchPredictionStep, _pred_step)  # noqa: F401  (_pred_step: one symbol through the prediction network, for callers of this module)
 from .loss import reduced_lengths
 
 
@@ -732,6 +732,100 @@ class StreamingBeamDecoder(_StreamingSlots):
         return self._timed()[6]
 
 
+class StreamingMultiBeamDecoder(StreamingBeamDecoder):
+    """Beam search with SEVERAL symbols per frame (time-synchronous, on the standard lattice: include/rnnt_beam_multi_stream.h) of up
+    to `slots` live audio streams at once, fed chunk by chunk: the streaming counterpart of beam_decode_batch(symbols_per_frame=E),
+    with the slot handling and the results of StreamingBeamDecoder.  It follows a model trained with the project's own loss,
+    which may emit several labels in one frame, and can return more labels than frames.
+
+    Each slot has 2 beam prediction-network rows (its open and its closed list); start(slots) resets a slot's 2 beam rows.  A
+    chunk of n encoder frames is exactly n (symbols_per_frame + 1) steps, each a joint step and a prediction-network step.
+    feed -> (best ids, lengths, stable) as the parent's; hypotheses(), nbest(), and with token_times=True timed_hypotheses() ->
+    (ids, frames), timed_nbest() -> (ids, lengths, scores, frames) and timed_stable_lengths(): the frame rows carry frames only, no
+    log-probabilities.  A hypothesis a closing was merged into reports the frames of the path it held.  context= and lm= are not
+    taken (ValueError), as offline.
+
+    max_length is N, the tokens one stream's hypothesis may hold; the default is 512.  With E symbols per frame a hypothesis can
+    reach 512 tokens in 512 / E encoder frames.  A hypothesis that holds N tokens is NOT reported as full: it offers no expansion
+    and goes on through the later frames on blanks alone, silently; lengths[s] == N is the only sign.  slots * 2 * beam <= 1024.
+
+    A stream delivered through any chunking, in any slot, beside any other traffic, ends with the n-best, stable, frames and timed
+    stable lengths of the same stream fed in one call to a 1-slot decoder: bitwise on an MI355X."""
+
+    def __init__(self, model, slots: int, max_chunk_frames: int, beam: int = 4, symbols_per_frame: int = 2,
+                 max_length: Optional[int] = None, token_times: bool = False, context=None, lm=None):
+        if context is not None or lm is not None:
+            raise ValueError("context= and lm= are not taken by the beam search with several symbols per frame")
+        K, E = int(beam), int(symbols_per_frame)
+        self.token_times = bool(token_times)
+        if not 1 <= K <= 16:
+            raise ValueError(f"beam must be in 1 ... 16, got {beam}")
+        if not 1 <= E <= 8:
+            raise ValueError(f"symbols_per_frame must be in 1 ... 8, got {symbols_per_frame}")
+        if int(slots) * 2 * K > MultiBeamStreamJoint.MAX_ROWS:
+            raise ValueError(f"slots * 2 * beam must be in 1 ... {MultiBeamStreamJoint.MAX_ROWS}, got {slots} * 2 * {beam}")
+        N = self.DEFAULT_MAX_LENGTH if max_length is None else int(max_length)
+        if N < 1:
+            raise ValueError(f"max_length must be >= 1, got {max_length}")
+        self._init_slots(model, slots, max_chunk_frames)
+        self.K, self.E, self.max_length = K, E, N
+        with self._eval():
+            self.bj = MultiBeamStreamJoint(model.joint, K, E, token_times=self.token_times)
+            dev = next(model.parameters()).device
+            self.bj.begin(self.S, self.Te, N, device=dev)
+            self.ps = PredictionStep(model.prediction, _joint_W1(self.bj))
+            self.pp = self.ps.begin(self.S * 2 * K)
+        self.dev = self.bj.parents.device
+
+    @torch.no_grad()
+    def start(self, slots) -> None:
+        m = self._mask(slots)
+        if not any(m):
+            return
+        with self._eval():
+            self.pp = self.ps.reset([v for v in m for _ in range(2 * self.K)])
+            self.bj.feed(None, [0] * self.S, reset=[int(v) for v in m], final=None)
+        self._pending = [p or q for p, q in zip(self._pending, m)]
+
+    @torch.no_grad()
+    def feed(self, mel_chunk: torch.Tensor, frames, final):
+        global LAST_STEPS
+        f = self.f
+        fr, fi = self._check_feed(mel_chunk, frames, final)
+        T = max(fr)
+        with self._eval():
+            enc = self._encode_chunk(mel_chunk, fr)
+            self.bj.feed(enc, [-(-v // f) for v in fr], reset=None, final=[int(v) for v in fi])
+            steps = -(-T // f) * (self.E + 1)  # (host data: every frame takes E + 1 rounds, so nothing is polled)
+            self.pp = _beam_loop(self.bj, self.ps, self.pp, steps, carry=True)
+            LAST_STEPS = steps
+            ids, lengths, _, stable = self.bj.results()[:4]
+        return ids[:, 0], lengths[:, 0], stable
+
+    def bias_states(self):
+        raise RuntimeError("the beam search with several symbols per frame takes no context=")
+
+    def lm_states(self):
+        raise RuntimeError("the beam search with several symbols per frame takes no lm=")
+
+    def timed_hypotheses(self):
+        """The best hypothesis of each slot with its frames: (ids int32 [slots, N] zero-padded, frames int32 [slots, N] -1
+        padded), counted in encoder frames from the slot's start across all its chunks.  Needs token_times=True."""
+        r = self._timed()
+        return r[0][:, 0], r[4][:, 0]
+
+    def timed_nbest(self):
+        """(ids [slots, beam, N], lengths [slots, beam], scores [slots, beam], frames [slots, beam, N]), best first.  Needs
+        token_times=True."""
+        r = self._timed()
+        return r[0], r[1], r[2], r[4]
+
+    def timed_stable_lengths(self):
+        """int32 [slots]: the leading tokens on which every hypothesis of a slot agrees in token AND emission frame; never more
+        than feed()'s `stable`, and final at frame boundaries (after a feed).  Needs token_times=True."""
+        return self._timed()[5]
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # Streaming transcription from raw audio
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -741,6 +835,9 @@ class StreamingTranscriber:
     of a StreamingBeamDecoder when `beam` is given.  The decoder is sized by the front end's max_rows; decoder_kwargs go to it
     (max_length, max_symbols_per_frame, check_every for greedy; max_length for beam).  context=biasing.ContextGraph (beam search
     only): contextual biasing, as StreamingBeamDecoder takes it; lm=lm.NgramLM (beam search only): LM shallow fusion, likewise.
+    symbols_per_frame=E (with beam=K; with tdt_durations, tdt_beam, context or lm: ValueError): the decoder is a
+    StreamingMultiBeamDecoder, the time-synchronous search with up to E symbols per frame (decoder_kwargs: max_length, token_times;
+    no words(): it keeps frames, not per-token log-probabilities).
     tdt_durations=[...] (together with beam: ValueError): the model is a token-and-duration transducer with that duration set,
     and the decoder is a tdt.StreamingTDTGreedyDecoder (decoder_kwargs: joint, max_length, max_symbols_per_frame, check_every) or,
     with tdt_beam=K, a tdt.StreamingTDTBeamDecoder of beam K (decoder_kwargs: joint, max_length, token_times; no context= / lm=,
@@ -753,8 +850,17 @@ class StreamingTranscriber:
     features.running_mean_log_mel for it.  A stream's result is bitwise independent of how its audio was chunked."""
 
     def __init__(self, model, hp, sample_rate, slots: int, max_chunk_samples: int, beam: Optional[int] = None,
-                 norm: str = "running", context=None, lm=None, tdt_durations=None, tdt_beam: Optional[int] = None, **decoder_kwargs):
+                 norm: str = "running", context=None, lm=None, tdt_durations=None, tdt_beam: Optional[int] = None,
+                 symbols_per_frame: Optional[int] = None, **decoder_kwargs):
         from .features import StreamingFrontEnd
+
+        if symbols_per_frame is not None:
+            if beam is None:
+                raise ValueError("symbols_per_frame= needs beam search: build the StreamingTranscriber with beam=")
+            if tdt_durations is not None or tdt_beam is not None:
+                raise ValueError("symbols_per_frame= does not go with tdt_durations= / tdt_beam=: the TDT searches are not time-synchronous")
+            if context is not None or lm is not None:
+                raise ValueError("context= and lm= are not taken by the beam search with several symbols per frame (symbols_per_frame=)")
 
         if tdt_durations is not None and beam is not None:
             raise ValueError("tdt_durations= does not go with beam=: the TDT beam search is tdt_beam=K, build the StreamingTranscriber "
@@ -782,6 +888,9 @@ class StreamingTranscriber:
             self.decoder = StreamingTDTGreedyDecoder(model, tdt_durations, slots, self.front.max_rows, **decoder_kwargs)
         elif beam is None:
             self.decoder = StreamingGreedyDecoder(model, slots, self.front.max_rows, **decoder_kwargs)
+        elif symbols_per_frame is not None:
+            self.decoder = StreamingMultiBeamDecoder(model, slots, self.front.max_rows, beam=beam, symbols_per_frame=symbols_per_frame,
+                                                     **decoder_kwargs)
         else:
             self.decoder = StreamingBeamDecoder(model, slots, self.front.max_rows, beam=beam, context=context, lm=lm, **decoder_kwargs)
 
@@ -819,6 +928,9 @@ class StreamingTranscriber:
         dec = self.decoder
         if getattr(dec, "durations", None) is not None and hasattr(dec, "nbest"):
             raise RuntimeError("words() needs per-token log-probabilities, which the TDT beam search (tdt_beam=) does not keep")
+        if isinstance(dec, StreamingMultiBeamDecoder):
+            raise RuntimeError("words() needs per-token log-probabilities, which the beam search with several symbols per frame "
+                               "(symbols_per_frame=) does not keep")
         if hasattr(dec, "timed_stable_lengths"):  # beam: one results call gives the best hypothesis and the timed stable length
             r = dec._timed()
             ids, frames, logp, stable = r[0][slot, 0].cpu(), r[4][slot, 0].cpu(), r[5][slot, 0].cpu(), int(r[6][slot])

@@ -1335,6 +1335,221 @@ class MultiBeamJoint(_EngineJoint):
         return hyps.to(dev), lengths.to(dev), scores.to(device=dev, dtype=self._sdtype)
 
 
+class MultiBeamStreamJoint(MultiBeamJoint):
+    """The joint of the streaming beam search with several symbols per frame (decoding.StreamingMultiBeamDecoder): the rule of
+    MultiBeamJoint over `slots` streams whose encoder frames arrive chunk by chunk, each slot keeping its lists from one feed to
+    the next.  include/rnnt_beam_multi_stream.h states the contract.
+
+    On an MI355X this is the ENGINE (compute_rnnt_multibeam_stream_begin / _feed / _step / _results,
+    libwarprnnt_multibeamstream.so): the object owns the workspace and W1 / b1 go into it, so the encoder side's projection runs in
+    the library with a fixed summation order.  CPU tensors and shapes the library refuses run the same state machine in torch with
+    float64 scores: the frame base, the frame rows (an entry a closing is added into keeps its own), both stable lengths.
+
+    begin(slots, max_chunk_frames, max_hyp_len) leaves every slot finished with an empty beam; feed(enc [slots, Te, H], frames
+    [slots], reset, final) hands every slot its chunk; then step(pred_proj=...) E + 1 times per encoder frame of the longest chunk,
+    each followed by a prediction-network step over the slots' 2 beam rows.  results() -> (hyps [slots, beam, max_hyp_len]
+    zero-padded, lengths, scores [slots, beam], stable [slots]); token_times=True adds frames int32 [slots, beam, max_hyp_len] (-1
+    padded, counted from the slot's reset) and timed_stable [slots] (<= stable).  `stable` is final at frame boundaries only."""
+
+    MAX_ROWS = 1024  # slots * 2 beam: the prediction network's rows
+
+    def __init__(self, joint: "JointLoss", beam: int = 4, symbols_per_frame: int = 2, joint_dtype: str = "auto",
+                 token_times: bool = False):
+        super().__init__(joint, beam, symbols_per_frame, None, joint_dtype)
+        self.token_times = bool(token_times)
+
+    def begin(self, slots: int, max_chunk_frames: int, max_hyp_len: int, device=None):
+        S, T, N, K = int(slots), int(max_chunk_frames), int(max_hyp_len), self.K
+        if S < 1 or S * 2 * K > self.MAX_ROWS:
+            raise ValueError(f"slots * 2 * beam must be in 1 ... {self.MAX_ROWS}, got {S} * 2 * {K}")
+        if T < 1 or N < 1:
+            raise ValueError("max_chunk_frames and max_hyp_len must be >= 1")
+        self.engine = self._takes
+        dev = self.W2.device if self.engine else (device if device is not None else self.joint.W2.device)
+        self.B, self.T, self.Tc, self.N = S, T, T, N
+        R = S * 2 * K
+        self.parents = torch.arange(R, dtype=torch.int32, device=dev)
+        self.emitted = torch.full((R,), -1, dtype=torch.int32, device=dev)
+        if self.engine:  # (the library's own answer: a size it refuses is a shape the stream kernels do not take)
+            n = ctypes.c_size_t(0)
+            self.H = int(self.W1.shape[0])
+            self.engine = _lib.load_multibeam_stream().get_rnnt_multibeam_stream_workspace_size(
+                T, S, K, self.E, N, self.H, self.Jp, self.V, self.dtype, int(self.token_times), ctypes.byref(n)) == _lib.STATUS_SUCCESS
+        if not self.engine:
+            self._open = [[] for _ in range(S)]  # (tokens, float64 score, frames), in list order
+            self._closed = [[] for _ in range(S)]
+            self._fin, self._Tb, self._tc, self._rnd, self._base = [True] * S, [0] * S, [0] * S, [0] * S, [0] * S
+            self._enc = None
+            self._sdtype = torch.promote_types(self.joint.W2.dtype, torch.float32)
+            return
+        self._timed = int(self.token_times)
+        with torch.cuda.device(dev):
+            self._ws = _workspace(self._ws, n.value, dev)
+            self._opts = _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, T, 1)
+            st = _lib.load_multibeam_stream().compute_rnnt_multibeam_stream_begin(
+                self.W1.data_ptr(), self.b1.data_ptr(), self.W2.data_ptr(), self.b2.data_ptr(), self.H, self.Jp, self.V, S, K, self.E, N,
+                self.dtype, self._timed, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_multibeam_stream_begin")
+
+    def feed(self, enc, frames, reset=None, final=None):
+        """enc [slots, Te, H] (None or Te = 0: no frames), frames [slots] encoder frames per slot, reset / final [slots] or None."""
+        S = self.B
+        Te = 0 if enc is None else int(enc.shape[1])
+        if Te > self.Tc:
+            raise ValueError(f"a feed takes at most {self.Tc} encoder frames, got {Te}")
+        if not self.engine:
+            return self._torch_feed(enc, Te, frames, reset, final)
+        dev = self.parents.device
+        if Te > 0:
+            enc = _aligned16(enc.to(device=dev, dtype=torch.float32))
+            if tuple(enc.shape) != (S, Te, self.H):
+                raise ValueError(f"enc must be [{S}, frames, {self.H}], got {tuple(enc.shape)}")
+        cv = lambda x: None if x is None else _device_i32(x, dev).reshape(S)  # noqa: E731
+        fr, rs, fi = cv(frames), cv(reset), cv(final)
+        self._feed_args = (enc, fr, rs, fi)  # (alive until the launches have read them)
+        st = _lib.load_multibeam_stream().compute_rnnt_multibeam_stream_feed(
+            ptr(enc) if Te > 0 else None, Te, fr.data_ptr(), ptr(rs), ptr(fi), self.H, self.Jp, self.V, S, self.K, self.E, self.N,
+            self.dtype, self._timed, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_multibeam_stream_feed")
+
+    def step(self, pred=None, *, pred_proj=None):
+        """One round of every slot that has a frame left -> (parents, emitted), int32 [slots 2 beam]; as MultiBeamJoint.step."""
+        if not self.engine:
+            return self._torch_step(pred, pred_proj)
+        pp = torch.matmul(pred.float(), self.W1).contiguous() if pred_proj is None else _projected_operand(pred_proj, self.Jp)
+        st = _lib.load_multibeam_stream().compute_rnnt_multibeam_stream_step(
+            pp.data_ptr(), self.parents.data_ptr(), self.emitted.data_ptr(), self.Jp, self.V, self.B, self.K, self.E, self.N, self.dtype,
+            self._timed, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_multibeam_stream_step")
+        return self.parents, self.emitted
+
+    def results(self):
+        S, K, N = self.B, self.K, self.N
+        if not self.engine:
+            return self._torch_results()
+        dev = self.parents.device
+        hyps = torch.empty(S, K, N, dtype=torch.int32, device=dev)
+        lengths = torch.empty(S, K, dtype=torch.int32, device=dev)
+        scores = torch.empty(S, K, dtype=torch.float32, device=dev)
+        stable = torch.empty(S, dtype=torch.int32, device=dev)
+        frames = torch.empty(S, K, N, dtype=torch.int32, device=dev) if self.token_times else None
+        tstable = torch.empty(S, dtype=torch.int32, device=dev) if self.token_times else None
+        st = _lib.load_multibeam_stream().compute_rnnt_multibeam_stream_results(
+            hyps.data_ptr(), lengths.data_ptr(), scores.data_ptr(), stable.data_ptr(), ptr(frames), ptr(tstable), self.Jp, self.V, S, K,
+            self.E, N, self.dtype, self._timed, self._ws.data_ptr(), self._opts)
+        _lib.check(st, "compute_rnnt_multibeam_stream_results")
+        if self.token_times:
+            return hyps, lengths, scores, stable, frames, tstable
+        return hyps, lengths, scores, stable
+
+    # ---- torch composition: the same state machine (tsd_stream_feed_kernel, multibeam_select_body.h, tsd_stream_results_kernel)
+    def _torch_feed(self, enc, Te, frames, reset, final):
+        S = self.B
+        vec = lambda x: [0] * S if x is None else [int(v) for v in torch.as_tensor(x).reshape(S).tolist()]  # noqa: E731
+        fr, rs, fi = vec(frames), vec(reset), vec(final)
+        for s in range(S):
+            if rs[s]:
+                self._open[s], self._fin[s], self._base[s] = [((), 0.0, ())], False, 0
+            elif not self._fin[s]:
+                self._base[s] += self._Tb[s]
+            self._closed[s] = []  # (round 0: what a feed finds unfinished of a frame's rounds is dropped)
+            self._tc[s], self._rnd[s] = 0, 0
+            if self._fin[s]:
+                self._Tb[s] = 0
+            else:
+                self._Tb[s] = min(max(fr[s], 0), Te)
+                self._fin[s] = fi[s] != 0
+        self._enc = enc if Te > 0 else None
+
+    def _torch_step(self, pred, pred_proj=None):
+        S, K, E, blank = self.B, self.K, self.E, self.blank
+        KR = 2 * K
+        parents, emitted = list(range(S * KR)), [-1] * (S * KR)
+        dev = self.parents.device
+        live = [s for s in range(S) if self._tc[s] < self._Tb[s]]
+        if live:
+            Te = self._enc.shape[1]
+            cur = torch.tensor([min(self._tc[s], Te - 1) for s in range(S)], device=self._enc.device)
+            e = self._enc[torch.arange(S, device=self._enc.device), cur]  # [S, H]
+            logits = _torch_cell_logits(self.joint, e.repeat_interleave(KR, 0), pred, pred_proj).double()  # [S 2K, V]
+            lp = (logits - torch.logsumexp(logits, dim=-1, keepdim=True)).tolist()
+        for b in live:
+            rb, rnd, frame = b * KR, self._rnd[b], self._base[b] + self._tc[b]
+            A, Bl = self._open[b], self._closed[b]
+            # closings: [sequence, score, the slot that holds its state, its frames]; a hit keeps its own frames
+            lst = [[y, s, K + j, f] for j, (y, s, f) in enumerate(Bl)]
+            for i, (y, s, f) in enumerate(A):
+                c = s + lp[rb + i][blank]
+                if c != c or c == -math.inf:
+                    continue
+                hit = next((x for x in lst if x[0] == y), None)
+                if hit is None:
+                    lst.append([y, c, i, f])
+                else:
+                    hi, lo = max(hit[1], c), min(hit[1], c)
+                    hit[1] = hi + math.log1p(math.exp(lo - hi))
+            lst.sort(key=lambda x: -x[1])  # (stable)
+            lst = lst[:K]
+            if rnd < E:
+                cands = []
+                for i, (y, s, f) in enumerate(A):
+                    if len(y) >= self.N:
+                        continue
+                    row = lp[rb + i]
+                    for v in range(self.V):
+                        sc = s + row[v]
+                        if v != blank and sc == sc and sc > -math.inf:
+                            cands.append((sc, i, v))
+                cands.sort(key=lambda c: (-c[0], c[1], c[2]))
+                cands = cands[:K]
+                for k, (sc, i, v) in enumerate(cands):
+                    parents[rb + k], emitted[rb + k] = rb + i, v
+                for k, x in enumerate(lst):
+                    parents[rb + K + k] = rb + x[2]
+                self._open[b] = [(A[i][0] + (v,), sc, A[i][2] + (frame,)) for sc, i, v in cands]
+                self._closed[b] = [(x[0], x[1], x[3]) for x in lst]
+                self._rnd[b] = rnd + 1
+            else:  # the frame turn
+                for k, x in enumerate(lst):
+                    parents[rb + k] = rb + x[2]
+                self._open[b] = [(x[0], x[1], x[3]) for x in lst]
+                self._closed[b] = []
+                self._rnd[b] = 0
+                self._tc[b] += 1
+        self.parents = torch.tensor(parents, dtype=torch.int32, device=dev)
+        self.emitted = torch.tensor(emitted, dtype=torch.int32, device=dev)
+        return self.parents, self.emitted
+
+    def _torch_results(self):
+        S, K, N = self.B, self.K, self.N
+        hyps = torch.zeros(S, K, N, dtype=torch.int32)
+        frames = torch.full((S, K, N), -1, dtype=torch.int32)
+        lengths = torch.zeros(S, K, dtype=torch.int32)
+        scores = torch.full((S, K), -math.inf, dtype=torch.float64)
+        stable = torch.zeros(S, dtype=torch.int32)
+        tstable = torch.zeros(S, dtype=torch.int32)
+        for s, beam in enumerate(self._open):
+            for k, (y, sc, f) in enumerate(beam):
+                hyps[s, k, : len(y)] = torch.tensor(y, dtype=torch.int32)
+                frames[s, k, : len(y)] = torch.tensor(f, dtype=torch.int32)
+                lengths[s, k], scores[s, k] = len(y), sc
+            if beam:
+                shortest = min(len(y) for y, _, _ in beam)
+                n = 0
+                while n < shortest and all(y[n] == beam[0][0][n] for y, _, _ in beam):
+                    n += 1
+                stable[s] = n
+                n = 0
+                while n < shortest and all(y[n] == beam[0][0][n] and f[n] == beam[0][2][n] for y, _, f in beam):
+                    n += 1
+                tstable[s] = n
+        dev = self.parents.device
+        out = hyps.to(dev), lengths.to(dev), scores.to(device=dev, dtype=self._sdtype), stable.to(dev)
+        if not self.token_times:
+            return out
+        return out + (frames.to(dev), tstable.to(dev))
+
+
 def _aligned16(x: torch.Tensor) -> torch.Tensor:
     x = x.detach().contiguous()
     return x if x.data_ptr() % 16 == 0 else x.clone()
