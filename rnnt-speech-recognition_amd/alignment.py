@@ -161,47 +161,76 @@ def _torch_path_modified(lpb, lpl, input_lengths, label_lengths):
 
 
 # ---- the engine ---------------------------------------------------------------------------------------------------
-class _Aligner:
-    """One alignment in flight on the engine: the workspace, the outputs and the slab feed."""
+# per lattice: what the slab check calls it, the library, the workspace query and the stem of its three entry points
+# (stem + "_cells", stem + "_path", stem: the whole tensor in one call)
+_ENGINES = {
+    "standard": ("align", _lib.load, _lib.align_workspace_bytes, "compute_rnnt_align"),
+    "modified": ("align", _lib.load_modalign, _lib.modified_align_workspace_bytes, "compute_rnnt_modified_align"),
+    "tdt": ("tdt align", _lib.load_tdtalign, _lib.tdt_align_workspace_bytes, "compute_rnnt_tdt_align"),
+}
 
-    def __init__(self, B, T, U, V, labels, input_lengths, label_lengths, blank, dev, topology="standard"):
-        if topology == "modified":  # libwarprnnt_modalign.so: the same three calls on a workspace of its own
-            self.lib, ws_bytes = _lib.load_modalign(), _lib.modified_align_workspace_bytes
-            self.names = ("compute_rnnt_modified_align_cells", "compute_rnnt_modified_align_path", "compute_rnnt_modified_align")
-        else:
-            self.lib, ws_bytes = _lib.load(), _lib.align_workspace_bytes
-            self.names = ("compute_rnnt_align_cells", "compute_rnnt_align_path", "compute_rnnt_align")
+
+class _Aligner:
+    """One alignment in flight on the engine: the workspace, the outputs and the slab feed.  A lattice whose entry points take
+    more than the standard one's (tdt._TDTAligner) sets cell_args (after alphabet_size), path_args (after input_lengths),
+    int_outputs and passes its logits' width and the extra arguments of its workspace query."""
+    cell_args = path_args = ()
+    int_outputs = 1  # int32 [B, U-1] outputs in front of token_logp
+
+    def __init__(self, B, T, U, V, labels, input_lengths, label_lengths, blank, dev, topology="standard", width=None, ws_args=()):
+        self.what, load, ws_bytes, self.stem = _ENGINES[topology]
+        self.lib = load()
         self.B, self.T, self.U, self.V, self.blank, self.dev = B, T, U, V, int(blank), dev
+        self.width = V if width is None else width
         self.labels = _as_i32(labels, dev)
         if self.labels.numel() == 0:
             self.labels = torch.zeros((B, 1), dtype=torch.int32, device=dev)
         self.il, self.ll = _as_i32(input_lengths, dev), _as_i32(label_lengths, dev)
         with torch.cuda.device(dev):
-            self.ws = torch.empty(ws_bytes(T, U, B), dtype=torch.uint8, device=dev)
+            self.ws = torch.empty(ws_bytes(T, U, B, *ws_args), dtype=torch.uint8, device=dev)
 
     def _opts(self):
         return _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, self.T, self.U)
 
-    def cells(self, slab: torch.Tensor, frame_offset: int) -> None:
-        if slab.dtype != torch.float32 or slab.dim() != 4 or slab.shape[0] != self.B or tuple(slab.shape[2:]) != (self.U, self.V):
-            raise ValueError(f"align: a slab must be float32 [{self.B}, frames, {self.U}, {self.V}], got {tuple(slab.shape)}")
-        slab = slab.contiguous()
+    def _run(self, suffix, *args):
         with torch.cuda.device(self.dev):
-            st = getattr(self.lib, self.names[0])(slab.data_ptr(), slab.shape[1], int(frame_offset), self.labels.data_ptr(),
-                                                  self.ll.data_ptr(), self.il.data_ptr(), self.V, self.B, self.ws.data_ptr(),
-                                                  self._opts())
-        _lib.check(st, self.names[0])
+            st = getattr(self.lib, self.stem + suffix)(*args, self.ws.data_ptr(), self._opts())
+        _lib.check(st, self.stem + suffix)
+
+    def _outputs(self):
+        n = max(self.U - 1, 1)
+        out = [torch.empty(self.B, n, dtype=torch.int32, device=self.dev) for _ in range(self.int_outputs)]
+        return out + [torch.empty(self.B, n, dtype=torch.float32, device=self.dev), torch.empty(self.B, dtype=torch.float32, device=self.dev)]
+
+    def _trim(self, out):
+        return tuple(x[:, : self.U - 1] for x in out[:-1]) + (out[-1],)
+
+    def cells(self, slab: torch.Tensor, frame_offset: int) -> None:
+        if slab.dtype != torch.float32 or slab.dim() != 4 or slab.shape[0] != self.B or tuple(slab.shape[2:]) != (self.U, self.width):
+            raise ValueError(f"{self.what}: a slab must be float32 [{self.B}, frames, {self.U}, {self.width}], got {tuple(slab.shape)}")
+        slab = slab.contiguous()
+        self._run("_cells", slab.data_ptr(), slab.shape[1], int(frame_offset), self.labels.data_ptr(), self.ll.data_ptr(),
+                  self.il.data_ptr(), self.V, *self.cell_args, self.B)
 
     def path(self):
-        n = max(self.U - 1, 1)
-        with torch.cuda.device(self.dev):
-            frames = torch.empty(self.B, n, dtype=torch.int32, device=self.dev)
-            logp = torch.empty(self.B, n, dtype=torch.float32, device=self.dev)
-            scores = torch.empty(self.B, dtype=torch.float32, device=self.dev)
-            st = getattr(self.lib, self.names[1])(frames.data_ptr(), logp.data_ptr(), scores.data_ptr(), self.ll.data_ptr(),
-                                                  self.il.data_ptr(), self.B, self.ws.data_ptr(), self._opts())
-        _lib.check(st, self.names[1])
-        return frames[:, : self.U - 1], logp[:, : self.U - 1], scores
+        out = self._outputs()
+        self._run("_path", *(x.data_ptr() for x in out), self.ll.data_ptr(), self.il.data_ptr(), *self.path_args, self.B)
+        return self._trim(out)
+
+    def whole(self, acts):
+        """cells on every frame of `acts` (contiguous), then path, in one call of the library."""
+        out = self._outputs()
+        self._run("", acts.data_ptr(), self.labels.data_ptr(), self.ll.data_ptr(), self.il.data_ptr(), self.V, *self.cell_args, self.B,
+                  *(x.data_ptr() for x in out))
+        return self._trim(out)
+
+    def slabs(self, joint, enc, pred, S):
+        """cells on the logits of `joint`, S frames at a time, then path."""
+        for t0 in range(0, self.T, S):
+            slab = joint.cell_logits(enc[:, t0:t0 + S].contiguous(), pred)
+            self.cells(slab, t0)
+            del slab  # back to the allocator before the next slab is asked for: one slab of logits is alive at a time
+        return self.path()
 
 
 @torch.no_grad()
@@ -229,16 +258,7 @@ def rnnt_align(acts, labels, input_lengths, label_lengths, blank_label: int = 0,
         path = _torch_path_modified if topology == "modified" else _torch_path
         return path(lpb, lpl, input_lengths, label_lengths)
     al = _Aligner(B, T, U, V, labels, input_lengths, label_lengths, blank_label, dev, topology)
-    acts_c = acts.detach().contiguous()
-    with torch.cuda.device(dev):
-        n = max(U - 1, 1)
-        frames = torch.empty(B, n, dtype=torch.int32, device=dev)
-        logp = torch.empty(B, n, dtype=torch.float32, device=dev)
-        scores = torch.empty(B, dtype=torch.float32, device=dev)
-        st = getattr(al.lib, al.names[2])(acts_c.data_ptr(), al.labels.data_ptr(), al.ll.data_ptr(), al.il.data_ptr(), V, B,
-                                          frames.data_ptr(), logp.data_ptr(), scores.data_ptr(), al.ws.data_ptr(), al._opts())
-    _lib.check(st, al.names[2])
-    return frames[:, : U - 1], logp[:, : U - 1], scores
+    return al.whole(acts.detach().contiguous())
 
 
 def slab_frames_for(B: int, T: int, U: int, V: int, slab_bytes: int = SLAB_BYTES) -> int:
@@ -270,12 +290,7 @@ def align_joint(joint, enc, pred, labels, input_lengths, label_lengths, slab_fra
         lpb, lpl = torch.cat([p[0] for p in parts], dim=1), torch.cat([p[1] for p in parts], dim=1)
         path = _torch_path_modified if topology == "modified" else _torch_path
         return path(lpb, lpl, input_lengths, label_lengths)
-    al = _Aligner(B, T, U, V, labels, input_lengths, label_lengths, joint.blank_label, dev, topology)
-    for t0 in range(0, T, S):
-        slab = joint.cell_logits(enc[:, t0:t0 + S].contiguous(), pred)
-        al.cells(slab, t0)
-        del slab  # back to the allocator before the next slab is asked for: one slab of logits is alive at a time
-    return al.path()
+    return _Aligner(B, T, U, V, labels, input_lengths, label_lengths, joint.blank_label, dev, topology).slabs(joint, enc, pred, S)
 
 
 # ---- frames -> time, tokens -> words ----------------------------------------------------------------------------------

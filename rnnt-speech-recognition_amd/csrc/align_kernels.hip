@@ -7,105 +7,47 @@
 //                                columns per thread; one wavefront up to 1024 columns, 1024 threads beyond), one decision bit per
 //                                cell, then the back-trace (wave 0, scalar walk over register-held bit windows) and the outputs.
 //
+// The normaliser, the cell decomposition, the lane dispatch, the DPP shift, the row loader, the <K, G, W> table and the back-trace
+// are those of rnnt_align_parts.h, shared with the modified and the TDT aligner; what is here is this lattice's own: where a cell
+// is stored, the diagonal-order step with its masks, the score and the outputs.
+//
 // Every sum has an order fixed by (V) alone in the cell pass and by the utterance's own cells in the sweep: an utterance's outputs
 // do not depend on the batch around it nor on how the frames were cut into slabs.
-#include "rnnt_align.h"
-
-#include <math.h>
+#include "rnnt_align_parts.h"
 
 namespace rnnt {
 
-// ---------------------------------------------------------------------------------------------
-// Cell pass.  A group of L lanes owns one lattice cell; lane j takes the 16-byte chunks j, j + L, j + 2L ... of its V logits and
-// keeps a running (max, sum of exp(x - max)); the L partial pairs are merged by a butterfly.  The chunk-to-lane map and the merge
-// order depend on V only, and the scalar-load variant (V not a multiple of 4, or an unaligned tensor) follows the same map, so
-// both give the same bits.
-// ---------------------------------------------------------------------------------------------
-constexpr float kAlignNegInit = -3.0e38f;  // finite: two lanes without elements merge to (this, 0), not to NaN
-
+// Cell pass (rnnt_align_parts.h): {lpb, lpl} of every cell of the utterance's lattice.
 template <int L, bool VEC>
 __global__ void __launch_bounds__(256) align_cells_kernel(const AlignParams p) {
-    constexpr int kCellsPerBlock = 256 / L;
-    const int tid = threadIdx.x;
-    const int j = tid % L;
-    const uint32_t ncells = (uint32_t)p.B * (uint32_t)p.S * (uint32_t)p.U;
-    const uint32_t c = blockIdx.x * (uint32_t)kCellsPerBlock + (uint32_t)(tid / L);
-    if (c >= ncells) return;
-    const uint32_t bt = fdiv(c, p.divU);
-    const int u = (int)(c - bt * (uint32_t)p.U);
-    const int b = (int)fdiv(bt, p.divS);
-    const int t = p.t0 + (int)(bt - (uint32_t)b * (uint32_t)p.S);
-    int Tb = p.input_lengths[b], Ub = p.label_lengths[b];
-    Tb = min(max(Tb, 1), p.T);
-    Ub = min(max(Ub, 0), p.U - 1);
-    if (t >= Tb || u > Ub) return;  // outside the utterance's lattice: not read (the whole group leaves together)
-
-    const int V = p.V;
-    const float *row = p.acts + (size_t)c * (size_t)V;
-    const int chunks = (V + 3) >> 2;
-    float m = kAlignNegInit, s = 0.0f;
-#pragma unroll 2
-    for (int ch = j; ch < chunks; ch += L) {
-        float4 x;
-        if (VEC) {
-            x = *reinterpret_cast<const float4 *>(row + 4 * ch);
-        } else {
-            const int i = 4 * ch;
-            x.x = row[i];
-            x.y = i + 1 < V ? row[i + 1] : -INFINITY;
-            x.z = i + 2 < V ? row[i + 2] : -INFINITY;
-            x.w = i + 3 < V ? row[i + 3] : -INFINITY;
-        }
-        const float nm = fmaxf(m, fmaxf(fmaxf(x.x, x.y), fmaxf(x.z, x.w)));
-        s = s * __expf(m - nm) + ((__expf(x.x - nm) + __expf(x.y - nm)) + (__expf(x.z - nm) + __expf(x.w - nm)));
-        m = nm;
-    }
-#pragma unroll
-    for (int off = L / 2; off >= 1; off >>= 1) {
-        const float m2 = __shfl_xor(m, off, 64), s2 = __shfl_xor(s, off, 64);
-        const float nm = fmaxf(m, m2);
-        const float a = s * __expf(m - nm), bsum = s2 * __expf(m2 - nm);
-        s = (j & off) ? bsum + a : a + bsum;  // lower lane's part first on both sides: the pair ends with the same bits
-        m = nm;
-    }
+    const int j = threadIdx.x % L;
+    AlignCell q;
+    if (!align_cell_of<L>(p, q)) return;
+    const int V = p.V, b = q.b, t = q.t, u = q.u;
+    const float *row = p.acts + (size_t)q.c * (size_t)V;
+    float m, s;
+    align_cell_max_sum<L, VEC>(row, V, j, m, s);
     if (j != 0) return;
     const float lse = m + __logf(s);
     float2 out;
     out.x = row[p.blank] - lse;
     out.y = 0.0f;
-    if (u < Ub) {
-        int lab = p.labels[(size_t)b * (size_t)(p.U - 1) + u];
-        lab = min(max(lab, 0), V - 1);
-        out.y = row[lab] - lse;
-    }
+    if (u < q.Ub) out.y = row[align_label(p, b, u, V)] - lse;
     int r = t + u;  // wrapped skew: diagonal n = t + u lives in row n mod T
     r = r >= p.T ? r % p.T : r;
     p.cells[((size_t)b * p.T + r) * (size_t)p.Up + u] = out;
 }
 
-template <int L>
-static hipError_t launch_cells_L(const AlignParams &p, bool vec, hipStream_t s) {
-    const uint32_t ncells = (uint32_t)p.B * (uint32_t)p.S * (uint32_t)p.U;
-    const uint32_t per = 256 / L;
-    const uint32_t grid = (ncells + per - 1) / per;
-    if (vec)
-        hipLaunchKernelGGL((align_cells_kernel<L, true>), dim3(grid), dim3(256), 0, s, p);
-    else
-        hipLaunchKernelGGL((align_cells_kernel<L, false>), dim3(grid), dim3(256), 0, s, p);
-    return hipGetLastError();
-}
-
 hipError_t launch_align_cells(const AlignParams &p, hipStream_t s) {
-    const int chunks = (p.V + 3) / 4;
     const bool vec = (p.V % 4 == 0) && (((uintptr_t)p.acts & 15) == 0);
-    // lanes per cell: the smallest power of two that gives every 16-byte chunk of a cell a lane, at most one wavefront
-    if (chunks <= 1) return launch_cells_L<1>(p, vec, s);
-    if (chunks <= 2) return launch_cells_L<2>(p, vec, s);
-    if (chunks <= 4) return launch_cells_L<4>(p, vec, s);
-    if (chunks <= 8) return launch_cells_L<8>(p, vec, s);
-    if (chunks <= 16) return launch_cells_L<16>(p, vec, s);
-    if (chunks <= 32) return launch_cells_L<32>(p, vec, s);
-    return launch_cells_L<64>(p, vec, s);
+    return dispatch_cell_lanes((p.V + 3) / 4, [&](auto L) {
+        constexpr int kL = decltype(L)::value;
+        if (vec)
+            hipLaunchKernelGGL((align_cells_kernel<kL, true>), dim3(align_cells_grid(p, kL)), dim3(256), 0, s, p);
+        else
+            hipLaunchKernelGGL((align_cells_kernel<kL, false>), dim3(align_cells_grid(p, kL)), dim3(256), 0, s, p);
+        return hipGetLastError();
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -114,34 +56,6 @@ hipError_t launch_align_cells(const AlignParams &p, hipStream_t s) {
 // diagonal n; only the last column's label offer crosses to the next thread (a whole-wave DPP shift, or LDS + one barrier per
 // diagonal in the wide kernel).  The tie rule of include/rnnt.h: the label arrival wins only if STRICTLY greater.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double align_from_lower_lane(const double x, const double fill) {
-    const long long xi = __double_as_longlong(x), fi = __double_as_longlong(fill);
-    const int lo = __builtin_amdgcn_update_dpp((int)fi, (int)xi, 0x138 /*wave_shr:1*/, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(fi >> 32), (int)(xi >> 32), 0x138, 0xf, 0xf, false);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-
-template <int K>
-struct AlignDiag {
-    float2 e[K];
-};
-
-template <int K>
-__device__ __forceinline__ void align_load_diag(AlignDiag<K> &d, const float2 *rowp) {
-    if constexpr (K % 2 == 0) {
-        const float4 *q = reinterpret_cast<const float4 *>(rowp);  // 16 K bytes per thread, 16-byte aligned (K even)
-#pragma unroll
-        for (int k = 0; k < K / 2; ++k) {
-            const float4 x = q[k];
-            d.e[2 * k] = make_float2(x.x, x.y);
-            d.e[2 * k + 1] = make_float2(x.z, x.w);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < K; ++k) d.e[k] = rowp[k];
-    }
-}
-
 template <int K, int G, bool WIDE>
 __global__ void __launch_bounds__(WIDE ? 1024 : 64) align_path_kernel(const AlignParams p) {
     constexpr int kThreads = WIDE ? 1024 : 64;
@@ -170,15 +84,15 @@ __global__ void __launch_bounds__(WIDE ? 1024 : 64) align_path_kernel(const Alig
     for (int uu = tid; uu < kFrames; uu += kThreads) fr[uu] = 0;  // (a NaN lattice may leave tokens unvisited: keep reads in bounds)
 
     int lrow = 0;  // row (= diagonal mod T) of the next diagonal to load
-    auto load_block = [&](AlignDiag<K>(&buf)[G]) {
+    auto load_block = [&](AlignRow<K>(&buf)[G]) {
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-            align_load_diag<K>(buf[g], cells + (size_t)lrow * Up + u0);
+            align_load_row<K>(buf[g], cells + (size_t)lrow * Up + u0);
             lrow = (lrow + 1 == T) ? 0 : lrow + 1;
         }
     };
     // one diagonal: n = destination diagonal, d = the cells of diagonal n - 1
-    auto step = [&](const int n, const AlignDiag<K> &d) {
+    auto step = [&](const int n, const AlignRow<K> &d) {
         double a[K], c[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -214,7 +128,7 @@ __global__ void __launch_bounds__(WIDE ? 1024 : 64) align_path_kernel(const Alig
         }
     };
 
-    AlignDiag<K> bufA[G], bufB[G];
+    AlignRow<K> bufA[G], bufB[G];
     load_block(bufA);
     for (int s0 = 0; s0 < last; s0 += 2 * G) {
         load_block(bufB);
@@ -242,33 +156,11 @@ __global__ void __launch_bounds__(WIDE ? 1024 : 64) align_path_kernel(const Alig
     __threadfence();  // the decision words are read back by other lanes below
     __syncthreads();
 
-    // Back-trace: T_b + U_b - 1 dependent steps, on wave 0 with wave-uniform (scalar) state.  Lane l holds the decision word of
-    // column wu - l of the current block of 32 diagonals; 32 steps move at most 32 columns, so a window of 64 columns anchored at
-    // the column the PREVIOUS block started from covers the block -- which is what lets the next block's window be loaded while
-    // this one is walked.  A step is a v_readlane and a few scalar instructions; no memory access is on the chain.
-    if (tid < 64) {
-        const int lane = tid;
-        int u = __builtin_amdgcn_readfirstlane(Ub), n = __builtin_amdgcn_readfirstlane(last);
-        auto load_window = [&](const int blk, const int wu) -> uint32_t {
-            const int col = wu - lane;
-            return (blk >= 0 && col >= 0) ? bits[(size_t)blk * Up + col] : 0u;
-        };
-        int blk = n >> 5, wu_cur = u;
-        uint32_t wcur = load_window(blk, wu_cur);
-        for (; blk >= 0; --blk) {
-            const int wu_nxt = u;
-            const uint32_t wnxt = load_window(blk - 1, wu_nxt);
-            const int nlo = max(blk * 32, 1);
-            for (; n >= nlo; --n) {
-                const uint32_t word = (uint32_t)__builtin_amdgcn_readlane((int)wcur, __builtin_amdgcn_readfirstlane(wu_cur - u));
-                const int bit = (int)((word >> (n & 31)) & 1u);
-                if (bit && lane == 0) fr[u - 1] = n - u;  // token u - 1 is emitted in frame t = n - u
-                u -= bit;
-            }
-            wcur = wnxt;
-            wu_cur = wu_nxt;
-        }
-    }
+    // Back-trace (rnnt_align_parts.h): T_b + U_b - 1 dependent steps on wave 0.  A set bit of diagonal n in column u: token u - 1
+    // is emitted in frame t = n - u.
+    if (tid < 64)
+        align_walk_bit_windows(bits, Up, tid, __builtin_amdgcn_readfirstlane(Ub), __builtin_amdgcn_readfirstlane(last),
+                               [&](const int u, const int n) { fr[u - 1] = n - u; });
     __syncthreads();
     for (int uu = tid; uu < p.U - 1; uu += kThreads) {
         int f = -1;
@@ -282,33 +174,12 @@ __global__ void __launch_bounds__(WIDE ? 1024 : 64) align_path_kernel(const Alig
     }
 }
 
-template <int K, int G, bool WIDE>
-static hipError_t launch_path_KG(const AlignParams &p, hipStream_t s) {
-    hipLaunchKernelGGL((align_path_kernel<K, G, WIDE>), dim3(p.B), dim3(WIDE ? 1024 : 64), 0, s, p);
-    return hipGetLastError();
-}
-
 hipError_t launch_align_path(const AlignParams &p, hipStream_t s) {
-    // diagonals in flight per buffer: about 32 cells of registers per thread and buffer
-    switch (sweep_K(p.U)) {
-        case 1: return launch_path_KG<1, 16, false>(p, s);
-        case 2: return launch_path_KG<2, 16, false>(p, s);
-        case 3: return launch_path_KG<3, 8, false>(p, s);
-        case 4: return launch_path_KG<4, 8, false>(p, s);
-        case 6: return launch_path_KG<6, 4, false>(p, s);
-        case 8: return launch_path_KG<8, 4, false>(p, s);
-        case 12: return launch_path_KG<12, 2, false>(p, s);
-        case 16: return launch_path_KG<16, 2, false>(p, s);
-        default: break;
-    }
-    switch (align_wide_K(p.U)) {  // more than 1024 columns: 1024 threads, 128 registers each
-        case 2: return launch_path_KG<2, 2, true>(p, s);
-        case 3: return launch_path_KG<3, 2, true>(p, s);
-        case 4: return launch_path_KG<4, 2, true>(p, s);
-        case 6: return launch_path_KG<6, 1, true>(p, s);
-        case 8: return launch_path_KG<8, 1, true>(p, s);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_align_path<2>(p.U, [&](auto K, auto G, auto WIDE) {
+        constexpr bool kWide = decltype(WIDE)::value;
+        hipLaunchKernelGGL((align_path_kernel<decltype(K)::value, decltype(G)::value, kWide>), dim3(p.B), dim3(kWide ? 1024 : 64), 0, s, p);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace rnnt

@@ -26,12 +26,14 @@ inline int align_wide_K(int U) {
     return 0;
 }
 
-inline AlignLayout make_align_layout(int T, int U, int B) {
+// The workspace of a lattice whose back-pointers take NB blocks of 32 sweep steps: the standard aligner here, the modified one in
+// rnnt_modalign.h.  The sweep geometry (threads, K, Up) depends on U alone and is the same for both.
+inline AlignLayout make_align_layout_nb(int T, int U, int B, int NB) {
     AlignLayout w;
     w.threads = sweep_K(U) ? 64 : 1024;
     w.K = sweep_K(U) ? sweep_K(U) : align_wide_K(U);
     w.Up = w.threads * w.K;
-    w.NB = (T + U - 2) / 32 + 1;  // diagonals 0 ... T + U - 2
+    w.NB = NB;
     size_t off = 0;
     auto take = [&](size_t bytes) {
         size_t o = off;
@@ -44,12 +46,17 @@ inline AlignLayout make_align_layout(int T, int U, int B) {
     return w;
 }
 
+inline AlignLayout make_align_layout(int T, int U, int B) {
+    return make_align_layout_nb(T, U, B, (T + U - 2) / 32 + 1);  // diagonals 0 ... T + U - 2
+}
+
+// The kernel argument of the standard and the modified aligner (the field order is the argument's layout).
 struct AlignParams {
     const float *acts;  // the slab [B][S][U][V] (cell pass only)
     const int *labels;  // [B][U-1]
     const int *label_lengths;
     const int *input_lengths;
-    float2 *cells;
+    float2 *cells;  // {lpb, lpl}: wrapped skew (standard) or row-major [t][u] (modified)
     uint32_t *bits;
     int *token_frames;  // [B][U-1]
     float *token_logp;  // [B][U-1]

@@ -1066,7 +1066,7 @@ rnntStatus_t compute_rnnt_align_path(int *token_frames, float *token_logp, float
         return RNNT_STATUS_INVALID_VALUE;
     // (the blank's range was checked against the vocabulary by the _cells calls that filled the workspace)
     const rnntStatus_t st =
-        check_align(label_lengths, label_lengths, input_lengths, workspace, options.blank_label + 2, minibatch, options);
+        check_align(label_lengths, label_lengths, input_lengths, workspace, vocab_holding(options.blank_label), minibatch, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
     AlignParams p;
     fill_align(p, nullptr, label_lengths, input_lengths, 0, minibatch, workspace, options);

@@ -17,45 +17,12 @@
 
 namespace rnnt {
 
-struct ModAlignLayout {
-    size_t lp, bits, total;
-    int Up, NB;
-};
-
-inline ModAlignLayout make_modalign_layout(int T, int U, int B) {
-    ModAlignLayout w;
-    const int K = sweep_K(U) ? sweep_K(U) : align_wide_K(U);
-    w.Up = (sweep_K(U) ? 64 : 1024) * K;
-    w.NB = T / 32 + 1;  // rows 0 ... T
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
-    };
-    w.lp = take((size_t)B * T * w.Up * 2 * sizeof(float));
-    w.bits = take((size_t)B * w.NB * w.Up * sizeof(uint32_t));
-    w.total = off;
-    return w;
+// the layout and the kernel argument are the standard aligner's (its `cells` is the lp above); only NB differs
+inline AlignLayout make_modalign_layout(int T, int U, int B) {
+    return make_align_layout_nb(T, U, B, T / 32 + 1);  // rows 0 ... T
 }
 
-struct ModAlignParams {
-    const float *acts;  // the slab [B][S][U][V] (cell pass only)
-    const int *labels;  // [B][U-1]
-    const int *label_lengths;
-    const int *input_lengths;
-    float2 *lp;
-    uint32_t *bits;
-    int *token_frames;  // [B][U-1]
-    float *token_logp;  // [B][U-1]
-    float *scores;      // [B]
-    int B, T, U, V, blank;
-    int S, t0;  // slab frames, first frame of the slab
-    int Up, NB;
-    FastDiv divU, divS;
-};
-
-hipError_t launch_modalign_cells(const ModAlignParams &p, hipStream_t s);
-hipError_t launch_modalign_path(const ModAlignParams &p, hipStream_t s);
+hipError_t launch_modalign_cells(const AlignParams &p, hipStream_t s);
+hipError_t launch_modalign_path(const AlignParams &p, hipStream_t s);
 
 }  // namespace rnnt

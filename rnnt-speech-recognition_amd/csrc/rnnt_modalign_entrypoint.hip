@@ -26,11 +26,11 @@ static rnntStatus_t check_common(const void *labels, const void *ll, const void 
     return RNNT_STATUS_SUCCESS;
 }
 
-static ModAlignParams make_params(const int *labels, const int *ll, const int *il, int V, int B, void *ws, const rnntOptions &o) {
-    const ModAlignLayout w = make_modalign_layout(o.maxT, o.maxU, B);
-    ModAlignParams p{};
+static AlignParams make_params(const int *labels, const int *ll, const int *il, int V, int B, void *ws, const rnntOptions &o) {
+    const AlignLayout w = make_modalign_layout(o.maxT, o.maxU, B);
+    AlignParams p{};
     p.labels = labels, p.label_lengths = ll, p.input_lengths = il;
-    p.lp = (float2 *)((char *)ws + w.lp);
+    p.cells = (float2 *)((char *)ws + w.cells);
     p.bits = (uint32_t *)((char *)ws + w.bits);
     p.B = B, p.T = o.maxT, p.U = o.maxU, p.V = V, p.blank = o.blank_label;
     p.Up = w.Up, p.NB = w.NB;
@@ -53,7 +53,7 @@ rnntStatus_t compute_rnnt_modified_align_cells(const float *acts_slab, int slab_
     const rnntStatus_t st = check_common(flat_labels, label_lengths, input_lengths, workspace, alphabet_size, minibatch, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
     if (slab_frames < 1 || frame_offset < 0 || (long long)frame_offset + slab_frames > options.maxT) return RNNT_STATUS_INVALID_VALUE;
-    ModAlignParams p = make_params(flat_labels, label_lengths, input_lengths, alphabet_size, minibatch, workspace, options);
+    AlignParams p = make_params(flat_labels, label_lengths, input_lengths, alphabet_size, minibatch, workspace, options);
     p.acts = acts_slab, p.S = slab_frames, p.t0 = frame_offset;
     p.divS = make_fastdiv((uint32_t)slab_frames);
     return from_hip(launch_modalign_cells(p, (hipStream_t)options.stream));
@@ -66,9 +66,9 @@ rnntStatus_t compute_rnnt_modified_align_path(int *token_frames, float *token_lo
         return RNNT_STATUS_INVALID_VALUE;
     // (the blank's range was checked against the vocabulary by the _cells calls that filled the workspace)
     const rnntStatus_t st =
-        check_common(label_lengths, label_lengths, input_lengths, workspace, options.blank_label + 2, minibatch, options);
+        check_common(label_lengths, label_lengths, input_lengths, workspace, vocab_holding(options.blank_label), minibatch, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
-    ModAlignParams p = make_params(nullptr, label_lengths, input_lengths, 0, minibatch, workspace, options);
+    AlignParams p = make_params(nullptr, label_lengths, input_lengths, 0, minibatch, workspace, options);
     p.token_frames = token_frames, p.token_logp = token_logp, p.scores = scores;
     return from_hip(launch_modalign_path(p, (hipStream_t)options.stream));
 }

@@ -82,8 +82,7 @@ rnntStatus_t compute_rnnt_tdt_align_path(int *token_frames, int *token_durations
     if (!outputs_ok(token_frames, token_durations, token_logp, scores)) return RNNT_STATUS_INVALID_VALUE;
     // (the blank's range was checked against the vocabulary by the _cells calls that filled the workspace)
     const rnntStatus_t st = check_common(label_lengths, input_lengths, durations, num_durations, workspace,
-                                         options.blank_label < 0x7ffffffe ? options.blank_label + 2 : options.blank_label, minibatch,
-                                         options);
+                                         vocab_holding(options.blank_label), minibatch, options);
     if (st != RNNT_STATUS_SUCCESS) return st;
     TdtAlignParams p = make_params(label_lengths, input_lengths, durations, num_durations, minibatch, workspace, options);
     p.token_frames = token_frames, p.token_durations = token_durations, p.token_logp = token_logp, p.scores = scores;

@@ -4,75 +4,48 @@
 //   tdtalign_cells_kernel<L, VEC>   one pass over a slab of logits: per live cell the two log-softmax normalisers (tokens [0, V),
 //                                   durations [V, V + D); f32, online max / sum, L lanes per cell), stored as the 2 D edge weights
 //                                   wb_i, wl_i (sigma folded in) on skewed rows.  The cell body of tdt_cells_kernel
-//                                   (rnnt_tdt_kernels.hip) on the chunk-to-lane map of modalign_cells_kernel.  HBM-bound.
+//                                   (rnnt_tdt_kernels.hip) on the chunk-to-lane map, the chunk load, the merge, the cell
+//                                   decomposition and the lane dispatch of rnnt_align_parts.h, which the standard and the modified
+//                                   aligner use too; the two-accumulator loop is its own.  HBM-bound.
 //   tdtalign_path_kernel<MAXUP>     one workgroup of Up threads per utterance: the max-plus sweep over the skewed rows n = t + u
 //                                   (one lattice column per thread, the last dmax + 2 rows of v in an LDS ring, one barrier per row,
 //                                   the weights of the next two rows in flight), one decision byte per node, then the back-trace over
-//                                   windows of decision bytes staged in LDS and the four outputs.
+//                                   windows of decision bytes staged in LDS and the four outputs.  Another algorithm than the
+//                                   bit-lattice sweeps of the other two aligners: it shares nothing with them.
 //
 // Every sum has an order fixed by V + D alone in the cell pass and every maximum an order fixed by the duration set in the sweep: an
 // utterance's outputs do not depend on the batch around it, on how the frames were cut into slabs nor on the load route.
+#include "rnnt_align_parts.h"
 #include "rnnt_tdtalign.h"
-
-#include <math.h>
 
 namespace rnnt {
 
-constexpr float kTdtAlignNegInit = -3.0e38f;             // finite: two lanes without elements merge to (this, 0), not to NaN
 constexpr int kTdtAlignRing = kTdtAlignMaxDuration + 2;  // rows n - dmax - 1 ... n
 constexpr int kTdtAlignNone = 0xFF;                      // the decision code of a node nothing arrives at
 constexpr int kWinRows = 64, kWinCols = 64;              // the back-trace's window of decision bytes
 
-// the merge of two (max, sum) pairs across lanes `off` apart; the lower lane's part first on both sides: the same bits in both
-__device__ __forceinline__ void tdtalign_merge(float &mx, float &s, const int j, const int off) {
-    const float m2 = __shfl_xor(mx, off, 64), s2 = __shfl_xor(s, off, 64);
-    const float nm = fmaxf(mx, m2);
-    const float a = s * __expf(mx - nm), bsum = s2 * __expf(m2 - nm);
-    s = (j & off) ? bsum + a : a + bsum;
-    mx = nm;
-}
-
 // ---------------------------------------------------------------------------------------------
-// Cell pass.  A group of L lanes owns one lattice cell; lane j takes the 16-byte chunks j, j + L, ... of its V + D logits and keeps a
-// running (max, sum of exp(x - max)) for the tokens and one for the durations; the partial pairs are merged by butterflies.  The
-// chunk-to-lane map and the merge order depend on V + D only, and the scalar-load variant (V + D not a multiple of 4, or an unaligned
-// slab) pads its last chunk with -inf and follows the same map, so both give the same bits.
+// Cell pass: the chunk-to-lane map, the chunk load and the merge of rnnt_align_parts.h over the V + D logits of a cell, with a running
+// (max, sum of exp(x - max)) for the tokens and one for the durations -- this file's own loop, since a chunk may straddle the
+// boundary between the two.
 // ---------------------------------------------------------------------------------------------
 template <int L, bool VEC>
 __global__ void __launch_bounds__(256) tdtalign_cells_kernel(const TdtAlignParams p) {
-    constexpr int kCellsPerBlock = 256 / L;
-    const int tid = threadIdx.x;
-    const int j = tid % L;
-    if (blockIdx.x == 0 && tid == 0) *p.sigma_slot = p.sigma;  // (every slab's call writes the same value)
-    const uint32_t ncells = (uint32_t)p.B * (uint32_t)p.S * (uint32_t)p.U;
-    const uint32_t c = blockIdx.x * (uint32_t)kCellsPerBlock + (uint32_t)(tid / L);
-    if (c >= ncells) return;
-    const uint32_t bs = fdiv(c, p.divU);
-    const int u = (int)(c - bs * (uint32_t)p.U);
-    const int b = (int)fdiv(bs, p.divS);
-    const int t = p.t0 + (int)(bs - (uint32_t)b * (uint32_t)p.S);
-    int Tb = p.input_lengths[b], Ub = p.label_lengths[b];
-    Tb = min(max(Tb, 1), p.T);
-    Ub = min(max(Ub, 0), p.U - 1);
-    if (t >= Tb || u > Ub) return;  // padding: not read (the whole group leaves together)
+    const int j = threadIdx.x % L;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *p.sigma_slot = p.sigma;  // (every slab's call writes the same value)
+    AlignCell q;
+    if (!align_cell_of<L>(p, q)) return;
+    const int b = q.b, t = q.t, u = q.u;
 
     const int V = p.V, D = p.D, R = V + D;
-    const float *row = p.acts + (size_t)c * (size_t)R;
+    const float *row = p.acts + (size_t)q.c * (size_t)R;
     const int chunks = (R + 3) >> 2;
-    float mv = kTdtAlignNegInit, sv = 0.0f, md = kTdtAlignNegInit, sd = 0.0f;
+    float mv = kAlignNegInit, sv = 0.0f, md = kAlignNegInit, sd = 0.0f;
 #pragma unroll 2
     for (int ch = j; ch < chunks; ch += L) {
         const int i = 4 * ch;
-        float x[4];
-        if (VEC) {
-            const float4 q = *reinterpret_cast<const float4 *>(row + i);
-            x[0] = q.x, x[1] = q.y, x[2] = q.z, x[3] = q.w;
-        } else {
-            x[0] = row[i];
-            x[1] = i + 1 < R ? row[i + 1] : -INFINITY;
-            x[2] = i + 2 < R ? row[i + 2] : -INFINITY;
-            x[3] = i + 3 < R ? row[i + 3] : -INFINITY;
-        }
+        const float4 x4 = align_load_chunk<VEC>(row, ch, R);
+        const float x[4] = {x4.x, x4.y, x4.z, x4.w};
         float nv = mv, nd = md;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -94,19 +67,15 @@ __global__ void __launch_bounds__(256) tdtalign_cells_kernel(const TdtAlignParam
     }
 #pragma unroll
     for (int off = L / 2; off >= 1; off >>= 1) {
-        tdtalign_merge(mv, sv, j, off);
-        tdtalign_merge(md, sd, j, off);
+        align_merge(mv, sv, j, off);
+        align_merge(md, sd, j, off);
     }
     const float lseV = mv + __logf(sv), lseD = md + __logf(sd);
     // the 2 + D logits the weights need are read again here (the lines are in cache): which lane holds them depends on V, the blank
     // and the label
     const float lpb = (row[p.blank] - lseV) - p.sigma;
     float lpl = 0.0f;
-    if (u < Ub) {
-        int lab = p.labels[(size_t)b * (size_t)(p.U - 1) + u];
-        lab = min(max(lab, 0), V - 1);
-        lpl = (row[lab] - lseV) - p.sigma;
-    }
+    if (u < q.Ub) lpl = (row[align_label(p, b, u, V)] - lseV) - p.sigma;
     const size_t plane = (size_t)p.N * (size_t)p.Up;
     float *w = p.w + (size_t)b * (size_t)(2 * D) * plane + (size_t)(t + u) * (size_t)p.Up + u;
     for (int i = j; i < D; i += L) {
@@ -116,29 +85,17 @@ __global__ void __launch_bounds__(256) tdtalign_cells_kernel(const TdtAlignParam
     }
 }
 
-template <int L>
-static hipError_t launch_cells_L(const TdtAlignParams &p, bool vec, hipStream_t s) {
-    const uint32_t ncells = (uint32_t)p.B * (uint32_t)p.S * (uint32_t)p.U;
-    const uint32_t per = 256 / L;
-    const uint32_t grid = (ncells + per - 1) / per;
-    if (vec)
-        hipLaunchKernelGGL((tdtalign_cells_kernel<L, true>), dim3(grid), dim3(256), 0, s, p);
-    else
-        hipLaunchKernelGGL((tdtalign_cells_kernel<L, false>), dim3(grid), dim3(256), 0, s, p);
-    return hipGetLastError();
-}
-
 hipError_t launch_tdtalign_cells(const TdtAlignParams &p, hipStream_t s) {
-    const int R = p.V + p.D, chunks = (R + 3) / 4;
+    const int R = p.V + p.D;
     const bool vec = (R % 4 == 0) && (((uintptr_t)p.acts & 15) == 0);
-    // lanes per cell: the smallest power of two that gives every 16-byte chunk of a cell a lane, at most one wavefront
-    if (chunks <= 1) return launch_cells_L<1>(p, vec, s);
-    if (chunks <= 2) return launch_cells_L<2>(p, vec, s);
-    if (chunks <= 4) return launch_cells_L<4>(p, vec, s);
-    if (chunks <= 8) return launch_cells_L<8>(p, vec, s);
-    if (chunks <= 16) return launch_cells_L<16>(p, vec, s);
-    if (chunks <= 32) return launch_cells_L<32>(p, vec, s);
-    return launch_cells_L<64>(p, vec, s);
+    return dispatch_cell_lanes((R + 3) / 4, [&](auto L) {
+        constexpr int kL = decltype(L)::value;
+        if (vec)
+            hipLaunchKernelGGL((tdtalign_cells_kernel<kL, true>), dim3(align_cells_grid(p, kL)), dim3(256), 0, s, p);
+        else
+            hipLaunchKernelGGL((tdtalign_cells_kernel<kL, false>), dim3(align_cells_grid(p, kL)), dim3(256), 0, s, p);
+        return hipGetLastError();
+    });
 }
 
 // ---------------------------------------------------------------------------------------------

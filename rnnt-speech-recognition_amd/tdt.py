@@ -1108,60 +1108,15 @@ def _align_path_torch(wb, wl, raw, input_lengths, label_lengths, dur):
     return frames.to(dev), durs.to(dev), logp.to(dev), scores
 
 
-class _TDTAligner:
-    """One TDT alignment in flight on the engine (libwarprnnt_tdtalign.so): the workspace, the outputs and the slab feed."""
+class _TDTAligner(_alignment._Aligner):
+    """One TDT alignment in flight on the engine (libwarprnnt_tdtalign.so): alignment._Aligner with the durations and sigma in its
+    calls and token_durations among its outputs."""
+    int_outputs = 2
 
     def __init__(self, B, T, U, V, labels, input_lengths, label_lengths, dur, blank, sigma, dev):
-        self.lib = _lib.load_tdtalign()
-        self.B, self.T, self.U, self.V, self.dur, self.blank, self.sigma, self.dev = B, T, U, V, dur, int(blank), sigma, dev
-        self.labels, self.il, self.ll = labels, input_lengths, label_lengths
-        self.d = (ctypes.c_int * len(dur))(*dur)
-        with torch.cuda.device(dev):
-            self.ws = torch.empty(_lib.tdt_align_workspace_bytes(T, U, B, len(dur)), dtype=torch.uint8, device=dev)
-
-    def _opts(self):
-        return _lib.make_options(torch.cuda.current_stream().cuda_stream, self.blank, self.T, self.U)
-
-    def _outputs(self):
-        n = max(self.U - 1, 1)
-        frames = torch.empty(self.B, n, dtype=torch.int32, device=self.dev)
-        durs = torch.empty(self.B, n, dtype=torch.int32, device=self.dev)
-        logp = torch.empty(self.B, n, dtype=torch.float32, device=self.dev)
-        scores = torch.empty(self.B, dtype=torch.float32, device=self.dev)
-        return frames, durs, logp, scores
-
-    def _trim(self, out):
-        return out[0][:, : self.U - 1], out[1][:, : self.U - 1], out[2][:, : self.U - 1], out[3]
-
-    def cells(self, slab: torch.Tensor, frame_offset: int) -> None:
-        R = self.V + len(self.dur)
-        if slab.dtype != torch.float32 or slab.dim() != 4 or slab.shape[0] != self.B or tuple(slab.shape[2:]) != (self.U, R):
-            raise ValueError(f"tdt align: a slab must be float32 [{self.B}, frames, {self.U}, {R}], got {tuple(slab.shape)}")
-        slab = slab.contiguous()
-        with torch.cuda.device(self.dev):
-            st = self.lib.compute_rnnt_tdt_align_cells(slab.data_ptr(), slab.shape[1], int(frame_offset), self.labels.data_ptr(),
-                                                       self.ll.data_ptr(), self.il.data_ptr(), self.V, self.d, len(self.dur),
-                                                       self.sigma, self.B, self.ws.data_ptr(), self._opts())
-        _lib.check(st, "compute_rnnt_tdt_align_cells")
-
-    def path(self):
-        with torch.cuda.device(self.dev):
-            out = self._outputs()
-            st = self.lib.compute_rnnt_tdt_align_path(out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(),
-                                                      self.ll.data_ptr(), self.il.data_ptr(), self.d, len(self.dur), self.B,
-                                                      self.ws.data_ptr(), self._opts())
-        _lib.check(st, "compute_rnnt_tdt_align_path")
-        return self._trim(out)
-
-    def whole(self, acts):
-        with torch.cuda.device(self.dev):
-            out = self._outputs()
-            st = self.lib.compute_rnnt_tdt_align(acts.data_ptr(), self.labels.data_ptr(), self.ll.data_ptr(), self.il.data_ptr(),
-                                                 self.V, self.d, len(self.dur), self.sigma, self.B, out[0].data_ptr(),
-                                                 out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), self.ws.data_ptr(),
-                                                 self._opts())
-        _lib.check(st, "compute_rnnt_tdt_align")
-        return self._trim(out)
+        d = (ctypes.c_int * len(dur))(*dur)
+        self.cell_args, self.path_args = (d, len(dur), sigma), (d, len(dur))
+        super().__init__(B, T, U, V, labels, input_lengths, label_lengths, blank, dev, "tdt", width=V + len(dur), ws_args=(len(dur),))
 
 
 @torch.no_grad()
@@ -1222,12 +1177,7 @@ def tdt_align_joint(joint, enc, pred, labels, input_lengths, label_lengths, dura
         parts = [_align_cells_torch(joint.cell_logits(enc[:, t0:t0 + S], pred), labels, dur, blank, sigma) for t0 in range(0, T, S)]
         wb, wl, raw = (torch.cat([p[k] for p in parts], dim=1) for k in range(3))
         return _align_path_torch(wb, wl, raw, il, ll, dur)
-    al = _TDTAligner(B, T, U, V, labels, il, ll, dur, blank, sigma, dev)
-    for t0 in range(0, T, S):
-        slab = joint.cell_logits(enc[:, t0:t0 + S].contiguous(), pred)
-        al.cells(slab, t0)
-        del slab  # back to the allocator before the next slab is asked for: one slab of logits is alive at a time
-    return al.path()
+    return _TDTAligner(B, T, U, V, labels, il, ll, dur, blank, sigma, dev).slabs(joint, enc, pred, S)
 
 
 def token_end_frames(token_frames, token_durations) -> torch.Tensor:

@@ -122,6 +122,14 @@ ENTRIES = {
 }
 LIB_OF = {fn: name for name, fns in ENTRIES.items() for fn in fns}
 SIG = {fn: s.split() for fns in ENTRIES.values() for fn, s in fns.items()}
+# The aligners' _path entry points take no alphabet_size and hand their shared checks a vocabulary made from the blank
+# (rnnt_host.h vocab_holding): call() knows them, the tables of rows above do not.
+ALIGN_PATH = {
+    "compute_rnnt_align_path": ("base", "token_frames token_logp scores label_lengths input_lengths minibatch workspace o"),
+    "compute_rnnt_modified_align_path": ("modalign", "token_frames token_logp scores label_lengths input_lengths minibatch workspace o"),
+    "compute_rnnt_tdt_align_path": ("tdtalign", "token_frames token_durations token_logp scores label_lengths input_lengths durations "
+                                                "num_durations minibatch workspace o"),
+}
 TDT = ("tdtgreedy", "tdtstream", "tdtbeam", "tdtbeamstream")
 
 # the well-formed call: every integer argument by name; every other name is a pointer (FAKE)
@@ -201,11 +209,11 @@ def _graph(lib_name):
 def call(fn, **spoilt):
     """The well-formed call of `fn` with the named arguments replaced.  Keys of OPTIONS replace fields of the options, "graph"
     the graph struct (None: a NULL graph), "durations" the duration set (a list; None: NULL)."""
-    name = LIB_OF[fn]
+    name, sig = (LIB_OF[fn], SIG[fn]) if fn in SIG else (ALIGN_PATH[fn][0], ALIGN_PATH[fn][1].split())
     lib = _lib._load(name)
     keep = []  # host memory the call reads
     args = []
-    for a in SIG[fn]:
+    for a in sig:
         if a == "o":
             args.append(_lib.make_options(0, **{k: spoilt.get(k, v) for k, v in OPTIONS.items()}))
         elif a == "sz":
@@ -296,6 +304,17 @@ def built():
 @pytest.mark.parametrize("fn,spoilt", _rows())
 def test_refused_before_anything_is_enqueued(fn, spoilt):
     assert call(fn, **spoilt) == INVALID
+
+
+@pytest.mark.parametrize("fn", list(ALIGN_PATH))
+def test_align_path_refuses_a_blank_no_vocabulary_holds(fn):
+    """blank_label = INT_MAX: no int vocabulary holds it; refused without computing blank_label + 2."""
+    for blank in (2**31 - 1, 2**31 - 2, -1):
+        assert call(fn, blank=blank) == INVALID, blank
+    import torch
+
+    if not torch.cuda.is_available():  # (the well-formed call passes validation and then fails for lack of a device)
+        assert call(fn) != INVALID and call(fn, blank=2**31 - 3) != INVALID
 
 
 def _no_device():
