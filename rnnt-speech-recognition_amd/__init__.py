@@ -24,6 +24,7 @@ from .tdt import rnnt_align_tdt, tdt_align_joint, token_end_frames  # noqa: F401
 from .tdt import TDTBeamJoint, tdt_beam_search_batch  # noqa: F401
 from .tdt import StreamingTDTBeamDecoder, TDTBeamStreamJoint  # noqa: F401
 from .tdt_joint import TDTJointLoss, rnnt_joint_loss_tdt, rnnt_joint_loss_tdt_and_grad  # noqa: F401
+from .ctc import CTCLoss, ctc_greedy_decode, ctc_loss, ctc_loss_and_grad  # noqa: F401
 
 __all__ = ["rnnt_loss", "rnnt_loss_and_grad", "RNNTLoss", "get_loss_fn", "reduced_lengths", "rnnt_joint_loss",
            "joint_logits", "JointLoss", "build", "LIB_PATH", "rnnt_align", "align_joint", "token_times", "word_times",
@@ -34,4 +35,5 @@ __all__ = ["rnnt_loss", "rnnt_loss_and_grad", "RNNTLoss", "get_loss_fn", "reduce
            "TDTGreedyJoint", "tdt_greedy_search_batch", "TDTGreedyStreamJoint", "StreamingTDTGreedyDecoder",
            "rnnt_align_tdt", "tdt_align_joint", "token_end_frames", "TDTBeamJoint", "tdt_beam_search_batch",
            "rnnt_joint_loss_tdt", "rnnt_joint_loss_tdt_and_grad", "TDTJointLoss",
-           "TDTBeamStreamJoint", "StreamingTDTBeamDecoder"]
+           "TDTBeamStreamJoint", "StreamingTDTBeamDecoder",
+           "ctc_loss", "ctc_loss_and_grad", "CTCLoss", "ctc_greedy_decode"]

@@ -258,6 +258,11 @@ _NEXT_SIGNATURES = {
         "compute_rnnt_multibeam_stream_step": [vp] * 3 + [ci] * 8 + [vp, opt],
         "compute_rnnt_multibeam_stream_results": [vp] * 6 + [ci] * 8 + [vp, opt],
     },
+    "ctc": {
+        "get_rnnt_ctc_workspace_size": [ci, ci, ci, sz],
+        "compute_rnnt_ctc_loss": [vp] * 6 + [ci, ci, vp, vp, opt],
+        "compute_rnnt_ctc_greedy": [vp, vp, ci, ci, vp, vp, vp, opt],
+    },
 }
 _BUILT_SIGNATURES = {**_EVERY_SIGNATURE, **_NEXT_SIGNATURES}
 _RESTYPES = {"rnntGetStatusString": ctypes.c_char_p}
@@ -383,6 +388,11 @@ def load_multibeam_stream():
     """libwarprnnt_multibeamstream.so: streaming beam search with several symbols per frame over slots,
     include/rnnt_beam_multi_stream.h."""
     return _load("multibeamstream")
+
+
+def load_ctc():
+    """libwarprnnt_ctc.so: the CTC loss and the greedy CTC decoder of the auxiliary head, include/rnnt_ctc.h."""
+    return _load("ctc")
 
 
 def status_string(status: int) -> str:
@@ -551,3 +561,7 @@ def multibeam_stream_workspace_bytes(max_chunk_frames: int, slots: int, beam: in
                                      enc_width: int, joint_size: int, alphabet_size: int, joint_dtype: int, timed: bool = False) -> int:
     return _size(load_multibeam_stream(), "get_rnnt_multibeam_stream_workspace_size", max_chunk_frames, slots, beam,
                  symbols_per_frame, max_hyp_len, enc_width, joint_size, alphabet_size, joint_dtype, int(bool(timed)))
+
+
+def ctc_workspace_bytes(maxT: int, maxU: int, minibatch: int) -> int:
+    return _size(load_ctc(), "get_rnnt_ctc_workspace_size", maxT, maxU, minibatch)

@@ -103,6 +103,9 @@ NEXT_LIBRARIES = {
     # projection; the base kernel objects and its own entry points (no object of "multibeam" is linked)
     "multibeamstream": Library("rnnt_beam_multi_stream.h", ("tsd_stream_kernels.hip", "rnnt_tsd_stream_entrypoint.hip"), _BASE_KERNELS,
                                "rnnt_tsdstream.map"),
+    # the CTC loss and the greedy CTC decoder of the auxiliary head (hybrid transducer + CTC training): its own kernels, entry
+    # points and workspace; it borrows nothing
+    "ctc": Library("rnnt_ctc.h", ("rnnt_ctc_kernels.hip", "rnnt_ctc_entrypoint.hip"), (), "rnnt_ctc.map"),
 }
 BUILT_LIBRARIES = {**EVERY_LIBRARY, **NEXT_LIBRARIES}
 
@@ -129,6 +132,7 @@ TDTJOINT_LIB_PATH = lib_path("tdtjoint")
 TDTBEAMSTREAM_LIB_PATH = lib_path("tdtbeamstream")
 MULTIBEAM_LIB_PATH = lib_path("multibeam")
 MULTIBEAMSTREAM_LIB_PATH = lib_path("multibeamstream")
+CTC_LIB_PATH = lib_path("ctc")
 # -fvisibility=hidden: the library exports exactly the entry points include/rnnt.h marks RNNT_API (tests/test_abi.py)
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wno-inline-asm"]
 # per-source extras.  -fno-slp-vectorize: no packed-f32 instructions (v_pk_fma_f32 ...) from the compiler -- in the linear sweeps

@@ -231,13 +231,26 @@ class Transducer(nn.Module):
     `simple_loss_scale`, `lm_only_scale`, `am_only_scale` are its settings): while `self.training`, `loss()` returns the two-pass
     pruned objective, simple_loss_scale * simple + pruned.  In eval mode it returns the full-lattice cost through `self.joint`,
     exactly as a "full" model does, and that is deliberate: the decoders use the full joint, and the evaluation figure stays the
-    model's negative log-likelihood, comparable between the two training modes."""
+    model's negative log-likelihood, comparable between the two training modes.
+
+    `ctc_weight` > 0 makes the model a hybrid transducer + CTC one: it adds `self.ctc_head`, a Linear from the encoder's output to
+    the vocabulary, and while `self.training`, `loss()` returns transducer + ctc_weight * ctc per utterance (ctc.ctc_loss on the
+    head's logits with the same blank, reduced lengths and labels; `ctc_zero_infinity` turns the +inf CTC cost of an utterance with
+    fewer frames than CTC needs into 0).  In eval mode `loss()` stays the transducer's negative log-likelihood, the rule of
+    loss="pruned".  `ctc_decode` is the head's greedy decoder.  With the default 0.0 nothing is constructed: state_dict() keys,
+    checkpoints and every code path are those of a model without the keyword."""
 
     def __init__(self, hp: HParams, blank_label: int = 0, lstm: str = "torch", fastemit_lambda: float = 0.0, loss: str = "full",
-                 s_range: int = 5, simple_loss_scale: float = 0.5, lm_only_scale: float = 0.25, am_only_scale: float = 0.0):
+                 s_range: int = 5, simple_loss_scale: float = 0.5, lm_only_scale: float = 0.25, am_only_scale: float = 0.0,
+                 ctc_weight: float = 0.0, ctc_zero_infinity: bool = True):
         super().__init__()
         if loss not in LOSS_MODES:
             raise ValueError(f"loss must be one of {LOSS_MODES}, got {loss!r}")
+        self.ctc_weight = float(ctc_weight)
+        if not (0.0 <= self.ctc_weight < float("inf")):  # (NaN fails the comparison)
+            raise ValueError(f"ctc_weight must be finite and >= 0, got {ctc_weight!r}")
+        self.ctc_zero_infinity = bool(ctc_zero_infinity)
+        self.blank_label = int(blank_label)
         self.loss_mode = loss
         self.hp = hp
         self.lstm_route = _check_lstm_route(lstm)
@@ -256,6 +269,8 @@ class Transducer(nn.Module):
             self.pruned = PrunedJointLoss(self.encoder.out_width, hp.joint_net_size, hp.vocab_size, s_range=s_range,
                                           simple_loss_scale=simple_loss_scale, lm_only_scale=lm_only_scale,
                                           am_only_scale=am_only_scale)
+        if self.ctc_weight > 0.0:
+            self.ctc_head = nn.Linear(self.encoder.out_width, hp.vocab_size)
 
     def forward(self, mel_specs, pred_inp):
         """-> (enc [B, T', H], pred [B, U, H]); U = L_max + 1 because pred_inp = [0] ++ labels
@@ -264,12 +279,30 @@ class Transducer(nn.Module):
 
     def loss(self, mel_specs, pred_inp, spec_lengths, label_lengths, labels):
         """Per-utterance costs with the reference's argument set (run_rnnt.py:262-273).  A loss="pruned" model in train mode
-        returns the two-pass pruned objective instead (the class docstring)."""
+        returns the two-pass pruned objective instead, and a hybrid model (ctc_weight > 0) in train mode adds ctc_weight times
+        the CTC cost of its head (the class docstring)."""
         enc, pred = self(mel_specs, pred_inp)
         t_len = reduced_lengths(spec_lengths, self.hp.time_reduction_factor)  # utils/loss.py:31-33
         if self.loss_mode == "pruned" and self.training:
-            return self.pruned(self.joint, enc, pred, labels, t_len, label_lengths)
-        return self.joint(enc, pred, labels, t_len, label_lengths)
+            costs = self.pruned(self.joint, enc, pred, labels, t_len, label_lengths)
+        else:
+            costs = self.joint(enc, pred, labels, t_len, label_lengths)
+        if self.ctc_weight > 0.0 and self.training:
+            from .ctc import ctc_loss
+
+            ctc = ctc_loss(self.ctc_head(enc), labels, t_len, label_lengths, self.blank_label, self.ctc_zero_infinity)
+            costs = costs + self.ctc_weight * ctc.to(costs.dtype)
+        return costs
+
+    @torch.no_grad()
+    def ctc_decode(self, mel_specs, spec_lengths, return_frames: bool = False):
+        """Greedy decoding of the CTC head: ctc.ctc_greedy_decode on the head's logits, frames counted after the time reduction."""
+        if self.ctc_weight <= 0.0:
+            raise RuntimeError("ctc_decode needs a hybrid model: Transducer(..., ctc_weight > 0)")
+        from .ctc import ctc_greedy_decode
+
+        t_len = reduced_lengths(spec_lengths, self.hp.time_reduction_factor)
+        return ctc_greedy_decode(self.ctc_head(self.encoder(mel_specs)), t_len, self.blank_label, return_frames)
 
     def logits(self, mel_specs, pred_inp):
         enc, pred = self(mel_specs, pred_inp)
@@ -293,6 +326,6 @@ def save_weights(model: nn.Module, path: str) -> None:
 
 
 def load_weights(model: nn.Module, path: str, map_location: Optional[str] = None, strict: bool = True) -> None:
-    """strict=False lets a checkpoint of a loss="full" model initialise a loss="pruned" one: the two heads of the first pass stay
-    at their initialisation."""
+    """strict=False lets a checkpoint of a loss="full" model initialise a loss="pruned" one (the two heads of the first pass stay
+    at their initialisation), and a checkpoint without a CTC head a hybrid model (ctc_weight > 0) in the same way."""
     model.load_state_dict(torch.load(path, map_location=map_location), strict=strict)
